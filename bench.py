@@ -39,6 +39,9 @@ Extra objects on the line:
                  its own process), its first chunk checked against the oracle: what a host gets that hands the
                  library 128 Mi-sample chunks -- the detector scan's per-chunk launches and waits spread over
                  twice the samples.  Reported beside the headline, never as `value`.
+
+--dump-outputs DIR writes what the timed path returned for its last chunk as DIR/<name>.npy (float64 / float32, at most
+64 MB): the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -208,6 +211,53 @@ def pack_records(irdm, demods, hb, cap):
         rec[:, :head] = demods[:, :head]
         rec[:, head:] = np.packbits(demods[:, head:head + nbits], axis=1)
     return k
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, irdm, bursts, demods, packed, lo, hi, t0_ns):
+    """--dump-outputs: the records the caller received for the stream samples [lo, hi) -- the bursts that start there and
+    the frames demodulated from them, in id order.  One float64 array per scalar field (DIR/burst_<field>.npy,
+    DIR/frame_<field>.npy; frame_timestamp in ns after the stream's start time, exact in float64), the hard bits as
+    float32 [frames, 896] (DIR/frame_bits.npy, valid up to frame_n_bits) and, for full records, DIR/frame_llr.npy.  Should
+    the frames exceed 64 MB, a fixed, seeded sample of them is written."""
+    def scalars(typ, raw):
+        d = np.dtype(typ)
+        names = [f for f in d.names if d.fields[f][0].shape == () and d.fields[f][0].kind != "V"]
+        sd = np.dtype({"names": names, "formats": [d.fields[f][0] for f in names],
+                       "offsets": [d.fields[f][1] for f in names], "itemsize": d.itemsize})
+        return np.ascontiguousarray(raw).view(sd).reshape(-1)
+
+    typ = irdm.DemodPacked if packed else irdm.Demod
+    b = scalars(irdm.Burst, bursts)
+    keep = (b["start"] >= lo) & (b["start"] < hi)
+    b = b[keep][np.argsort(b["id"][keep], kind="stable")]
+    f = scalars(typ, demods)
+    sel = np.flatnonzero(np.isin(f["id"], b["id"]))
+    sel = sel[np.lexsort((f["timestamp"][sel], f["id"][sel]))]
+    row = 8 * len(f.dtype.names) + 4 * irdm.MAX_BITS * (1 if packed else 2)
+    room = (DUMP_LIMIT_BYTES - 8 * len(b.dtype.names) * len(b)) // row
+    if len(sel) > room:
+        sel = sel[np.sort(np.random.default_rng(0).choice(len(sel), room, replace=False))]
+    f = f[sel]
+    raw = np.ascontiguousarray(demods)[sel]
+    off = typ.bits.offset
+    if packed:
+        bits = np.unpackbits(raw[:, off:off + irdm.MAX_BITS // 8], axis=1)
+    else:
+        bits = raw[:, off:off + irdm.MAX_BITS]
+    out = {"burst_" + k: b[k].astype(np.float64) for k in b.dtype.names}
+    out.update({"frame_" + k: f[k].astype(np.float64) for k in f.dtype.names if k != "timestamp"})
+    out["frame_timestamp"] = (f["timestamp"] - np.uint64(t0_ns)).astype(np.float64)
+    out["frame_bits"] = bits.astype(np.float32)
+    if not packed:
+        off = typ.llr.offset
+        out["frame_llr"] = np.ascontiguousarray(raw[:, off:off + 4 * irdm.MAX_BITS]).view(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return len(b), len(f)
 
 
 def bench_time_shard(args, torch, dist, irdm, rank, world, local, device, cdev, backend):
@@ -482,7 +532,14 @@ def main():
                     help="N = 1, cf32: a second, separately timed run of this script with chunks of twice the samples (same scene "
                          "generator and density, same options), N steps, parity-checked on its first chunk -> `chunk_x2` on the "
                          "JSON line (never `value`); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="--shard streams: after the timed steps, write what the timed path returned for its last chunk (the "
+                         "bursts that start in it and their demodulated frames, rank 0) as DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.shard != "streams":
+        ap.error("--dump-outputs needs --shard streams")
 
     import torch
     import torch.distributed as dist
@@ -609,6 +666,8 @@ def main():
     # look-ahead, the other chunks' stages running beside them): what parity_checked compares with the oracle run over a
     # two-chunk prefix of the stream.  Everything the context emits during the warm-up is kept (records leave in stream order).
     head = {"bursts": [], "demods": [], "open": True}
+    # what the last timed step and the drain behind it returned (--dump-outputs)
+    last = {"bursts": [], "demods": []}
 
     def step(record):
         ta = time.perf_counter()
@@ -621,6 +680,7 @@ def main():
         if head["open"] and not record:
             head["bursts"].append(bursts.copy()); head["demods"].append(demods.copy())
         if record:
+            last["bursts"], last["demods"] = [bursts], [demods]
             host["feed_call"] += (tb - ta) * 1e3
             host["poll"] += (tc - tb) * 1e3
         if world > 1:
@@ -669,6 +729,7 @@ def main():
         tb_ = pipe.poll_bursts_raw()
         pipe.drop_frames()
         tail = poll_demods()
+        last["bursts"].append(tb_); last["demods"].append(tail)
         totals["demods"] += len(tail)
         totals["bursts"] += len(tb_)
         if world > 1:
@@ -701,6 +762,12 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+
+    if args.dump_outputs and rank == 0:
+        lo = (args.warmup + args.steps - 1) * n          # the last timed chunk's samples in the stream
+        nbd, nfd = dump_outputs(args.dump_outputs, irdm, np.concatenate(last["bursts"]), np.concatenate(last["demods"]),
+                                packed, lo, lo + n, pipe.cfg.start_time_ns)
+        print("bench: %d bursts, %d frames of chunk %d -> %s" % (nbd, nfd, lo // n, args.dump_outputs), file=sys.stderr)
 
     ms = {k: v / K for k, v in stage.items()}
     value = world * n * K / dt / 1e6

@@ -12,6 +12,7 @@ import pytest
 
 import orc
 import siggen
+from refpins import refpins  # noqa: F401  (fixture)
 
 F = C.POINTER(C.c_float)
 
@@ -24,7 +25,8 @@ def crand(rng, n, scale=1.0):
     return ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * scale).astype(np.complex64)
 
 
-def test_fir_ccf_and_dec(oracle, reflib):
+def test_fir_ccf_and_dec(oracle, refpins):
+    R = refpins.lib
     rng = np.random.default_rng(1)
     taps = rng.standard_normal(801).astype(np.float32)
     x = crand(rng, 801 + 40 * 300)
@@ -33,97 +35,113 @@ def test_fir_ccf_and_dec(oracle, reflib):
         b = np.zeros(n_out, np.complex64)
         if dec == 1:
             oracle.orc_fir_ccf(fp(taps), 801, fp(x), fp(a), n_out)
-            reflib.generic_fir_ccf(fp(taps), 801, fp(x), fp(b), n_out)
+            if R:
+                R.generic_fir_ccf(fp(taps), 801, fp(x), fp(b), n_out)
         else:
             oracle.orc_fir_ccf_dec(fp(taps), 801, fp(x), fp(a), n_out, dec)
-            reflib.generic_fir_ccf_dec(fp(taps), 801, fp(x), fp(b), n_out, dec)
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+            if R:
+                R.generic_fir_ccf_dec(fp(taps), 801, fp(x), fp(b), n_out, dec)
+        refpins.same("fir_ccf_dec/%d" % dec, a, b)
 
 
-def test_small_kernels(oracle, reflib):
+def test_small_kernels(oracle, refpins):
+    R = refpins.lib
     rng = np.random.default_rng(2)
     n = 8192
     x = crand(rng, n, 0.01)
     w = rng.random(n).astype(np.float32)
     a = np.zeros(n, np.complex64); b = np.zeros(n, np.complex64)
     oracle.orc_window_cf(fp(x), fp(w), fp(a), n)
-    reflib.generic_window_cf(fp(x), fp(w), fp(b), n)
-    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    if R:
+        R.generic_window_cf(fp(x), fp(w), fp(b), n)
+    refpins.same("window_cf", a, b)
 
     ma = np.zeros(n, np.float32); mb = np.zeros(n, np.float32)
     oracle.orc_fftshift_mag(fp(x), fp(ma), n)
-    reflib.generic_fftshift_mag(fp(x), fp(mb), n)
-    assert np.array_equal(ma.view(np.uint32), mb.view(np.uint32))
+    if R:
+        R.generic_fftshift_mag(fp(x), fp(mb), n)
+    refpins.same("fftshift_mag", ma, mb)
 
     s1 = rng.random(n).astype(np.float32) * 3; s2 = s1.copy()
     old = rng.random(n).astype(np.float32); new = rng.random(n).astype(np.float32)
     oracle.orc_baseline_update(fp(s1), fp(old), fp(new), n)
-    reflib.generic_baseline_update(fp(s2), fp(old), fp(new), n)
-    assert np.array_equal(s1.view(np.uint32), s2.view(np.uint32))
+    if R:
+        R.generic_baseline_update(fp(s2), fp(old), fp(new), n)
+    refpins.same("baseline_update", s1, s2)
 
     base = rng.random(n).astype(np.float32); base[::17] = 0; base[5] = -1
     ra = np.zeros(n, np.float32); rb = np.zeros(n, np.float32)
     oracle.orc_relative_mag(fp(new), fp(base), fp(ra), n)
-    reflib.generic_relative_mag(fp(new), fp(base), fp(rb), n)
-    assert np.array_equal(ra.view(np.uint32), rb.view(np.uint32))
+    if R:
+        R.generic_relative_mag(fp(new), fp(base), fp(rb), n)
+    refpins.same("relative_mag", ra, rb)
 
     i8 = rng.integers(-128, 128, 2 * n, dtype=np.int8)
     ca = np.zeros(n, np.complex64); cb = np.zeros(n, np.complex64)
     oracle.orc_convert_i8_cf(i8.ctypes.data_as(C.c_void_p), fp(ca), C.c_size_t(n))
-    reflib.generic_convert_i8_cf(i8.ctypes.data_as(C.c_void_p), fp(cb), C.c_size_t(n))
-    assert np.array_equal(ca.view(np.uint32), cb.view(np.uint32))
+    if R:
+        R.generic_convert_i8_cf(i8.ctypes.data_as(C.c_void_p), fp(cb), C.c_size_t(n))
+    refpins.same("convert_i8_cf", ca, cb)
 
     oracle.orc_mag_squared(fp(x), fp(ma), n)
-    reflib.generic_mag_squared(fp(x), fp(mb), n)
-    assert np.array_equal(ma.view(np.uint32), mb.view(np.uint32))
-    assert oracle.orc_max_float(fp(ma), n) == reflib.generic_max_float(fp(mb), n)
+    if R:
+        R.generic_mag_squared(fp(x), fp(mb), n)
+    refpins.same("mag_squared", ma, mb)
+    refpins.same("max_float", np.float32(oracle.orc_max_float(fp(ma), n)), np.float32(R.generic_max_float(fp(mb), n)) if R else None)
 
     w256 = rng.random(256).astype(np.float32)
     qa = np.zeros(256, np.complex64); qb = np.zeros(256, np.complex64)
     oracle.orc_csquare_window(fp(x), fp(w256), fp(qa), 256)
-    reflib.generic_csquare_window(fp(x), fp(w256), fp(qb), 256)
-    assert np.array_equal(qa.view(np.uint32), qb.view(np.uint32))
+    if R:
+        R.generic_csquare_window(fp(x), fp(w256), fp(qb), 256)
+    refpins.same("csquare_window", qa, qb)
 
     t = rng.random(20).astype(np.float32); r = rng.random(1000).astype(np.float32)
     fa = np.zeros(900, np.float32); fb = np.zeros(900, np.float32)
     oracle.orc_fir_fff(fp(t), 20, fp(r), fp(fa), 900)
-    reflib.generic_fir_fff(fp(t), 20, fp(r), fp(fb), 900)
-    assert np.array_equal(fa.view(np.uint32), fb.view(np.uint32))
+    if R:
+        R.generic_fir_fff(fp(t), 20, fp(r), fp(fb), 900)
+    refpins.same("fir_fff", fa, fb)
 
 
-def test_windows_and_taps(oracle, reflib):
+def test_windows_and_taps(oracle, refpins):
+    R = refpins.lib
     libc = C.CDLL(None)
     libc.free.argtypes = [C.c_void_p]
     for n in (256, 2048, 8192, 16384):
         a = np.zeros(n, np.float32); b = np.zeros(n, np.float32)
         oracle.orc_blackman_window(fp(a), n)
-        reflib.blackman_window(fp(b), n)
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+        if R:
+            R.blackman_window(fp(b), n)
+        refpins.same("blackman_window/%d" % n, a, b)
 
-    def cmp(ours, theirs_ptr, nt):
-        theirs = np.ctypeslib.as_array(theirs_ptr, (nt.value,)).copy()
-        libc.free(C.cast(theirs_ptr, C.c_void_p))
-        assert len(ours) == nt.value
-        assert np.array_equal(ours.view(np.uint32), theirs.view(np.uint32))
+    def cmp(key, ours, design, *args):
+        theirs = None
+        if R:
+            nt = C.c_int()
+            theirs_ptr = getattr(R, design)(C.byref(nt), *args)
+            theirs = np.ctypeslib.as_array(theirs_ptr, (nt.value,)).copy()
+            libc.free(C.cast(theirs_ptr, C.c_void_p))
+        refpins.same(key, ours, theirs)      # (arrays of different lengths differ)
 
     out = np.zeros(2048, np.float32)
-    nt = C.c_int()
     n = oracle.orc_lpf_taps(fp(out), 2048, C.c_float(1.0), C.c_float(1e7), C.c_float(1e5), C.c_float(5e4))
     assert n == 801
-    cmp(out[:n].copy(), reflib.lpf_taps(C.byref(nt), 1.0, 1e7, 1e5, 5e4), nt)
+    cmp("lpf_taps/detector", out[:n].copy(), "lpf_taps", 1.0, 1e7, 1e5, 5e4)
     n = oracle.orc_lpf_taps(fp(out), 2048, C.c_float(1.0), C.c_float(250000.0), C.c_float(20000.0), C.c_float(40000.0))
     assert n == 25
-    cmp(out[:n].copy(), reflib.lpf_taps(C.byref(nt), 1.0, 250000.0, 20000.0, 40000.0), nt)
+    cmp("lpf_taps/250k", out[:n].copy(), "lpf_taps", 1.0, 250000.0, 20000.0, 40000.0)
     n = oracle.orc_rrc_taps(fp(out), 2048, C.c_float(1.0), C.c_float(250000.0), C.c_float(25000.0), C.c_float(0.4), 51)
-    cmp(out[:n].copy(), reflib.rrc_taps(C.byref(nt), 1.0, 250000.0, 25000.0, 0.4, 51), nt)
+    cmp("rrc_taps", out[:n].copy(), "rrc_taps", 1.0, 250000.0, 25000.0, 0.4, 51)
     n = oracle.orc_rc_taps(fp(out), 2048, C.c_float(250000.0), C.c_float(25000.0), C.c_float(0.4), 51)
-    cmp(out[:n].copy(), reflib.rc_taps(C.byref(nt), 250000.0, 25000.0, 0.4, 51), nt)
+    cmp("rc_taps", out[:n].copy(), "rc_taps", 250000.0, 25000.0, 0.4, 51)
     n = oracle.orc_box_taps(fp(out), 2048, 20)
-    cmp(out[:n].copy(), reflib.box_taps(C.byref(nt), 20), nt)
+    cmp("box_taps", out[:n].copy(), "box_taps", 20)
 
 
 @pytest.mark.parametrize("theta", [-2.3, -0.01, 0.4, 1.234])
-def test_rotator_recurrence(oracle, reflib, theta):
+def test_rotator_recurrence(oracle, refpins, theta):
+    R = refpins.lib
     rng = np.random.default_rng(3)
     n = 300000
     x = crand(rng, n, 0.05)
@@ -131,9 +149,9 @@ def test_rotator_recurrence(oracle, reflib, theta):
     pa = np.array([1, 0], np.float32); pb = pa.copy()
     a = np.zeros(n, np.complex64); b = np.zeros(n, np.complex64)
     oracle.orc_rotator_rotate_n(fp(pa), fp(inc), fp(a), fp(x), n)
-    reflib.ref_rotator_rotate_n(fp(pb), fp(inc), fp(b), fp(x), n)
-    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    assert np.array_equal(pa.view(np.uint32), pb.view(np.uint32))
+    if R:
+        R.ref_rotator_rotate_n(fp(pb), fp(inc), fp(b), fp(x), n)
+    refpins.same("rotator/%r" % theta, [a, pa], [b, pb])
 
 
 def _oracle_frames():
@@ -158,11 +176,14 @@ def _ref_demod(reflib, f):
 
 
 @pytest.mark.parametrize("gardner", [1, 0])
-def test_stage_c_matches_reference(oracle, reflib, gardner):
+def test_stage_c_matches_reference(oracle, refpins, gardner):
+    reflib = refpins.lib
     frames = _oracle_frames()
     assert len(frames) >= 6
-    reflib.ref_set_use_gardner(gardner)
+    if reflib:
+        reflib.ref_set_use_gardner(gardner)
     n_ok = 0
+    ours, theirs = [], []
     rng = np.random.default_rng(9)
     variants = []
     for f in frames:
@@ -178,25 +199,35 @@ def test_stage_c_matches_reference(oracle, reflib, gardner):
     for f in variants:
         d = orc.Demod()
         r_o = oracle.orc_qpsk_demod(C.byref(f), gardner, C.byref(d))
-        r = _ref_demod(reflib, f)
-        assert r_o == r[0]
+        # (what is compared: the verdict, and for an accepted frame the fields below, bit for bit)
+        ours.append((r_o, d.direction, d.confidence, np.float32(d.level), d.n_symbols, d.n_payload_symbols, d.n_bits,
+                     bytes(d.bits[:d.n_bits]), np.array(d.llr[:d.n_bits], np.float32), d.center_frequency)
+                    if r_o else (r_o,))
+        if reflib:
+            r = _ref_demod(reflib, f)
+            assert r_o == r[0]
+            theirs.append((r[0], r[1], r[2], np.float32(r[3])) + r[4:] if r[0] else (r[0],))
         if not r_o:
             continue
         n_ok += 1
-        assert (d.direction, d.confidence, d.n_symbols, d.n_payload_symbols, d.n_bits) == (r[1], r[2], r[4], r[5], r[6])
-        assert np.float32(d.level).view(np.uint32) == np.float32(r[3]).view(np.uint32)
-        assert bytes(d.bits[:d.n_bits]) == r[7]
-        assert np.array_equal(np.array(d.llr[:d.n_bits], np.float32).view(np.uint32), r[8].view(np.uint32))
-        assert d.center_frequency == r[9]
-    reflib.ref_set_use_gardner(1)
+        if reflib:
+            assert (d.direction, d.confidence, d.n_symbols, d.n_payload_symbols, d.n_bits) == (r[1], r[2], r[4], r[5], r[6])
+            assert np.float32(d.level).view(np.uint32) == np.float32(r[3]).view(np.uint32)
+            assert bytes(d.bits[:d.n_bits]) == r[7]
+            assert np.array_equal(np.array(d.llr[:d.n_bits], np.float32).view(np.uint32), r[8].view(np.uint32))
+            assert d.center_frequency == r[9]
+    if reflib:
+        reflib.ref_set_use_gardner(1)
+    refpins.same("qpsk_demod/gardner%d" % gardner, ours, theirs)
     assert n_ok >= 8
 
 
-def test_fir_ccf_dec_avx2_order(oracle, reflib):
+def test_fir_ccf_dec_avx2_order(oracle, refpins):
     """orc_fir_ccf_dec_avx2 == the reference's avx2_fir_ccf_dec (simd_avx2.c:62-108, compiled in place with the
     reference's own flags: -std=c99 -O3 -mavx2 -mfma), bit for bit: four fused accumulators, horizontal sum, scalar tail.
     This is the decimating FIR the reference runs by default on x86 (simd_init) and the order the product's decimator
     follows with option fir_order 1."""
+    R = refpins.lib
     rng = np.random.default_rng(11)
     for ntaps in (801, 800, 803, 25):
         taps = np.zeros(ntaps + 8, np.float32)          # (the AVX2 kernel loads taps four at a time)
@@ -206,19 +237,22 @@ def test_fir_ccf_dec_avx2_order(oracle, reflib):
             a = np.zeros(n_out, np.complex64)
             b = np.zeros(n_out, np.complex64)
             oracle.orc_fir_ccf_dec_avx2(fp(taps), ntaps, fp(x), fp(a), n_out, dec)
-            reflib.avx2_fir_ccf_dec(fp(taps), ntaps, fp(x), fp(b), n_out, dec)
-            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (ntaps, dec)
+            if R:
+                R.avx2_fir_ccf_dec(fp(taps), ntaps, fp(x), fp(b), n_out, dec)
+            refpins.same("avx2_fir_ccf_dec/%d/%d" % (ntaps, dec), a, b)
             c = np.zeros(n_out, np.complex64)
             oracle.orc_fir_ccf_dec(fp(taps), ntaps, fp(x), fp(c), n_out, dec)
             assert not np.array_equal(a.view(np.uint32), c.view(np.uint32)) or ntaps < 100      # the two orders differ in rounding
 
 
-def test_avx2_forms_of_the_small_kernels(oracle, reflib):
+def test_avx2_forms_of_the_small_kernels(oracle, refpins):
     """The other dispatched kernels whose AVX2 form rounds differently (simd_avx2.c): fir_ccf (:28-55: outputs four at a
     time with fused multiply-adds, the last n % 4 generic), fir_fff (:115-138: eight at a time, the last n % 8 generic),
     fftshift_mag (:177-221) and mag_squared (:304-323): fma(re, re, im*im).  Each oracle restatement equals the
     reference's kernel bit for bit at lengths with and without a tail; the kernels whose two forms are the same
-    operations agree with EACH OTHER bit for bit (window_cf, csquare_window, baseline_update, relative_mag, max_float)."""
+    operations agree with EACH OTHER bit for bit (window_cf, csquare_window, baseline_update, relative_mag, max_float), and
+    with the oracle's."""
+    R = refpins.lib
     rng = np.random.default_rng(23)
     bits = lambda v: v.view(np.uint32)
     for ntaps in (25, 51, 20, 7):
@@ -227,54 +261,75 @@ def test_avx2_forms_of_the_small_kernels(oracle, reflib):
             x = crand(rng, n + ntaps + 8, scale=float(rng.uniform(0.01, 10.0)))
             a = np.zeros(max(n, 1), np.complex64); b = np.zeros(max(n, 1), np.complex64); c = np.zeros(max(n, 1), np.complex64)
             oracle.orc_fir_ccf_avx2(fp(taps), ntaps, fp(x), fp(a), n)
-            reflib.avx2_fir_ccf(fp(taps), ntaps, fp(x), fp(b), n)
-            assert np.array_equal(bits(a), bits(b)), ("fir_ccf", ntaps, n)
+            if R:
+                R.avx2_fir_ccf(fp(taps), ntaps, fp(x), fp(b), n)
+            refpins.same("avx2_fir_ccf/%d/%d" % (ntaps, n), a, b)
             oracle.orc_fir_ccf(fp(taps), ntaps, fp(x), fp(c), n)
             if n % 4:                                   # the tail is the generic form
                 assert np.array_equal(bits(a)[-2 * (n % 4):], bits(c)[-2 * (n % 4):])
             xr = rng.standard_normal(n + ntaps + 8).astype(np.float32)
             ar = np.zeros(max(n, 1), np.float32); br = np.zeros(max(n, 1), np.float32)
             oracle.orc_fir_fff_avx2(fp(taps), ntaps, fp(xr), fp(ar), n)
-            reflib.avx2_fir_fff(fp(taps), ntaps, fp(xr), fp(br), n)
-            assert np.array_equal(bits(ar), bits(br)), ("fir_fff", ntaps, n)
+            if R:
+                R.avx2_fir_fff(fp(taps), ntaps, fp(xr), fp(br), n)
+            refpins.same("avx2_fir_fff/%d/%d" % (ntaps, n), ar, br)
     differs = 0
     for n in (0, 1, 3, 4, 7, 8, 100, 4099):
         x = crand(rng, n + 8, scale=3.0)
         a = np.zeros(max(n, 1), np.float32); b = np.zeros(max(n, 1), np.float32); c = np.zeros(max(n, 1), np.float32)
         oracle.orc_mag_squared_avx2(fp(x), fp(a), n)
-        reflib.avx2_mag_squared(fp(x), fp(b), n)
+        if R:
+            R.avx2_mag_squared(fp(x), fp(b), n)
         oracle.orc_mag_squared(fp(x), fp(c), n)
-        assert np.array_equal(bits(a), bits(b)), ("mag_squared", n)
+        refpins.same("avx2_mag_squared/%d" % n, a, b)
         differs += int(not np.array_equal(bits(a), bits(c)))
     assert differs >= 2                                  # fused and separately rounded sums differ in the last bit
     for n in (4, 8, 12, 4096, 8192, 16384):
         x = crand(rng, n, scale=2.0)
         a = np.zeros(n, np.float32); b = np.zeros(n, np.float32)
         oracle.orc_fftshift_mag_avx2(fp(x), fp(a), n)
-        reflib.avx2_fftshift_mag(fp(x), fp(b), n)
-        assert np.array_equal(bits(a), bits(b)), ("fftshift_mag", n)
+        if R:
+            R.avx2_fftshift_mag(fp(x), fp(b), n)
+        refpins.same("avx2_fftshift_mag/%d" % n, a, b)
     # the same operations in both forms
     n = 1027
     x = crand(rng, n + 8, scale=2.0)
     w = rng.uniform(0.0, 1.0, n + 8).astype(np.float32)
+    def both_forms(key, ours, call, *args):
+        """the reference's generic and AVX2 forms of one kernel: the same bits, and the oracle's"""
+        theirs = None
+        if R:
+            theirs, t2 = np.zeros_like(ours), np.zeros_like(ours)
+            getattr(R, "generic_" + call)(*args, fp(theirs), n)
+            getattr(R, "avx2_" + call)(*args, fp(t2), n)
+            assert np.array_equal(bits(theirs), bits(t2)), call
+        refpins.same(key, ours, theirs)
+
     for name in ("window_cf", "csquare_window"):
-        a = np.zeros(n, np.complex64); b = np.zeros(n, np.complex64)
-        getattr(reflib, "generic_" + name)(fp(x), fp(w), fp(a), n)
-        getattr(reflib, "avx2_" + name)(fp(x), fp(w), fp(b), n)
-        assert np.array_equal(bits(a), bits(b)), name
+        a = np.zeros(n, np.complex64)
+        getattr(oracle, "orc_" + name)(fp(x), fp(w), fp(a), n)
+        both_forms("both_forms/" + name, a, name, fp(x), fp(w))
     s0 = rng.uniform(0, 100, n).astype(np.float32); old = rng.uniform(0, 1, n).astype(np.float32); new = rng.uniform(0, 1, n).astype(np.float32)
-    sa, sb = s0.copy(), s0.copy()
-    reflib.generic_baseline_update(fp(sa), fp(old), fp(new), n)
-    reflib.avx2_baseline_update(fp(sb), fp(old), fp(new), n)
-    assert np.array_equal(bits(sa), bits(sb))
+    sa = s0.copy()
+    oracle.orc_baseline_update(fp(sa), fp(old), fp(new), n)
+    theirs = None
+    if R:
+        theirs, sb = s0.copy(), s0.copy()
+        R.generic_baseline_update(fp(theirs), fp(old), fp(new), n)
+        R.avx2_baseline_update(fp(sb), fp(old), fp(new), n)
+        assert np.array_equal(bits(theirs), bits(sb))
+    refpins.same("both_forms/baseline_update", sa, theirs)
     base = s0.copy(); base[::7] = 0.0
-    ra = np.zeros(n, np.float32); rb = np.zeros(n, np.float32)
-    reflib.generic_relative_mag(fp(new), fp(base), fp(ra), n)
-    reflib.avx2_relative_mag(fp(new), fp(base), fp(rb), n)
-    assert np.array_equal(bits(ra), bits(rb))
-    reflib.generic_max_float.restype = C.c_float
-    reflib.avx2_max_float.restype = C.c_float
-    assert reflib.generic_max_float(fp(new), n) == reflib.avx2_max_float(fp(new), n)
+    ra = np.zeros(n, np.float32)
+    oracle.orc_relative_mag(fp(new), fp(base), fp(ra), n)
+    both_forms("both_forms/relative_mag", ra, "relative_mag", fp(new), fp(base))
+    theirs = None
+    if R:
+        R.generic_max_float.restype = C.c_float
+        R.avx2_max_float.restype = C.c_float
+        theirs = np.float32(R.generic_max_float(fp(new), n))
+        assert theirs == R.avx2_max_float(fp(new), n)
+    refpins.same("both_forms/max_float", np.float32(oracle.orc_max_float(fp(new), n)), theirs)
 
 
 def test_whole_stream_in_the_avx2_forms_differs_only_in_rounding(oracle):
@@ -302,16 +357,24 @@ def test_whole_stream_in_the_avx2_forms_differs_only_in_rounding(oracle):
     assert same < len(r0.frames)                          # ... but not the same bits
 
 
-def test_avx2_variant_differs_only_in_float_rounding(reflib):
+def test_avx2_variant_differs_only_in_float_rounding(oracle, refpins):
     """The reference's AVX2 path is NOT bit-identical to its scalar path: the oracle restates both forms of
     the decimating FIR (orc_fir_ccf_dec / orc_fir_ccf_dec_avx2) and pins each to its reference kernel."""
+    R = refpins.lib
     rng = np.random.default_rng(4)
     taps = rng.standard_normal(801).astype(np.float32)
     pad = np.zeros(808, np.float32); pad[:801] = taps
     x = crand(rng, 801 + 40 * 64)
     a = np.zeros(64, np.complex64); b = np.zeros(64, np.complex64)
-    reflib.generic_fir_ccf_dec(fp(pad), 801, fp(x), fp(a), 64, 40)
-    reflib.avx2_fir_ccf_dec(fp(pad), 801, fp(x), fp(b), 64, 40)
+    oracle.orc_fir_ccf_dec(fp(pad), 801, fp(x), fp(a), 64, 40)
+    oracle.orc_fir_ccf_dec_avx2(fp(pad), 801, fp(x), fp(b), 64, 40)
+    ra, rb = (np.zeros(64, np.complex64), np.zeros(64, np.complex64)) if R else (None, None)
+    if R:
+        R.generic_fir_ccf_dec(fp(pad), 801, fp(x), fp(ra), 64, 40)
+        R.avx2_fir_ccf_dec(fp(pad), 801, fp(x), fp(rb), 64, 40)
+        assert np.allclose(ra, rb, rtol=1e-4, atol=1e-4)
+    refpins.same("generic_vs_avx2/generic", a, ra)
+    refpins.same("generic_vs_avx2/avx2", b, rb)
     assert np.allclose(a, b, rtol=1e-4, atol=1e-4)
 
 
@@ -321,11 +384,13 @@ import numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
 import orc, irdm
 R = orc.ref()
-R.ref_frame_output_line.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_float, C.c_float, C.c_int, C.c_float,
+if R is not None:
+  R.ref_frame_output_line.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_float, C.c_float, C.c_int, C.c_float,
                                     C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_char_p, C.c_int]
 file_info = sys.argv[3]
 fi_keep = C.create_string_buffer(file_info.encode())      # frame_output_init keeps the POINTER (frame_output.c:101-104)
-R.ref_frame_output_init(fi_keep if file_info else None)
+if R is not None:
+  R.ref_frame_output_init(fi_keep if file_info else None)
 rng = np.random.default_rng(int(sys.argv[4]))
 out = []
 t = 1700000000 * 10**9 + int(rng.integers(0, 10**9))
@@ -348,6 +413,8 @@ for k in range(40):
     for i, b in enumerate(bits):
         d.bits[i] = int(b)
     demods.append(d)
+    if R is None:
+        continue
     buf = C.create_string_buffer(4096)
     n = R.ref_frame_output_line(d.id, d.timestamp, d.center_frequency, d.magnitude, d.noise, d.confidence, d.level,
                                 d.n_payload_symbols, d.n_bits, bits.ctypes.data_as(C.POINTER(C.c_uint8)), buf, 4096)
@@ -362,12 +429,12 @@ for d in demods:
     b = C.create_string_buffer(4096)
     orc.lib().orc_format_raw(C.byref(o), file_info.encode(), C.byref(t0), b, 4096)
     oracle.append(b.value.decode())
-print(json.dumps(dict(ref=out, ours=ours, oracle=oracle, batch=batch)))
+print(json.dumps(dict(ref=out if R is not None else None, ours=ours, oracle=oracle, batch=batch)))
 '''
 
 
 @pytest.mark.parametrize("file_info,seed", [("golden", 1), ("", 2)])
-def test_raw_line_printer_matches_frame_output_c(reflib, file_info, seed):
+def test_raw_line_printer_matches_frame_output_c(refpins, file_info, seed):
     """frame_output_print (frame_output.c:160-199, the reference's object code, stdout captured) vs the oracle's
     orc_format_raw vs the product's irdm_format_raw / _batch: byte-identical lines for random records, including the
     automatic "i-<t0>-t1" file info.  Runs in a child process: frame_output.c latches t0 and file_info in statics."""
@@ -381,7 +448,9 @@ def test_raw_line_printer_matches_frame_output_c(reflib, file_info, seed):
                        capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(r.stdout.strip().splitlines()[-1])
-    assert len(d["ref"]) == 40
-    assert d["ref"] == d["oracle"] == d["ours"]
-    assert d["batch"] == "".join(d["ref"])
-    assert d["ref"][0].startswith("RAW: golden " if file_info else "RAW: i-17000000")
+    assert (d["ref"] is None) == (refpins.lib is None)
+    refpins.same("frame_output_line/%s/%d" % (file_info, seed), d["oracle"], d["ref"])
+    assert len(d["oracle"]) == 40
+    assert d["oracle"] == d["ours"]
+    assert d["batch"] == "".join(d["oracle"])
+    assert d["oracle"][0].startswith("RAW: golden " if file_info else "RAW: i-17000000")

@@ -18,6 +18,7 @@ import pytest
 
 import irdm
 import siggen
+from refpins import refpins  # noqa: F401  (fixture)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -72,13 +73,18 @@ def _compat_layouts():
         return out
 
 
-def test_golden_layouts_are_the_reference_headers(reflib):
-    """(authoring container) the committed table is what the reference's headers give here"""
-    ref = _ref_layouts(reflib)
-    assert len(ref) >= 34
-    if os.environ.get("IRDM_WRITE_GOLDEN") == "1":
-        json.dump(ref, open(GOLDEN, "w"), indent=1, sort_keys=True)
-    assert json.load(open(GOLDEN)) == ref
+def test_golden_layouts_are_the_reference_headers(refpins):
+    """the committed table is what the reference's headers give (read out of oracle/_ref where it is built)"""
+    ref = None
+    if refpins.lib:
+        ref = _ref_layouts(refpins.lib)
+        assert len(ref) >= 34
+        if os.environ.get("IRDM_WRITE_GOLDEN") == "1":
+            json.dump(ref, open(GOLDEN, "w"), indent=1, sort_keys=True)
+        assert json.load(open(GOLDEN)) == ref
+    table = json.load(open(GOLDEN))
+    assert len(table) >= 34
+    refpins.same("layouts", sorted(table.items()), sorted(ref.items()) if ref else None)
 
 
 def test_compat_header_layouts_equal_the_reference():
@@ -100,12 +106,9 @@ def _frame(uplink, spoil, seed):
     return np.ascontiguousarray(x)
 
 
-@pytest.mark.parametrize("case", ["downlink", "uplink", "uw_fails"])
-def test_save_bursts_file_pair_is_the_reference(reflib, case, tmp_path):
-    x = _frame(case == "uplink", case == "uw_fails", seed={"downlink": 1, "uplink": 2, "uw_fails": 3}[case])
-    given_dir = 2 if case == "uplink" else 1
-    args = dict(id=730, ts=1700000000123456789, cf=1626270833.0 + 0.4, mag=23.456, noise=-112.345, uw=3.21)
-    ref_dir, our_dir = str(tmp_path / "ref"), str(tmp_path / "ours")
+def _ref_save_burst(reflib, x, given_dir, args, ref_dir):
+    """the reference's qpsk_demod on the frame with save_bursts_dir set: the file pair lands in ref_dir; returns its verdict
+    and the direction it settled on"""
     reflib.ref_set_save_bursts_dir.argtypes = [C.c_char_p]
     reflib.ref_qpsk_demod_save.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_float, C.c_float, C.c_int, C.c_double, C.c_uint64,
                                            C.c_uint64, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_int)]
@@ -117,19 +120,39 @@ def test_save_bursts_file_pair_is_the_reference(reflib, case, tmp_path):
                                         args["cf"], args["id"], args["ts"], args["mag"], args["noise"], args["uw"], C.byref(left))
     finally:
         reflib.ref_set_save_bursts_dir(None)
-    assert ok == (0 if case == "uw_fails" else 1)
-    assert left.value == {"downlink": 1, "uplink": 2, "uw_fails": 0}[case]
+    return ok, left.value
+
+
+@pytest.mark.parametrize("case", ["downlink", "uplink", "uw_fails"])
+def test_save_bursts_file_pair_is_the_reference(refpins, case, tmp_path):
+    x = _frame(case == "uplink", case == "uw_fails", seed={"downlink": 1, "uplink": 2, "uw_fails": 3}[case])
+    given_dir = 2 if case == "uplink" else 1
+    args = dict(id=730, ts=1700000000123456789, cf=1626270833.0 + 0.4, mag=23.456, noise=-112.345, uw=3.21)
+    ref_dir, our_dir = str(tmp_path / "ref"), str(tmp_path / "ours")
+    reflib = refpins.lib
+    # the reference's verdict and the direction its qpsk_demod settles on (the file pair's name and .meta carry it)
+    want = (0 if case == "uw_fails" else 1, {"downlink": 1, "uplink": 2, "uw_fails": 0}[case])
+    if reflib:
+        assert _ref_save_burst(reflib, x, given_dir, args, ref_dir) == want
+    ok, left = want
     info = irdm.FrameInfo()
     info.id, info.timestamp, info.center_frequency = args["id"], args["ts"], args["cf"]
     info.sample_rate, info.samples_per_symbol = 250000.0, 10.0
     info.direction, info.magnitude, info.noise, info.uw_start = given_dir, args["mag"], args["noise"], args["uw"]
     info.num_samples, info.drop_reason = len(x), 0
-    info.demod_ok = 0 if case == "uw_fails" else 1
-    info.demod_direction = left.value              # (what the pipeline reports in irdm_frame_info_t.demod_direction, qpsk_demod.c:444)
+    info.demod_ok = ok
+    info.demod_direction = left              # (what the pipeline reports in irdm_frame_info_t.demod_direction, qpsk_demod.c:444)
     assert irdm.save_burst(info, x.view(np.float32), our_dir) == 0
-    ref_files, our_files = sorted(os.listdir(ref_dir)), sorted(os.listdir(our_dir))
-    assert ref_files == our_files and len(ref_files) == 2, (ref_files, our_files)
-    for f in ref_files:
-        assert open(os.path.join(ref_dir, f), "rb").read() == open(os.path.join(our_dir, f), "rb").read(), f
+    our_files = sorted(os.listdir(our_dir))
+    assert len(our_files) == 2, our_files
+    if reflib:
+        ref_files = sorted(os.listdir(ref_dir))
+        assert ref_files == our_files, (ref_files, our_files)
+        for f in ref_files:
+            assert open(os.path.join(ref_dir, f), "rb").read() == open(os.path.join(our_dir, f), "rb").read(), f
+
+    def pair(d):
+        return [(f, open(os.path.join(d, f), "rb").read()) for f in sorted(os.listdir(d))]
+    refpins.same("save_burst/" + case, pair(our_dir), pair(ref_dir) if reflib else None)
     meta = open(os.path.join(our_dir, [f for f in our_files if f.endswith(".meta")][0])).read()
     assert "direction: %s\n" % {"downlink": "DL", "uplink": "UL", "uw_fails": "UN"}[case] in meta
