@@ -210,6 +210,23 @@ typedef struct {
     int32_t pad;
 } irdm_ida_t;
 
+/* ida_decode()'s result for one frame of the packed record path in 88 bytes (option "parsed_records" 1): the fields
+ * irdm_ida_t takes from the decoder; the frame's own (direction, timestamp, levels, ...) are in the irdm_demod_packed_t
+ * it belongs to.  bch_stream holds the first 256 bits of the decoded stream 8 per byte, MSB first (bit i is
+ * (bch_stream[i / 8] >> (7 - i % 8)) & 1); bch_len counts all of them, as ida_burst_t.bch_len does.
+ * irdm_ida_unpack turns the pair into the irdm_ida_t the "decode_ida" path returns. */
+typedef struct {
+    int32_t ok;                /* ida_decode()'s return value; every other field is 0 when it is 0 */
+    uint32_t lcw3_val;
+    uint8_t ft, lcw_ft, lcw_code, ec_lcw;
+    uint8_t da_ctr, da_len, cont, crc_ok;
+    uint16_t stored_crc, computed_crc;
+    uint8_t fixederrs, payload_len;
+    uint16_t bch_len;
+    uint8_t payload[32];
+    uint8_t bch_stream[32];
+} irdm_ida_packed_t;
+
 /* option "chunk_marks" 1: one mark per batch of records a context pushes to its queues -- the chunk they belong to (chunks
  * counted from 0 in the order fed) and how many records each queue received, in queue order.  A chunk without bursts
  * leaves no mark; a chunk with more bursts than a batch holds leaves several, one after the other. */
@@ -290,6 +307,8 @@ int irdm_poll_bursts(irdm_pipeline_t *p, irdm_burst_t *out, int max);
 int irdm_poll_frames(irdm_pipeline_t *p, irdm_frame_info_t *out, float *samples_out /* max*2*4440 or NULL */, int max);
 int irdm_poll_demods(irdm_pipeline_t *p, irdm_demod_t *out, int max);
 int irdm_poll_demods_packed(irdm_pipeline_t *p, irdm_demod_packed_t *out, int max);   /* option "packed_records" 1 */
+/* option "parsed_records" 1: exactly one record per irdm_poll_demods_packed record, in the same order */
+int irdm_poll_ida_packed(irdm_pipeline_t *p, irdm_ida_packed_t *out, int max);
 
 /* "tagged N bursts total" (burst_detect.c:350-351) and stat_sample_count (main.c:199) */
 uint64_t irdm_tagged_bursts(const irdm_pipeline_t *p);
@@ -443,6 +462,7 @@ int irdm_group_poll_demods(irdm_group_t *g, irdm_demod_t *out, int max);
 int irdm_group_poll_demods_packed(irdm_group_t *g, irdm_demod_packed_t *out, int max);
 int irdm_group_poll_decoded(irdm_group_t *g, irdm_decoded_t *out, int max);
 int irdm_group_poll_ida(irdm_group_t *g, irdm_ida_t *out, int max);
+int irdm_group_poll_ida_packed(irdm_group_t *g, irdm_ida_packed_t *out, int max);   /* option "parsed_records" 1 */
 /* what the group rests on in a single context: the marks (option "chunk_marks") and the number of chunks whose records
  * are all in the queues */
 int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max);
@@ -456,6 +476,11 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *   "packed_records"      0/1, default 0: 1 = only burst records and compact frame records (irdm_poll_demods_packed: what
  *                         frame_output_print reads, hard bits 8 per byte, no LLRs), written to pinned memory by the chain's
  *                         last kernel
+ *   "parsed_records"      0/1, default 0: 1 = "packed_records", and ida_decode() (LCW, BCH(31,20) with Chase on the LLRs,
+ *                         CRC) of every frame on the device, behind the demodulator, on its bits and LLRs where it leaves
+ *                         them: irdm_poll_ida_packed returns one irdm_ida_packed_t per compact frame record, written to
+ *                         pinned memory by that kernel.  With "decode_frames", "decode_ida" or "keep_frame_samples" the
+ *                         chain is on the full-record path and neither kind of compact record is queued.
  *   "chunk_marks"         0/1, default 0: see irdm_chunk_mark_t (what a group merges its members' records with)
  *   "decode_frames" / "decode_ida"   0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
@@ -528,6 +553,19 @@ long long irdm_format_raw_batch(const irdm_demod_t *f, int n, const char *file_i
 int irdm_format_raw_packed(const irdm_demod_packed_t *f, const char *file_info, uint64_t *t0_io, char *buf, size_t cap);
 long long irdm_format_raw_packed_batch(const irdm_demod_packed_t *f, int n, const char *file_info, uint64_t *t0_io,
                                        char *buf, size_t cap);
+
+/* 3b. IDA line (frame_output.c:203-361, --parsed)                      */
+/* ------------------------------------------------------------------ */
+/* The irdm_ida_t the "decode_ida" path makes of the same frame (lcw_header included) from a compact pair. */
+void irdm_ida_unpack(const irdm_ida_packed_t *ida, const irdm_demod_packed_t *f, irdm_ida_t *out);
+/* frame_output_print_ida's line for a decoded burst (b->ok != 0): "IDA: p-<t0 s> ..." whatever the file info.  t0_io is
+ * shared with irdm_format_raw*, as the reference's one ensure_initialized is.  bits past the 256 bch_stream keeps are not
+ * printed (the reference reads past the array there).  Returns the line length incl. '\n', or -1. */
+int irdm_format_ida(const irdm_ida_t *b, uint64_t *t0_io, char *buf, size_t cap);
+/* --parsed: per frame the IDA line where idas[i].ok, the RAW line otherwise (main.c:322-331), concatenated.
+ * cap >= n * IRDM_RAW_LINE_MAX always suffices.  Returns the total length or -1. */
+long long irdm_format_parsed_packed_batch(const irdm_demod_packed_t *f, const irdm_ida_packed_t *idas, int n,
+                                          const char *file_info, uint64_t *t0_io, char *buf, size_t cap);
 
 /* --save-bursts (qpsk_demod.c:339-389): writes <dir>/<timestamp>_<freq>_<id>_<DL|UL|UN>.cf32 (the frame's cf32 samples at
  * 250 kHz) and the matching .meta text file for one downmixed frame (info->drop_reason == 0), creating dir if needed.

@@ -1,5 +1,6 @@
 // api.cpp -- options and statistics of a context, the kernel clock, the RAW line printer (frame_output.c:160-199) and the
 // --save-bursts file pair (qpsk_demod.c:339-389).
+#include <stdarg.h>
 #include "pipeline.hpp"
 
 namespace irdmh {
@@ -10,6 +11,7 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     // ---- what a caller chooses (include/irdm_hip.h documents every key) ----
     if (!strcmp(key, "keep_frame_samples")) { p->keep_frame_samples = value; return 0; }
     if (!strcmp(key, "packed_records")) { p->packed_records = value; return 0; }
+    if (!strcmp(key, "parsed_records")) { p->parsed_records = value; return 0; }
     if (!strcmp(key, "chunk_marks")) { p->chunk_marks = value ? 1 : 0; if (!value) p->q_marks.clear(); return 0; }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
@@ -205,6 +207,151 @@ extern "C" long long irdm_format_raw_packed_batch(const irdm_demod_packed_t *f, 
     size_t pos = 0;
     for (int i = 0; i < n; i++) {
         const int len = irdm_format_raw_packed(&f[i], file_info, t0_io, buf + pos, cap - pos);
+        if (len < 0) return -1;
+        pos += (size_t)len;
+    }
+    return (long long)pos;
+}
+
+// ===========================================================================
+// 3b. IDA line (frame_output.c:203-361, --parsed)
+// ===========================================================================
+extern "C" void irdm_ida_unpack(const irdm_ida_packed_t *ida, const irdm_demod_packed_t *f, irdm_ida_t *out)
+{
+    if (!ida || !f || !out) return;
+    // the IdaOut the decode_ida path would have, then its finish_ida with the frame fields that path reads
+    IdaOut d;
+    memset(&d, 0, sizeof(d));
+    d.ok = ida->ok;
+    d.ft = ida->ft; d.lcw_ft = ida->lcw_ft; d.lcw_code = ida->lcw_code; d.ec_lcw = ida->ec_lcw;
+    d.lcw3_val = ida->lcw3_val;
+    d.da_ctr = ida->da_ctr; d.da_len = ida->da_len; d.cont = ida->cont; d.crc_ok = ida->crc_ok;
+    d.stored_crc = ida->stored_crc; d.computed_crc = ida->computed_crc;
+    d.fixederrs = ida->fixederrs; d.payload_len = ida->payload_len; d.bch_len = ida->bch_len;
+    memcpy(d.payload, ida->payload, sizeof(d.payload));
+    for (int i = 0; i < 256; i++) d.bch_stream[i] = (uint8_t)((ida->bch_stream[i >> 3] >> (7 - (i & 7))) & 1);
+    irdm_demod_t fr;
+    memset(&fr, 0, offsetof(irdm_demod_t, bits));
+    fr.id = f->id;
+    fr.direction = f->direction;
+    fr.timestamp = f->timestamp;
+    fr.center_frequency = f->center_frequency;
+    fr.magnitude = f->magnitude;
+    fr.noise = f->noise;
+    fr.level = f->level;
+    fr.confidence = f->confidence;
+    fr.n_payload_symbols = f->n_payload_symbols;
+    *out = finish_ida(d, fr);
+}
+
+namespace {
+
+// an snprintf-style appender that fails once the line does not fit
+struct LineBuf {
+    char *buf;
+    size_t cap, pos = 0;
+    bool bad = false;
+    void printf(const char *fmt, ...) __attribute__((format(printf, 2, 3)))
+    {
+        if (bad) return;
+        va_list ap;
+        va_start(ap, fmt);
+        const int n = vsnprintf(buf + pos, cap - pos, fmt, ap);
+        va_end(ap);
+        if (n < 0 || (size_t)n >= cap - pos) bad = true;
+        else pos += (size_t)n;
+    }
+    void put(char c)
+    {
+        if (bad || pos + 1 >= cap) { bad = true; return; }
+        buf[pos++] = c;
+        buf[pos] = 0;
+    }
+};
+
+}  // namespace
+
+extern "C" int irdm_format_ida(const irdm_ida_t *b, uint64_t *t0_io, char *buf, size_t cap)
+{
+    if (!b || !t0_io || !buf || cap == 0) return -1;
+    if (*t0_io == 0) *t0_io = (b->timestamp / 1000000000ULL) * 1000000000ULL;
+    const uint64_t t0 = *t0_io;
+    LineBuf o{ buf, cap };
+    buf[0] = 0;
+    char parsed_info[64];
+    snprintf(parsed_info, sizeof(parsed_info), "p-%llu", (unsigned long long)(t0 / 1000000000ULL));
+    const double ts_ms = (double)(b->timestamp - t0) / 1000000.0;
+    const int freq_hz = (int)(b->frequency + 0.5);
+    const double leveldb = (b->level > 0) ? 20.0 * log10(b->level) : -99.99;
+    const double noise = b->noise, snr = b->magnitude;
+    const char *dir = b->direction == 2 ? "UL" : "DL";                  // DIR_UPLINK
+    const int syms = b->n_symbols < 0 ? 0 : b->n_symbols;
+    o.printf("IDA: %s %014.4f %010d %3d%% %06.2f|%07.2f|%05.2f %3d %s ", parsed_info, ts_ms, freq_hz, b->confidence,
+             leveldb, noise, snr, syms, dir);
+    o.printf("%.*s", (int)sizeof(b->lcw_header), b->lcw_header);
+    const uint8_t *bs = b->bch_stream;
+    const int bch_len = b->bch_len;
+    if (bch_len >= 20) {
+        o.printf("%c%c%c", '0' + bs[0], '0' + bs[1], '0' + bs[2]);
+        o.printf(" cont=%c", '0' + bs[3]);
+        o.printf(" %c", '0' + bs[4]);
+        o.printf(" ctr=%c%c%c", '0' + bs[5], '0' + bs[6], '0' + bs[7]);
+        o.printf(" %c%c%c", '0' + bs[8], '0' + bs[9], '0' + bs[10]);
+        o.printf(" len=%02d", b->da_len);
+        o.printf(" 0:%c%c%c%c", '0' + bs[16], '0' + bs[17], '0' + bs[18], '0' + bs[19]);
+        o.printf(" [");
+        // the payload's tail behind da_len all zero: da_len bytes, else all 20 with '!' at da_len (:261-289)
+        bool all_zero = true;
+        if (b->da_len > 0)
+            for (int i = b->da_len + 1; i < 20; i++)
+                if (b->payload[i] != 0) { all_zero = false; break; }
+        const int nbytes = b->da_len > 0 && all_zero ? b->da_len : 20;
+        for (int i = 0; i < nbytes; i++) {
+            if (i > 0) o.put(nbytes == 20 && i == b->da_len && b->da_len > 0 && b->da_len < 20 ? '!' : '.');
+            o.printf("%02x", b->payload[i]);
+        }
+        o.printf("]");
+        for (int i = nbytes * 3; i < 60; i++) o.put(' ');               // hex + ']' padded to 60 columns
+        if (b->da_len > 0) {
+            o.printf(" %04x/%04x", b->stored_crc, b->computed_crc);
+            o.printf(b->crc_ok ? " CRC:OK" : " CRC:no");
+        } else {
+            o.printf("  ---   ");
+        }
+        const int shown = bch_len < 256 ? bch_len : 256;
+        if (bch_len > 9 * 20 + 16) {
+            o.put(' ');
+            for (int i = 9 * 20 + 16; i < shown; i++) o.put((char)('0' + bs[i]));
+        } else {
+            o.printf(" 0000");
+        }
+        if (b->da_len > 0 && bch_len >= 9 * 20) {
+            o.printf(" SBD: ");
+            for (int i = 0; i < 20; i++) {
+                int byte = 0;
+                for (int k = 0; k < 8; k++) byte = (byte << 1) | bs[1 * 20 + i * 8 + k];
+                o.put(byte >= 32 && byte < 127 ? (char)byte : '.');
+            }
+        }
+    }
+    o.put('\n');
+    return o.bad ? -1 : (int)o.pos;
+}
+
+extern "C" long long irdm_format_parsed_packed_batch(const irdm_demod_packed_t *f, const irdm_ida_packed_t *idas, int n,
+                                                     const char *file_info, uint64_t *t0_io, char *buf, size_t cap)
+{
+    if (!f || !idas || n < 0 || !t0_io || !buf) return -1;
+    size_t pos = 0;
+    for (int i = 0; i < n; i++) {
+        int len;
+        if (idas[i].ok) {
+            irdm_ida_t b;
+            irdm_ida_unpack(&idas[i], &f[i], &b);
+            len = irdm_format_ida(&b, t0_io, buf + pos, cap - pos);
+        } else {
+            len = irdm_format_raw_packed(&f[i], file_info, t0_io, buf + pos, cap - pos);
+        }
         if (len < 0) return -1;
         pos += (size_t)len;
     }

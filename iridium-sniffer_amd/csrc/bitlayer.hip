@@ -462,6 +462,269 @@ __global__ __launch_bounds__(64) void ida_decode_kernel(const DemodOut *__restri
     o.ok = 1;
 }
 
+// ---------------------------------------------------------------------------
+// ida_decode() on the packed record path (option parsed_records): the same decode as ida_decode_kernel, with LLRs, ONE
+// WAVEFRONT PER FRAME, its IdaPacked record written straight into pinned host memory.
+//   * LCW: lane k < 46 fetches LCW bit k, one ballot makes the three words; the three small BCH codes are wavefront-uniform.
+//   * payload: one 31-bit chunk per lane (at most 6 full 124-bit blocks of four chunks + 3 tail chunks), in the
+//     reference's order: the algebraic decode of every chunk at once; then the chunks that need Chase, in stream order,
+//     each with its 31 candidate flip masks on lanes 1..31 and the lowest mask that decodes winning (the serial loop's
+//     first success).  The five least reliable positions are chosen by the chunk's own lane, the serial partial
+//     selection sort literally (its swaps decide ties), over the chunk's LLRs in LDS.
+//   * the stream: which chunks the serial loop would have accepted (a prefix: it stops at the first failure or the
+//     512-bit cap) is wavefront-uniform arithmetic on a ballot; the accepted chunks' 20 data bits go to LDS, the header
+//     fields, payload bytes, CRC-CCITT (byte-wise table, the same remainder as the bit-serial form) and the packed
+//     stream come from there.
+// The frame's bits and LLRs are the DemodOut demod_par_kernel wrote on the device (keep_bits).  The record is complete in
+// pinned memory, behind a system-scope fence, when the stream reaches the host's synchronisation -- as demod_export's.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kIdaChunks = 28;                                          // 4 * (826 / 124) + the tail's (<= 3)
+
+struct Crc16Tab { uint16_t v[256]; };
+constexpr Crc16Tab make_crc16_tab()
+{
+    Crc16Tab t{};
+    for (int i = 0; i < 256; i++) {
+        unsigned c = (unsigned)i << 8;
+        for (int j = 0; j < 8; j++) c = (c & 0x8000u) ? ((c << 1) ^ 0x1021u) & 0xffffu : (c << 1) & 0xffffu;
+        t.v[i] = (uint16_t)c;
+    }
+    return t;
+}
+__constant__ Crc16Tab c_crc16 = make_crc16_tab();
+
+__device__ __forceinline__ bool da_table_ok(unsigned syn, const int2 *__restrict__ syn_da)
+{
+    return syn == 0 || (syn < 2048 && syn_da[syn].x >= 0);
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void ida_packed_kernel(const DemodOut *__restrict__ frames, int n_frames,
+                                                        const int2 *__restrict__ syn_da,
+                                                        const int2 *__restrict__ syn_l1, const int2 *__restrict__ syn_l2,
+                                                        const int2 *__restrict__ syn_l3, IdaPacked *__restrict__ hp_ida)
+{
+    __shared__ uint8_t s_bits[kMaxBits - 70];              // the payload's hard bits (behind access code and LCW)
+    __shared__ float s_llr[kMaxBits - 70];
+    __shared__ float s_cl[kIdaChunks][32];                  // a chunk's 31 LLRs in codeword order
+    __shared__ uint8_t s_pos[kIdaChunks][32];               // its selection sort's permutation
+    __shared__ uint8_t s_st[512];                           // the reference's bch_stream, one bit per byte
+    __shared__ uint8_t s_msg[64];                           // the CRC's message bytes
+    __shared__ __attribute__((aligned(4))) IdaPacked s_rec;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (b >= n_frames) return;
+    if (lane < 22) reinterpret_cast<uint32_t *>(&s_rec)[lane] = 0;
+    const DemodOut &f = frames[b];
+    const int ok_in = f.ok, ns_in = f.n_symbols, direction = f.direction;
+    const int n_bits = ok_in ? 2 * ns_in : 0;
+    // the record: ok = 0 for every frame ida_decode() rejects
+    auto emit = [&]() {
+        __syncthreads();
+        if (lane < 22) reinterpret_cast<uint32_t *>(hp_ida + b)[lane] = reinterpret_cast<const uint32_t *>(&s_rec)[lane];
+        __threadfence_system();
+    };
+    if (n_bits < 24 + 46 + 124 || n_bits > kMaxBits || (direction != 1 && direction != 2)) { emit(); return; }
+    const uint8_t *data = f.bits + 24;
+    const int data_len = n_bits - 24;
+
+    // ---- decode_lcw (:193-252)
+    const unsigned long long lm =
+        __builtin_amdgcn_ballot_w64(lane < 46 && (data[(c_lcw_perm[lane < 46 ? lane : 0] - 1) ^ 1] & 1));
+    unsigned v1 = 0, v2 = 0, v3 = 0;
+    for (int k = 0; k < 46; k++) {
+        const unsigned bk = (unsigned)(lm >> k) & 1u;
+        if (k < 7) v1 = (v1 << 1) | bk;
+        else if (k < 20) v2 = (v2 << 1) | bk;
+        else v3 = (v3 << 1) | bk;
+    }
+    v2 <<= 1;
+    const unsigned s1 = gf2_rem(29u, 5, v1), s2 = gf2_rem(465u, 9, v2), s3 = gf2_rem(41u, 6, v3);
+    bool lcw_ok = true;
+    if (s1 != 0) { if (s1 >= 16 || syn_l1[s1].x < 0) lcw_ok = false; else v1 ^= (unsigned)syn_l1[s1].y; }
+    if (lcw_ok && s2 != 0) { if (s2 >= 256 || syn_l2[s2].x < 0) lcw_ok = false; else v2 ^= (unsigned)syn_l2[s2].y; }
+    if (lcw_ok && s3 != 0) { if (s3 >= 32 || syn_l3[s3].x < 0) lcw_ok = false; else v3 ^= (unsigned)syn_l3[s3].y; }
+    const int ft = (int)(v1 >> 4) & 7;
+    const int payload_len = data_len - 46;
+    if (!lcw_ok || ft != 2 || payload_len < 124) { emit(); return; }
+    const int d2 = (int)(v2 >> 8) & 0x3F;
+
+    // ---- the payload's bits and LLRs into LDS
+    for (int i = lane; i < payload_len; i += 64) {
+        s_bits[i] = data[46 + i] & 1;
+        s_llr[i] = f.llr[24 + 46 + i];
+    }
+    const int n_full = payload_len / 124, remain = payload_len % 124;
+    const int ns = remain / 2, hl = ns - 1;
+    const int clen = 2 * hl > 128 ? 128 : 2 * hl;
+    const int n_tail = remain >= 4 && ns > 1 ? clen / 31 : 0;
+    const int n_chunks = 4 * n_full + n_tail;
+    __syncthreads();
+
+    // ---- descramble_payload (:276-377): every chunk's algebraic decode at once
+    const bool mine = lane < n_chunks;
+    unsigned cw = 0, cor = 0;
+    bool good = false, need = false;
+    int fixed = 0;
+    if (mine) {
+        const bool tail = lane >= 4 * n_full;
+        const int c = lane & 3, blk = lane >> 2;
+        const int off = (c == 0 ? 3 : c == 1 ? 1 : c == 2 ? 2 : 0) * 31;
+        const int base = tail ? n_full * 124 : blk * 124;
+        const int tpos = (lane - 4 * n_full) * 31;
+        for (int k = 0; k < 31; k++) {
+            int idx;
+            if (!tail) {
+                const int j = off + k;
+                idx = j < 62 ? deint_index(62, 0, j) : deint_index(62, 1, j - 62);
+            } else {
+                const int t = tpos + k;                                 // combined = h2[1..] then h1[1..]
+                idx = t < hl ? deint_index(ns, 1, t + 1) : deint_index(ns, 0, t - hl + 1);
+            }
+            cw = (cw << 1) | (unsigned)s_bits[base + idx];
+            s_cl[lane][k] = s_llr[base + idx];
+        }
+        const unsigned syn = gf2_rem(3545u, 12, cw);
+        if (syn == 0) { cor = cw; good = true; }
+        else if (syn < 2048 && syn_da[syn].x >= 0) { cor = cw ^ (unsigned)syn_da[syn].y; good = true; fixed = 1; }
+        else need = true;
+    }
+    // Chase (:107-172): the five least reliable positions, by the chunk's lane
+    unsigned fm[kChase] = { 0, 0, 0, 0, 0 };
+    if (need) {
+        for (int i = 0; i < 31; i++) s_pos[lane][i] = (uint8_t)i;
+        for (int i = 0; i < kChase; i++) {
+            int mi = i;
+            float mv = s_cl[lane][s_pos[lane][i]];
+            for (int j = i + 1; j < 31; j++) {
+                const float v = s_cl[lane][s_pos[lane][j]];
+                if (v < mv) { mv = v; mi = j; }
+            }
+            const uint8_t t = s_pos[lane][i]; s_pos[lane][i] = s_pos[lane][mi]; s_pos[lane][mi] = t;
+        }
+#pragma unroll
+        for (int i = 0; i < kChase; i++) fm[i] = 1u << (30 - s_pos[lane][i]);
+    }
+    // ... and its 31 candidates across the wavefront, chunk after chunk in stream order (behind the first chunk that
+    // fails, nothing is accepted: the loop stops there)
+    unsigned long long pend = __builtin_amdgcn_ballot_w64(need);
+    while (pend) {
+        const int c = __builtin_ctzll(pend);
+        pend &= pend - 1;
+        const unsigned cwc = (unsigned)__shfl((int)cw, c);
+        unsigned fl = cwc;
+#pragma unroll
+        for (int k = 0; k < kChase; k++) {
+            const unsigned fk = (unsigned)__shfl((int)fm[k], c);
+            if (lane & (1 << k)) fl ^= fk;
+        }
+        const unsigned syn = gf2_rem(3545u, 12, fl);
+        const bool hit = lane >= 1 && lane < 32 && da_table_ok(syn, syn_da);
+        const unsigned long long hits = __builtin_amdgcn_ballot_w64(hit);
+        if (!hits) break;
+        const int m = __builtin_ctzll(hits);
+        const unsigned res = (unsigned)__shfl((int)(syn == 0 ? fl : fl ^ (unsigned)syn_da[hit ? syn : 0].y), m);
+        if (lane == c) { cor = res; good = true; fixed = 1; }
+    }
+    // the chunks the serial loop accepts
+    const unsigned long long gm = __builtin_amdgcn_ballot_w64(mine && good);
+    const int max_bch = 512;
+    int len = 0;
+    bool failed = false;
+    for (int blk = 0; blk < n_full && !failed; blk++)
+        for (int c = 0; c < 4; c++) {
+            if (len + 20 > max_bch) break;
+            if (!((gm >> (4 * blk + c)) & 1)) { failed = true; break; }
+            len += 20;
+        }
+    if (!failed && remain >= 4 && len + 2 * (remain / 2 - 1) <= max_bch && ns > 1 && len + 20 <= max_bch)
+        for (int t = 0; t < n_tail && len + 20 <= max_bch; t++) {
+            if (!((gm >> (4 * n_full + t)) & 1)) break;
+            len += 20;
+        }
+    const int n_acc = len / 20;
+    const unsigned long long acc = n_acc >= 64 ? ~0ull : (1ull << n_acc) - 1;
+    const int fixederrs = __popcll(__builtin_amdgcn_ballot_w64(fixed != 0) & acc);
+    if (len < 196) { emit(); return; }                                  // :577-578
+    if (lane < n_acc) {
+        const unsigned d = (cor >> 11) & 0xfffffu;
+        for (int i = 0; i < 20; i++) s_st[20 * lane + i] = (uint8_t)((d >> (19 - i)) & 1u);
+    }
+    __syncthreads();
+
+    // ---- the IDA header (:580-637)
+    const int cont = s_st[3];
+    const int da_ctr = (s_st[5] << 2) | (s_st[6] << 1) | s_st[7];
+    const int da_len = (s_st[11] << 4) | (s_st[12] << 3) | (s_st[13] << 2) | (s_st[14] << 1) | s_st[15];
+    if (((s_st[17] << 2) | (s_st[18] << 1) | s_st[19]) != 0 || da_len > 20) { emit(); return; }
+    const int plen = da_len > 0 ? da_len : 20;
+    if (lane < 32) {
+        unsigned by = 0, bs = 0;
+        for (int k = 0; k < 8; k++) {
+            by = (by << 1) | (lane < plen ? s_st[20 + lane * 8 + k] : 0u);
+            bs = (bs << 1) | (8 * lane + k < len ? s_st[8 * lane + k] : 0u);
+        }
+        s_rec.payload[lane] = (uint8_t)by;
+        s_rec.bch_stream[lane] = (uint8_t)bs;
+    }
+    int crc_ok = 0;
+    unsigned stored = 0, computed = 0;
+    if (da_len > 0) {
+        for (int k = 0; k < 16; k++) stored = (stored << 1) | s_st[9 * 20 + k];
+        const int crc_bits = 20 + 12 + (len - 20 - 4);
+        const int n_bytes = (crc_bits + 7) / 8;
+        if (n_bytes <= 64) {
+            // message bit bp: the stream's first 20 bits, 12 zero bits, the stream from bit 20 on; zero padding
+            if (lane < n_bytes) {
+                unsigned by = 0;
+                for (int k = 0; k < 8; k++) {
+                    const int bp = 8 * lane + k;
+                    unsigned bit = 0;
+                    if (bp < 20) bit = s_st[bp];
+                    else if (bp >= 32 && bp < crc_bits) bit = s_st[20 + (bp - 32)];
+                    by = (by << 1) | bit;
+                }
+                s_msg[lane] = (uint8_t)by;
+            }
+            __syncthreads();
+            unsigned crc = 0xFFFFu;
+            for (int k = 0; k < n_bytes; k++) crc = ((crc << 8) ^ c_crc16.v[((crc >> 8) ^ s_msg[k]) & 0xffu]) & 0xffffu;
+            computed = crc;
+            crc_ok = computed == 0;
+        }
+    }
+    if (lane == 0) {
+        s_rec.ok = 1;
+        s_rec.lcw3_val = v3 >> 5;
+        s_rec.ft = (uint8_t)ft;
+        s_rec.lcw_ft = (uint8_t)((d2 >> 4) & 3);
+        s_rec.lcw_code = (uint8_t)(d2 & 0xF);
+        s_rec.ec_lcw = (uint8_t)((s1 != 0) + (s2 != 0) + (s3 != 0));
+        s_rec.da_ctr = (uint8_t)da_ctr;
+        s_rec.da_len = (uint8_t)da_len;
+        s_rec.cont = (uint8_t)cont;
+        s_rec.crc_ok = (uint8_t)crc_ok;
+        s_rec.stored_crc = (uint16_t)stored;
+        s_rec.computed_crc = (uint16_t)computed;
+        s_rec.fixederrs = (uint8_t)fixederrs;
+        s_rec.payload_len = (uint8_t)plen;
+        s_rec.bch_len = (uint16_t)len;
+    }
+    emit();
+}
+
+int launch_ida_packed(const DemodOut *frames, int n_frames, const int2 *syn_da, const int2 *syn_l1, const int2 *syn_l2,
+                      const int2 *syn_l3, IdaPacked *hp_ida, hipStream_t stream)
+{
+    if (n_frames <= 0) return 0;
+    hipLaunchKernelGGL(ida_packed_kernel, dim3(n_frames), dim3(64), 0, stream, frames, n_frames, syn_da, syn_l1, syn_l2,
+                       syn_l3, hp_ida);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_ida_decode(const DemodOut *frames, int n_frames, const int2 *syn_da, const int2 *syn_l1, const int2 *syn_l2,
                       const int2 *syn_l3, int use_llr, const int *n_bits, const int *direction, IdaOut *out,
                       hipStream_t stream)

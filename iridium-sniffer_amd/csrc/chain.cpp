@@ -572,11 +572,16 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
     IRDM_HIP_CHECK(hipEventRecord(b.ev[2], st));
     // the chain's results: work records and demodulator output.  packed_records (136 bytes per burst instead of 4.5 KB: hard
     // bits 8 per byte, no LLRs): written into pinned host memory by the demodulator's last kernel itself
-    b.packed = p->packed_records && !p->decode_frames && !p->decode_ida && !p->keep_frame_samples;
+    // parsed_records: the same, and ida_decode() of every frame behind it, on the bits and LLRs the demodulator leaves
+    // on the device (IdaPacked, 88 bytes per burst, written to pinned memory by that kernel)
+    b.packed = (p->packed_records || p->parsed_records) && !p->decode_frames && !p->decode_ida && !p->keep_frame_samples;
+    b.parsed = b.packed && p->parsed_records;
     if (launch_demod(b.d_work, nb, b.d_frames, p->cfg.use_gardner, p->sps, b.d_demod_ws, b.d_demod, st,
-                     b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr) != 0)
+                     b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr, b.parsed ? 1 : 0) != 0)
         return -1;
     IRDM_HIP_CHECK(hipEventRecord(b.ev[3], st));
+    if (b.parsed)
+        return launch_ida_packed(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_ida, st);
     if (b.packed) return 0;
     if (p->decode_frames) {
         // post-demod bit layer on the demodulator's device-resident output (frames that failed the unique word
@@ -686,6 +691,11 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             o.ok = 1;
             o.total_phase = d.total_phase;
             memcpy(o.bits, d.bits, sizeof(o.bits));
+            if (b.parsed) {
+                static_assert(sizeof(irdm_ida_packed_t) == sizeof(IdaPacked), "the device record is the public one");
+                p->q_ida_packed.emplace_back();
+                memcpy(&p->q_ida_packed.back(), &b.hp_ida[i], sizeof(IdaPacked));
+            }
             if (d.n_symbols > 0) {
                 const double duration = (double)d.n_symbols / 25000;
                 o.center_frequency = b.h_cfreq[i] + d.total_phase / duration / M_PI / 2.0;

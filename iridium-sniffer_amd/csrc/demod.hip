@@ -339,7 +339,8 @@ __device__ __forceinline__ void demod_export(const BurstWork *__restrict__ w, in
 
 __global__ __launch_bounds__(64) void demod_par_kernel(const BurstWork *__restrict__ work, int n_bursts,
                                                        const float2 *__restrict__ ws, DemodOut *__restrict__ out,
-                                                       DemodPacked *__restrict__ hp_packed, BurstWork *__restrict__ hp_work)
+                                                       DemodPacked *__restrict__ hp_packed, BurstWork *__restrict__ hp_work,
+                                                       int keep_bits)
 {
     __shared__ float2 s_po[kMaxSymbols];
     __shared__ float s_mag[kMaxSymbols];      // sqrtf(re^2 + im^2) of the PLL output (:205, :231)
@@ -468,7 +469,7 @@ __global__ __launch_bounds__(64) void demod_par_kernel(const BurstWork *__restri
     }
     if (hp_packed) {
         demod_export(work + b, lane, ok, s_res[1], s_res[3], ns, s_resf[0], s_resf[1], s_sym, hp_packed, hp_work, b);
-        return;
+        if (!keep_bits) return;             // (parsed_records: ida_packed_kernel reads the bits and LLRs below)
     }
     if (!ok) return;
     // steps 5-7: decode_dqpsk (:264-273), bits MSB first (:329-335), LLR (:498-503): per-symbol independent
@@ -485,13 +486,15 @@ __global__ __launch_bounds__(64) void demod_par_kernel(const BurstWork *__restri
 }
 
 int launch_demod(const BurstWork *work, int n_bursts, const float2 *frames, int use_gardner,
-                 float sps, float2 *ws, DemodOut *out, hipStream_t stream, DemodPacked *hp_packed, BurstWork *hp_work)
+                 float sps, float2 *ws, DemodOut *out, hipStream_t stream, DemodPacked *hp_packed, BurstWork *hp_work,
+                 int keep_bits)
 {
     if (n_bursts <= 0) return 0;
     hipLaunchKernelGGL(demod_seq_kernel, dim3((n_bursts + kSeqFrames - 1) / kSeqFrames), dim3(128),
                        sizeof(float2) * kSeqFrames * kSeqPitch, stream, work, n_bursts,
                        frames, use_gardner, sps, ws, out);
-    hipLaunchKernelGGL(demod_par_kernel, dim3(n_bursts), dim3(64), 0, stream, work, n_bursts, ws, out, hp_packed, hp_work);
+    hipLaunchKernelGGL(demod_par_kernel, dim3(n_bursts), dim3(64), 0, stream, work, n_bursts, ws, out, hp_packed, hp_work,
+                       keep_bits);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

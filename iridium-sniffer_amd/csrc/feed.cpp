@@ -362,6 +362,12 @@ extern "C" int irdm_poll_demods_packed(irdm_pipeline_t *p, irdm_demod_packed_t *
     return drain(p->q_packed, out, max);
 }
 
+extern "C" int irdm_poll_ida_packed(irdm_pipeline_t *p, irdm_ida_packed_t *out, int max)
+{
+    if (!p || !out || max < 0) return -1;
+    return drain(p->q_ida_packed, out, max);
+}
+
 extern "C" int irdm_poll_bursts(irdm_pipeline_t *p, irdm_burst_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;

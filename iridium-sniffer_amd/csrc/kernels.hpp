@@ -165,10 +165,15 @@ int launch_ida_decode(const DemodOut *frames, int n_frames, const int2 *syn_da, 
                       hipStream_t stream);
 int launch_frame_decode(const DemodOut *frames, int n_frames, const int2 *syn_ra, const int2 *syn_hdr, int use_llr,
                         const int *n_bits, DecodedOut *out, hipStream_t stream);
+// parsed_records: ida_decode() of the frames demod_par_kernel has just finished (their bits and LLRs device-resident,
+// launch_demod with keep_bits), one wavefront per frame, each frame's IdaPacked written straight into pinned host memory
+int launch_ida_packed(const DemodOut *frames, int n_frames, const int2 *syn_da, const int2 *syn_l1, const int2 *syn_l2,
+                      const int2 *syn_l3, IdaPacked *hp_ida, hipStream_t stream);
 // hp_packed / hp_work != nullptr (packed_records): demod_par_kernel writes the DemodPacked and work records straight into
-// pinned host memory -- the chain's last launch
+// pinned host memory -- the chain's last launch, unless keep_bits: then the DemodOut's bits and LLRs are written as well,
+// on the device, for launch_ida_packed behind it
 int launch_demod(const BurstWork *work, int n_bursts, const float2 *frames, int use_gardner,
                  float sps, float2 *ws, DemodOut *out, hipStream_t stream, DemodPacked *hp_packed = nullptr,
-                 BurstWork *hp_work = nullptr);
+                 BurstWork *hp_work = nullptr, int keep_bits = 0);
 
 }  // namespace irdm

@@ -180,4 +180,20 @@ struct IdaOut {
     uint8_t bch_stream[256];
 };
 
+// the IdaOut of one frame in 88 bytes (option parsed_records): written into pinned host memory by ida_packed_kernel,
+// word for word the public irdm_ida_packed_t; bch_stream holds the first 256 bits of the decoded stream 8 per byte, MSB
+// first (bch_len may be larger: the reference keeps 256 of them too, ida_decode.c:656-657)
+struct IdaPacked {
+    int32_t ok;
+    uint32_t lcw3_val;
+    uint8_t ft, lcw_ft, lcw_code, ec_lcw;
+    uint8_t da_ctr, da_len, cont, crc_ok;
+    uint16_t stored_crc, computed_crc;
+    uint8_t fixederrs, payload_len;
+    uint16_t bch_len;
+    uint8_t payload[32];
+    uint8_t bch_stream[32];
+};
+static_assert(sizeof(IdaPacked) == 88 && sizeof(IdaPacked) % 4 == 0, "written as 22 words, one per lane");
+
 }  // namespace irdm

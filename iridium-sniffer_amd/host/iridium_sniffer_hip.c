@@ -131,6 +131,11 @@ static irdm_group_t *g_group;
 #define irdm_poll_demods(p, o, m) (g_group ? irdm_group_poll_demods(g_group, o, m) : irdm_poll_demods(p, o, m))
 #define irdm_poll_bursts(p, o, m) (g_group ? irdm_group_poll_bursts(g_group, o, m) : irdm_poll_bursts(p, o, m))
 #define irdm_poll_frames(p, o, s, m) (g_group ? irdm_group_poll_frames(g_group, o, s, m) : irdm_poll_frames(p, o, s, m))
+#define irdm_poll_ida_packed(p, o, m) (g_group ? irdm_group_poll_ida_packed(g_group, o, m) : irdm_poll_ida_packed(p, o, m))
+#define irdm_poll_ida(p, o, m) (g_group ? irdm_group_poll_ida(g_group, o, m) : irdm_poll_ida(p, o, m))
+
+/* --parsed (main.c:322-331): per frame the IDA line where ida_decode() succeeds, the RAW line otherwise */
+static int g_parsed;
 
 static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, uint64_t *t0, char *line, size_t cap)
 {
@@ -138,13 +143,33 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
     if (!g_save_dir) {
         /* RAW lines need no LLRs: compact records (hard bits 8 per byte), 176 bytes per frame instead of 4.5 KB */
         static irdm_demod_packed_t dp[256];
+        static irdm_ida_packed_t ip[256];
         while ((n = irdm_poll_demods_packed(p, dp, 256)) > 0) {
-            const long long len = irdm_format_raw_packed_batch(dp, n, file_info, t0, line, cap);   /* one write per batch */
+            long long len;
+            if (g_parsed) {
+                /* one compact IDA record per compact frame record, decoded on the GPU (option parsed_records) */
+                if (irdm_poll_ida_packed(p, ip, n) != n) { fprintf(stderr, "--parsed: IDA records out of step\n"); exit(1); }
+                len = irdm_format_parsed_packed_batch(dp, ip, n, file_info, t0, line, cap);
+            } else {
+                len = irdm_format_raw_packed_batch(dp, n, file_info, t0, line, cap);   /* one write per batch */
+            }
             if (len > 0) fwrite(line, 1, (size_t)len, stdout);
         }
     }
+    static irdm_ida_t ida[256];
     while ((n = irdm_poll_demods(p, d, 256)) > 0) {
-        const long long len = irdm_format_raw_batch(d, n, file_info, t0, line, cap);     /* one write per batch */
+        long long len = 0;
+        if (g_parsed) {
+            /* the full-record path (--save-bursts): option decode_ida, one irdm_ida_t per frame record */
+            if (irdm_poll_ida(p, ida, n) != n) { fprintf(stderr, "--parsed: IDA records out of step\n"); exit(1); }
+            for (int i = 0; i < n && len >= 0; i++) {
+                const int l = ida[i].ok ? irdm_format_ida(&ida[i], t0, line + len, cap - (size_t)len)
+                                        : irdm_format_raw(&d[i], file_info, t0, line + len, cap - (size_t)len);
+                len = l < 0 ? -1 : len + l;
+            }
+        } else {
+            len = irdm_format_raw_batch(d, n, file_info, t0, line, cap);     /* one write per batch */
+        }
         if (len > 0) fwrite(line, 1, (size_t)len, stdout);
     }
     irdm_burst_t tmp[256];
@@ -197,6 +222,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--group-loopback")) loopback = 1;      /* test aid: --gpus 1 hands the detector state to itself over RCCL */
         else if (!strcmp(a, "--no-gardner")) gardner = 0;
         else if (!strcmp(a, "--save-bursts")) save_dir = NEXT();   /* options.c --save-bursts: IQ + .meta per downmixed frame */
+        else if (!strcmp(a, "--parsed")) g_parsed = 1;              /* options.c --parsed: IDA lines where they decode */
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -211,7 +237,7 @@ int main(int argc, char **argv)
         }
     }
     if (!file || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--gpus N]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--gpus N]\n", argv[0]);
         return 2;
     }
     if (!format) format = ext_of(file);              /* autodetect by extension, options.c:533-544 */
@@ -268,6 +294,10 @@ int main(int argc, char **argv)
     }
     if (save_dir) SET_OPTION("keep_frame_samples", 1);
     else SET_OPTION("packed_records", 1);
+    if (g_parsed && SET_OPTION(save_dir ? "decode_ida" : "parsed_records", 1) != 0) {
+        fprintf(stderr, "--parsed: the library refused the IDA decoder\n");
+        return 1;
+    }
     g_save_dir = save_dir;
     if (verbose) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
                          gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");

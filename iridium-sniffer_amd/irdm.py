@@ -86,6 +86,15 @@ class Ida(C.Structure):
                 ("pad", C.c_int32)]
 
 
+class IdaPacked(C.Structure):
+    """irdm_ida_packed_t: ida_decode()'s fields for one packed frame (option parsed_records); bch_stream 8 bits per byte"""
+    _fields_ = [("ok", C.c_int32), ("lcw3_val", C.c_uint32), ("ft", C.c_uint8), ("lcw_ft", C.c_uint8),
+                ("lcw_code", C.c_uint8), ("ec_lcw", C.c_uint8), ("da_ctr", C.c_uint8), ("da_len", C.c_uint8),
+                ("cont", C.c_uint8), ("crc_ok", C.c_uint8), ("stored_crc", C.c_uint16), ("computed_crc", C.c_uint16),
+                ("fixederrs", C.c_uint8), ("payload_len", C.c_uint8), ("bch_len", C.c_uint16),
+                ("payload", C.c_uint8 * 32), ("bch_stream", C.c_uint8 * 32)]
+
+
 _lib = None
 
 
@@ -147,6 +156,13 @@ def lib():
         L.irdm_poll_demods_packed.argtypes = [C.c_void_p, C.POINTER(DemodPacked), C.c_int]
         L.irdm_poll_decoded.argtypes = [C.c_void_p, C.POINTER(Decoded), C.c_int]
         L.irdm_poll_ida.argtypes = [C.c_void_p, C.POINTER(Ida), C.c_int]
+        L.irdm_poll_ida_packed.argtypes = [C.c_void_p, C.POINTER(IdaPacked), C.c_int]
+        L.irdm_ida_unpack.argtypes = [C.POINTER(IdaPacked), C.POINTER(DemodPacked), C.POINTER(Ida)]
+        L.irdm_ida_unpack.restype = None
+        L.irdm_format_ida.argtypes = [C.POINTER(Ida), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+        L.irdm_format_parsed_packed_batch.argtypes = [C.POINTER(DemodPacked), C.POINTER(IdaPacked), C.c_int, C.c_char_p,
+                                                      C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+        L.irdm_format_parsed_packed_batch.restype = C.c_longlong
         L.irdm_ida_decode_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.c_int, C.POINTER(Ida)]
         L.irdm_frame_decode_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.c_int, C.POINTER(Decoded)]
         L.irdm_tagged_bursts.argtypes = [C.c_void_p]
@@ -194,6 +210,7 @@ def lib():
         L.irdm_group_poll_demods_packed.argtypes = [C.c_void_p, C.POINTER(DemodPacked), C.c_int]
         L.irdm_group_poll_decoded.argtypes = [C.c_void_p, C.POINTER(Decoded), C.c_int]
         L.irdm_group_poll_ida.argtypes = [C.c_void_p, C.POINTER(Ida), C.c_int]
+        L.irdm_group_poll_ida_packed.argtypes = [C.c_void_p, C.POINTER(IdaPacked), C.c_int]
         L.irdm_chunks_complete.argtypes = [C.c_void_p]
         L.irdm_chunks_complete.restype = C.c_uint64
         L.irdm_required_overlap.argtypes = [C.c_void_p]
@@ -450,6 +467,10 @@ class Pipeline:
     def poll_demods_packed(self):
         return self._poll(self.L.irdm_poll_demods_packed, DemodPacked)
 
+    def poll_ida_packed(self):
+        """option parsed_records 1: one IdaPacked per polled DemodPacked, in the same order"""
+        return self._poll(self.L.irdm_poll_ida_packed, IdaPacked)
+
     def drop_frames(self, chunk=4096):
         """Discard queued frame records (metadata only path)."""
         buf = (FrameInfo * chunk)()
@@ -656,6 +677,9 @@ class Group:
     def poll_ida(self):
         return self._poll(self.L.irdm_group_poll_ida, Ida)
 
+    def poll_ida_packed(self):
+        return self._poll(self.L.irdm_group_poll_ida_packed, IdaPacked)
+
     def poll_frames(self, chunk=64):
         infos, samples = [], []
         buf = (FrameInfo * chunk)()
@@ -698,6 +722,43 @@ def format_raw(demods, file_info="golden"):
             raise RuntimeError("irdm_format_raw failed")
         out.append(buf.value.decode())
     return out
+
+
+def ida_unpack(ida_packed, demod_packed):
+    """irdm_ida_unpack: the Ida record the decode_ida path makes of the same frame"""
+    out = Ida()
+    lib().irdm_ida_unpack(C.byref(ida_packed), C.byref(demod_packed), C.byref(out))
+    return out
+
+
+def format_ida(idas, t0=0):
+    """frame_output_print_ida for a list of Ida records (ok != 0), t0 shared along the list; returns the lines"""
+    L = lib()
+    t = C.c_uint64(t0)
+    buf = C.create_string_buffer(4096)
+    out = []
+    for b in idas:
+        n = L.irdm_format_ida(C.byref(b), C.byref(t), buf, 4096)
+        if n < 0:
+            raise RuntimeError("irdm_format_ida failed")
+        out.append(buf.raw[:n].decode("latin-1"))
+    return out
+
+
+def format_parsed_packed_batch(demods, idas, file_info=None, t0=0):
+    """irdm_format_parsed_packed_batch: --parsed's text for paired DemodPacked / IdaPacked lists"""
+    L = lib()
+    n = len(demods)
+    assert len(idas) == n
+    arr = (DemodPacked * max(n, 1))(*demods)
+    ida = (IdaPacked * max(n, 1))(*idas)
+    cap = max(n, 1) * 1280
+    buf = C.create_string_buffer(cap)
+    t = C.c_uint64(t0)
+    rc = L.irdm_format_parsed_packed_batch(arr, ida, n, file_info.encode() if file_info else None, C.byref(t), buf, cap)
+    if rc < 0:
+        raise RuntimeError("irdm_format_parsed_packed_batch failed")
+    return buf.raw[:rc].decode("latin-1")
 
 
 def format_raw_batch(demods, file_info="golden"):
