@@ -567,6 +567,70 @@ int irdm_format_ida(const irdm_ida_t *b, uint64_t *t0_io, char *buf, size_t cap)
 long long irdm_format_parsed_packed_batch(const irdm_demod_packed_t *f, const irdm_ida_packed_t *idas, int n,
                                           const char *file_info, uint64_t *t0_io, char *buf, size_t cap);
 
+/* 3c. IDA reassembly, SBD and ACARS (--acars, --acars-json)            */
+/* ------------------------------------------------------------------ */
+/* Host C, once per IDA burst and once per message: the reference's ida_reassemble / ida_reassemble_flush
+ * (ida_decode.c:669-748), SBD extraction and multi-packet reassembly (sbd_acars.c:1002-1218) and its ACARS printer as it
+ * builds without libacars (sbd_acars.c:603-998; no ARINC-622 decoding).  Contexts are opaque, one thread each. */
+
+/* one reassembled IDA message: the arguments of ida_message_cb (ida_decode.h:76-79) */
+typedef struct {
+    uint8_t data[256];
+    int32_t len;
+    int32_t direction;         /* ir_direction_t: 1 DL, 2 UL */
+    uint64_t timestamp;        /* the last burst's */
+    double frequency;          /* the first burst's */
+    float magnitude;           /* the last burst's */
+    int32_t pad;
+} irdm_ida_message_t;
+
+typedef struct irdm_ida_reasm irdm_ida_reasm_t;
+irdm_ida_reasm_t *irdm_ida_reasm_create(void);
+void irdm_ida_reasm_destroy(irdm_ida_reasm_t *r);
+/* Per record in stream order (main.c:357-361): ida_reassemble when b[i].ok, then ida_reassemble_flush at b[i].timestamp.
+ * A frame ida_decode() did not take still flushes: give it ok = 0 and the frame's timestamp (irdm_poll_ida leaves that
+ * 0).  Completed messages go to out in order, at most one per record: max >= n.  Returns their count, or -1. */
+int irdm_ida_reasm_push(irdm_ida_reasm_t *r, const irdm_ida_t *b, int n, irdm_ida_message_t *out, int max);
+/* the same from the packed record path's pairs (through irdm_ida_unpack); every frame flushes at its own timestamp */
+int irdm_ida_reasm_push_packed(irdm_ida_reasm_t *r, const irdm_demod_packed_t *f, const irdm_ida_packed_t *idas, int n,
+                               irdm_ida_message_t *out, int max);
+
+typedef struct {
+    int32_t json;              /* 1: --acars-json's lines (messages with errors dropped), 0: the text lines */
+    int32_t fixed_origin;      /* 1: the wall clock of the first printed message is origin_sec + origin_nsec; 0: read
+                                  CLOCK_REALTIME then (ts_ensure_init, sbd_acars.c:306-313) */
+    int64_t origin_sec, origin_nsec;
+    const char *station;       /* --station (copied), NULL for none */
+} irdm_acars_config_t;
+
+/* acars_print_stats's counters (sbd_acars.c:291-299) */
+typedef struct {
+    int32_t ida_total, sbd_total, sbd_short, sbd_single, sbd_multi_ok, sbd_multi_frag, sbd_broken;
+    int32_t acars_total, acars_errors;
+} irdm_acars_stats_t;
+
+typedef struct irdm_acars irdm_acars_t;
+irdm_acars_t *irdm_acars_create(const irdm_acars_config_t *cfg);
+void irdm_acars_destroy(irdm_acars_t *a);
+/* acars_ida_cb for n messages: the lines the reference prints, concatenated in buf (NUL-terminated; a line may hold NUL
+ * bytes where the message does, so use the returned length).  At most one line per message of at most
+ * IRDM_ACARS_LINE_MAX bytes.  Returns the length, or -1 when cap is too small (the messages are consumed all the same). */
+#define IRDM_ACARS_LINE_MAX 8192
+long long irdm_acars_feed(irdm_acars_t *a, const irdm_ida_message_t *m, int n, char *buf, size_t cap);
+int irdm_acars_stats(const irdm_acars_t *a, irdm_acars_stats_t *out);
+/* acars_print_stats's stderr text (sbd_acars.c:1336-1349).  Returns its length, or -1. */
+int irdm_acars_format_stats(const irdm_acars_t *a, char *buf, size_t cap);
+/* --acars on the packed record path: per frame (main.c:322-361) its IDA line when parsed and idas[i].ok, no RAW line
+ * (frame_output_print returns under --acars before it sets t0, frame_output.c:162-168), then the ACARS lines of the
+ * messages the frame completes.  State lives in r and a across calls.  cap >= n * (IRDM_RAW_LINE_MAX +
+ * IRDM_ACARS_LINE_MAX) always suffices.  Returns the length, or -1. */
+long long irdm_format_acars_packed_batch(irdm_ida_reasm_t *r, irdm_acars_t *a, const irdm_demod_packed_t *f,
+                                         const irdm_ida_packed_t *idas, int n, int parsed, uint64_t *t0_io, char *buf,
+                                         size_t cap);
+/* the same from full records and the "decode_ida" path's irdm_ida_t (--save-bursts) */
+long long irdm_format_acars_batch(irdm_ida_reasm_t *r, irdm_acars_t *a, const irdm_demod_t *f, const irdm_ida_t *idas,
+                                  int n, int parsed, uint64_t *t0_io, char *buf, size_t cap);
+
 /* --save-bursts (qpsk_demod.c:339-389): writes <dir>/<timestamp>_<freq>_<id>_<DL|UL|UN>.cf32 (the frame's cf32 samples at
  * 250 kHz) and the matching .meta text file for one downmixed frame (info->drop_reason == 0), creating dir if needed.
  * samples: 2 * info->num_samples floats as returned by irdm_poll_frames with "keep_frame_samples" = 1.

@@ -4,7 +4,9 @@
  * Mirrors the reference's file-mode surface (options.c:186-551, main.c:223-284, frame_output.c:160-199):
  *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
- * IQ file in, iridium-toolkit "RAW:" lines on stdout, "burst_detect: tagged N bursts total" on stderr
+ *                         [--parsed] [--acars] [--acars-json] [--station ID]
+ * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
+ * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps).  Everything between the file
  * read and the line printer runs on the GPU through the C-ABI in include/irdm_hip.h; there is no CPU
  * path here (the reference's own --no-gpu binary is the CPU path).
@@ -136,6 +138,11 @@ static irdm_group_t *g_group;
 
 /* --parsed (main.c:322-331): per frame the IDA line where ida_decode() succeeds, the RAW line otherwise */
 static int g_parsed;
+/* --acars / --acars-json (main.c:357-361): IDA reassembly, SBD and ACARS on the host for the whole stream; RAW lines are
+ * suppressed (frame_output.c:162-168) */
+static irdm_ida_reasm_t *g_reasm;
+static irdm_acars_t *g_acars;
+static char g_acars_line[256 * (IRDM_RAW_LINE_MAX + IRDM_ACARS_LINE_MAX)];
 
 static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, uint64_t *t0, char *line, size_t cap)
 {
@@ -146,7 +153,13 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         static irdm_ida_packed_t ip[256];
         while ((n = irdm_poll_demods_packed(p, dp, 256)) > 0) {
             long long len;
-            if (g_parsed) {
+            if (g_acars) {
+                if (irdm_poll_ida_packed(p, ip, n) != n) { fprintf(stderr, "--acars: IDA records out of step\n"); exit(1); }
+                len = irdm_format_acars_packed_batch(g_reasm, g_acars, dp, ip, n, g_parsed, t0, g_acars_line, sizeof g_acars_line);
+                if (len < 0) { fprintf(stderr, "--acars: formatting failed\n"); exit(1); }
+                if (len > 0) fwrite(g_acars_line, 1, (size_t)len, stdout);
+                continue;
+            } else if (g_parsed) {
                 /* one compact IDA record per compact frame record, decoded on the GPU (option parsed_records) */
                 if (irdm_poll_ida_packed(p, ip, n) != n) { fprintf(stderr, "--parsed: IDA records out of step\n"); exit(1); }
                 len = irdm_format_parsed_packed_batch(dp, ip, n, file_info, t0, line, cap);
@@ -159,7 +172,13 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
     static irdm_ida_t ida[256];
     while ((n = irdm_poll_demods(p, d, 256)) > 0) {
         long long len = 0;
-        if (g_parsed) {
+        if (g_acars) {
+            if (irdm_poll_ida(p, ida, n) != n) { fprintf(stderr, "--acars: IDA records out of step\n"); exit(1); }
+            len = irdm_format_acars_batch(g_reasm, g_acars, d, ida, n, g_parsed, t0, g_acars_line, sizeof g_acars_line);
+            if (len < 0) { fprintf(stderr, "--acars: formatting failed\n"); exit(1); }
+            if (len > 0) fwrite(g_acars_line, 1, (size_t)len, stdout);
+            continue;
+        } else if (g_parsed) {
             /* the full-record path (--save-bursts): option decode_ida, one irdm_ida_t per frame record */
             if (irdm_poll_ida(p, ida, n) != n) { fprintf(stderr, "--parsed: IDA records out of step\n"); exit(1); }
             for (int i = 0; i < n && len >= 0; i++) {
@@ -208,6 +227,9 @@ int main(int argc, char **argv)
     int gpus = 0;               /* --gpus N: one stream across N GPUs of this process (0: one context on device 0) */
     int chunk_given = 0, loopback = 0;
     const char *save_dir = NULL;
+    int acars = 0, acars_json = 0, has_origin = 0;
+    const char *station = NULL;
+    long long origin_sec = 0, origin_nsec = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -223,6 +245,28 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--no-gardner")) gardner = 0;
         else if (!strcmp(a, "--save-bursts")) save_dir = NEXT();   /* options.c --save-bursts: IQ + .meta per downmixed frame */
         else if (!strcmp(a, "--parsed")) g_parsed = 1;              /* options.c --parsed: IDA lines where they decode */
+        else if (!strcmp(a, "--acars")) acars = 1;                  /* options.c:401-408: ACARS from reassembled IDA */
+        else if (!strcmp(a, "--acars-json")) acars = acars_json = 1;
+        else if (!strcmp(a, "--station")) station = NEXT();         /* options.c --station=ID (getopt takes both forms) */
+        else if (!strncmp(a, "--station=", 10)) station = a + 10;
+        else if (!strcmp(a, "--acars-origin")) {
+            /* test aid: SEC[.NNNNNNNNN] is the wall clock of the first printed ACARS message instead of CLOCK_REALTIME */
+            const char *v = NEXT();
+            char *end;
+            origin_sec = strtoll(v, &end, 10);
+            if (*end == '.') {
+                int digits = 0;
+                for (end++; *end >= '0' && *end <= '9' && digits < 9; end++, digits++) origin_nsec = origin_nsec * 10 + (*end - '0');
+                for (; digits < 9; digits++) origin_nsec *= 10;
+            }
+            if (*end) { fprintf(stderr, "--acars-origin %s: expected SEC[.NNNNNNNNN]\n", v); return 2; }
+            has_origin = 1;
+        }
+        else if (!strcmp(a, "--acars-udp") || !strncmp(a, "--acars-udp=", 12) || !strcmp(a, "--feed") || !strncmp(a, "--feed=", 7) ||
+                 !strcmp(a, "--gsmtap") || !strncmp(a, "--gsmtap=", 9) || !strcmp(a, "--web") || !strncmp(a, "--web=", 6)) {
+            fprintf(stderr, "%s: network output is not built in this binary (ACARS goes to stdout with --acars / --acars-json)\n", a);
+            return 2;
+        }
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -237,7 +281,7 @@ int main(int argc, char **argv)
         }
     }
     if (!file || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--gpus N]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--gpus N]\n", argv[0]);
         return 2;
     }
     if (!format) format = ext_of(file);              /* autodetect by extension, options.c:533-544 */
@@ -294,9 +338,23 @@ int main(int argc, char **argv)
     }
     if (save_dir) SET_OPTION("keep_frame_samples", 1);
     else SET_OPTION("packed_records", 1);
-    if (g_parsed && SET_OPTION(save_dir ? "decode_ida" : "parsed_records", 1) != 0) {
-        fprintf(stderr, "--parsed: the library refused the IDA decoder\n");
+    if ((g_parsed || acars) && SET_OPTION(save_dir ? "decode_ida" : "parsed_records", 1) != 0) {
+        fprintf(stderr, "%s: the library refused the IDA decoder\n", g_parsed ? "--parsed" : "--acars");
         return 1;
+    }
+    if (acars) {
+        irdm_acars_config_t ac;
+        memset(&ac, 0, sizeof(ac));
+        ac.json = acars_json;
+        ac.station = station;
+        ac.fixed_origin = has_origin;
+        ac.origin_sec = origin_sec;
+        ac.origin_nsec = origin_nsec;
+        g_reasm = irdm_ida_reasm_create();
+        g_acars = irdm_acars_create(&ac);
+        if (!g_reasm || !g_acars) { fprintf(stderr, "--acars: out of memory\n"); return 1; }
+        /* main.c:617-629, without the network endpoints this binary does not build */
+        fprintf(stderr, "ACARS: enabled (%s output%s)\n", acars_json ? "JSON" : "text", station ? ", station set" : "");
     }
     g_save_dir = save_dir;
     if (verbose) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
@@ -371,6 +429,10 @@ int main(int argc, char **argv)
     }
     fprintf(stderr, "burst_detect: tagged %lu bursts total\n",
             (unsigned long)(g_group ? (uint64_t)irdm_group_get_stat(g_group, "tagged") : irdm_tagged_bursts(p)));
+    if (g_acars) {
+        char st[512];
+        if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */
+    }
     /* Everything is printed and flushed.  Giving 5-9 GB of device memory, the pinned buffers and the HIP runtime back piece
      * by piece took 0.2 s of a 0.77 s run; the process is about to end and the kernel reclaims all of it at once, so the
      * binary leaves here unless IRDM_CLEAN_EXIT=1 asks for the orderly teardown (leak checkers, embedding tests). */
@@ -385,6 +447,8 @@ int main(int argc, char **argv)
     irdm_host_free(rd.buf[0]);
     irdm_host_free(rd.buf[1]);
     free(d);
+    irdm_acars_destroy(g_acars);
+    irdm_ida_reasm_destroy(g_reasm);
     if (f != stdin) fclose(f);
     if (timing) fprintf(stderr, "irdm timing: teardown %.3f s\n", now_s() - t_down);
     return rc;

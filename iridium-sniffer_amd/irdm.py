@@ -95,6 +95,24 @@ class IdaPacked(C.Structure):
                 ("payload", C.c_uint8 * 32), ("bch_stream", C.c_uint8 * 32)]
 
 
+class IdaMessage(C.Structure):
+    """irdm_ida_message_t: one reassembled IDA message (ida_message_cb's arguments)"""
+    _fields_ = [("data", C.c_uint8 * 256), ("len", C.c_int32), ("direction", C.c_int32), ("timestamp", C.c_uint64),
+                ("frequency", C.c_double), ("magnitude", C.c_float), ("pad", C.c_int32)]
+
+
+class AcarsConfig(C.Structure):
+    _fields_ = [("json", C.c_int32), ("fixed_origin", C.c_int32), ("origin_sec", C.c_int64), ("origin_nsec", C.c_int64),
+                ("station", C.c_char_p)]
+
+
+class AcarsStats(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("ida_total", "sbd_total", "sbd_short", "sbd_single", "sbd_multi_ok",
+                                         "sbd_multi_frag", "sbd_broken", "acars_total", "acars_errors")]
+
+
+ACARS_LINE_MAX = 8192
+RAW_LINE_MAX = 1280
 _lib = None
 
 
@@ -220,6 +238,25 @@ def lib():
         L.irdm_bytes_per_sample.argtypes = [C.c_void_p]
         L.irdm_bytes_per_sample.restype = C.c_size_t
         L.irdm_wait_ingest.argtypes = [C.c_void_p]
+        if hasattr(L, "irdm_ida_reasm_create"):            # (csrc/acars.cpp; the emulated test build leaves it out)
+            L.irdm_ida_reasm_create.restype = C.c_void_p
+            L.irdm_ida_reasm_create.argtypes = []
+            L.irdm_ida_reasm_destroy.argtypes = [C.c_void_p]
+            L.irdm_ida_reasm_push.argtypes = [C.c_void_p, C.POINTER(Ida), C.c_int, C.POINTER(IdaMessage), C.c_int]
+            L.irdm_ida_reasm_push_packed.argtypes = [C.c_void_p, C.POINTER(DemodPacked), C.POINTER(IdaPacked), C.c_int,
+                                                     C.POINTER(IdaMessage), C.c_int]
+            L.irdm_acars_create.restype = C.c_void_p
+            L.irdm_acars_create.argtypes = [C.POINTER(AcarsConfig)]
+            L.irdm_acars_destroy.argtypes = [C.c_void_p]
+            L.irdm_acars_feed.restype = C.c_longlong
+            L.irdm_acars_feed.argtypes = [C.c_void_p, C.POINTER(IdaMessage), C.c_int, C.c_char_p, C.c_size_t]
+            L.irdm_acars_stats.argtypes = [C.c_void_p, C.POINTER(AcarsStats)]
+            L.irdm_acars_format_stats.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+            for name, rec, ida in (("irdm_format_acars_packed_batch", DemodPacked, IdaPacked),
+                                   ("irdm_format_acars_batch", Demod, Ida)):
+                getattr(L, name).restype = C.c_longlong
+                getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rec), C.POINTER(ida), C.c_int, C.c_int,
+                                             C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -783,3 +820,101 @@ def save_burst(info, samples, dirname):
     s = np.ascontiguousarray(samples, np.float32)
     return L.irdm_save_burst(C.byref(info), s.ctypes.data_as(C.POINTER(C.c_float)), dirname.encode())
 
+
+# ---------------------------------------------------------------- --acars (csrc/acars.cpp) ----
+class IdaReassembler:
+    """irdm_ida_reasm_*: ida_reassemble + ida_reassemble_flush per frame record, state across calls"""
+
+    def __init__(self):
+        self._L = lib()
+        self._h = self._L.irdm_ida_reasm_create()
+        if not self._h:
+            raise MemoryError("irdm_ida_reasm_create")
+
+    def push(self, idas):
+        """Ida records in stream order (ok 0 with the frame's timestamp: a frame that only flushes) -> IdaMessage list"""
+        n = len(idas)
+        arr = (Ida * max(n, 1))(*idas)
+        out = (IdaMessage * max(n, 1))()
+        k = self._L.irdm_ida_reasm_push(self._h, arr, n, out, max(n, 1))
+        if k < 0:
+            raise RuntimeError("irdm_ida_reasm_push failed")
+        return [out[i] for i in range(k)]
+
+    def push_packed(self, demods, idas):
+        n = len(demods)
+        assert len(idas) == n
+        d = (DemodPacked * max(n, 1))(*demods)
+        i = (IdaPacked * max(n, 1))(*idas)
+        out = (IdaMessage * max(n, 1))()
+        k = self._L.irdm_ida_reasm_push_packed(self._h, d, i, n, out, max(n, 1))
+        if k < 0:
+            raise RuntimeError("irdm_ida_reasm_push_packed failed")
+        return [out[j] for j in range(k)]
+
+    def close(self):
+        if self._h:
+            self._L.irdm_ida_reasm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class AcarsPrinter:
+    """irdm_acars_*: SBD extraction + ACARS lines for reassembled IDA messages; origin (sec, nsec) fixes the wall clock"""
+
+    def __init__(self, json=False, station=None, origin=None):
+        self._L = lib()
+        self._station = station.encode() if station is not None else None
+        cfg = AcarsConfig(1 if json else 0, 1 if origin is not None else 0, origin[0] if origin else 0,
+                          origin[1] if origin else 0, self._station)
+        self._h = self._L.irdm_acars_create(C.byref(cfg))
+        if not self._h:
+            raise MemoryError("irdm_acars_create")
+
+    def feed(self, msgs):
+        """IdaMessage list -> the printed bytes"""
+        n = len(msgs)
+        arr = (IdaMessage * max(n, 1))(*msgs)
+        cap = max(n, 1) * ACARS_LINE_MAX
+        buf = C.create_string_buffer(cap)
+        k = self._L.irdm_acars_feed(self._h, arr, n, buf, cap)
+        if k < 0:
+            raise RuntimeError("irdm_acars_feed failed")
+        return buf.raw[:k]
+
+    def stats(self):
+        s = AcarsStats()
+        self._L.irdm_acars_stats(self._h, C.byref(s))
+        return {n: getattr(s, n) for n, _ in AcarsStats._fields_}
+
+    def stats_text(self):
+        buf = C.create_string_buffer(1024)
+        k = self._L.irdm_acars_format_stats(self._h, buf, 1024)
+        if k < 0:
+            raise RuntimeError("irdm_acars_format_stats failed")
+        return buf.raw[:k]
+
+    def format_packed_batch(self, reasm, demods, idas, parsed=False, t0=None):
+        """irdm_format_acars_packed_batch: --acars's stdout bytes for paired DemodPacked / IdaPacked records;
+        t0: a c_uint64 shared across calls (the IDA line printer's)"""
+        n = len(demods)
+        assert len(idas) == n
+        d = (DemodPacked * max(n, 1))(*demods)
+        i = (IdaPacked * max(n, 1))(*idas)
+        cap = max(n, 1) * (RAW_LINE_MAX + ACARS_LINE_MAX)
+        buf = C.create_string_buffer(cap)
+        t = t0 if t0 is not None else C.c_uint64(0)
+        k = self._L.irdm_format_acars_packed_batch(reasm._h, self._h, d, i, n, 1 if parsed else 0, C.byref(t), buf, cap)
+        if k < 0:
+            raise RuntimeError("irdm_format_acars_packed_batch failed")
+        return buf.raw[:k]
+
+    def close(self):
+        if self._h:
+            self._L.irdm_acars_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
