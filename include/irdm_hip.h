@@ -227,6 +227,21 @@ typedef struct {
     uint8_t bch_stream[32];
 } irdm_ida_packed_t;
 
+/* frame_decode()'s result for one frame of the packed record path in 80 bytes (option "frame_records" 1): the fields
+ * irdm_decoded_t takes from the decoder, in narrow types (pos_xyz are 12-bit signed, page_msc 5 bits).  type is 0 for
+ * every frame frame_decode() does not take, and every other field is 0 then.  irdm_frame_unpack turns the record and the
+ * irdm_demod_packed_t it belongs to into the irdm_decoded_t the "decode_frames" path returns. */
+typedef struct {
+    uint8_t type;              /* 0 FRAME_UNKNOWN, 1 FRAME_IRA, 2 FRAME_IBC */
+    uint8_t sat_id, beam_id, n_pages;
+    int16_t pos_xyz[3];
+    uint16_t bch_len;
+    uint8_t timeslot, sv_blocking, bc_type, pad;
+    uint32_t iri_time;
+    uint32_t page_tmsi[12];
+    uint8_t page_msc[12];
+} irdm_frame_packed_t;
+
 /* option "chunk_marks" 1: one mark per batch of records a context pushes to its queues -- the chunk they belong to (chunks
  * counted from 0 in the order fed) and how many records each queue received, in queue order.  A chunk without bursts
  * leaves no mark; a chunk with more bursts than a batch holds leaves several, one after the other. */
@@ -309,6 +324,8 @@ int irdm_poll_demods(irdm_pipeline_t *p, irdm_demod_t *out, int max);
 int irdm_poll_demods_packed(irdm_pipeline_t *p, irdm_demod_packed_t *out, int max);   /* option "packed_records" 1 */
 /* option "parsed_records" 1: exactly one record per irdm_poll_demods_packed record, in the same order */
 int irdm_poll_ida_packed(irdm_pipeline_t *p, irdm_ida_packed_t *out, int max);
+/* option "frame_records" 1: exactly one record per irdm_poll_demods_packed record, in the same order */
+int irdm_poll_frame_packed(irdm_pipeline_t *p, irdm_frame_packed_t *out, int max);
 
 /* "tagged N bursts total" (burst_detect.c:350-351) and stat_sample_count (main.c:199) */
 uint64_t irdm_tagged_bursts(const irdm_pipeline_t *p);
@@ -463,6 +480,7 @@ int irdm_group_poll_demods_packed(irdm_group_t *g, irdm_demod_packed_t *out, int
 int irdm_group_poll_decoded(irdm_group_t *g, irdm_decoded_t *out, int max);
 int irdm_group_poll_ida(irdm_group_t *g, irdm_ida_t *out, int max);
 int irdm_group_poll_ida_packed(irdm_group_t *g, irdm_ida_packed_t *out, int max);   /* option "parsed_records" 1 */
+int irdm_group_poll_frame_packed(irdm_group_t *g, irdm_frame_packed_t *out, int max);   /* option "frame_records" 1 */
 /* what the group rests on in a single context: the marks (option "chunk_marks") and the number of chunks whose records
  * are all in the queues */
 int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max);
@@ -481,6 +499,12 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         them: irdm_poll_ida_packed returns one irdm_ida_packed_t per compact frame record, written to
  *                         pinned memory by that kernel.  With "decode_frames", "decode_ida" or "keep_frame_samples" the
  *                         chain is on the full-record path and neither kind of compact record is queued.
+ *   "frame_records"       0/1, default 0: 1 = "packed_records", and frame_decode() (access code, IBC / IRA blocks, BCH(31,21)
+ *                         with Chase on the LLRs) of every frame on the device, behind the demodulator, on its bits and
+ *                         LLRs where it leaves them: irdm_poll_frame_packed returns one irdm_frame_packed_t per compact
+ *                         frame record, written to pinned memory by that kernel.  May be combined with "parsed_records"
+ *                         (both kernels run on the same frames).  "decode_frames", "decode_ida" and "keep_frame_samples"
+ *                         win as for "parsed_records".
  *   "chunk_marks"         0/1, default 0: see irdm_chunk_mark_t (what a group merges its members' records with)
  *   "decode_frames" / "decode_ida"   0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
@@ -567,6 +591,10 @@ int irdm_format_ida(const irdm_ida_t *b, uint64_t *t0_io, char *buf, size_t cap)
 long long irdm_format_parsed_packed_batch(const irdm_demod_packed_t *f, const irdm_ida_packed_t *idas, int n,
                                           const char *file_info, uint64_t *t0_io, char *buf, size_t cap);
 
+/* The irdm_decoded_t the "decode_frames" path makes of the same frame from a compact pair: lat / lon / alt with the host
+ * libm (parse_ira's expressions), id / timestamp / frequency from the frame record. */
+void irdm_frame_unpack(const irdm_frame_packed_t *fr, const irdm_demod_packed_t *f, irdm_decoded_t *out);
+
 /* 3c. IDA reassembly, SBD and ACARS (--acars, --acars-json)            */
 /* ------------------------------------------------------------------ */
 /* Host C, once per IDA burst and once per message: the reference's ida_reassemble / ida_reassemble_flush
@@ -630,6 +658,47 @@ long long irdm_format_acars_packed_batch(irdm_ida_reasm_t *r, irdm_acars_t *a, c
 /* the same from full records and the "decode_ida" path's irdm_ida_t (--save-bursts) */
 long long irdm_format_acars_batch(irdm_ida_reasm_t *r, irdm_acars_t *a, const irdm_demod_t *f, const irdm_ida_t *idas,
                                   int n, int parsed, uint64_t *t0_io, char *buf, size_t cap);
+
+/* 3d. Doppler positioning (--position)                                  */
+/* ------------------------------------------------------------------ */
+/* Host C: the reference's positioning engine (doppler_pos.c) -- per-satellite measurement buffers of decoded IRA frames,
+ * channel-frequency and velocity estimation, the motion-based visibility cluster, iterated weighted least squares with
+ * height aiding, outlier and per-satellite screening and the solution-jump guard -- with all of its state in one object
+ * (one thread each).  Doubles are those of the reference's own build, operation for operation. */
+
+/* doppler_solution_t (doppler_pos.h) */
+typedef struct {
+    double lat, lon;           /* degrees */
+    double alt;                /* metres */
+    double hdop;
+    int32_t n_measurements, n_satellites, converged, pad;
+} irdm_position_t;
+
+typedef struct irdm_doppler irdm_doppler_t;
+/* doppler_pos_init + doppler_pos_set_height(height_m) (main.c:597-604) */
+irdm_doppler_t *irdm_doppler_create(double height_m);
+void irdm_doppler_destroy(irdm_doppler_t *d);
+/* doppler_pos_add_measurement(&f->ira, f->frequency, f->timestamp) for a type 1 (IRA) record (main.c:333-343); other
+ * records are ignored.  Returns 1 when the measurement was stored, 0 when it was not. */
+int irdm_doppler_add(irdm_doppler_t *d, const irdm_decoded_t *f);
+/* doppler_pos_solve: 1 and a solution, or 0 (out still holds the satellite and measurement counts).  The solver's
+ * unconditional "DOPPLER: ... FAIL" lines are kept for the formatters below and dropped here. */
+int irdm_doppler_solve(irdm_doppler_t *d, irdm_position_t *out);
+/* --position's schedule runs on stream time: tick T = 10, 20, ... s after start_time_ns (the context's
+ * irdm_start_time_ns).  Set before the first batch. */
+void irdm_doppler_set_origin(irdm_doppler_t *d, uint64_t start_time_ns);
+/* --position for one poll batch, in output order: before the first frame whose timestamp - start_time_ns >= T s, the
+ * solve for tick T, printed as the reference's stats thread prints it (main.c:506-519): the POSITION line on success, the
+ * waiting line on failure when T % 60 == 0.  Then the frame's IRA record, if any, into the buffers (frames with ok set;
+ * frame_decode's failures give type 0).  Returns the stderr bytes (NUL-terminated), or -1 when cap is too small.
+ * cap >= 4096 per tick the batch crosses always suffices. */
+long long irdm_format_doppler_packed_batch(irdm_doppler_t *d, const irdm_demod_packed_t *f, const irdm_frame_packed_t *fr,
+                                           int n, char *buf, size_t cap);
+/* the same from the "decode_frames" path's records (--save-bursts) */
+long long irdm_format_doppler_batch(irdm_doppler_t *d, const irdm_decoded_t *f, int n, char *buf, size_t cap);
+/* the end of the stream at end_ns (the clock of the timestamps: start_time_ns + samples / rate): the ticks up to it not yet
+ * run, then one final solve, always printed (its POSITION line, or the waiting line).  Returns the bytes, or -1. */
+long long irdm_doppler_finish(irdm_doppler_t *d, uint64_t end_ns, char *buf, size_t cap);
 
 /* --save-bursts (qpsk_demod.c:339-389): writes <dir>/<timestamp>_<freq>_<id>_<DL|UL|UN>.cf32 (the frame's cf32 samples at
  * 250 kHz) and the matching .meta text file for one downmixed frame (info->drop_reason == 0), creating dir if needed.

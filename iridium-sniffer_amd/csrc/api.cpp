@@ -12,6 +12,7 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     if (!strcmp(key, "keep_frame_samples")) { p->keep_frame_samples = value; return 0; }
     if (!strcmp(key, "packed_records")) { p->packed_records = value; return 0; }
     if (!strcmp(key, "parsed_records")) { p->parsed_records = value; return 0; }
+    if (!strcmp(key, "frame_records")) { p->frame_records = value; return 0; }
     if (!strcmp(key, "chunk_marks")) { p->chunk_marks = value ? 1 : 0; if (!value) p->q_marks.clear(); return 0; }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
@@ -242,6 +243,26 @@ extern "C" void irdm_ida_unpack(const irdm_ida_packed_t *ida, const irdm_demod_p
     fr.confidence = f->confidence;
     fr.n_payload_symbols = f->n_payload_symbols;
     *out = finish_ida(d, fr);
+}
+
+extern "C" void irdm_frame_unpack(const irdm_frame_packed_t *fr, const irdm_demod_packed_t *f, irdm_decoded_t *out)
+{
+    if (!fr || !f || !out) return;
+    // the DecodedOut the decode_frames path would have, then its finish_decoded with the frame fields that path reads
+    DecodedOut d;
+    memset(&d, 0, sizeof(d));
+    d.type = fr->type;
+    d.sat_id = fr->sat_id;
+    d.beam_id = fr->beam_id;
+    for (int k = 0; k < 3; k++) d.pos_xyz[k] = fr->pos_xyz[k];
+    d.n_pages = fr->n_pages;
+    for (int k = 0; k < 12; k++) { d.page_tmsi[k] = fr->page_tmsi[k]; d.page_msc[k] = fr->page_msc[k]; }
+    d.timeslot = fr->timeslot;
+    d.sv_blocking = fr->sv_blocking;
+    d.bc_type = fr->bc_type;
+    d.iri_time = fr->iri_time;
+    d.bch_len = fr->bch_len;
+    *out = finish_decoded(d, f->id, f->timestamp, f->center_frequency);
 }
 
 namespace {

@@ -716,6 +716,241 @@ __global__ __launch_bounds__(64) void ida_packed_kernel(const DemodOut *__restri
     emit();
 }
 
+// ---------------------------------------------------------------------------
+// frame_decode() on the packed record path (option frame_records): the same decode as frame_decode_kernel, ONE WAVEFRONT
+// PER FRAME, its FramePacked record written straight into pinned host memory.
+//   * the access code: lanes 0..23 and one ballot; the frame's bits and LLRs behind it are staged in LDS.
+//   * IBC (header BCH(7,3) wavefront-uniform), then IRA: one lane per BCH(31,21) block -- the IBC head's two, the IRA
+//     head's three, and the two of every more_blocks pair the stream's length and cap allow -- all decoded at once.
+//     frame_decode() stops at the first block that fails (decode or parity) and keeps whole pairs before it: what it
+//     accepts is a prefix, wavefront-uniform arithmetic on one ballot.
+//   * Chase (:224-295): the blocks that need it, in block order, each with its 31 flip masks on lanes 1..31 and the
+//     lowest mask that decodes winning (the serial loop's first success); the five least reliable positions are chosen
+//     by the block's own lane, the serial partial selection sort literally (its swaps decide ties), over the block's
+//     LLRs in LDS.  Blocks behind the first failure are never needed and not tried.
+//   * the accepted blocks' 21 data bits go to LDS; parse_ibc / parse_ira read them there, one lane per paging block.
+// The frame's bits and LLRs are the DemodOut demod_par_kernel wrote on the device (keep_bits).  The record is complete in
+// pinned memory, behind a system-scope fence, when the stream reaches the host's synchronisation -- as demod_export's.
+// ---------------------------------------------------------------------------
+namespace {
+
+constexpr int kFrameBlocks = 23;      // IRA: 3 head blocks + 10 more_blocks pairs (63 + 10 * 42 <= 512 bits); IBC: <= 8
+
+// where a block's 32 bits lie among the data bits: gather_block(data + base, first, stride)
+struct BlockAt {
+    int base, first, stride;
+};
+
+__device__ __forceinline__ int block_bit(const BlockAt &g, int k)           // data bit of block position k (0..31)
+{
+    return g.base + 2 * (g.first - g.stride * (k >> 1)) + (k & 1);
+}
+
+__device__ __forceinline__ bool ra_table_ok(unsigned syn, const int2 *__restrict__ syn_ra)
+{
+    return syn == 0 || (syn < 1024 && syn_ra[syn].x >= 0);
+}
+
+// chase_bch_decode_p + check_parity32 of blocks 0..n-1 (lane j: block j at g): the ballot of the blocks that pass, in
+// block order up to the first one that does not (bits behind it are not meaningful); lane j's corrected codeword in *cor_out
+__device__ __forceinline__ unsigned long long decode_blocks(int lane, int n, const BlockAt &g, const uint8_t *s_bits,
+                                                            const float *s_llr, float (*s_cl)[32], uint8_t (*s_pos)[32],
+                                                            const int2 *__restrict__ syn_ra, unsigned *cor_out)
+{
+    const bool mine = lane < n;
+    unsigned cw = 0, par = 0, cor = 0;
+    bool good = false, need = false;
+    if (mine) {
+        for (int k = 0; k < 31; k++) {
+            const int idx = block_bit(g, k);
+            cw = (cw << 1) | (unsigned)s_bits[idx];
+            s_cl[lane][k] = s_llr[idx];
+        }
+        par = s_bits[block_bit(g, 31)];
+        const unsigned syn = gf2_rem(kPolyRa, 11, cw);
+        if (syn == 0) { cor = cw; good = true; }
+        else if (syn < 1024 && syn_ra[syn].x >= 0) { cor = cw ^ (unsigned)syn_ra[syn].y; good = true; }
+        else need = true;
+    }
+    // blocks behind one that decodes but fails its parity are never looked at
+    const unsigned long long bad = __builtin_amdgcn_ballot_w64(mine && good && !parity_ok(cor, par));
+    const unsigned long long before = bad ? (1ull << __builtin_ctzll(bad)) - 1 : ~0ull;
+    need = need && ((before >> lane) & 1);
+    unsigned fm[kChase] = { 0, 0, 0, 0, 0 };
+    if (need) {
+        for (int i = 0; i < 31; i++) s_pos[lane][i] = (uint8_t)i;
+        for (int i = 0; i < kChase; i++) {
+            int mi = i;
+            float mv = s_cl[lane][s_pos[lane][i]];
+            for (int j = i + 1; j < 31; j++) {
+                const float v = s_cl[lane][s_pos[lane][j]];
+                if (v < mv) { mv = v; mi = j; }
+            }
+            const uint8_t t = s_pos[lane][i]; s_pos[lane][i] = s_pos[lane][mi]; s_pos[lane][mi] = t;
+        }
+#pragma unroll
+        for (int i = 0; i < kChase; i++) fm[i] = 1u << (30 - s_pos[lane][i]);
+    }
+    unsigned long long pend = __builtin_amdgcn_ballot_w64(need);
+    while (pend) {
+        const int c = __builtin_ctzll(pend);
+        pend &= pend - 1;
+        unsigned fl = (unsigned)__shfl((int)cw, c);
+#pragma unroll
+        for (int k = 0; k < kChase; k++) {
+            const unsigned fk = (unsigned)__shfl((int)fm[k], c);
+            if (lane & (1 << k)) fl ^= fk;
+        }
+        const unsigned syn = gf2_rem(kPolyRa, 11, fl);
+        const bool hit = lane >= 1 && lane < 32 && ra_table_ok(syn, syn_ra);
+        const unsigned long long hits = __builtin_amdgcn_ballot_w64(hit);
+        if (!hits) break;
+        const int m = __builtin_ctzll(hits);
+        const unsigned res = (unsigned)__shfl((int)(syn == 0 ? fl : fl ^ (unsigned)syn_ra[hit ? syn : 0].y), m);
+        if (lane == c) { cor = res; good = true; }
+        if (!parity_ok(res, (unsigned)__shfl((int)par, c))) break;
+    }
+    *cor_out = cor;
+    return __builtin_amdgcn_ballot_w64(mine && good && parity_ok(cor, par));
+}
+
+// the 21 data bits of a corrected block into the stream (append21), one bit per byte
+__device__ __forceinline__ void put21(uint8_t *s_st, int at, unsigned corrected)
+{
+    const unsigned d = (corrected >> 10) & 0x1fffffu;
+    for (int i = 0; i < 21; i++) s_st[at + i] = (uint8_t)((d >> (20 - i)) & 1u);
+}
+
+__device__ __forceinline__ unsigned lfield(const uint8_t *s_st, int k, int n)                   // extract_uint
+{
+    unsigned v = 0;
+    for (int i = 0; i < n; i++) v = (v << 1) | s_st[k + i];
+    return v;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void frame_packed_kernel(const DemodOut *__restrict__ frames, int n_frames,
+                                                          const int2 *__restrict__ syn_ra, const int2 *__restrict__ syn_hdr,
+                                                          FramePacked *__restrict__ hp_frame)
+{
+    __shared__ uint8_t s_bits[kMaxBits];                    // the hard bits behind the access code
+    __shared__ float s_llr[kMaxBits];
+    __shared__ float s_cl[kFrameBlocks][32];                // a block's 31 LLRs in codeword order
+    __shared__ uint8_t s_pos[kFrameBlocks][32];             // its selection sort's permutation
+    __shared__ uint8_t s_st[512];                           // the decoded stream, one bit per byte (:466, :545)
+    __shared__ __attribute__((aligned(4))) FramePacked s_rec;
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (b >= n_frames) return;
+    if (lane < 20) reinterpret_cast<uint32_t *>(&s_rec)[lane] = 0;
+    const DemodOut &f = frames[b];
+    const int n_bits = f.ok ? 2 * f.n_symbols : 0;
+    // the record: type 0 (FRAME_UNKNOWN) for every frame frame_decode() does not take
+    auto emit = [&]() {
+        __syncthreads();
+        if (lane < 20) reinterpret_cast<uint32_t *>(hp_frame + b)[lane] = reinterpret_cast<const uint32_t *>(&s_rec)[lane];
+        __threadfence_system();
+    };
+    if (n_bits < 24 || n_bits > kMaxBits) { emit(); return; }
+    // ---- access codes (:428-431)
+    const unsigned long long am = __builtin_amdgcn_ballot_w64(lane < 24 && (f.bits[lane < 24 ? lane : 0] & 1));
+    unsigned acc = 0;
+    for (int k = 0; k < 24; k++) acc = (acc << 1) | ((unsigned)(am >> k) & 1u);
+    if (acc != 0x3030F3u && acc != 0xCC3CFCu) { emit(); return; }
+    const int data_len = n_bits - 24;
+    for (int i = lane; i < data_len; i += 64) {
+        s_bits[i] = f.bits[24 + i] & 1;
+        s_llr[i] = f.llr[24 + i];
+    }
+    __syncthreads();
+    unsigned cor;
+
+    if (data_len >= 6 + 64) {                                           // ---- IBC (:441-505)
+        unsigned hv = 0;
+        for (int k = 0; k < 6; k++) hv = (hv << 1) | (unsigned)s_bits[k];
+        const unsigned hs = gf2_rem(kPolyHdr, 5, hv);
+        bool hdr_ok = hs == 0;
+        if (!hdr_ok && hs < 16 && syn_hdr[hs].x >= 0) { hv ^= (unsigned)syn_hdr[hs].y; hdr_ok = true; }
+        if (hdr_ok) {
+            // the head pair, and the more_blocks pairs the 262-bit limit and the 256-bit stream allow
+            const int ibc_max = data_len < 262 ? data_len : 262;
+            int n_pairs = 1;
+            while (6 + 64 * n_pairs + 64 <= ibc_max && 42 * n_pairs + 42 <= 256) n_pairs++;
+            const BlockAt g{ 6 + 64 * (lane >> 1), 31 - (lane & 1), 2 };
+            const unsigned long long ok = decode_blocks(lane, 2 * n_pairs, g, s_bits, s_llr, s_cl, s_pos, syn_ra, &cor);
+            if ((ok & 3u) == 3u) {
+                int n_acc = 1;
+                while (n_acc < n_pairs && ((ok >> (2 * n_acc)) & 3u) == 3u) n_acc++;
+                if (lane < 2 * n_acc) put21(s_st, 21 * lane, cor);
+                __syncthreads();
+                if (lane == 0) {                                        // parse_ibc (:368-393); len >= 42
+                    const int len = 42 * n_acc;
+                    s_rec.type = 2;
+                    s_rec.bch_len = (uint16_t)len;
+                    s_rec.bc_type = (uint8_t)((hv >> 4) & 7u);
+                    s_rec.sat_id = (uint8_t)lfield(s_st, 0, 7);
+                    s_rec.beam_id = (uint8_t)lfield(s_st, 7, 6);
+                    s_rec.timeslot = s_st[14];
+                    s_rec.sv_blocking = s_st[15];
+                    if (len >= 84 && lfield(s_st, 42, 6) == 1u) s_rec.iri_time = lfield(s_st, 52, 32);
+                }
+                emit();
+                return;
+            }
+        }
+    }
+
+    if (data_len >= 96) {                                               // ---- IRA (:514-595)
+        int n_pairs = 0;
+        while (96 + 64 * n_pairs + 64 <= data_len && 63 + 42 * n_pairs + 42 <= 512) n_pairs++;
+        const BlockAt g = lane < 3 ? BlockAt{ 0, 47 - lane, 3 } : BlockAt{ 96 + 64 * ((lane - 3) >> 1), 31 - ((lane - 3) & 1), 2 };
+        const unsigned long long ok = decode_blocks(lane, 3 + 2 * n_pairs, g, s_bits, s_llr, s_cl, s_pos, syn_ra, &cor);
+        if ((ok & 7u) == 7u) {
+            int n_acc = 0;
+            while (n_acc < n_pairs && ((ok >> (3 + 2 * n_acc)) & 3u) == 3u) n_acc++;
+            const int len = 63 + 42 * n_acc;
+            if (lane < 3 + 2 * n_acc) put21(s_st, 21 * lane, cor);
+            __syncthreads();
+            // parse_ira (:317-366): paging block p on lane p; the list ends at the first all-ones block
+            const int off = 63 + 42 * lane;
+            const bool page = lane < 12 && off + 42 <= len;
+            bool all1 = true;
+            unsigned tmsi = 0, msc = 0;
+            if (page) {
+                for (int k = 0; k < 42; k++) all1 = all1 && s_st[off + k];
+                tmsi = lfield(s_st, off, 32);
+                msc = lfield(s_st, off + 34, 5);
+            }
+            const int n_pages = __builtin_ctzll(~__builtin_amdgcn_ballot_w64(page && !all1));
+            if (lane < n_pages) {
+                s_rec.page_tmsi[lane] = tmsi;
+                s_rec.page_msc[lane] = (uint8_t)msc;
+            }
+            if (lane == 0) {
+                s_rec.type = 1;
+                s_rec.bch_len = (uint16_t)len;
+                s_rec.sat_id = (uint8_t)lfield(s_st, 0, 7);
+                s_rec.beam_id = (uint8_t)lfield(s_st, 7, 6);
+                for (int k = 0; k < 3; k++) {                           // extract_signed12
+                    const int mag = (int)lfield(s_st, 13 + 12 * k + 1, 11);
+                    s_rec.pos_xyz[k] = (int16_t)(s_st[13 + 12 * k] ? mag - (1 << 11) : mag);
+                }
+                s_rec.n_pages = (uint8_t)n_pages;
+            }
+        }
+    }
+    emit();
+}
+
+int launch_frame_packed(const DemodOut *frames, int n_frames, const int2 *syn_ra, const int2 *syn_hdr, FramePacked *hp_frame,
+                        hipStream_t stream)
+{
+    if (n_frames <= 0) return 0;
+    hipLaunchKernelGGL(frame_packed_kernel, dim3(n_frames), dim3(64), 0, stream, frames, n_frames, syn_ra, syn_hdr, hp_frame);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_ida_packed(const DemodOut *frames, int n_frames, const int2 *syn_da, const int2 *syn_l1, const int2 *syn_l2,
                       const int2 *syn_l3, IdaPacked *hp_ida, hipStream_t stream)
 {

@@ -574,14 +574,21 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
     // bits 8 per byte, no LLRs): written into pinned host memory by the demodulator's last kernel itself
     // parsed_records: the same, and ida_decode() of every frame behind it, on the bits and LLRs the demodulator leaves
     // on the device (IdaPacked, 88 bytes per burst, written to pinned memory by that kernel)
-    b.packed = (p->packed_records || p->parsed_records) && !p->decode_frames && !p->decode_ida && !p->keep_frame_samples;
+    // frame_records: likewise frame_decode() of every frame (FramePacked, 80 bytes per burst, frame_packed_kernel); with
+    // parsed_records as well, both kernels read the same device-resident frames, one behind the other
+    b.packed = (p->packed_records || p->parsed_records || p->frame_records) && !p->decode_frames && !p->decode_ida &&
+               !p->keep_frame_samples;
     b.parsed = b.packed && p->parsed_records;
+    b.framed = b.packed && p->frame_records;
     if (launch_demod(b.d_work, nb, b.d_frames, p->cfg.use_gardner, p->sps, b.d_demod_ws, b.d_demod, st,
-                     b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr, b.parsed ? 1 : 0) != 0)
+                     b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr, b.parsed || b.framed ? 1 : 0) != 0)
         return -1;
     IRDM_HIP_CHECK(hipEventRecord(b.ev[3], st));
-    if (b.parsed)
-        return launch_ida_packed(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_ida, st);
+    if (b.parsed &&
+        launch_ida_packed(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_ida, st) != 0)
+        return -1;
+    if (b.framed && launch_frame_packed(b.d_demod, nb, p->d_syn_ra, p->d_syn_hdr, b.hp_frame, st) != 0)
+        return -1;
     if (b.packed) return 0;
     if (p->decode_frames) {
         // post-demod bit layer on the demodulator's device-resident output (frames that failed the unique word
@@ -695,6 +702,11 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
                 static_assert(sizeof(irdm_ida_packed_t) == sizeof(IdaPacked), "the device record is the public one");
                 p->q_ida_packed.emplace_back();
                 memcpy(&p->q_ida_packed.back(), &b.hp_ida[i], sizeof(IdaPacked));
+            }
+            if (b.framed) {
+                static_assert(sizeof(irdm_frame_packed_t) == sizeof(FramePacked), "the device record is the public one");
+                p->q_frame_packed.emplace_back();
+                memcpy(&p->q_frame_packed.back(), &b.hp_frame[i], sizeof(FramePacked));
             }
             if (d.n_symbols > 0) {
                 const double duration = (double)d.n_symbols / 25000;

@@ -48,6 +48,7 @@ void pipeline_free(irdm_pipeline *p)
         if (b.hp_demod) (void)hipHostFree(b.hp_demod);
         if (b.hp_packed) (void)hipHostFree(b.hp_packed);
         if (b.hp_ida) (void)hipHostFree(b.hp_ida);
+        if (b.hp_frame) (void)hipHostFree(b.hp_frame);
         if (b.owns_buffers) {
             void *own[] = { b.d_work, b.d_tiles, b.d_dec, b.d_lpf, b.d_rrc_ws, b.d_frames, b.d_demod_ws, b.d_demod,
                             b.d_decoded, b.d_ida };
@@ -453,6 +454,7 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
         ok = ok && hipHostMalloc(reinterpret_cast<void **>(&b.hp_demod), sizeof(DemodOut) * (size_t)p->burst_cap, hipHostMallocDefault) == hipSuccess;
         ok = ok && hipHostMalloc(reinterpret_cast<void **>(&b.hp_packed), sizeof(DemodPacked) * (size_t)p->burst_cap, hipHostMallocDefault) == hipSuccess;
         ok = ok && hipHostMalloc(reinterpret_cast<void **>(&b.hp_ida), sizeof(IdaPacked) * (size_t)p->burst_cap, hipHostMallocDefault) == hipSuccess;
+        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&b.hp_frame), sizeof(FramePacked) * (size_t)p->burst_cap, hipHostMallocDefault) == hipSuccess;
         ok = ok && hipHostMalloc(reinterpret_cast<void **>(&b.hp_flag), 64, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess &&
              hipHostGetDevicePointer(reinterpret_cast<void **>(&b.hp_flag_dev), b.hp_flag, 0) == hipSuccess;
         if (ok) memset(b.hp_flag, 0, 64);

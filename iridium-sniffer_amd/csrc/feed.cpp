@@ -368,6 +368,12 @@ extern "C" int irdm_poll_ida_packed(irdm_pipeline_t *p, irdm_ida_packed_t *out, 
     return drain(p->q_ida_packed, out, max);
 }
 
+extern "C" int irdm_poll_frame_packed(irdm_pipeline_t *p, irdm_frame_packed_t *out, int max)
+{
+    if (!p || !out || max < 0) return -1;
+    return drain(p->q_frame_packed, out, max);
+}
+
 extern "C" int irdm_poll_bursts(irdm_pipeline_t *p, irdm_burst_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;

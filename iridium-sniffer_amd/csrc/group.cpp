@@ -126,6 +126,7 @@ struct ChunkRecords {
     std::vector<irdm_demod_t> demods;
     std::vector<irdm_demod_packed_t> packed;
     std::vector<irdm_ida_packed_t> ida_packed;          // parsed_records: one per packed record
+    std::vector<irdm_frame_packed_t> frame_packed;      // frame_records: one per packed record
     std::vector<irdm_decoded_t> decoded;
     std::vector<irdm_ida_t> ida;
 };
@@ -169,7 +170,7 @@ struct irdm_group {
     bool closed = false;
     bool broken = false;                 // a transfer or a staging step failed midway: the counters of the chunks staged so far
                                          // may be ahead of what was fed -- every later stage / feed / flush call fails cleanly
-    int loopback = 0, keep_samples = 0, parsed = 0;
+    int loopback = 0, keep_samples = 0, parsed = 0, framed = 0;
     // merged output
     std::map<uint64_t, ChunkRecords> store;
     uint64_t next_emit = 0;
@@ -179,6 +180,7 @@ struct irdm_group {
     std::deque<irdm_demod_t> q_demods;
     std::deque<irdm_demod_packed_t> q_packed;
     std::deque<irdm_ida_packed_t> q_ida_packed;
+    std::deque<irdm_frame_packed_t> q_frame_packed;
     std::deque<irdm_decoded_t> q_decoded;
     std::deque<irdm_ida_t> q_ida;
     uint64_t st_hops = 0, st_hop_bytes = 0, st_scatter_bytes = 0, st_overlap_bytes = 0, st_late = 0;
@@ -258,6 +260,13 @@ int drain_member(irdm_group *g, int r)
                 if (mk.n_packed && irdm_poll_ida_packed(mb.p, cr.ida_packed.data() + at, (int)mk.n_packed) != (int)mk.n_packed)
                     return -1;
             }
+            if (g->framed) {
+                at = cr.frame_packed.size();
+                cr.frame_packed.resize(at + mk.n_packed);
+                if (mk.n_packed &&
+                    irdm_poll_frame_packed(mb.p, cr.frame_packed.data() + at, (int)mk.n_packed) != (int)mk.n_packed)
+                    return -1;
+            }
             at = cr.decoded.size();
             cr.decoded.resize(at + mk.n_decoded);
             if (mk.n_decoded && irdm_poll_decoded(mb.p, cr.decoded.data() + at, (int)mk.n_decoded) != (int)mk.n_decoded) return -1;
@@ -286,6 +295,7 @@ void emit_ready(irdm_group *g)
             g->q_demods.insert(g->q_demods.end(), cr.demods.begin(), cr.demods.end());
             g->q_packed.insert(g->q_packed.end(), cr.packed.begin(), cr.packed.end());
             g->q_ida_packed.insert(g->q_ida_packed.end(), cr.ida_packed.begin(), cr.ida_packed.end());
+            g->q_frame_packed.insert(g->q_frame_packed.end(), cr.frame_packed.begin(), cr.frame_packed.end());
             g->q_decoded.insert(g->q_decoded.end(), cr.decoded.begin(), cr.decoded.end());
             g->q_ida.insert(g->q_ida.end(), cr.ida.begin(), cr.ida.end());
             g->store.erase(it);
@@ -681,6 +691,7 @@ extern "C" int irdm_group_set_option(irdm_group_t *g, const char *key, int value
     for (Member &mb : g->m) rc |= irdm_set_option(mb.p, key, value);
     if (rc == 0 && !strcmp(key, "keep_frame_samples")) g->keep_samples = value;
     if (rc == 0 && !strcmp(key, "parsed_records")) g->parsed = value;
+    if (rc == 0 && !strcmp(key, "frame_records")) g->framed = value;
     return rc ? -1 : 0;
 }
 
@@ -781,6 +792,12 @@ extern "C" int irdm_group_poll_ida_packed(irdm_group_t *g, irdm_ida_packed_t *ou
 {
     if (!g || !out || max < 0) return -1;
     return drain(g->q_ida_packed, out, max);
+}
+
+extern "C" int irdm_group_poll_frame_packed(irdm_group_t *g, irdm_frame_packed_t *out, int max)
+{
+    if (!g || !out || max < 0) return -1;
+    return drain(g->q_frame_packed, out, max);
 }
 
 extern "C" int irdm_group_poll_decoded(irdm_group_t *g, irdm_decoded_t *out, int max)

@@ -110,11 +110,13 @@ struct BatchCtx {
     DemodOut *hp_demod;
     DemodPacked *hp_packed;                 // packed_records: the demodulator's result without LLRs, bits 8 per byte (pinned; written by demod_par_kernel)
     IdaPacked *hp_ida;                      // parsed_records: ida_decode() of each of them (pinned; written by ida_packed_kernel)
+    FramePacked *hp_frame;                  // frame_records: frame_decode() of each of them (pinned; written by frame_packed_kernel)
     uint32_t *hp_flag, *hp_flag_dev;    // [0] sequence number the helper publishes, [1] time-out flag of the waiting kernel
     int4 *hp_rot_new, *hp_rot_new_dev, *d_rot_new;   // (bin, row, from, to) of the checkpoint runs this batch has to build: mapped pinned / device
     uint32_t cfo_seq;
     bool packed;                 // this batch came back as DemodPacked records
     bool parsed;                 // ... and IdaPacked records
+    bool framed;                 // ... and FramePacked records
     bool cfo_on_device;          // this batch's libm step ran on the device: h_cfreq is filled from the returned records
     std::vector<double> h_cfreq;
     std::vector<irdm_burst_t> recs;
@@ -306,6 +308,8 @@ struct irdm_pipeline {
     int packed_records;         // option: queue irdm_demod_packed_t records only
     int parsed_records;         // option: packed_records, and one irdm_ida_packed_t per irdm_demod_packed_t
     std::deque<irdm_ida_packed_t> q_ida_packed;
+    int frame_records;          // option: packed_records, and one irdm_frame_packed_t per irdm_demod_packed_t
+    std::deque<irdm_frame_packed_t> q_frame_packed;
     // option "chunk_marks": one mark per batch of records pushed to the queues above -- which chunk (in the order fed)
     // they belong to and how many records went to each queue -- for a caller that merges the records of several contexts
     // in stream order (group.cpp)

@@ -196,4 +196,17 @@ struct IdaPacked {
 };
 static_assert(sizeof(IdaPacked) == 88 && sizeof(IdaPacked) % 4 == 0, "written as 22 words, one per lane");
 
+// the DecodedOut of one frame in 80 bytes (option frame_records): written into pinned host memory by frame_packed_kernel,
+// word for word the public irdm_frame_packed_t (pos_xyz are 12-bit signed, page_msc 5 bits, bch_len <= 512)
+struct FramePacked {
+    uint8_t type, sat_id, beam_id, n_pages;
+    int16_t pos_xyz[3];
+    uint16_t bch_len;
+    uint8_t timeslot, sv_blocking, bc_type, pad;
+    uint32_t iri_time;
+    uint32_t page_tmsi[12];
+    uint8_t page_msc[12];
+};
+static_assert(sizeof(FramePacked) == 80 && sizeof(FramePacked) % 4 == 0, "written as 20 words, one per lane");
+
 }  // namespace irdm

@@ -4,13 +4,15 @@
  * Mirrors the reference's file-mode surface (options.c:186-551, main.c:223-284, frame_output.c:160-199):
  *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
- *                         [--parsed] [--acars] [--acars-json] [--station ID]
+ *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
- * (burst_detect.c:350-351, the line test-configurations.sh:140 greps).  Everything between the file
+ * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
+ * "POSITION:" lines on stderr (main.c:506-519), solved every 10 s of stream time instead of wall-clock time.  Everything between the file
  * read and the line printer runs on the GPU through the C-ABI in include/irdm_hip.h; there is no CPU
  * path here (the reference's own --no-gpu binary is the CPU path).
  */
+#include <err.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -135,6 +137,8 @@ static irdm_group_t *g_group;
 #define irdm_poll_frames(p, o, s, m) (g_group ? irdm_group_poll_frames(g_group, o, s, m) : irdm_poll_frames(p, o, s, m))
 #define irdm_poll_ida_packed(p, o, m) (g_group ? irdm_group_poll_ida_packed(g_group, o, m) : irdm_poll_ida_packed(p, o, m))
 #define irdm_poll_ida(p, o, m) (g_group ? irdm_group_poll_ida(g_group, o, m) : irdm_poll_ida(p, o, m))
+#define irdm_poll_frame_packed(p, o, m) (g_group ? irdm_group_poll_frame_packed(g_group, o, m) : irdm_poll_frame_packed(p, o, m))
+#define irdm_poll_decoded(p, o, m) (g_group ? irdm_group_poll_decoded(g_group, o, m) : irdm_poll_decoded(p, o, m))
 
 /* --parsed (main.c:322-331): per frame the IDA line where ida_decode() succeeds, the RAW line otherwise */
 static int g_parsed;
@@ -143,6 +147,15 @@ static int g_parsed;
 static irdm_ida_reasm_t *g_reasm;
 static irdm_acars_t *g_acars;
 static char g_acars_line[256 * (IRDM_RAW_LINE_MAX + IRDM_ACARS_LINE_MAX)];
+/* --position (main.c:333-343, :506-519): every frame's IRA record into the Doppler solver, its POSITION lines on stderr */
+static irdm_doppler_t *g_dop;
+static char g_dop_text[1 << 20];
+
+static void position_out(long long len)
+{
+    if (len < 0) { fprintf(stderr, "--position: formatting failed\n"); exit(1); }
+    if (len > 0) fwrite(g_dop_text, 1, (size_t)len, stderr);
+}
 
 static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, uint64_t *t0, char *line, size_t cap)
 {
@@ -151,8 +164,14 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         /* RAW lines need no LLRs: compact records (hard bits 8 per byte), 176 bytes per frame instead of 4.5 KB */
         static irdm_demod_packed_t dp[256];
         static irdm_ida_packed_t ip[256];
+        static irdm_frame_packed_t fp[256];
         while ((n = irdm_poll_demods_packed(p, dp, 256)) > 0) {
             long long len;
+            if (g_dop) {
+                /* one compact frame_decode() record per compact frame record, decoded on the GPU (option frame_records) */
+                if (irdm_poll_frame_packed(p, fp, n) != n) { fprintf(stderr, "--position: frame records out of step\n"); exit(1); }
+                position_out(irdm_format_doppler_packed_batch(g_dop, dp, fp, n, g_dop_text, sizeof g_dop_text));
+            }
             if (g_acars) {
                 if (irdm_poll_ida_packed(p, ip, n) != n) { fprintf(stderr, "--acars: IDA records out of step\n"); exit(1); }
                 len = irdm_format_acars_packed_batch(g_reasm, g_acars, dp, ip, n, g_parsed, t0, g_acars_line, sizeof g_acars_line);
@@ -170,8 +189,14 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         }
     }
     static irdm_ida_t ida[256];
+    static irdm_decoded_t dec[256];
     while ((n = irdm_poll_demods(p, d, 256)) > 0) {
         long long len = 0;
+        if (g_dop) {
+            /* the full-record path (--save-bursts): option decode_frames, one irdm_decoded_t per frame record */
+            if (irdm_poll_decoded(p, dec, n) != n) { fprintf(stderr, "--position: frame records out of step\n"); exit(1); }
+            position_out(irdm_format_doppler_batch(g_dop, dec, n, g_dop_text, sizeof g_dop_text));
+        }
         if (g_acars) {
             if (irdm_poll_ida(p, ida, n) != n) { fprintf(stderr, "--acars: IDA records out of step\n"); exit(1); }
             len = irdm_format_acars_batch(g_reasm, g_acars, d, ida, n, g_parsed, t0, g_acars_line, sizeof g_acars_line);
@@ -230,6 +255,8 @@ int main(int argc, char **argv)
     int acars = 0, acars_json = 0, has_origin = 0;
     const char *station = NULL;
     long long origin_sec = 0, origin_nsec = 0;
+    int position = 0;
+    double position_height = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -249,6 +276,16 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--acars-json")) acars = acars_json = 1;
         else if (!strcmp(a, "--station")) station = NEXT();         /* options.c --station=ID (getopt takes both forms) */
         else if (!strncmp(a, "--station=", 10)) station = a + 10;
+        else if (!strcmp(a, "--position") || !strncmp(a, "--position=", 11)) {
+            /* options.c:391-398 (getopt optional_argument: only the --position=H form takes a value); the web map the
+             * reference also turns on here is not built */
+            position = 1;
+            if (a[10] == '=') {
+                position_height = atof(a + 11);
+                if (position_height < 0 || position_height > 9000)
+                    errx(1, "--position height must be 0-9000 m (got %.0f)", position_height);
+            }
+        }
         else if (!strcmp(a, "--acars-origin")) {
             /* test aid: SEC[.NNNNNNNNN] is the wall clock of the first printed ACARS message instead of CLOCK_REALTIME */
             const char *v = NEXT();
@@ -281,7 +318,7 @@ int main(int argc, char **argv)
         }
     }
     if (!file || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--gpus N]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N]\n", argv[0]);
         return 2;
     }
     if (!format) format = ext_of(file);              /* autodetect by extension, options.c:533-544 */
@@ -356,6 +393,17 @@ int main(int argc, char **argv)
         /* main.c:617-629, without the network endpoints this binary does not build */
         fprintf(stderr, "ACARS: enabled (%s output%s)\n", acars_json ? "JSON" : "text", station ? ", station set" : "");
     }
+    if (position) {
+        if (SET_OPTION(save_dir ? "decode_frames" : "frame_records", 1) != 0) {
+            fprintf(stderr, "--position: the library refused the frame decoder\n");
+            return 1;
+        }
+        g_dop = irdm_doppler_create(position_height);
+        if (!g_dop) { fprintf(stderr, "--position: out of memory\n"); return 1; }
+        /* stream time: the frames' timestamps count from the context's start time */
+        irdm_doppler_set_origin(g_dop, irdm_start_time_ns(p));
+        fprintf(stderr, "Doppler positioning: enabled (height aiding: %.0f m)\n", position_height);     /* main.c:597-605 */
+    }
     g_save_dir = save_dir;
     if (verbose) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
                          gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");
@@ -422,6 +470,9 @@ int main(int argc, char **argv)
     if (rc == 0 && (g_group ? irdm_group_flush(g_group) : irdm_flush(p)) < 0) { fprintf(stderr, "burst_detect: GPU processing failed\n"); rc = 1; }
     drain(p, d, file_info, &t0, line, sizeof line);
     fflush(stdout);
+    if (g_dop && rc == 0)          /* the ticks up to the stream's end (samples / rate), then the final solve */
+        position_out(irdm_doppler_finish(g_dop, irdm_start_time_ns(p) + (uint64_t)((double)fed / rate * 1e9), g_dop_text,
+                                         sizeof g_dop_text));
     if (timing) {
         const double t_done = now_s();
         fprintf(stderr, "irdm timing: startup %.3f s (HIP initialisation + device context), stream %.3f s for %llu samples = %.1f Msamples/s\n",
@@ -449,6 +500,7 @@ int main(int argc, char **argv)
     free(d);
     irdm_acars_destroy(g_acars);
     irdm_ida_reasm_destroy(g_reasm);
+    irdm_doppler_destroy(g_dop);
     if (f != stdin) fclose(f);
     if (timing) fprintf(stderr, "irdm timing: teardown %.3f s\n", now_s() - t_down);
     return rc;

@@ -95,6 +95,20 @@ class IdaPacked(C.Structure):
                 ("payload", C.c_uint8 * 32), ("bch_stream", C.c_uint8 * 32)]
 
 
+class FramePacked(C.Structure):
+    """irdm_frame_packed_t: frame_decode()'s fields for one packed frame (option frame_records), in narrow types"""
+    _fields_ = [("type", C.c_uint8), ("sat_id", C.c_uint8), ("beam_id", C.c_uint8), ("n_pages", C.c_uint8),
+                ("pos_xyz", C.c_int16 * 3), ("bch_len", C.c_uint16), ("timeslot", C.c_uint8), ("sv_blocking", C.c_uint8),
+                ("bc_type", C.c_uint8), ("pad", C.c_uint8), ("iri_time", C.c_uint32), ("page_tmsi", C.c_uint32 * 12),
+                ("page_msc", C.c_uint8 * 12)]
+
+
+class Position(C.Structure):
+    """irdm_position_t: doppler_solution_t"""
+    _fields_ = [("lat", C.c_double), ("lon", C.c_double), ("alt", C.c_double), ("hdop", C.c_double),
+                ("n_measurements", C.c_int32), ("n_satellites", C.c_int32), ("converged", C.c_int32), ("pad", C.c_int32)]
+
+
 class IdaMessage(C.Structure):
     """irdm_ida_message_t: one reassembled IDA message (ida_message_cb's arguments)"""
     _fields_ = [("data", C.c_uint8 * 256), ("len", C.c_int32), ("direction", C.c_int32), ("timestamp", C.c_uint64),
@@ -176,6 +190,8 @@ def lib():
         L.irdm_poll_ida.argtypes = [C.c_void_p, C.POINTER(Ida), C.c_int]
         L.irdm_poll_ida_packed.argtypes = [C.c_void_p, C.POINTER(IdaPacked), C.c_int]
         L.irdm_ida_unpack.argtypes = [C.POINTER(IdaPacked), C.POINTER(DemodPacked), C.POINTER(Ida)]
+        L.irdm_poll_frame_packed.argtypes = [C.c_void_p, C.POINTER(FramePacked), C.c_int]
+        L.irdm_frame_unpack.argtypes = [C.POINTER(FramePacked), C.POINTER(DemodPacked), C.POINTER(Decoded)]
         L.irdm_ida_unpack.restype = None
         L.irdm_format_ida.argtypes = [C.POINTER(Ida), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
         L.irdm_format_parsed_packed_batch.argtypes = [C.POINTER(DemodPacked), C.POINTER(IdaPacked), C.c_int, C.c_char_p,
@@ -229,6 +245,7 @@ def lib():
         L.irdm_group_poll_decoded.argtypes = [C.c_void_p, C.POINTER(Decoded), C.c_int]
         L.irdm_group_poll_ida.argtypes = [C.c_void_p, C.POINTER(Ida), C.c_int]
         L.irdm_group_poll_ida_packed.argtypes = [C.c_void_p, C.POINTER(IdaPacked), C.c_int]
+        L.irdm_group_poll_frame_packed.argtypes = [C.c_void_p, C.POINTER(FramePacked), C.c_int]
         L.irdm_chunks_complete.argtypes = [C.c_void_p]
         L.irdm_chunks_complete.restype = C.c_uint64
         L.irdm_required_overlap.argtypes = [C.c_void_p]
@@ -238,6 +255,20 @@ def lib():
         L.irdm_bytes_per_sample.argtypes = [C.c_void_p]
         L.irdm_bytes_per_sample.restype = C.c_size_t
         L.irdm_wait_ingest.argtypes = [C.c_void_p]
+        if hasattr(L, "irdm_doppler_create"):              # (csrc/doppler.cpp; the emulated test build leaves it out)
+            L.irdm_doppler_create.restype = C.c_void_p
+            L.irdm_doppler_create.argtypes = [C.c_double]
+            L.irdm_doppler_destroy.argtypes = [C.c_void_p]
+            L.irdm_doppler_add.argtypes = [C.c_void_p, C.POINTER(Decoded)]
+            L.irdm_doppler_solve.argtypes = [C.c_void_p, C.POINTER(Position)]
+            L.irdm_doppler_set_origin.argtypes = [C.c_void_p, C.c_uint64]
+            L.irdm_format_doppler_packed_batch.restype = C.c_longlong
+            L.irdm_format_doppler_packed_batch.argtypes = [C.c_void_p, C.POINTER(DemodPacked), C.POINTER(FramePacked),
+                                                           C.c_int, C.c_char_p, C.c_size_t]
+            L.irdm_format_doppler_batch.restype = C.c_longlong
+            L.irdm_format_doppler_batch.argtypes = [C.c_void_p, C.POINTER(Decoded), C.c_int, C.c_char_p, C.c_size_t]
+            L.irdm_doppler_finish.restype = C.c_longlong
+            L.irdm_doppler_finish.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_ida_reasm_create"):            # (csrc/acars.cpp; the emulated test build leaves it out)
             L.irdm_ida_reasm_create.restype = C.c_void_p
             L.irdm_ida_reasm_create.argtypes = []
@@ -508,6 +539,10 @@ class Pipeline:
         """option parsed_records 1: one IdaPacked per polled DemodPacked, in the same order"""
         return self._poll(self.L.irdm_poll_ida_packed, IdaPacked)
 
+    def poll_frame_packed(self):
+        """option frame_records 1: one FramePacked per polled DemodPacked, in the same order"""
+        return self._poll(self.L.irdm_poll_frame_packed, FramePacked)
+
     def drop_frames(self, chunk=4096):
         """Discard queued frame records (metadata only path)."""
         buf = (FrameInfo * chunk)()
@@ -717,6 +752,9 @@ class Group:
     def poll_ida_packed(self):
         return self._poll(self.L.irdm_group_poll_ida_packed, IdaPacked)
 
+    def poll_frame_packed(self):
+        return self._poll(self.L.irdm_group_poll_frame_packed, FramePacked)
+
     def poll_frames(self, chunk=64):
         infos, samples = [], []
         buf = (FrameInfo * chunk)()
@@ -765,6 +803,13 @@ def ida_unpack(ida_packed, demod_packed):
     """irdm_ida_unpack: the Ida record the decode_ida path makes of the same frame"""
     out = Ida()
     lib().irdm_ida_unpack(C.byref(ida_packed), C.byref(demod_packed), C.byref(out))
+    return out
+
+
+def frame_unpack(frame_packed, demod_packed):
+    """irdm_frame_unpack: the Decoded record the decode_frames path makes of the same frame"""
+    out = Decoded()
+    lib().irdm_frame_unpack(C.byref(frame_packed), C.byref(demod_packed), C.byref(out))
     return out
 
 
@@ -914,6 +959,56 @@ class AcarsPrinter:
     def close(self):
         if self._h:
             self._L.irdm_acars_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+# ---------------------------------------------------------------- --position (csrc/doppler.cpp) ----
+class Doppler:
+    """irdm_doppler_*: the Doppler positioning engine, state across calls; origin: the stream's start_time_ns"""
+
+    def __init__(self, height_m=0.0, origin=0):
+        self._L = lib()
+        self._h = self._L.irdm_doppler_create(float(height_m))
+        if not self._h:
+            raise MemoryError("irdm_doppler_create")
+        self._L.irdm_doppler_set_origin(self._h, origin)
+
+    def add(self, decoded):
+        return self._L.irdm_doppler_add(self._h, C.byref(decoded))
+
+    def solve(self):
+        """(return value, Position)"""
+        s = Position()
+        r = self._L.irdm_doppler_solve(self._h, C.byref(s))
+        return r, s
+
+    def _text(self, fn, *args, cap):
+        buf = C.create_string_buffer(cap)
+        k = fn(self._h, *args, buf, cap)
+        if k < 0:
+            raise RuntimeError(fn.__name__ + " failed")
+        return buf.raw[:k].decode()
+
+    def format_batch(self, decoded, cap=1 << 20):
+        """irdm_format_doppler_batch: the stderr text of one batch of Decoded records"""
+        n = len(decoded)
+        return self._text(self._L.irdm_format_doppler_batch, (Decoded * max(n, 1))(*decoded), n, cap=cap)
+
+    def format_packed_batch(self, demods, frames, cap=1 << 20):
+        n = len(demods)
+        assert len(frames) == n
+        return self._text(self._L.irdm_format_doppler_packed_batch, (DemodPacked * max(n, 1))(*demods),
+                          (FramePacked * max(n, 1))(*frames), n, cap=cap)
+
+    def finish(self, end_ns, cap=1 << 20):
+        return self._text(self._L.irdm_doppler_finish, C.c_uint64(end_ns), cap=cap)
+
+    def close(self):
+        if self._h:
+            self._L.irdm_doppler_destroy(self._h)
             self._h = None
 
     def __del__(self):
