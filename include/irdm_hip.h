@@ -389,6 +389,12 @@ int irdm_poll_decoded(irdm_pipeline_t *p, irdm_decoded_t *out, int max);
  * irdm_poll_ida returns one record per irdm_poll_demods record (ok = 0 when ida_decode() returns 0).
  * Multi-burst reassembly (ida_reassemble) stays on the host and consumes these records. */
 int irdm_ida_decode_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, int use_llr, irdm_ida_t *out);
+/* The packed record path's kernels alone, batched: frame_decode() / ida_decode() of n frames into the records options
+ * "frame_records" / "parsed_records" poll, written by the kernels into pinned host memory.  As behind the demodulator they
+ * always use the LLRs and read in[i].direction; in[i].n_bits must be even (the kernels take 2 * n_symbols bits).
+ * Returns 0, or -1 (an odd or out-of-range n_bits among them included). */
+int irdm_frame_packed_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_frame_packed_t *out);
+int irdm_ida_packed_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_ida_packed_t *out);
 int irdm_poll_ida(irdm_pipeline_t *p, irdm_ida_t *out, int max);
 
 /* ---- time-chunk sharding of ONE stream across GPUs ----

@@ -298,6 +298,16 @@ __device__ __forceinline__ int deint_index(int n_sym, int half, int j)
     return 2 * s + (j & 1);
 }
 
+// position t of the tail's combined stream (h2[1..] then h1[1..], each half ns - 1 = hl bits) -> input bit index from the
+// tail's start.  An odd ns leaves h2[ns - 1] unwritten by de_interleave_n (t = hl - 1); the reference's build reads there
+// what its last full block's de-interleave left in the same storage: that block's half2[ns - 1], 124 bits back.
+// (h1[ns - 1], t = 2 hl - 1, is in no chunk for an odd ns.)
+__device__ __forceinline__ int tail_index(int ns, int hl, int t)
+{
+    if (t < hl) return (ns & 1) && t == hl - 1 ? deint_index(62, 1, ns - 1) - 124 : deint_index(ns, 1, t + 1);
+    return deint_index(ns, 0, t - hl + 1);
+}
+
 __device__ __forceinline__ void put20(uint8_t *stream, int &len, unsigned corrected)
 {
     const unsigned d = (corrected >> 11) & 0xfffffu;
@@ -389,8 +399,7 @@ __global__ __launch_bounds__(64) void ida_decode_kernel(const DemodOut *__restri
                 unsigned cw = 0;
                 float l[31];
                 for (int k = 0; k < 31; k++) {
-                    const int t = pos + k;                              // combined = h2[1..] then h1[1..]
-                    const int idx = t < hl ? deint_index(ns, 1, t + 1) : deint_index(ns, 0, t - hl + 1);
+                    const int idx = tail_index(ns, hl, pos + k);        // combined = h2[1..] then h1[1..]
                     cw = (cw << 1) | (unsigned)(b[idx] & 1);
                     l[k] = bl ? bl[idx] : 0.0f;
                 }
@@ -581,8 +590,7 @@ __global__ __launch_bounds__(64) void ida_packed_kernel(const DemodOut *__restri
                 const int j = off + k;
                 idx = j < 62 ? deint_index(62, 0, j) : deint_index(62, 1, j - 62);
             } else {
-                const int t = tpos + k;                                 // combined = h2[1..] then h1[1..]
-                idx = t < hl ? deint_index(ns, 1, t + 1) : deint_index(ns, 0, t - hl + 1);
+                idx = tail_index(ns, hl, tpos + k);                     // >= -124: inside the last full block
             }
             cw = (cw << 1) | (unsigned)s_bits[base + idx];
             s_cl[lane][k] = s_llr[base + idx];

@@ -1,5 +1,6 @@
 // state.cpp -- detector-state export / import and history seeding (time-chunk sharding), and the stage-level batch
-// entry points (irdm_downmix_burst, irdm_qpsk_demod_batch, irdm_frame_decode_batch, irdm_ida_decode_batch).
+// entry points (irdm_downmix_burst, irdm_qpsk_demod_batch, irdm_frame_decode_batch, irdm_ida_decode_batch,
+// irdm_frame_packed_batch, irdm_ida_packed_batch).
 #include "pipeline.hpp"
 
 namespace irdmh {
@@ -396,6 +397,56 @@ extern "C" int irdm_ida_decode_batch(irdm_pipeline_t *p, const irdm_demod_t *in,
         for (int i = 0; i < nb; i++) out[base + i] = finish_ida(p->h_ida[i], in[base + i]);
     }
     return 0;
+}
+
+// the packed record path's kernels alone: frame_packed_kernel / ida_packed_kernel read n_bits as 2 * n_symbols, the
+// direction and the LLRs from the record (the chain's keep_bits DemodOut), and write their records into pinned host memory
+template <typename Rec, typename Launch>
+static int packed_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, Rec *out, Launch launch)
+{
+    if (!p || !in || !out || n < 0) return -1;
+    for (int i = 0; i < n; i++)
+        if (in[i].n_bits < 0 || in[i].n_bits > kMaxBits || (in[i].n_bits & 1)) return -1;
+    pipeline_enter(p);
+    Rec *hp = nullptr;
+    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(Rec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
+                                 hipHostMallocDefault));
+    int rc = 0;
+    for (int base = 0; base < n && rc == 0; base += p->burst_cap) {
+        const int nb = std::min(p->burst_cap, n - base);
+        p->h_demod.assign(nb, DemodOut());
+        for (int i = 0; i < nb; i++) {
+            const irdm_demod_t &f = in[base + i];
+            DemodOut &d = p->h_demod[i];
+            d.ok = 1;
+            d.direction = f.direction;
+            d.n_symbols = f.n_bits / 2;
+            memcpy(d.bits, f.bits, sizeof(d.bits));
+            memcpy(d.llr, f.llr, sizeof(d.llr));
+        }
+        rc = hipMemcpyAsync(p->d_demod, p->h_demod.data(), sizeof(DemodOut) * nb, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
+                     launch(p, nb, hp) == 0 && hipStreamSynchronize(p->stream) == hipSuccess
+                 ? 0 : -1;
+        if (rc == 0) memcpy(out + base, hp, sizeof(Rec) * nb);
+    }
+    (void)hipHostFree(hp);
+    return rc;
+}
+
+extern "C" int irdm_frame_packed_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_frame_packed_t *out)
+{
+    static_assert(sizeof(irdm_frame_packed_t) == sizeof(FramePacked), "the public record is the kernel's");
+    return packed_batch(p, in, n, reinterpret_cast<FramePacked *>(out), [](irdm_pipeline_t *q, int nb, FramePacked *hp) {
+        return launch_frame_packed(q->d_demod, nb, q->d_syn_ra, q->d_syn_hdr, hp, q->stream);
+    });
+}
+
+extern "C" int irdm_ida_packed_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_ida_packed_t *out)
+{
+    static_assert(sizeof(irdm_ida_packed_t) == sizeof(IdaPacked), "the public record is the kernel's");
+    return packed_batch(p, in, n, reinterpret_cast<IdaPacked *>(out), [](irdm_pipeline_t *q, int nb, IdaPacked *hp) {
+        return launch_ida_packed(q->d_demod, nb, q->d_syn_da, q->d_syn_l1, q->d_syn_l2, q->d_syn_l3, hp, q->stream);
+    });
 }
 
 }  // namespace irdmh

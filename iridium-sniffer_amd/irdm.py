@@ -199,6 +199,8 @@ def lib():
         L.irdm_format_parsed_packed_batch.restype = C.c_longlong
         L.irdm_ida_decode_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.c_int, C.POINTER(Ida)]
         L.irdm_frame_decode_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.c_int, C.POINTER(Decoded)]
+        L.irdm_ida_packed_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.POINTER(IdaPacked)]
+        L.irdm_frame_packed_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.POINTER(FramePacked)]
         L.irdm_tagged_bursts.argtypes = [C.c_void_p]
         L.irdm_tagged_bursts.restype = C.c_uint64
         L.irdm_sample_count.argtypes = [C.c_void_p]
@@ -418,6 +420,24 @@ class Pipeline:
         out = (Decoded * max(n, 1))()
         if self.L.irdm_frame_decode_batch(self.h, arr, n, 1 if use_llr else 0, out) != 0:
             raise RuntimeError("irdm_frame_decode_batch failed")
+        return [out[i] for i in range(n)]
+
+    def ida_packed_batch(self, demods):
+        """irdm_ida_packed_batch: ida_packed_kernel for a list of Demod records (even n_bits; LLRs and direction used)."""
+        n = len(demods)
+        arr = (Demod * max(n, 1))(*demods)
+        out = (IdaPacked * max(n, 1))()
+        if self.L.irdm_ida_packed_batch(self.h, arr, n, out) != 0:
+            raise RuntimeError("irdm_ida_packed_batch failed")
+        return [out[i] for i in range(n)]
+
+    def frame_packed_batch(self, demods):
+        """irdm_frame_packed_batch: frame_packed_kernel for a list of Demod records (even n_bits; LLRs used)."""
+        n = len(demods)
+        arr = (Demod * max(n, 1))(*demods)
+        out = (FramePacked * max(n, 1))()
+        if self.L.irdm_frame_packed_batch(self.h, arr, n, out) != 0:
+            raise RuntimeError("irdm_frame_packed_batch failed")
         return [out[i] for i in range(n)]
 
     def feed_host_ptr(self, ptr, n_samples):

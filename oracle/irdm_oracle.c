@@ -1970,6 +1970,21 @@ static int da_descramble(const uint8_t *data, const float *llr, int data_len, ui
         const float *ll = llr ? llr + n_full * 124 : NULL;
         da_deint(data + n_full * 124, ns, h1, h2);
         if (ll) da_deintf(ll, ns, l1, l2);
+        /* An odd ns leaves h2[ns - 1] (and h1[ns - 1]) unwritten, and h2[ns - 1] lies inside the first tail chunk whenever
+         * the tail has one.  The reference's optimised build keeps its tail h2 / lh2 in the storage of the last full
+         * block's half2 / lhalf2, so what it reads there is that block's half2[ns - 1] (lhalf2[ns - 1]): pinned by
+         * test_oracle_bitlayer's long frames.  (h1[ns - 1] would sit at position 2 ns - 3 of the combined stream, which no
+         * chunk reaches for an odd ns.) */
+        if (ns & 1) {
+            uint8_t q1[62], q2[62];
+            da_deint(data + (n_full - 1) * 124, 62, q1, q2);
+            h2[ns - 1] = q2[ns - 1];
+            if (ll) {
+                float r1[62], r2[62];
+                da_deintf(llr + (n_full - 1) * 124, 62, r1, r2);
+                l2[ns - 1] = r2[ns - 1];
+            }
+        }
         if (ns > 1 && len + 20 <= max_bch) {
             uint8_t comb[128];
             float lcomb[128];

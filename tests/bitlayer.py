@@ -71,7 +71,11 @@ def ira_stream(sat, beam, x, y, z, pages, rng, terminate=True):
 def ira_frame(stream, uplink=False):
     """data stream (multiple of 21 bits; 63 header + 42 per page) -> frame bits incl. access code"""
     assert len(stream) % 21 == 0 and len(stream) >= 63
-    blocks = [bch_block32(stream[i:i + 21]) for i in range(0, len(stream), 21)]
+    return ira_frame_blocks([bch_block32(stream[i:i + 21]) for i in range(0, len(stream), 21)], uplink)
+
+
+def ira_frame_blocks(blocks, uplink=False):
+    """3 head blocks + pairs of 32-element blocks -> frame; the elements may be labels (block_positions)"""
     bits = list(ACCESS_UL if uplink else ACCESS_DL) + interleave3(*blocks[:3])
     rest = blocks[3:]
     for i in range(0, len(rest) - 1, 2):
@@ -83,8 +87,11 @@ def ibc_frame(bc_type, stream, uplink=False):
     """bc_type 0..3 (what 6 header bits can carry), stream = multiple of 42 data bits"""
     assert len(stream) % 42 == 0 and len(stream) >= 42
     hv = (bc_type << 4) | gf2_rem(POLY_HDR, bc_type << 4)
-    bits = list(ACCESS_UL if uplink else ACCESS_DL) + to_bits(hv, 6)
-    blocks = [bch_block32(stream[i:i + 21]) for i in range(0, len(stream), 21)]
+    return ibc_frame_blocks(to_bits(hv, 6), [bch_block32(stream[i:i + 21]) for i in range(0, len(stream), 21)], uplink)
+
+
+def ibc_frame_blocks(hdr6, blocks, uplink=False):
+    bits = list(ACCESS_UL if uplink else ACCESS_DL) + list(hdr6)
     for i in range(0, len(blocks), 2):
         bits += interleave2(blocks[i], blocks[i + 1])
     return bits
@@ -201,3 +208,181 @@ def ida_frame(lcw, stream200, rng, uplink=False):
     bits += interleave_n(h1, h2, 32)
     assert len(bits) == 382
     return bits
+
+
+# ------------------------------------------------ long frames, error placement, tied LLRs ----
+IDA_MAX_CHUNKS = 28        # 6 full 124-bit blocks of 4 chunks (kMaxBits = 896) + at most 3 tail chunks; 25 fit the 512-bit stream
+
+
+def ida_tail_chunks(ns):
+    """31-bit chunks the tail of ns symbols holds: its halves without their first bits, 2 * (ns - 1) bits"""
+    return min(3, 2 * (ns - 1) // 31) if ns > 1 else 0
+
+
+def ida_long_frame(lcw, chunks, n_full, ns, fill, uplink=False):
+    """access code + LCW + n_full 124-bit blocks (chunks 4b..4b+3, air order 3,1,2,0) + a tail of ns symbols whose halves,
+    without their first bits, (h2[1..] then h1[1..]) begin with the remaining chunks.  `fill` yields every other element:
+    the halves' first bits, what follows the chunks, and symbol 0 of an odd tail (de_interleave_n reads neither half from
+    it).  The elements may be labels (block_positions)."""
+    assert 4 * n_full <= len(chunks) <= 4 * n_full + ida_tail_chunks(ns)
+    out = list(ACCESS_UL if uplink else ACCESS_DL) + list(lcw)
+    for blk in range(n_full):
+        s = chunks[4 * blk:4 * blk + 4]
+        comb = list(s[3]) + list(s[1]) + list(s[2]) + list(s[0])
+        out += interleave_n(comb[:62], comb[62:], 62)
+    if ns:
+        comb = [x for c in chunks[4 * n_full:] for x in c]
+        comb += [next(fill) for _ in range(max(0, 2 * (ns - 1) - len(comb)))]
+        h2 = [next(fill)] + comb[:ns - 1]
+        h1 = [next(fill)] + comb[ns - 1:]
+        t = interleave_n(h1, h2, ns)
+        if ns % 2:
+            t[0], t[1] = next(fill), next(fill)
+        out += t
+    return out
+
+
+def block_positions(build, blocks, width, *args, **kw):
+    """frame bit index of every element of every block: `build` run on labels instead of bits"""
+    lab = [[("b", i, k) for k in range(width)] for i in range(len(blocks))]
+    frame = build(lab, *args, **kw)
+    pos = [[None] * width for _ in blocks]
+    for j, x in enumerate(frame):
+        if isinstance(x, tuple) and x[0] == "b":
+            pos[x[1]][x[2]] = j
+    return pos
+
+
+def labels():
+    k = 0
+    while True:
+        yield ("f", k)
+        k += 1
+
+
+def bits_from(rng):
+    while True:
+        yield int(rng.integers(0, 2))
+
+
+def syndrome_table(poly, nbits, max_err, size):
+    """remainder -> error pattern of every 1- and 2-bit pattern, the first one found winning (build_syndrome_table)"""
+    t = {}
+    for b1 in range(nbits):
+        r = gf2_rem(poly, 1 << b1)
+        if r < size:
+            t[r] = 1 << b1
+    if max_err >= 2:
+        for b1 in range(nbits):
+            for b2 in range(b1 + 1, nbits):
+                r = gf2_rem(poly, (1 << b1) | (1 << b2))
+                if r < size and r not in t:
+                    t[r] = (1 << b1) | (1 << b2)
+    return t
+
+
+_SYN = {}
+
+
+def chase_model(cw_bits, llr31, poly=POLY_DA, size=2048):
+    """chase_bch_da / chase_bch_decode_p's BCH part on a 31-bit codeword (bits in air order), for coverage counts:
+    ('table' | 'chase' | 'fail', the codewords every flip mask 1..31 decodes to in mask order, whether the fifth and sixth
+    smallest LLRs are equal -- a tie the selection sort's swaps decide)"""
+    if poly not in _SYN:
+        _SYN[poly] = syndrome_table(poly, 31, 2, size)
+    tab = _SYN[poly]
+    cw = int("".join(str(int(b)) for b in cw_bits), 2)
+    syn = gf2_rem(poly, cw)
+    if syn == 0 or syn in tab:
+        return "table", [], False
+    pos = list(range(31))
+    for i in range(5):
+        mi = i
+        for j in range(i + 1, 31):
+            if llr31[pos[j]] < llr31[pos[mi]]:
+                mi = j
+        pos[i], pos[mi] = pos[mi], pos[i]
+    srt = sorted(float(v) for v in llr31)
+    hits = []
+    for mask in range(1, 32):
+        f = cw
+        for k in range(5):
+            if mask & (1 << k):
+                f ^= 1 << (30 - pos[k])
+        syn = gf2_rem(poly, f)
+        if syn == 0 or syn in tab:
+            hits.append(f ^ tab.get(syn, 0))
+    return ("chase" if hits else "fail"), hits, srt[4] == srt[5]
+
+
+def tie_llr(llr, mode, rng):
+    """reliabilities with ties: 'quarter' (rounded to multiples of 1/4), 'two' (two values), 'equal' (one value off the
+    weak bits), 'zero' (all zero), anything else unchanged"""
+    llr = np.asarray(llr, np.float32)
+    if mode == "quarter":
+        return np.round(llr * 4.0).astype(np.float32) / 4.0
+    if mode == "two":
+        return np.where(llr < 0.5, 0.25, 1.0).astype(np.float32)
+    if mode == "equal":
+        return np.where(llr < 0.5, llr, 1.0).astype(np.float32)
+    if mode == "zero":
+        return np.zeros_like(llr)
+    return llr
+
+
+def plant_errors(bits, llr, positions, n, rng, weak=None, tie_fifth=False):
+    """flip n of a block's bits (positions: its frame indices); weak: how many of the flipped bits get a low LLR (all of
+    them by default).  tie_fifth: the block's five lowest LLRs end in a tie -- positions 5 and 6 of the sorted order
+    carry the same value, so the selection sort's swaps decide which of the two is flipped.  A position of None (the
+    element an odd IDA tail does not carry) is left alone"""
+    positions = [q for q in positions if q is not None]
+    idx = [int(i) for i in rng.choice(len(positions), size=n, replace=False)]
+    weak = n if weak is None else weak
+    for j, i in enumerate(idx):
+        bits[positions[i]] ^= 1
+        if j < weak:
+            llr[positions[i]] = 0.05 * float(rng.random())
+    if tie_fifth:
+        rest = [i for i in range(len(positions)) if i not in idx]
+        order = [int(i) for i in rng.permutation(rest)]
+        k = 0
+        for j in range(weak, 4):            # four distinct low values below the tie, then the tie
+            llr[positions[order[k]]] = 0.06 + 0.01 * j
+            k += 1
+        for i in order[k:k + 2]:
+            llr[positions[i]] = 0.2
+    return idx
+
+
+_PROOF = {}
+
+
+def chase_proof(poly=POLY_DA, size=2048):
+    """(five positions W, syndrome s) such that no flip of a subset of W turns a word of syndrome s into one the table or
+    a zero syndrome accepts: a block whose five least reliable bits are W and whose syndrome is s fails Chase decoding.
+    Found by a seeded search (rare for BCH(31,20): about one 5-set in 200 has such an s)."""
+    if poly not in _PROOF:
+        bad = np.zeros(size, bool)
+        bad[0] = True
+        bad[list(syndrome_table(poly, 31, 2, size))] = True
+        rng = np.random.default_rng(12345)
+        while poly not in _PROOF:
+            W = sorted(int(w) for w in rng.choice(31, 5, replace=False))
+            T = np.array([gf2_rem(poly, sum(1 << (30 - W[k]) for k in range(5) if m >> k & 1)) for m in range(32)])
+            ok = ~bad[np.bitwise_xor.outer(np.arange(size), T)].any(axis=1)
+            if ok.any():
+                _PROOF[poly] = (W, int(np.flatnonzero(ok)[0]))
+    return _PROOF[poly]
+
+
+def plant_failure(bits, llr, positions, poly=POLY_DA, size=2048):
+    """make a block (positions: the frame indices of its 31 codeword bits) fail Chase decoding: its five least reliable
+    bits are chase_proof's W and the error pattern is the proof's syndrome itself (bits 30 - b for every bit b of s)"""
+    W, s = chase_proof(poly, size)
+    for k, q in enumerate(positions):
+        if q is None:
+            continue
+        llr[q] = 0.01 + 0.01 * W.index(k) if k in W else max(float(llr[q]), 1.0)
+    for b in range(11):
+        if s >> b & 1 and positions[30 - b] is not None:
+            bits[positions[30 - b]] ^= 1

@@ -221,3 +221,95 @@ def test_pipeline_decodes_ida_bursts_like_the_oracle():
             n_ok += 1
             n_crc += g.crc_ok
     assert n_ok >= 6 and n_crc >= 5, (n_ok, n_crc)
+
+
+# ------------------------------------------- all four decode kernels on the corpora, packed records and unpacking ----
+import bitlayer_checks as BC                                                # noqa: E402
+
+
+def _demods(sel):
+    out = []
+    for k, (b, l, d) in enumerate(sel):
+        r = to_demod(b, l, k)
+        r.direction = d
+        r.magnitude, r.noise, r.level, r.confidence, r.n_payload_symbols = 1.5 + k, -3.0, 0.25 * k, k % 100, k % 400
+        out.append(r)
+    return out
+
+
+def _packed_of(dm):
+    f = irdm.DemodPacked()
+    for name in ("id", "timestamp", "center_frequency", "direction", "magnitude", "noise", "confidence", "level",
+                 "n_symbols", "n_payload_symbols", "n_bits", "ok"):
+        setattr(f, name, getattr(dm, name))
+    return f
+
+
+CAP = 32                                                                    # burst_cap: every corpus takes several launches
+
+
+@pytest.mark.parametrize("seed", (0, 1))
+def test_ida_kernels_on_the_corpora(seed):
+    """ida_decode_kernel and ida_packed_kernel on make_ida_cases and the long IDA frames against the oracle; every packed
+    record unpacked equals ida_decode_kernel's record of the same frame with LLRs"""
+    cases = BC.ida_corpus(seed)
+    p = irdm.Pipeline(2_000_000, max_chunk_samples=32768, max_bursts_per_chunk=CAP)
+    try:
+        for use_llr in (True, False):
+            sel = [c for c in cases if (c[1] is not None) == use_llr]
+            assert len(sel) > CAP
+            got = p.ida_decode_batch(_demods(sel), use_llr=use_llr)
+            for k, ((b, l, d), g) in enumerate(zip(sel, got)):
+                BC.same_ida(g, BC.oracle_ida(b, l, d), k)
+                assert g.id == 10 * k
+        sel = [(b, l if l is not None else np.zeros(len(b), np.float32), d) for b, l, d in cases if len(b) % 2 == 0]
+        assert len(sel) > CAP
+        dem = _demods(sel)
+        packed = p.ida_packed_batch(dem)
+        full = p.ida_decode_batch(dem, use_llr=True)
+        for k, ((b, l, d), g, fu, dm) in enumerate(zip(sel, packed, full, dem)):
+            BC.same_ida_packed(g, BC.oracle_ida(b, l, d), k)
+            u = irdm.ida_unpack(g, _packed_of(dm))
+            BC.same_ida(u, fu, k)
+            for f in ("lcw_header", "id", "timestamp", "frequency", "direction", "magnitude", "noise", "level", "confidence",
+                      "n_symbols"):
+                assert getattr(u, f) == getattr(fu, f), (k, f, getattr(u, f), getattr(fu, f))
+        BC.assert_packed_ida_coverage(sel)
+        odd = _demods([(bl.ACCESS_DL + [0] * 301, None, 1)])
+        with pytest.raises(RuntimeError):
+            p.ida_packed_batch(odd)                                         # the packed kernels take 2 * n_symbols bits
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("seed", (0, 1))
+def test_frame_kernels_on_the_corpora(seed):
+    """frame_decode_kernel and frame_packed_kernel on make_cases and the long IRA / IBC frames against the oracle (lat /
+    lon bit for bit); every packed record unpacked equals frame_decode_kernel's record of the same frame with LLRs"""
+    cases = [(b, l, 0) for b, l in BC.frame_corpus(seed)]
+    p = irdm.Pipeline(2_000_000, max_chunk_samples=32768, max_bursts_per_chunk=CAP)
+    try:
+        L = orc.lib()
+        L.orc_frame_decode.restype = C.c_int
+        for use_llr in (True, False):
+            sel = [c for c in cases if (c[1] is not None) == use_llr]
+            assert len(sel) > CAP
+            got = p.frame_decode_batch(_demods(sel), use_llr=use_llr)
+            for k, ((b, l, _), g) in enumerate(zip(sel, got)):
+                same(g, decode_with(L.orc_frame_decode, b, l)[1])
+                assert g.id == 10 * k
+        sel = [(b, l if l is not None else np.zeros(len(b), np.float32), 0) for b, l, _ in cases if len(b) % 2 == 0]
+        assert len(sel) > CAP
+        dem = _demods(sel)
+        packed = p.frame_packed_batch(dem)
+        full = p.frame_decode_batch(dem, use_llr=True)
+        for k, ((b, l, _), g, fu, dm) in enumerate(zip(sel, packed, full, dem)):
+            BC.same_frame_packed(g, BC.oracle_frame(b, l), k)
+            u = irdm.frame_unpack(g, _packed_of(dm))
+            same(u, fu)
+            assert (u.id, u.timestamp, u.frequency) == (fu.id, fu.timestamp, fu.frequency), k
+        BC.assert_packed_frame_coverage([(b, l) for b, l, _ in sel])
+        with pytest.raises(RuntimeError):
+            p.frame_packed_batch(_demods([(bl.ACCESS_DL + [0] * 301, None, 1)]))
+    finally:
+        p.close()

@@ -14,6 +14,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import irdm
 import orc
 import scenes
 import siggen
@@ -407,6 +408,14 @@ def test_stage_c_kernels_long_frames_full_workgroups_and_positions_outside_the_w
 
 # ---- csrc/bitlayer.hip on the same emulation: frame_decode against the oracle (pinned to the reference's object code) ----
 
+class IdaOut(C.Structure):
+    _fields_ = [("ok", C.c_int32), ("ft", C.c_int32), ("lcw_ft", C.c_int32), ("lcw_code", C.c_int32),
+                ("ec_lcw", C.c_int32), ("lcw3_val", C.c_uint32), ("da_ctr", C.c_int32), ("da_len", C.c_int32),
+                ("cont", C.c_int32), ("crc_ok", C.c_int32), ("stored_crc", C.c_uint32), ("computed_crc", C.c_uint32),
+                ("fixederrs", C.c_int32), ("payload_len", C.c_int32), ("bch_len", C.c_int32),
+                ("payload", C.c_uint8 * 32), ("bch_stream", C.c_uint8 * 256)]
+
+
 class DecodedOut(C.Structure):
     _fields_ = [("type", C.c_int32), ("sat_id", C.c_int32), ("beam_id", C.c_int32), ("pos_xyz", C.c_int32 * 3),
                 ("n_pages", C.c_int32), ("page_tmsi", C.c_uint32 * 12), ("page_msc", C.c_int32 * 12), ("timeslot", C.c_int32),
@@ -430,6 +439,16 @@ def bitlayer_emul():
     L.bitlayer_emul_frame_decode.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.c_int,
                                              C.POINTER(DecodedOut)]
     L.bitlayer_emul_sizes.argtypes = [C.POINTER(C.c_int)] * 2
+    L.bitlayer_emul_frame_packed.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int,
+                                             C.POINTER(irdm.FramePacked)]
+    L.bitlayer_emul_ida_decode.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(IdaOut)]
+    L.bitlayer_emul_ida_packed.argtypes = [C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int), C.c_int, C.POINTER(irdm.IdaPacked)]
+    L.bitlayer_emul_record_sizes.argtypes = [C.POINTER(C.c_int)] * 3
+    sz = [C.c_int() for _ in range(3)]
+    L.bitlayer_emul_record_sizes(*[C.byref(v) for v in sz])
+    assert [v.value for v in sz] == [C.sizeof(IdaOut), C.sizeof(irdm.IdaPacked), C.sizeof(irdm.FramePacked)]
     return L
 
 
@@ -474,3 +493,72 @@ def test_frame_decode_kernel_matches_the_oracle(bitlayer_emul, seed):
             assert tuple(g.page_tmsi)[:g.n_pages] == tuple(o.page_tmsi)[:o.n_pages], k
             assert tuple(g.page_msc)[:g.n_pages] == tuple(o.page_msc)[:o.n_pages], k
         assert types[1] and types[2] and types[0], types
+
+
+# ---- the other three decode kernels on the emulation: ida_decode_kernel, ida_packed_kernel, frame_packed_kernel ----
+import bitlayer_checks as BC                                               # noqa: E402
+
+
+def _arrays(sel, max_bits):
+    n = len(sel)
+    hb = np.zeros((n, max_bits), np.uint8)
+    sl = np.zeros((n, max_bits), np.float32)
+    nb = np.zeros(n, np.int32)
+    for k, (bits, llr) in enumerate(sel):
+        hb[k, :len(bits)] = bits
+        nb[k] = len(bits)
+        if llr is not None:
+            sl[k, :len(llr)] = llr
+    return hb, sl, nb
+
+
+def _ptrs(hb, sl, nb):
+    return hb.ctypes.data_as(C.POINTER(C.c_uint8)), orc.fptr(sl), nb.ctypes.data_as(C.POINTER(C.c_int))
+
+
+@pytest.mark.parametrize("seed", (0, 1))
+def test_ida_kernels_match_the_oracle(bitlayer_emul, seed):
+    """ida_decode_kernel (every frame, hard decisions where the case has no LLRs) and ida_packed_kernel (the frames of
+    even length, LLRs always: zeros where the case has none) on make_ida_cases and the long corpus: every field equals
+    the oracle's ida_decode, bch_stream up to min(bch_len, 256) bits"""
+    cases = BC.ida_corpus(seed)
+    L = bitlayer_emul
+    for use_llr in (True, False):
+        sel = [c for c in cases if (c[1] is not None) == use_llr]
+        hb, sl, nb = _arrays([(b, l) for b, l, d in sel], orc.MAX_BITS)
+        dirs = np.array([d for b, l, d in sel], np.int32)
+        out = (IdaOut * len(sel))()
+        assert L.bitlayer_emul_ida_decode(*_ptrs(hb, sl, nb), dirs.ctypes.data_as(C.POINTER(C.c_int)), len(sel),
+                                          int(use_llr), out) == 0
+        for k, (b, l, d) in enumerate(sel):
+            BC.same_ida(out[k], BC.oracle_ida(b, l, d), k)
+    sel = [(b, l if l is not None else np.zeros(len(b), np.float32), d) for b, l, d in cases if len(b) % 2 == 0]
+    hb, sl, nb = _arrays([(b, l) for b, l, d in sel], orc.MAX_BITS)
+    dirs = np.array([d for b, l, d in sel], np.int32)
+    out = (irdm.IdaPacked * len(sel))()
+    assert L.bitlayer_emul_ida_packed(*_ptrs(hb, sl, nb), dirs.ctypes.data_as(C.POINTER(C.c_int)), len(sel), out) == 0
+    for k, (b, l, d) in enumerate(sel):
+        BC.same_ida_packed(out[k], BC.oracle_ida(b, l, d), k)
+    BC.assert_packed_ida_coverage(sel)
+
+
+@pytest.mark.parametrize("seed", (0, 1))
+def test_frame_kernels_match_the_oracle_on_long_frames(bitlayer_emul, seed):
+    """frame_decode_kernel and frame_packed_kernel on the long IRA / IBC corpus (and frame_packed_kernel on make_cases):
+    every field equals the oracle's frame_decode"""
+    cases = BC.frame_corpus(seed)
+    L = bitlayer_emul
+    for use_llr in (True, False):
+        sel = [c for c in cases if (c[1] is not None) == use_llr]
+        hb, sl, nb = _arrays(sel, orc.MAX_BITS)
+        out = (DecodedOut * len(sel))()
+        assert L.bitlayer_emul_frame_decode(*_ptrs(hb, sl, nb), len(sel), int(use_llr), out) == 0
+        for k, (b, l) in enumerate(sel):
+            BC.same_frame(out[k], BC.oracle_frame(b, l), k)
+    sel = [(b, l if l is not None else np.zeros(len(b), np.float32)) for b, l in cases if len(b) % 2 == 0]
+    hb, sl, nb = _arrays(sel, orc.MAX_BITS)
+    out = (irdm.FramePacked * len(sel))()
+    assert L.bitlayer_emul_frame_packed(*_ptrs(hb, sl, nb), len(sel), out) == 0
+    for k, (b, l) in enumerate(sel):
+        BC.same_frame_packed(out[k], BC.oracle_frame(b, l), k)
+    BC.assert_packed_frame_coverage(sel)
