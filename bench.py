@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- IQ Msamples/s end-to-end (detect -> downmix -> demod) on 10 MHz cf32.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one pass of the whole hot path (K1..K7) over one chunk of
 synthetic 10 MHz cf32 IQ that is already resident in HBM (complex
@@ -14,6 +14,10 @@ partitions by stream / time-chunk, no data-path collective); per step the demodu
 frame records are gathered to rank 0 over RCCL.  `value` = samples all ranks processed
 / max-over-ranks wall time.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: nothing else.  --full also
+measures and checks everything beside the headline (N = 1, rank 0: the stage_ms_alone / kernel_clock_ms_alone steps,
+pcie_inclusive, detect_only, file_to_raw, cpu_baseline, parity_checked, chunk_x2); without it those objects are null.
+
 Extra objects on the line:
   roofline       dominant KERNEL (the decimator, or K1 on scenes with few bursts: the longer device span per
                  launch of the two; the detector scan is a chain of ~10 short launches and is reported under
@@ -24,8 +28,10 @@ Extra objects on the line:
                  ms_per_launch, vs the 8 TB/s HBM peak; kernel_ms_rocprof = the same kernel's average in the
                  newest committed rocprofv3 summary of this configuration (profiles/); stage_ms = HIP-event
                  brackets of the stages on their streams (they include what a launch waits in its queue);
-                 stage_ms_alone / kernel_clock_ms_alone = the same from a few extra steps at pipeline_depth 0
+                 stage_ms_alone / kernel_clock_ms_alone (--full) = the same from a few extra steps at pipeline_depth 0
                  (one kernel on the chip at a time).
+The objects below come with --full:
+  pcie_inclusive the same scene fed from pinned host memory, cf32 / ci16 / ci8, separately timed steps.
   cpu_baseline   the CPU oracle (C port of the reference, the decimating FIR in the order of the reference's
                  AVX2 kernel like the product's default) in the reference's thread layout
                  (1 detector + 4 downmix + 1 demod thread, main.c:175) on a bounded prefix of the
@@ -500,19 +506,22 @@ def main():
                          "while the per-burst chains of the previous depth + 1 chunks and chunk k+1's FFT run (results later, "
                          "identical); 0 = every feed returns its own chunk's results.  (A chain is ~3 ms of dependent launches "
                          "in run: with three contexts the period was that latency / 3, profiles/r5_depth_sweep.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (N = 1): the extra steps and processes the options "
+                         "below shape, the CPU oracle baselines and the parity check; a plain run skips all of them")
     ap.add_argument("--cpu-samples", type=int, default=64 * 1024 * 1024,
-                    help="prefix of the stream the CPU oracle is timed on (0 = skip)")
-    ap.add_argument("--cpu-passes", type=int, default=3, help="one-core oracle passes over that prefix (~3 s each)")
+                    help="--full: prefix of the stream the CPU oracle is timed on (0 = skip)")
+    ap.add_argument("--cpu-passes", type=int, default=3, help="--full: one-core oracle passes over that prefix (~3 s each)")
     ap.add_argument("--shard", choices=("streams", "time"), default="streams",
                     help="streams (default): one independent stream per GPU (BASELINE config 5 / the headline metric at N=1); "
                          "time: ONE 12 MHz stream, consecutive time-chunks on consecutive ranks with the detector state handed "
                          "rank to rank over RCCL (BASELINE config 4)")
     ap.add_argument("--alone-steps", type=int, default=4,
-                    help="extra steps at pipeline_depth 0 (stage times with one kernel on the chip at a time, and the records "
+                    help="--full: extra steps at pipeline_depth 0 (stage times with one kernel on the chip at a time, and the records "
                          "for the parity check; 0 = skip)")
-    ap.add_argument("--detect-steps", type=int, default=10, help="extra detect-only steps (BASELINE config 2; 0 = skip)")
+    ap.add_argument("--detect-steps", type=int, default=10, help="--full: extra detect-only steps (BASELINE config 2; 0 = skip)")
     ap.add_argument("--file-run", type=int, default=2,
-                    help="1: also time the C99 binary on the chunk written to a file; 2: and on a 600 Msample recording")
+                    help="--full: 1 = also time the C99 binary on the chunk written to a file; 2 = and on a 600 Msample recording")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=INT",
                     help="irdm_set_option before the run (kernel-variant A/B: fir_generic=1, fft_radix2=1, scan_mode=1)")
     ap.add_argument("--packed", type=int, default=1,
@@ -523,13 +532,13 @@ def main():
     ap.add_argument("--lookahead", type=int, default=1,
                     help="pipeline_depth >= 1: 1 = irdm_feed_begin(k+1) before irdm_feed_end(k); 0 = irdm_feed_device")
     ap.add_argument("--host-steps", type=int, default=6,
-                    help="extra, separately timed steps fed from pinned HOST memory (PCIe-inclusive rate; 0 = skip)")
+                    help="--full: extra, separately timed steps fed from pinned HOST memory (PCIe-inclusive rate; 0 = skip)")
     ap.add_argument("--cpu-layout", type=int, default=1,
-                    help="0: skip the thread-layout CPU runs (cpu_baseline = the one-core pass): what the chunk_x2 sub-run uses")
+                    help="--full: 0 = skip the thread-layout CPU runs (cpu_baseline = the one-core pass): what the chunk_x2 sub-run uses")
     ap.add_argument("--parity-chunks", type=int, default=2, choices=(1, 2),
-                    help="parity_checked over the stream's first two chunks (default) or the first one only")
+                    help="--full: parity_checked over the stream's first two chunks (default) or the first one only")
     ap.add_argument("--big-chunk-steps", type=int, default=20,
-                    help="N = 1, cf32: a second, separately timed run of this script with chunks of twice the samples (same scene "
+                    help="--full, N = 1, cf32: a second, separately timed run of this script with chunks of twice the samples (same scene "
                          "generator and density, same options), N steps, parity-checked on its first chunk -> `chunk_x2` on the "
                          "JSON line (never `value`); 0 = skip")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -540,6 +549,9 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.shard != "streams":
         ap.error("--dump-outputs needs --shard streams")
+    if not args.full:
+        # a plain run: the headline alone, none of the extra measurements and checks behind the timed steps
+        args.cpu_samples = args.host_steps = args.alone_steps = args.detect_steps = args.file_run = args.big_chunk_steps = 0
 
     import torch
     import torch.distributed as dist
@@ -664,8 +676,9 @@ def main():
 
     # the records of the stream's FIRST TWO chunks as the timed context produces them (pipeline_depth 3, fed in place with
     # look-ahead, the other chunks' stages running beside them): what parity_checked compares with the oracle run over a
-    # two-chunk prefix of the stream.  Everything the context emits during the warm-up is kept (records leave in stream order).
-    head = {"bursts": [], "demods": [], "open": True}
+    # two-chunk prefix of the stream.  Everything the context emits during the warm-up is kept (records leave in stream order)
+    # when that check runs (--full).
+    head ={"bursts": [], "demods": [], "open": args.cpu_samples > 0}
     # what the last timed step and the drain behind it returned (--dump-outputs)
     last = {"bursts": [], "demods": []}
 
@@ -708,7 +721,8 @@ def main():
         pipe.flush()
         wb = pipe.poll_bursts_raw(); pipe.drop_frames(); wd = poll_demods()
         # (the warm-up chunks' records that were still in flight leave together here, in chunk order)
-        head["bursts"].append(wb.copy()); head["demods"].append(wd.copy())
+        if head["open"]:
+            head["bursts"].append(wb.copy()); head["demods"].append(wd.copy())
     head["open"] = False
     head["chunks"] = args.warmup
     if world > 1:
@@ -1134,7 +1148,7 @@ def main():
     if rank == 0 and world == 1 and args.big_chunk_steps > 0 and args.format == "cf32" and args.shard == "streams":
         try:
             import subprocess
-            cmd = [sys.executable, os.path.abspath(__file__), "--samples", str(2 * n), "--steps", str(args.big_chunk_steps),
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--samples", str(2 * n), "--steps", str(args.big_chunk_steps),
                    "--warmup", "5", "--density", str(args.density), "--sample-rate", str(fs), "--depth", str(args.depth),
                    "--packed", str(args.packed), "--ingest", str(args.ingest), "--lookahead", str(args.lookahead),
                    "--cpu-samples", str(2 * n if args.cpu_samples > 0 else 0), "--cpu-passes", "1", "--cpu-layout", "0",

@@ -7,6 +7,8 @@ placed on an arbitrary carrier.  Nothing here is on the product path.
 Symbol model (what the reference demodulator expects, qpsk_demod.c:217-225,
 :264-273, iridium.h:30-31): quadrant q -> exp(j(pi/4 + q*pi/2)).
 """
+import functools
+
 import numpy as np
 
 SYMBOL_RATE = 25000
@@ -28,6 +30,12 @@ KNOWN_ANSWER_BITS = (
 
 def rrc_pulse(sps, alpha=0.4, span=5):
     """Unit-energy root-raised-cosine, +-span symbols, times sqrt(sps)."""
+    return _rrc_pulse(sps, alpha, span).copy()
+
+
+@functools.lru_cache(maxsize=None)
+def _rrc_pulse(sps, alpha, span):
+    # (one evaluation per shape: a scene of hundreds of bursts at 10 MHz would otherwise spend most of its time here)
     n = np.arange(-span * sps, span * sps + 1, dtype=np.float64)
     t = n / sps
     h = np.empty_like(t)

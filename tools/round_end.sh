@@ -11,7 +11,7 @@ tail -n 4 "$OUT/tests.log"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 tail -n 2 "$OUT/smoke.log"
 if [ "${2:-}" = quick ]; then
-  timeout 600 python bench.py 2>"$OUT/b.err" | tail -1 > "$OUT/b.json"
+  timeout 600 python bench.py --full 2>"$OUT/b.err" | tail -1 > "$OUT/b.json"
   head -c 400 "$OUT/b.json"; echo
 else
   tools/measure_round.sh "${1:-final}" > "$OUT/measure.log" 2>&1
