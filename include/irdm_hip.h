@@ -62,6 +62,16 @@ int gpu_burst_fft_process_device(gpu_burst_fft_t *g, const void *d_input, void *
 #define IRDM_FMT_CI16 1   /* options.c FMT_CI16: raw int16 pairs; narrowed to (int8)(v >> 8) (main.c:245-246) in the
                              kernels' load stage, on the device */
 #define IRDM_FMT_CF32 2   /* options.c FMT_CF32 */
+/* Full-precision interleaved int16 I/Q, 4 bytes per sample, converted in the kernels' load stage exactly as the
+ * reference's live paths convert the same hardware's samples:
+ *   IRDM_FMT_CI16_FULL  (float)v * (1.0f / 32768.0f)   SoapySDR CS16 (soapysdr.c:213-216)
+ *   IRDM_FMT_SC16Q11    (float)v * (1.0f / 2048.0f)    bladeRF SC16Q11 (bladerf.c:93-96)
+ * Contract: a context in either format produces exactly -- bit for bit, not within a tolerance -- the records (bursts,
+ * frames, demods with their LLRs, packed, parsed and frame records) of an IRDM_FMT_CF32 context fed the same samples
+ * converted to float and multiplied by the scale: int16 -> float is exact, and the power-of-two scale keeps every
+ * product exact and far from the subnormal range.  irdm_create refuses any format outside 0..4. */
+#define IRDM_FMT_CI16_FULL 3
+#define IRDM_FMT_SC16Q11   4
 
 typedef struct {
     double center_frequency;   /* -c, burst_config_t.center_frequency (burst_detect.h:52) */

@@ -205,22 +205,48 @@ __host__ __device__ __forceinline__ unsigned bitrev(unsigned v, int bits)
 //   fmt 2: cf32 as is (burst_detector_feed_cf32, burst_detect.c:846)
 //   fmt 0: ci8, int8 / 128.0f (simd_convert_i8_cf, simd_generic.c:147-153)
 //   fmt 1: ci16, narrowed to int8 by (int8_t)(v >> 8) (spewer_thread, main.c:245-246), then as ci8
+//   fmt 3: ci16 at full precision, int16 * (1.0f / 32768.0f) (the SoapySDR CS16 live path, soapysdr.c:213-216)
+//   fmt 4: bladeRF SC16Q11, int16 * (1.0f / 2048.0f) (the bladeRF live path, bladerf.c:93-96)
+// Formats 3 and 4 are exact: int16 -> float is, and a power-of-two scale keeps every product a normal float, so a
+// context in either format computes what a cf32 context computes on v.astype(np.float32) * scale, bit for bit.
+template <int FMT>       // (FMT 3 or 4)
+__host__ __device__ __forceinline__ float i16_full(int v)
+{
+    return (float)v * (FMT == 3 ? 1.0f / 32768.0f : 1.0f / 2048.0f);
+}
+
+// bytes per sample of a device format
+template <int FMT>
+constexpr int kFmtBytes = FMT == 2 ? 8 : (FMT == 0 ? 2 : 4);
+
 template <int FMT>
 __device__ __forceinline__ float2 load_iq(const void *__restrict__ iq, size_t i)
 {
+    static_assert(FMT >= 0 && FMT <= 4, "device sample format");
     if (FMT == 2) {
         return reinterpret_cast<const float2 *>(iq)[i];
     } else if (FMT == 1) {
         const short2 v = reinterpret_cast<const short2 *>(iq)[i];
         return make_float2((float)(v.x >> 8) / 128.0f, (float)(v.y >> 8) / 128.0f);
+    } else if (FMT == 3 || FMT == 4) {
+        const short2 v = reinterpret_cast<const short2 *>(iq)[i];
+        return make_float2(i16_full<FMT>(v.x), i16_full<FMT>(v.y));
     } else {
         const char2 v = reinterpret_cast<const char2 *>(iq)[i];
         return make_float2((float)v.x / 128.0f, (float)v.y / 128.0f);
     }
 }
+// (irdm_create admits formats 0..4 only; anything else reads as NaN rather than as some other format)
 __device__ __forceinline__ float2 load_iq(int fmt, const void *__restrict__ iq, size_t i)
 {
-    return fmt == 2 ? load_iq<2>(iq, i) : (fmt == 1 ? load_iq<1>(iq, i) : load_iq<0>(iq, i));
+    switch (fmt) {
+    case 2: return load_iq<2>(iq, i);
+    case 1: return load_iq<1>(iq, i);
+    case 3: return load_iq<3>(iq, i);
+    case 4: return load_iq<4>(iq, i);
+    case 0: return load_iq<0>(iq, i);
+    default: return make_float2(__builtin_nanf(""), __builtin_nanf(""));
+    }
 }
 
 }  // namespace irdm

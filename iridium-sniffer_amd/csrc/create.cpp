@@ -158,8 +158,13 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
         delete p;
         return nullptr;
     }
+    if (cfg->format < IRDM_FMT_CI8 || cfg->format > IRDM_FMT_SC16Q11) {
+        fprintf(stderr, "irdm_hip: unknown sample format %d\n", cfg->format);
+        delete p;
+        return nullptr;
+    }
     p->dev_fmt = cfg->format;
-    p->bps = p->dev_fmt == 2 ? 8 : (p->dev_fmt == 1 ? 4 : 2);
+    p->bps = p->dev_fmt == IRDM_FMT_CF32 ? 8 : (p->dev_fmt == IRDM_FMT_CI8 ? 2 : 4);
     p->max_chunk = cfg->max_chunk_samples ? cfg->max_chunk_samples : ((size_t)64 << 20);
     p->max_chunk = (p->max_chunk + p->feed_block - 1) / p->feed_block * p->feed_block;
     p->burst_cap = cfg->max_bursts_per_chunk > 0 ? cfg->max_bursts_per_chunk : 4096;

@@ -7,11 +7,11 @@
 namespace irdm {
 
 // ---------------------------------------------------------------------------
-// K1: load (ci8 | cf32) -> Blackman/0.42 window -> N-point pinned FFT in LDS ->
+// K1: load (ci8 | ci16 | cf32, load_iq) -> Blackman/0.42 window -> N-point pinned FFT in LDS ->
 //     fftshift -> |.|^2  (simd_window_cf + fftwf_execute + simd_fftshift_mag,
 //     burst_detect.c:679-687; opencl/burst_fft.c:52-80 window_multiply /
 //     fftshift_magnitude).  One workgroup per frame, grid-stride.
-//     HBM: 8 B (cf32) or 2 B (ci8) read + 4 B written per sample.
+//     HBM: 8 B (cf32), 4 B (the int16 formats) or 2 B (ci8) read + 4 B written per sample.
 // ---------------------------------------------------------------------------
 template <int LOGN, int NT, int FMT>
 __global__ __launch_bounds__(NT) void fft_mag_kernel(const void *__restrict__ iq,
@@ -272,6 +272,11 @@ __device__ __forceinline__ void load_pair(__amdgpu_buffer_rsrc_t r, int lane, in
         const short r0 = (short)(v.x & 0xffff), i0 = (short)(v.x >> 16), r1 = (short)(v.y & 0xffff), i1 = (short)(v.y >> 16);
         x0 = v2f{ (float)(r0 >> 8) / 128.0f, (float)(i0 >> 8) / 128.0f };     // load_iq<1>
         x1 = v2f{ (float)(r1 >> 8) / 128.0f, (float)(i1 >> 8) / 128.0f };
+    } else if (FMT == 3 || FMT == 4) {
+        const int2 v = __builtin_bit_cast(int2, __builtin_amdgcn_raw_buffer_load_b64(r, lane * 8, soff, 2));
+        const short r0 = (short)(v.x & 0xffff), i0 = (short)(v.x >> 16), r1 = (short)(v.y & 0xffff), i1 = (short)(v.y >> 16);
+        x0 = v2f{ i16_full<FMT>(r0), i16_full<FMT>(i0) };                    // load_iq<3>, load_iq<4>
+        x1 = v2f{ i16_full<FMT>(r1), i16_full<FMT>(i1) };
     } else {
         const int v = __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4, soff, 2);
         const signed char r0 = (signed char)(v & 0xff), i0 = (signed char)((v >> 8) & 0xff);
@@ -337,7 +342,7 @@ __global__ __launch_bounds__((1 << LOGN) / 32, 4) void fft_mag_p32_kernel(const 
 {
     using G_ = P32<LOGN>;
     constexpr int N = G_::N, T = G_::T, G = G_::G, REGION = G_::REGION;
-    constexpr int BPS = FMT == 2 ? 8 : (FMT == 1 ? 4 : 2);
+    constexpr int BPS = kFmtBytes<FMT>;
     __shared__ int s_cnt;
     __builtin_amdgcn_s_setprio(2);      // the scan of this chunk waits for K1; it shares SIMDs with the per-burst chains
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -543,7 +548,10 @@ static int launch_p32(int fmt, const void *iq, const float *window, const float2
     } while (0)
     if (fmt == 2) IRDM_LAUNCH_P32(2);
     else if (fmt == 1) IRDM_LAUNCH_P32(1);
-    else IRDM_LAUNCH_P32(0);
+    else if (fmt == 3) IRDM_LAUNCH_P32(3);
+    else if (fmt == 4) IRDM_LAUNCH_P32(4);
+    else if (fmt == 0) IRDM_LAUNCH_P32(0);
+    else return -1;
 #undef IRDM_LAUNCH_P32
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -566,18 +574,23 @@ static int launch_r16(int fmt, const void *iq, const float *window, const float2
     } while (0)
     if (fmt == 2) IRDM_LAUNCH_R16(2);
     else if (fmt == 1) IRDM_LAUNCH_R16(1);
-    else IRDM_LAUNCH_R16(0);
+    else if (fmt == 3) IRDM_LAUNCH_R16(3);
+    else if (fmt == 4) IRDM_LAUNCH_R16(4);
+    else if (fmt == 0) IRDM_LAUNCH_R16(0);
+    else return -1;
 #undef IRDM_LAUNCH_R16
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// K1 with the candidate lists of the band scan (see fft_mag_r16_kernel); 1 if this FFT size has no such kernel
+// K1 with the candidate lists of the band scan (see fft_mag_r16_kernel); 1 if this FFT size has no such kernel, -1 for
+// an unknown sample format
 int launch_fft_mag_lists(int log_n, int fmt, const void *iq, const float *window, const float2 *tw, float *mag,
                          int n_frames, const float *pre, unsigned *counts, ListEntry *entries, int cap,
                          hipStream_t stream, unsigned long long *kclk, int order)
 {
     if (n_frames <= 0) return 0;
-    if (fmt < 0 || fmt > 2 || log_n < 12 || log_n > 14) return 1;
+    if (fmt < 0 || fmt > 4) return -1;
+    if (log_n < 12 || log_n > 14) return 1;
     if (log_n == 13) return launch_p32<13, true>(fmt, iq, window, tw, mag, n_frames, pre, counts, entries, cap, kclk, stream, order);
     if (log_n == 14) return launch_p32<14, true>(fmt, iq, window, tw, mag, n_frames, pre, counts, entries, cap, kclk, stream, order);
     return launch_r16<12, true>(fmt, iq, window, tw, mag, n_frames, pre, counts, entries, cap, stream, order);
@@ -589,7 +602,7 @@ int launch_fft_mag(int log_n, int fmt, const void *iq, const float *window, cons
     if (n_frames <= 0) return 0;
     const int grid = n_frames < 4096 ? n_frames : 4096;
     const int f = fmt;
-    if (f < 0 || f > 2) return -1;
+    if (f < 0 || f > 4) return -1;
     if (log_n == 13) return launch_p32<13, false>(fmt, iq, window, tw, mag, n_frames, nullptr, nullptr, nullptr, 0, kclk, stream, order);
     if (log_n == 14) return launch_p32<14, false>(fmt, iq, window, tw, mag, n_frames, nullptr, nullptr, nullptr, 0, kclk, stream, order);
     if (log_n == 12) return launch_r16<12, false>(fmt, iq, window, tw, mag, n_frames, nullptr, nullptr, nullptr, 0, stream, order);
@@ -605,7 +618,10 @@ int launch_fft_mag(int log_n, int fmt, const void *iq, const float *window, cons
     do {                                                                                       \
         if (f == 2) IRDM_LAUNCH_FFT_F(LOGN, NT, 2);                                            \
         else if (f == 1) IRDM_LAUNCH_FFT_F(LOGN, NT, 1);                                       \
-        else IRDM_LAUNCH_FFT_F(LOGN, NT, 0);                                                   \
+        else if (f == 3) IRDM_LAUNCH_FFT_F(LOGN, NT, 3);                                       \
+        else if (f == 4) IRDM_LAUNCH_FFT_F(LOGN, NT, 4);                                       \
+        else if (f == 0) IRDM_LAUNCH_FFT_F(LOGN, NT, 0);                                       \
+        else return -1;                                                                        \
     } while (0)
     switch (log_n) {
     case 8:  IRDM_LAUNCH_FFT(8, 64); break;

@@ -79,6 +79,18 @@ __device__ __forceinline__ void load_piece(const void *__restrict__ base, size_t
                 x[4 * u + k] = v2f{ (float)(re >> 8) / 128.0f, (float)(im >> 8) / 128.0f };
             }
         }
+    } else if (FMT == 3 || FMT == 4) {
+        const int4 *g = reinterpret_cast<const int4 *>(reinterpret_cast<const short2 *>(base) + idx);   // 4 samples per 16 B
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const int4 v = g[u];
+            const int w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const short re = (short)(w[k] & 0xffff), im = (short)(w[k] >> 16);
+                x[4 * u + k] = v2f{ i16_full<FMT>(re), i16_full<FMT>(im) };
+            }
+        }
     } else {
         const int4 v = *reinterpret_cast<const int4 *>(reinterpret_cast<const char2 *>(base) + idx);    // 8 samples per 16 B
         const int w[4] = { v.x, v.y, v.z, v.w };
@@ -520,7 +532,10 @@ static int launch_fir_f_fmt(const SampleSource &src, const FirGeom *geom, int n_
     const int grid = 7 * n_cu < n_tiles ? 7 * n_cu : n_tiles;
     if (src.fmt == 2) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 2>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 1) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 1>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
-    else hipLaunchKernelGGL((fir_decimate_kernel_f<M, 0>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 3) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 3>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 4) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 4>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 0) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 0>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -542,7 +557,10 @@ static int launch_fir_r_fmt(const SampleSource &src, const FirGeom *geom, int n_
     // one single-wavefront workgroup per strip
     if (src.fmt == 2) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 2>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 1) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 1>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
-    else hipLaunchKernelGGL((fir_decimate_kernel_r<M, 0>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 3) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 3>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 4) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 4>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 0) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 0>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -104,7 +104,7 @@ struct SampleSource {
     const void *ring;         // history ring, same format, indexed by absolute index % ring_len
     uint64_t ring_len;
     uint64_t ref_ring;        // the REFERENCE's ring size (burst_detect.c:292-296): stale slot = a - ref_ring
-    int fmt;                  // 0 ci8, 2 cf32
+    int fmt;                  // device sample format (IRDM_FMT_*, load_iq)
 };
 
 // downmix.hip

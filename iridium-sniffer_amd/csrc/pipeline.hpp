@@ -132,7 +132,7 @@ struct irdm_pipeline {
     irdm_config_t cfg;
     DetParams P;
     int dev_fmt;                // device sample format == cfg.format: 0 ci8, 1 ci16 (narrowed in the load stage,
-                                // main.c:245-246), 2 cf32
+                                // main.c:245-246), 2 cf32, 3 ci16 full precision, 4 SC16Q11 (common.hpp load_iq)
     size_t bps;                 // bytes per device sample
     int feed_block, decim, out_rate;
     float peak_signal_db;    // burst_detector_peak_signal over the finished bursts (starts at 0 like the reference's calloc)

@@ -2,7 +2,7 @@
  * iridium_sniffer_hip.c -- file-mode command line over the MI355X hot path, plain C99.
  *
  * Mirrors the reference's file-mode surface (options.c:186-551, main.c:223-284, frame_output.c:160-199):
- *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB]
+ *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
@@ -11,6 +11,9 @@
  * "POSITION:" lines on stderr (main.c:506-519), solved every 10 s of stream time instead of wall-clock time.  Everything between the file
  * read and the line printer runs on the GPU through the C-ABI in include/irdm_hip.h; there is no CPU
  * path here (the reference's own --no-gpu binary is the CPU path).
+ * --format ci16-full and --format sc16q11 read interleaved int16 at full precision, scaled as the reference's live
+ * SoapySDR CS16 (v / 32768) and bladeRF SC16Q11 (v / 2048) paths scale it; ci16 (and a .ci16 / .cs16 file) is the
+ * reference's file path, narrowed to 8 bits.
  */
 #include <err.h>
 #include <stdint.h>
@@ -318,14 +321,19 @@ int main(int argc, char **argv)
         }
     }
     if (!file || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N]\n", argv[0]);
         return 2;
     }
+    const int format_given = format != NULL;
     if (!format) format = ext_of(file);              /* autodetect by extension, options.c:533-544 */
     int fmt = IRDM_FMT_CI8;
     size_t bps = 2;
     if (!strcmp(format, "cf32") || !strcmp(format, "fc32") || !strcmp(format, "cfile")) { fmt = IRDM_FMT_CF32; bps = 8; }
     else if (!strcmp(format, "ci16") || !strcmp(format, "cs16")) { fmt = IRDM_FMT_CI16; bps = 4; }
+    /* full-precision int16 (the reference's SoapySDR CS16 and bladeRF live conversions): by --format only, the extension
+     * autodetect above is the reference's */
+    else if (format_given && !strcmp(format, "ci16-full")) { fmt = IRDM_FMT_CI16_FULL; bps = 4; }
+    else if (format_given && !strcmp(format, "sc16q11")) { fmt = IRDM_FMT_SC16Q11; bps = 4; }
 
     irdm_config_t c;
     memset(&c, 0, sizeof(c));

@@ -15,6 +15,9 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IRDM_LIB") or os.path.join(PKG_DIR, "libirdm_hip.so")
 
 FMT_CI8, FMT_CI16, FMT_CF32 = 0, 1, 2
+# full-precision int16 I/Q (include/irdm_hip.h): records equal a cf32 context's on v.astype(np.float32) * FMT_SCALE[fmt]
+FMT_CI16_FULL, FMT_SC16Q11 = 3, 4
+FMT_SCALE = {FMT_CI16_FULL: 1.0 / 32768.0, FMT_SC16Q11: 1.0 / 2048.0}
 MAX_FRAME_SAMPLES = 4440
 MAX_BITS = 896
 
