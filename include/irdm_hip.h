@@ -321,6 +321,8 @@ void irdm_host_free(void *ptr);
 void *irdm_device_alloc(int device, size_t bytes);
 void irdm_device_free(void *dptr);
 int irdm_device_upload(void *dptr, const void *host, size_t bytes);
+/* synchronous copy back to host memory (tests, tools) */
+int irdm_device_download(void *host, const void *dptr, size_t bytes);
 /* synchronous device-to-device copy on the current device (e.g. a resident chunk into its irdm_ingest_ptr slot) */
 int irdm_device_copy(void *dst, const void *src, size_t bytes);
 
@@ -721,6 +723,67 @@ long long irdm_doppler_finish(irdm_doppler_t *d, uint64_t end_ns, char *buf, siz
  * samples: 2 * info->num_samples floats as returned by irdm_poll_frames with "keep_frame_samples" = 1.
  * Returns 0, or -1 (no frame / I/O error, message on stderr as the reference prints). */
 int irdm_save_burst(const irdm_frame_info_t *info, const float *samples, const char *dir);
+
+/* 3e. Band-select front end (K0): a wideband capture decimated on the GPU  */
+/* ------------------------------------------------------------------ */
+/* An object beside the pipeline (no reference counterpart: the reference is given a stream at the detector's rate).  It
+ * shifts the band of interest to the centre, low-passes and decimates by an integer D, and writes cf32 at in_rate / D
+ * straight into the pipeline's ingest slot (irdm_ingest_ptr), so captures at rates irdm_create refuses -- 25 .. 61.44 MS/s --
+ * run through the unchanged pipeline, created as IRDM_FMT_CF32 at irdm_frontend_out_rate with centre frequency
+ * capture centre + irdm_frontend_applied_shift_hz:
+ *
+ *   y[m] = sum_k h[k] r[m D + c - k],  r[n] = x[n] T[(q n) mod 65536],  c = (ntaps - 1) / 2,  r = 0 outside the stream
+ *
+ *   x  the capture in any IRDM_FMT_*, converted as the pipeline's kernels convert it
+ *   q  = round(shift_hz * 65536 / in_rate); T[i] = cos(-2 pi i / 65536) + i sin(-2 pi i / 65536); the phase index comes from
+ *      the 64-bit stream position, so the rotator has no drift and does not depend on how the stream is cut
+ *   h  the pipeline's own low-pass design (Blackman-Harris), cut-off 0.5 out_rate, transition parameter 0.09 out_rate:
+ *      ntaps ~ 44.4 D, flat to 0.42 out_rate, more than 80 dB down from 0.58 out_rate on
+ * Centre-aligned: output m sits at capture sample m D, the filter adds no delay.  The arithmetic is a fixed sequence of
+ * float operations (tests/frontend_model.c restates it in plain C, bit for bit).  The output does
+ * not depend on how the input is cut into feeds; the samples a later output still needs are carried on the device.
+ * One thread per object; every call puts the thread on the object's device. */
+typedef struct {
+    int device;                /* HIP device ordinal (the pipeline's) */
+    int in_rate;               /* capture sample rate, Hz */
+    int in_format;             /* IRDM_FMT_* of the capture */
+    int decim;                 /* D, 2 .. 16; in_rate must be a multiple of it */
+    double shift_hz;           /* band centre - capture centre; |shift_hz| <= in_rate / 2 */
+} irdm_frontend_config_t;
+
+typedef struct irdm_frontend irdm_frontend_t;
+/* NULL (message on stderr) for in_rate / D not an integer, D outside 2 .. 16, an unknown format, a shift beyond half the
+ * capture rate, or an output rate irdm_create would refuse. */
+irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *cfg);
+void irdm_frontend_destroy(irdm_frontend_t *fe);
+int irdm_frontend_out_rate(const irdm_frontend_t *fe);
+/* q * in_rate / 65536: the shift that is applied, what the pipeline's centre frequency is computed from */
+double irdm_frontend_applied_shift_hz(const irdm_frontend_t *fe);
+int irdm_frontend_ntaps(const irdm_frontend_t *fe);
+/* the taps h[0 .. ntaps-1]; returns ntaps, or -1 when max is too small */
+int irdm_frontend_taps(const irdm_frontend_t *fe, float *out, int max);
+/* Stage-level entry: the next n_in samples of the capture (device memory, in_format); the outputs they complete -- output m
+ * needs input m D + c -- are written to d_out (device memory, cf32).  stream: a hipStream_t as void*; NULL = the front end's
+ * own stream, and the call returns when the outputs are written.  Returns the number of outputs, or -1 (more than out_cap
+ * among them; nothing is consumed then). */
+long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap, void *stream);
+/* the end of the stream for the stage-level entry: zeros behind the last sample, ceil(n_in_total / D) outputs in all */
+long long irdm_frontend_finish_device(irdm_frontend_t *fe, void *d_out, size_t out_cap, void *stream);
+/* The feeder: converts into irdm_ingest_ptr's slot (into a scratch chunk at pipeline_depth 0) and calls irdm_feed_device with
+ * whole multiples of the pipeline's feed_block, at most max_chunk_samples at a time; the remainder waits for the next call.
+ * p: an IRDM_FMT_CF32 context at irdm_frontend_out_rate on the same device.  n_in is arbitrary.  _device: stream = the
+ * producer of d_in or NULL (as irdm_feed_device); d_in must stay unchanged until irdm_frontend_wait_input returns.
+ * _host: the buffer (pinned for speed) may be reused when the call returns.  Return the bursts whose records became pollable,
+ * or -1. */
+int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream);
+int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in);
+/* the end of the stream: the zero-padded rest, the held-back remainder as the pipeline's last chunk, then irdm_flush(p) */
+int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p);
+/* host wait until everything enqueued so far has read its input buffer */
+int irdm_frontend_wait_input(irdm_frontend_t *fe);
+/* irdm_kernel_clock for K0 (always on): the kernel's own spans on the device summed since the last reset.  Waits for the
+ * front end's stream. */
+int irdm_frontend_kernel_clock(irdm_frontend_t *fe, double *sum_ms, uint64_t *launches, int reset);
 
 /* The fine-CFO step's cexpf(i x) (burst_downmix.c:716-717) as the device evaluates it -- glibc's sincosf restated,
  * csrc/libm_port.hpp -- for n arbitrary arguments (test / audit surface: tests/test_gpu_libm.py,

@@ -103,6 +103,18 @@ bool chain_stream_create(irdm_pipeline *, hipStream_t *out, int prio)
     return hipStreamCreateWithPriority(out, hipStreamNonBlocking, prio) == hipSuccess;
 }
 
+// The sample rates a context takes: the detector's FFT size follows the rate (burst_detect.c:184-185), K1 exists for
+// 2^8 .. 2^14 points and the scans keep their active list in LDS.  (Also asked by irdm_frontend_create for its output rate.)
+bool rate_supported(int fs, int *fft_size)
+{
+    if (fs <= 0) return false;
+    const int n = 1 << (int)round(log2(fs / 1000.0));
+    const int width = 40000 / (fs / n > 0 ? fs / n : 1);
+    const int max_bursts = (int)((fs / (float)40000) * 0.8f);
+    if (fft_size) *fft_size = n;
+    return !(n < kScanThreads || n > 16384 || max_bursts + n / (width > 0 ? width : 1) + 8 > kMaxActive);
+}
+
 extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
 {
     if (!cfg || cfg->sample_rate <= 0) return nullptr;
@@ -147,8 +159,9 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
     P.max_len = (int)(fs * 0.09);
     const float tdb = cfg->threshold_db > 0 ? cfg->threshold_db : 16.0f;
     P.threshold = powf(10.0f, tdb / 10.0f) / kHistory / 1.72f;
-    if (P.n < kScanThreads || P.n > 16384 || P.max_bursts + P.n / (P.width > 0 ? P.width : 1) + 8 > kMaxActive) {
+    if (!rate_supported(fs, nullptr)) {
         fprintf(stderr, "irdm_hip: unsupported sample rate %d (fft_size %d)\n", fs, P.n);
+        fprintf(stderr, "irdm_hip: a wideband capture goes through the band-select front end: --band-center / --decimate, irdm_frontend_create\n");
         delete p;
         return nullptr;
     }

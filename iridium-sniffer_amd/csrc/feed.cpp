@@ -307,6 +307,13 @@ extern "C" int irdm_device_upload(void *dptr, const void *host, size_t bytes)
     return 0;
 }
 
+extern "C" int irdm_device_download(void *host, const void *dptr, size_t bytes)
+{
+    if ((!dptr || !host) && bytes) return -1;
+    IRDM_HIP_CHECK(hipMemcpy(host, dptr, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 extern "C" int irdm_device_copy(void *dst, const void *src, size_t bytes)
 {
     if ((!dst || !src) && bytes) return -1;

@@ -1,0 +1,358 @@
+// frontend.cpp -- irdm_frontend_*: the band-select front end's object (K0, frontend.hip): taps, tables, the carried tail,
+// and the feeder that converts a wideband capture into the pipeline's ingest slot.
+//
+// Stream bookkeeping.  total = capture samples received, n_out = outputs produced.  Output m reads the inputs
+// m D - c .. m D + c, so after `total` samples the outputs below floor((total - 1 - c) / D) + 1 are complete, and the samples
+// from n_out D - c on are still needed: they are kept, raw, in a device tail buffer (at most ntaps - 1 + D of them) and the
+// kernel reads [tail | chunk] as one sequence.  The flush treats everything behind the last sample as zero and brings
+// the count to ceil(total / D).
+#include "pipeline.hpp"
+
+struct irdm_frontend {
+    irdm_frontend_config_t cfg;
+    int D, fmt, bps, ntaps, c, out_rate;
+    long long q;
+    std::vector<float> taps;
+    float *d_hr = nullptr, *d_G = nullptr;
+    float2 *d_T = nullptr;
+    void *d_tail[2] = { nullptr, nullptr };
+    int cur = 0;
+    long long n_tail = 0;
+    uint64_t total = 0, n_out = 0;
+    bool finished = false;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_caller = nullptr;
+    unsigned long long *d_kclk = nullptr;
+    // the feeder: outputs written but not fed yet lie at base[0 .. pend)
+    float2 *base = nullptr, *d_scratch = nullptr;
+    size_t room = 0, pend = 0;
+    void *d_stage = nullptr;
+    size_t stage_bytes = 0;
+};
+
+namespace irdmh {
+
+static void fe_free(irdm_frontend *fe)
+{
+    if (!fe) return;
+    (void)hipSetDevice(fe->cfg.device);
+    if (fe->stream) (void)hipStreamSynchronize(fe->stream);
+    void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage };
+    for (void *q : ptrs)
+        if (q) (void)hipFree(q);
+    if (fe->ev_in) (void)hipEventDestroy(fe->ev_in);
+    if (fe->ev_caller) (void)hipEventDestroy(fe->ev_caller);
+    if (fe->stream) (void)hipStreamDestroy(fe->stream);
+    delete fe;
+}
+
+extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *cfg)
+{
+    if (!cfg) return nullptr;
+    if (cfg->decim < 2 || cfg->decim > 16) {
+        fprintf(stderr, "irdm_hip: front end: decimation %d outside 2 .. 16\n", cfg->decim);
+        return nullptr;
+    }
+    if (cfg->in_rate <= 0 || cfg->in_rate % cfg->decim != 0) {
+        fprintf(stderr, "irdm_hip: front end: sample rate %d is not a multiple of the decimation %d\n", cfg->in_rate, cfg->decim);
+        return nullptr;
+    }
+    if (cfg->in_format < IRDM_FMT_CI8 || cfg->in_format > IRDM_FMT_SC16Q11) {
+        fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
+        return nullptr;
+    }
+    const int out_rate = cfg->in_rate / cfg->decim;
+    int fft = 0;
+    if (!rate_supported(out_rate, &fft)) {
+        fprintf(stderr, "irdm_hip: front end: output rate %d (%d / %d) is not one the pipeline takes (fft_size %d)\n", out_rate,
+                cfg->in_rate, cfg->decim, fft);
+        return nullptr;
+    }
+    const long long q = llround(cfg->shift_hz * 65536.0 / (double)cfg->in_rate);
+    if (q < -32768 || q > 32768) {
+        fprintf(stderr, "irdm_hip: front end: shift %.1f Hz is beyond half the capture rate %d\n", cfg->shift_hz, cfg->in_rate);
+        return nullptr;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        fprintf(stderr, "irdm_hip: no HIP device -- there is no CPU fallback in this library\n");
+        return nullptr;
+    }
+    if (hipSetDevice(cfg->device) != hipSuccess) return nullptr;
+    irdm_frontend *fe = new (std::nothrow) irdm_frontend();
+    if (!fe) return nullptr;
+    fe->cfg = *cfg;
+    fe->D = cfg->decim;
+    fe->fmt = cfg->in_format;
+    fe->bps = fe->fmt == IRDM_FMT_CF32 ? 8 : (fe->fmt == IRDM_FMT_CI8 ? 2 : 4);
+    fe->out_rate = out_rate;
+    fe->q = q;
+    fe->taps = design_lpf(1.0f, (float)cfg->in_rate, 0.5f * (float)out_rate, 0.09f * (float)out_rate);
+    fe->ntaps = (int)fe->taps.size();
+    fe->c = (fe->ntaps - 1) / 2;
+    const int R = 8, D = fe->D, nt = fe->ntaps;
+    if (nt < (R - 1) * D + 1 || frontend_lds_bytes(D, nt) > 160 * 1024) {
+        fprintf(stderr, "irdm_hip: front end: %d taps at decimation %d do not fit the kernel\n", nt, D);
+        delete fe;
+        return nullptr;
+    }
+    // reversed taps (ascending input order), the table of the full steps, the rotation table (built in double)
+    std::vector<float> hr(nt), G((size_t)(nt - (R - 1) * D) * R);
+    for (int j = 0; j < nt; j++) hr[j] = fe->taps[nt - 1 - j];
+    for (int i = (R - 1) * D; i < nt; i++)
+        for (int r = 0; r < R; r++) G[(size_t)(i - (R - 1) * D) * R + r] = hr[i - r * D];
+    std::vector<float2> T(65536);
+    for (int i = 0; i < 65536; i++) {
+        const double a = -2.0 * M_PI * (double)i / 65536.0;
+        T[i] = make_float2((float)cos(a), (float)sin(a));
+    }
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    const int prio_k1 = prio_hi < prio_lo - 1 ? prio_hi + 1 : prio_hi;          // K1's class (create.cpp)
+    const size_t tail_bytes = (size_t)(nt + D + 16) * 8;
+    std::vector<unsigned long long> kinit(kKClkWords, 0ull);
+    for (int i = 0; i < 64; i++) kinit[i] = ~0ull;
+    bool ok = (fe->d_hr = dev_upload(hr.data(), hr.size())) != nullptr;
+    ok = ok && (fe->d_G = dev_upload(G.data(), G.size())) != nullptr;
+    ok = ok && (fe->d_T = dev_upload(T.data(), T.size())) != nullptr;
+    ok = ok && (fe->d_kclk = dev_upload(kinit.data(), kinit.size())) != nullptr;
+    ok = ok && hipMalloc(&fe->d_tail[0], tail_bytes) == hipSuccess && hipMalloc(&fe->d_tail[1], tail_bytes) == hipSuccess;
+    ok = ok && hipStreamCreateWithPriority(&fe->stream, hipStreamNonBlocking, prio_k1) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&fe->ev_in, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&fe->ev_caller, hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
+        fe_free(fe);
+        return nullptr;
+    }
+    return fe;
+}
+
+extern "C" void irdm_frontend_destroy(irdm_frontend_t *fe) { fe_free(fe); }
+extern "C" int irdm_frontend_out_rate(const irdm_frontend_t *fe) { return fe ? fe->out_rate : -1; }
+extern "C" double irdm_frontend_applied_shift_hz(const irdm_frontend_t *fe)
+{
+    return fe ? (double)fe->q * (double)fe->cfg.in_rate / 65536.0 : 0.0;
+}
+extern "C" int irdm_frontend_ntaps(const irdm_frontend_t *fe) { return fe ? fe->ntaps : -1; }
+extern "C" int irdm_frontend_taps(const irdm_frontend_t *fe, float *out, int max)
+{
+    if (!fe || !out || max < fe->ntaps) return -1;
+    memcpy(out, fe->taps.data(), sizeof(float) * (size_t)fe->ntaps);
+    return fe->ntaps;
+}
+
+// outputs complete once `total` samples are in (flush: with zeros behind them)
+static uint64_t fe_outputs(const irdm_frontend *fe, uint64_t total, bool flush)
+{
+    if (flush) return (total + (uint64_t)fe->D - 1) / (uint64_t)fe->D;
+    return total > (uint64_t)fe->c ? (total - 1 - (uint64_t)fe->c) / (uint64_t)fe->D + 1 : 0;
+}
+
+// outputs [fe->n_out, m1) of [tail | d_in] into out
+static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1, float2 *out, hipStream_t s)
+{
+    if (m1 <= fe->n_out) return 0;
+    FrontendArgs a;
+    a.tail = fe->d_tail[fe->cur];
+    a.in = d_in;
+    a.n_tail = fe->n_tail;
+    a.n_in = (long long)n_in;
+    a.pos0 = (long long)fe->total - fe->n_tail;
+    a.m0 = (long long)fe->n_out;
+    a.m1 = (long long)m1;
+    a.out = out;
+    a.q16 = (unsigned)(fe->q & 0xffff);
+    a.ntaps = fe->ntaps;
+    a.fmt = fe->fmt;
+    if (launch_frontend(fe->D, a, fe->d_hr, fe->d_G, fe->d_T, s, fe->d_kclk) != 0) return -1;
+    if (launch_kclk_fold(fe->d_kclk, s) != 0) return -1;
+    fe->n_out = m1;
+    return 0;
+}
+
+// the chunk has been consumed: keep what later outputs need, advance the stream position
+static int fe_commit(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream_t s)
+{
+    const uint64_t total = fe->total + n_in;
+    const long long need = (long long)(fe->n_out * (uint64_t)fe->D) - fe->c;       // first sample still needed
+    const long long start = std::min<long long>(std::max<long long>(need, 0), (long long)total);
+    const long long pos0 = (long long)fe->total - fe->n_tail;
+    const int n_new = (int)((long long)total - start);
+    if (n_new > fe->ntaps + fe->D + 16) return -1;                                 // (cannot happen: see the header comment)
+    if (launch_frontend_tail(fe->d_tail[fe->cur], fe->n_tail, d_in, (long long)n_in, start - pos0, n_new, fe->bps,
+                             fe->d_tail[fe->cur ^ 1], s) != 0)
+        return -1;
+    fe->cur ^= 1;
+    fe->n_tail = n_new;
+    fe->total = total;
+    return 0;
+}
+
+extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
+                                              void *stream_v)
+{
+    if (!fe || fe->finished || (!d_in && n_in) || !d_out) return -1;
+    const uint64_t m1 = fe_outputs(fe, fe->total + n_in, false);
+    const uint64_t n = m1 - fe->n_out;
+    if (n > out_cap) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : fe->stream;
+    if (fe_emit(fe, d_in, n_in, m1, static_cast<float2 *>(d_out), s) != 0) return -1;
+    if (fe_commit(fe, d_in, n_in, s) != 0) return -1;
+    IRDM_HIP_CHECK(hipEventRecord(fe->ev_in, s));
+    if (!stream_v) IRDM_HIP_CHECK(hipStreamSynchronize(s));
+    return (long long)n;
+}
+
+extern "C" long long irdm_frontend_finish_device(irdm_frontend_t *fe, void *d_out, size_t out_cap, void *stream_v)
+{
+    if (!fe || fe->finished || !d_out) return -1;
+    const uint64_t m1 = fe_outputs(fe, fe->total, true);
+    const uint64_t n = m1 - fe->n_out;
+    if (n > out_cap) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : fe->stream;
+    if (fe_emit(fe, nullptr, 0, m1, static_cast<float2 *>(d_out), s) != 0) return -1;
+    fe->finished = true;
+    if (!stream_v) IRDM_HIP_CHECK(hipStreamSynchronize(s));
+    return (long long)n;
+}
+
+// ---- the feeder ----
+
+// where the next outputs go: the pipeline's ingest slot for as many samples as lie between the stream position and the
+// end of the ring (at most a chunk), or the scratch chunk (pipeline_depth 0)
+static int fe_acquire(irdm_frontend *fe, irdm_pipeline *p)
+{
+    size_t room = p->max_chunk;
+    if (p->depth) room = (size_t)std::min<uint64_t>(room, p->ring_len - p->begun_samples % p->ring_len);
+    room = room / (size_t)p->feed_block * (size_t)p->feed_block;
+    void *slot = room ? irdm_ingest_ptr(p, room) : nullptr;
+    if (!slot) {
+        if (!fe->d_scratch && hipMalloc(reinterpret_cast<void **>(&fe->d_scratch), p->max_chunk * sizeof(float2)) != hipSuccess) return -1;
+        slot = fe->d_scratch;
+        room = p->max_chunk;
+    }
+    fe->base = static_cast<float2 *>(slot);
+    fe->room = room;
+    return 0;
+}
+
+// outputs up to m1 of [tail | d_in] into the pipeline; every whole multiple of feed_block that accumulates is fed.
+// last: the end of the stream -- what remains is fed as the ragged last chunk.
+static int fe_pump(irdm_frontend *fe, irdm_pipeline *p, const void *d_in, size_t n_in, uint64_t m1, bool last)
+{
+    int bursts = 0;
+    for (;;) {
+        if (!fe->base && fe_acquire(fe, p) != 0) return -1;
+        const size_t take = (size_t)std::min<uint64_t>(fe->room - fe->pend, m1 - fe->n_out);
+        if (fe_emit(fe, d_in, n_in, fe->n_out + take, fe->base + fe->pend, fe->stream) != 0) return -1;
+        fe->pend += take;
+        const bool done = fe->n_out == m1;
+        size_t feedable = fe->pend / (size_t)p->feed_block * (size_t)p->feed_block;
+        if (last && done) feedable = fe->pend;
+        if (feedable) {
+            const int rc = irdm_feed_device(p, fe->base, feedable, fe->stream);
+            if (rc < 0) return -1;
+            bursts += rc;
+            const float2 *rest = fe->base + feedable;
+            const size_t n_rest = fe->pend - feedable;
+            fe->base = nullptr;
+            fe->pend = 0;
+            if (n_rest) {
+                if (fe_acquire(fe, p) != 0) return -1;
+                // (in the ring the remainder already lies where the next slot begins, unless the ring wraps there)
+                if (fe->base != rest)
+                    IRDM_HIP_CHECK(hipMemcpyAsync(fe->base, rest, n_rest * sizeof(float2), hipMemcpyDeviceToDevice, fe->stream));
+                fe->pend = n_rest;
+            }
+        }
+        if (done) break;
+    }
+    return bursts;
+}
+
+static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
+{
+    if (!fe || !p || fe->finished) return -1;
+    if (p->dev_fmt != IRDM_FMT_CF32 || p->cfg.sample_rate != fe->out_rate || p->cfg.device != fe->cfg.device) {
+        fprintf(stderr, "irdm_hip: front end: the pipeline must be a cf32 context at %d samples/s on device %d\n", fe->out_rate,
+                fe->cfg.device);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream_v)
+{
+    if (fe_check(fe, p) != 0 || (!d_in && n_in)) return -1;
+    pipeline_enter(p);
+    if (stream_v && static_cast<hipStream_t>(stream_v) != fe->stream) {
+        IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
+        IRDM_HIP_CHECK(hipStreamWaitEvent(fe->stream, fe->ev_caller, 0));
+    }
+    const int bursts = fe_pump(fe, p, d_in, n_in, fe_outputs(fe, fe->total + n_in, false), false);
+    if (bursts < 0) return -1;
+    if (fe_commit(fe, d_in, n_in, fe->stream) != 0) return -1;
+    IRDM_HIP_CHECK(hipEventRecord(fe->ev_in, fe->stream));
+    return bursts;
+}
+
+extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in)
+{
+    if (fe_check(fe, p) != 0 || (!h_in && n_in)) return -1;
+    pipeline_enter(p);
+    const size_t bytes = n_in * (size_t)fe->bps;
+    if (bytes > fe->stage_bytes) {
+        IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+        if (fe->d_stage) (void)hipFree(fe->d_stage);
+        fe->d_stage = nullptr;
+        fe->stage_bytes = 0;
+        IRDM_HIP_CHECK(hipMalloc(&fe->d_stage, bytes));
+        fe->stage_bytes = bytes;
+    }
+    // (one staging buffer: the copy is ordered behind the kernels that read the previous chunk, on the same stream)
+    if (bytes) IRDM_HIP_CHECK(hipMemcpyAsync(fe->d_stage, h_in, bytes, hipMemcpyHostToDevice, fe->stream));
+    IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
+    const int bursts = irdm_frontend_feed_device(fe, p, fe->d_stage, n_in, nullptr);
+    IRDM_HIP_CHECK(hipEventSynchronize(fe->ev_caller));          // the host buffer has been read
+    return bursts;
+}
+
+extern "C" int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p)
+{
+    if (fe_check(fe, p) != 0) return -1;
+    pipeline_enter(p);
+    int bursts = fe_pump(fe, p, nullptr, 0, fe_outputs(fe, fe->total, true), true);
+    if (bursts < 0) return -1;
+    fe->finished = true;
+    const int rc = irdm_flush(p);
+    return rc < 0 ? -1 : bursts + rc;
+}
+
+extern "C" int irdm_frontend_wait_input(irdm_frontend_t *fe)
+{
+    if (!fe) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    IRDM_HIP_CHECK(hipEventSynchronize(fe->ev_in));
+    return 0;
+}
+
+extern "C" int irdm_frontend_kernel_clock(irdm_frontend_t *fe, double *sum_ms, uint64_t *launches, int reset)
+{
+    if (!fe) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+    unsigned long long h[3] = { 0, 0, 0 };
+    IRDM_HIP_CHECK(hipMemcpy(h, fe->d_kclk + 128, sizeof(h), hipMemcpyDeviceToHost));
+    if (sum_ms) *sum_ms = (double)h[0] * 1e-5;                   // 10 ns ticks
+    if (launches) *launches = h[1];
+    if (reset) {
+        const unsigned long long z[3] = { 0, 0, 0 };
+        IRDM_HIP_CHECK(hipMemcpy(fe->d_kclk + 128, z, sizeof(z), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+}  // namespace irdmh

@@ -1,0 +1,271 @@
+// frontend.hip -- K0, the band-select front end: frequency shift + real low-pass + integer decimation of a wideband capture,
+// in front of K1 (no reference counterpart: the reference is given a stream at the detector's rate).
+//
+//   y[m] = sum_k h[k] * r[m D + c - k],   r[n] = x[n] * T[(q n) mod 65536],   c = (ntaps - 1) / 2,   r[n] = 0 outside the stream
+//
+// Arithmetic contract (restated in plain C in tests/frontend_model.c):
+//   x[n]   the sample converted exactly as load_iq converts it (common.hpp)
+//   r[n]   = cmul(x[n], T[i]), i = (q n) mod 65536 from the 64-bit stream position: four rounded products, one rounded
+//            difference, one rounded sum (common.hpp cmul).  Outside the stream r[n] is +0 + 0i, not a product.
+//   y[m]   per component ONE accumulator, starting at +0, and ntaps fused multiply-adds in ASCENDING INPUT ORDER:
+//            acc = fmaf(h[ntaps - 1 - j], r[m D - c + j], acc),  j = 0 .. ntaps - 1
+//
+// Shape.  A workgroup of NT lanes makes a tile of NT * 8 consecutive outputs.  Its (NT * 8 - 1) D + ntaps input samples are
+// converted and rotated ONCE, by the load stage, into LDS (8 bytes per sample; every sample feeds ntaps / D ~ 44 outputs).
+// A lane then owns 8 CONSECUTIVE outputs: an input sample read from LDS (one ds_read_b64) goes into up to 8 accumulator
+// pairs (8 v_pk_fma_f32), so the tap loop is on the VALU side of the LDS port (128 B/clk per CU = one 64-lane ds_read_b64 in
+// 4 clocks, the time of four packed FMAs on the four SIMDs).  Lane l's window starts 8 D samples behind lane l - 1's; a row
+// of 8 D samples is followed by one pad sample so that the lane stride (8 D + 1) is odd and the 64 reads of an instruction
+// fall into different banks.  In step i every lane multiplies by the SAME taps h'[i - r D], r = 0 .. 7: wavefront-uniform,
+// read as one aligned 8-dword scalar load per step from a table the host lays out (G[i][r]); the (8 - 1) D steps at either
+// end, where only some of the 8 outputs take part, are unrolled with their taps from the plain reversed array.
+// Finished outputs go through LDS once more so that the global stores are consecutive 8-byte stores per lane.
+//
+// Bounds: every global read goes through fe_load, which returns zero for a position outside [tail | chunk]; every global
+// write is guarded by m < m1.  LDS: (cnt + cnt / (8 D) + 1) samples, the host computes the same expression.
+#include "common.hpp"
+#include "types.hpp"
+#include "kernels.hpp"
+
+namespace irdm {
+
+constexpr int kFeR = 8;               // outputs per lane
+
+// a pair of fused multiply-adds with a common factor (v_pk_fma_f32)
+#if defined(IRDM_HIP_EMULATED)
+struct fe_v2 { float x, y; };
+static inline fe_v2 fe_fma(float t, fe_v2 s, fe_v2 a) { return fe_v2{ fmaf(t, s.x, a.x), fmaf(t, s.y, a.y) }; }
+#else
+typedef float fe_v2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ fe_v2 fe_fma(float t, fe_v2 s, fe_v2 a) { return __builtin_elementwise_fma(fe_v2{ t, t }, s, a); }
+#endif
+
+int frontend_threads(int D)
+{
+    // NT * 8 * D <= 8192 staged samples (64 KB) per tile
+    return D <= 4 ? 256 : (D <= 8 ? 128 : 64);
+}
+
+// staged samples of a tile and their LDS footprint in samples (rows of 8 D + one pad each)
+static inline long long fe_tile_samples(int D, int nt, int ntaps) { return (long long)(nt * kFeR - 1) * D + ntaps; }
+size_t frontend_lds_bytes(int D, int ntaps)
+{
+    const long long cnt = fe_tile_samples(D, frontend_threads(D), ntaps);
+    return (size_t)(cnt + cnt / (kFeR * D) + 1) * sizeof(float2);
+}
+
+// stream position n -> the rotated sample r[n]
+__device__ __forceinline__ float2 fe_load(const FrontendArgs &a, long long n, const float2 *__restrict__ T)
+{
+    const long long v = n - a.pos0;
+    if (n < 0 || v < 0 || v >= a.n_tail + a.n_in) return make_float2(0.0f, 0.0f);
+    const float2 x = v < a.n_tail ? load_iq(a.fmt, a.tail, (size_t)v) : load_iq(a.fmt, a.in, (size_t)(v - a.n_tail));
+    const unsigned i = (a.q16 * (unsigned)((unsigned long long)n & 0xffffull)) & 0xffffu;
+    return cmul(x, T[i]);
+}
+
+// The load stage of a tile that lies wholly inside the chunk (all but the first and last tiles of a launch): no bounds, one
+// format, eight samples and their table entries requested before the first is used -- a lane's loads are otherwise
+// issued and waited for one at a time, and with one or two wavefronts per SIMD nothing hides them (measured at D = 5:
+// the kernel's span 4.0 ms per 64 Mi outputs with the general loop alone).  The same operations on the same operands.
+template <int FMT, int NT, int RD>
+__device__ __forceinline__ void fe_stage_inside(const FrontendArgs &a, long long v0, long long n_start, int cnt,
+                                                const float2 *__restrict__ T, fe_v2 *s, int tid)
+{
+    constexpr int U = 8;
+    int g = tid;
+    for (; g + (U - 1) * NT < cnt; g += U * NT) {
+        float2 x[U], t[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int gu = g + u * NT;
+            x[u] = load_iq<FMT>(a.in, (size_t)(v0 + gu));
+            t[u] = T[(a.q16 * (unsigned)((unsigned long long)(n_start + gu) & 0xffffull)) & 0xffffu];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const int gu = g + u * NT;
+            const float2 r = cmul(x[u], t[u]);
+            s[gu + gu / RD] = fe_v2{ r.x, r.y };
+        }
+    }
+    for (; g < cnt; g += NT) {
+        const float2 x = load_iq<FMT>(a.in, (size_t)(v0 + g));
+        const float2 r = cmul(x, T[(a.q16 * (unsigned)((unsigned long long)(n_start + g) & 0xffffull)) & 0xffffu]);
+        s[g + g / RD] = fe_v2{ r.x, r.y };
+    }
+}
+
+template <int D, int NT>
+__global__ __launch_bounds__(NT) void frontend_kernel(FrontendArgs a, const float *__restrict__ hr, const float *__restrict__ G,
+                                                      const float2 *__restrict__ T, unsigned long long *__restrict__ kclk)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char fe_lds[];
+    constexpr int R = kFeR, RD = R * D, TO = NT * R;
+    fe_v2 *s = reinterpret_cast<fe_v2 *>(fe_lds);
+    const int tid = threadIdx.x;
+    const int ntaps = a.ntaps;
+    kclk_enter(kclk);
+    const long long mt = a.m0 + (long long)blockIdx.x * TO;              // the tile's first output
+    const long long n_start = mt * D - (ntaps - 1) / 2;                 // ... and its first input sample
+    const int cnt = (TO - 1) * D + ntaps;
+
+    // ---- load stage: convert, rotate, into LDS ----
+    const long long v0 = n_start - a.pos0 - a.n_tail;                   // the tile's first sample as an index into the chunk
+    if (n_start >= 0 && v0 >= 0 && v0 + cnt <= a.n_in) {
+        switch (a.fmt) {
+        case 2: fe_stage_inside<2, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        case 1: fe_stage_inside<1, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        case 3: fe_stage_inside<3, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        case 4: fe_stage_inside<4, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        default: fe_stage_inside<0, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        }
+    } else {
+        for (int g = tid; g < cnt; g += NT) {
+            const float2 r = fe_load(a, n_start + g, T);
+            s[g + g / RD] = fe_v2{ r.x, r.y };
+        }
+    }
+    __syncthreads();
+
+    // ---- the taps: lane `tid` owns outputs mt + R tid + r; in step i it reads its sample i (input (mt + R tid) D - c + i) ----
+    const fe_v2 *w = s + tid * (RD + 1);
+    fe_v2 acc[R];
+#pragma unroll
+    for (int r = 0; r < R; r++) acc[r] = fe_v2{ 0.0f, 0.0f };
+    // steps 0 .. (R - 1) D - 1: output r joins at step r D
+#pragma unroll
+    for (int b = 0; b < R - 1; b++) {
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            const int i = b * D + p;
+            const fe_v2 x = w[i + i / RD];
+#pragma unroll
+            for (int r = 0; r <= b; r++) acc[r] = fe_fma(hr[i - r * D], x, acc[r]);
+        }
+    }
+    // steps (R - 1) D .. ntaps - 1: all R outputs, taps G[i - (R - 1) D][r] = hr[i - r D]
+    // in blocks of U steps, the next block's taps (scalar loads) and samples (LDS reads) requested before the current
+    // block's multiply-adds: neither latency is waited for while there is arithmetic to issue
+    {
+        constexpr int U = 4;
+        const float *g = G;
+        int i = (R - 1) * D;
+        float tc[U * R];
+        fe_v2 xc[U];
+        auto fetch = [&](float (&t)[U * R], fe_v2 (&x)[U], const float *gp, int at) {
+#pragma unroll
+            for (int k = 0; k < U * R; k++) t[k] = gp[k];
+#pragma unroll
+            for (int u = 0; u < U; u++) x[u] = w[at + u + (at + u) / RD];
+        };
+        if (i + U <= ntaps) fetch(tc, xc, g, i);
+#pragma unroll 1
+        for (; i + U <= ntaps; i += U, g += U * R) {
+            float tn[U * R];
+            fe_v2 xn[U];
+            const bool more = i + 2 * U <= ntaps;
+            // (the last block fetches itself again: in bounds, unused)
+            fetch(tn, xn, more ? g + U * R : g, more ? i + U : i);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; u++)
+#pragma unroll
+                for (int r = 0; r < R; r++) acc[r] = fe_fma(tc[u * R + r], xc[u], acc[r]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < U * R; k++) tc[k] = tn[k];
+#pragma unroll
+            for (int u = 0; u < U; u++) xc[u] = xn[u];
+        }
+#pragma unroll 1
+        for (; i < ntaps; i++, g += R) {
+            const fe_v2 x = w[i + i / RD];
+#pragma unroll
+            for (int r = 0; r < R; r++) acc[r] = fe_fma(g[r], x, acc[r]);
+        }
+    }
+    // steps ntaps .. ntaps + (R - 1) D - 1: output r has left after step r D + ntaps - 1
+#pragma unroll
+    for (int b = 0; b < R - 1; b++) {
+#pragma unroll
+        for (int p = 0; p < D; p++) {
+            const int e = b * D + p, i = ntaps + e;
+            const fe_v2 x = w[i + i / RD];
+#pragma unroll
+            for (int r = b + 1; r < R; r++) acc[r] = fe_fma(hr[i - r * D], x, acc[r]);
+        }
+    }
+    __syncthreads();
+
+    // ---- outputs through LDS (rows of R + 1), then consecutive stores ----
+#pragma unroll
+    for (int r = 0; r < R; r++) s[tid * (R + 1) + r] = acc[r];
+    __syncthreads();
+    for (int o = tid; o < TO; o += NT) {
+        const long long m = mt + o;
+        if (m < a.m1) {
+            const fe_v2 y = s[(o / R) * (R + 1) + (o % R)];
+            a.out[m - a.m0] = make_float2(y.x, y.y);
+        }
+    }
+    kclk_leave(kclk);
+}
+
+template <int D>
+static int launch_frontend_d(const FrontendArgs &a, const float *hr, const float *G, const float2 *T, hipStream_t stream,
+                             unsigned long long *kclk)
+{
+    constexpr int NT = D <= 4 ? 256 : (D <= 8 ? 128 : 64);
+    const long long n_out = a.m1 - a.m0;
+    const long long tiles = (n_out + NT * kFeR - 1) / (NT * kFeR);
+    if (tiles <= 0) return 0;
+    if (tiles > 0x7fffffffll) return -1;
+    const size_t lds = frontend_lds_bytes(D, a.ntaps);
+    if (lds > 160 * 1024) return -1;
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&frontend_kernel<D, NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+        return -1;
+    hipLaunchKernelGGL((frontend_kernel<D, NT>), dim3((unsigned)tiles), dim3(NT), lds, stream, a, hr, G, T, kclk);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// outputs [a.m0, a.m1) of the front end into a.out; hr: the taps reversed (ntaps), G: the table of the full steps
+// ((ntaps - 7 D) rows of 8), T: the 65536-entry rotation table
+int launch_frontend(int D, const FrontendArgs &a, const float *hr, const float *G, const float2 *T, hipStream_t stream,
+                    unsigned long long *kclk)
+{
+    if (a.ntaps < (kFeR - 1) * D + 1 || a.fmt < 0 || a.fmt > 4 || a.m1 < a.m0 || a.pos0 < 0) return -1;
+    switch (D) {
+#define FE_CASE(d) case d: return launch_frontend_d<d>(a, hr, G, T, stream, kclk);
+    FE_CASE(2) FE_CASE(3) FE_CASE(4) FE_CASE(5) FE_CASE(6) FE_CASE(7) FE_CASE(8) FE_CASE(9) FE_CASE(10) FE_CASE(11)
+    FE_CASE(12) FE_CASE(13) FE_CASE(14) FE_CASE(15) FE_CASE(16)
+#undef FE_CASE
+    default: return -1;
+    }
+}
+
+// The samples a later output still needs: new_tail[i] = [tail | chunk][from + i], raw bytes (bps per sample).
+__global__ __launch_bounds__(256) void frontend_tail_kernel(const unsigned char *__restrict__ tail, long long n_tail,
+                                                            const unsigned char *__restrict__ in, long long n_in, long long from,
+                                                            int n_new, int bps, unsigned char *__restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_new) return;
+    const long long v = from + i;
+    if (v < 0 || v >= n_tail + n_in) return;
+    const unsigned char *src = v < n_tail ? tail + (size_t)v * bps : in + (size_t)(v - n_tail) * bps;
+    for (int b = 0; b < bps; b++) out[(size_t)i * bps + b] = src[b];
+}
+
+int launch_frontend_tail(const void *tail, long long n_tail, const void *in, long long n_in, long long from, int n_new, int bps,
+                         void *out, hipStream_t stream)
+{
+    if (n_new <= 0) return 0;
+    hipLaunchKernelGGL(frontend_tail_kernel, dim3((unsigned)((n_new + 255) / 256)), dim3(256), 0, stream,
+                       static_cast<const unsigned char *>(tail), n_tail, static_cast<const unsigned char *>(in), n_in, from, n_new,
+                       bps, static_cast<unsigned char *>(out));
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace irdm

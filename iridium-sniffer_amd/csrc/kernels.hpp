@@ -180,4 +180,22 @@ int launch_demod(const BurstWork *work, int n_bursts, const float2 *frames, int 
                  float sps, float2 *ws, DemodOut *out, hipStream_t stream, DemodPacked *hp_packed = nullptr,
                  BurstWork *hp_work = nullptr, int keep_bits = 0);
 
+// frontend.hip (K0): one launch's view of the capture -- the carried tail in front of the chunk, raw samples of format fmt
+struct FrontendArgs {
+    const void *tail;            // n_tail samples that precede the chunk
+    const void *in;              // the chunk, n_in samples
+    long long n_tail, n_in;
+    long long pos0;              // stream position of tail[0]
+    long long m0, m1;            // outputs [m0, m1) are produced; out[m - m0]
+    float2 *out;
+    unsigned q16;                // the quantised shift modulo 65536
+    int ntaps, fmt;
+};
+int frontend_threads(int D);
+size_t frontend_lds_bytes(int D, int ntaps);
+int launch_frontend(int D, const FrontendArgs &a, const float *hr, const float *G, const float2 *T, hipStream_t stream,
+                    unsigned long long *kclk);
+int launch_frontend_tail(const void *tail, long long n_tail, const void *in, long long n_in, long long from, int n_new, int bps,
+                         void *out, hipStream_t stream);
+
 }  // namespace irdm

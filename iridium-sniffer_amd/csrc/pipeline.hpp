@@ -378,6 +378,7 @@ struct irdm_pipeline {
 static inline void pipeline_enter(const irdm_pipeline *p) { (void)hipSetDevice(p->cfg.device); }
 
 namespace irdmh {
+bool rate_supported(int fs, int *fft_size);      // create.cpp: a sample rate irdm_create takes
 
 template <typename T>
 static int drain(std::deque<T> &q, T *out, int max)

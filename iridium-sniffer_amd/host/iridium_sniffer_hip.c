@@ -5,6 +5,7 @@
  *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
+ *                         [--band-center HZ --decimate D]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -14,6 +15,10 @@
  * --format ci16-full and --format sc16q11 read interleaved int16 at full precision, scaled as the reference's live
  * SoapySDR CS16 (v / 32768) and bladeRF SC16Q11 (v / 2048) paths scale it; ci16 (and a .ci16 / .cs16 file) is the
  * reference's file path, narrowed to 8 bits.
+ * --band-center HZ --decimate D (both or neither): the file is a wideband capture -- -r and -c describe it -- and the band
+ * around HZ is shifted to the centre, low-passed and decimated by D (2 .. 16) on the GPU in front of the detector
+ * (irdm_frontend_*): a 50 MS/s capture with --decimate 5 runs as a 10 MS/s stream centred at HZ (at the nearest multiple
+ * of RATE / 65536 from -c, printed with -v).  --chunk stays in samples of the decimated stream.
  */
 #include <err.h>
 #include <stdint.h>
@@ -260,6 +265,8 @@ int main(int argc, char **argv)
     long long origin_sec = 0, origin_nsec = 0;
     int position = 0;
     double position_height = 0;
+    int decimate = 0, band_given = 0;      /* --band-center / --decimate: the band-select front end */
+    double band_center = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -307,6 +314,8 @@ int main(int argc, char **argv)
             fprintf(stderr, "%s: network output is not built in this binary (ACARS goes to stdout with --acars / --acars-json)\n", a);
             return 2;
         }
+        else if (!strcmp(a, "--band-center")) { band_center = atof(NEXT()); band_given = 1; }
+        else if (!strcmp(a, "--decimate")) decimate = atoi(NEXT());
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -321,9 +330,18 @@ int main(int argc, char **argv)
         }
     }
     if (!file || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D]\n", argv[0]);
         return 2;
     }
+    if (band_given != (decimate != 0)) {
+        fprintf(stderr, "--band-center and --decimate go together\n");
+        return 2;
+    }
+    if (decimate && gpus > 1) {
+        fprintf(stderr, "--band-center / --decimate: one GPU only (--gpus %d)\n", gpus);
+        return 2;
+    }
+    if (decimate) gpus = 0;
     const int format_given = format != NULL;
     if (!format) format = ext_of(file);              /* autodetect by extension, options.c:533-544 */
     int fmt = IRDM_FMT_CI8;
@@ -335,12 +353,27 @@ int main(int argc, char **argv)
     else if (format_given && !strcmp(format, "ci16-full")) { fmt = IRDM_FMT_CI16_FULL; bps = 4; }
     else if (format_given && !strcmp(format, "sc16q11")) { fmt = IRDM_FMT_SC16Q11; bps = 4; }
 
+    /* the front end first: the context behind it runs at its output rate, centred where the applied shift puts it */
+    irdm_frontend_t *fe = NULL;
+    if (decimate) {
+        irdm_frontend_config_t fc;
+        memset(&fc, 0, sizeof(fc));
+        fc.in_rate = (int)rate;
+        fc.in_format = fmt;
+        fc.decim = decimate;
+        fc.shift_hz = band_center - freq;
+        fe = irdm_frontend_create(&fc);
+        if (!fe) {
+            fprintf(stderr, "irdm_frontend_create failed (no MI355X / bad parameters)\n");
+            return 1;
+        }
+    }
     irdm_config_t c;
     memset(&c, 0, sizeof(c));
-    c.center_frequency = freq;
-    c.sample_rate = (int)rate;
+    c.center_frequency = fe ? freq + irdm_frontend_applied_shift_hz(fe) : freq;
+    c.sample_rate = fe ? irdm_frontend_out_rate(fe) : (int)rate;
     c.threshold_db = (float)db;
-    c.format = fmt;
+    c.format = fe ? IRDM_FMT_CF32 : fmt;
     c.feed_block = 32768;
     c.use_gardner = gardner;
     /* (several GPUs: a chunk must hold the samples a member is given from in front of its chunk -- 2 s of signal, the
@@ -415,8 +448,13 @@ int main(int argc, char **argv)
     g_save_dir = save_dir;
     if (verbose) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
                          gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");
+    if (verbose && fe)
+        fprintf(stderr, "front end: %d -> %d samples/s, %d taps, shift %.3f Hz applied (%.3f asked), centre %.3f Hz\n", (int)rate,
+                irdm_frontend_out_rate(fe), irdm_frontend_ntaps(fe), irdm_frontend_applied_shift_hz(fe), band_center - freq,
+                c.center_frequency);
     /* a group is fed a super-step at a time: one chunk per member */
-    const size_t step = chunk * (size_t)(gpus > 0 ? gpus : 1);
+    /* (behind a front end the reader's chunk is D pipeline chunks of capture samples) */
+    const size_t step = chunk * (size_t)(gpus > 0 ? gpus : 1) * (size_t)(fe ? decimate : 1);
 
     FILE *f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
     if (!f) { perror(file); return 1; }
@@ -458,7 +496,8 @@ int main(int argc, char **argv)
         sem_wait(&rd.filled);
         const size_t r = rd.n[k];
         if (r == 0) break;                          /* end of file */
-        if (rc == 0 && (g_group ? irdm_group_feed_host(g_group, rd.buf[k], r) : irdm_feed_host(p, rd.buf[k], r)) < 0) {
+        if (rc == 0 && (fe ? irdm_frontend_feed_host(fe, p, rd.buf[k], r)
+                           : g_group ? irdm_group_feed_host(g_group, rd.buf[k], r) : irdm_feed_host(p, rd.buf[k], r)) < 0) {
             fprintf(stderr, "burst_detect: GPU processing failed\n");
             rc = 1;
         }
@@ -475,7 +514,7 @@ int main(int argc, char **argv)
         sem_post(&rd.sl[i].go);
         pthread_join(rd.sl[i].th, NULL);
     }
-    if (rc == 0 && (g_group ? irdm_group_flush(g_group) : irdm_flush(p)) < 0) { fprintf(stderr, "burst_detect: GPU processing failed\n"); rc = 1; }
+    if (rc == 0 && (fe ? irdm_frontend_flush(fe, p) : g_group ? irdm_group_flush(g_group) : irdm_flush(p)) < 0) { fprintf(stderr, "burst_detect: GPU processing failed\n"); rc = 1; }
     drain(p, d, file_info, &t0, line, sizeof line);
     fflush(stdout);
     if (g_dop && rc == 0)          /* the ticks up to the stream's end (samples / rate), then the final solve */
@@ -501,6 +540,7 @@ int main(int argc, char **argv)
         _exit(rc);
     }
     const double t_down = now_s();
+    irdm_frontend_destroy(fe);
     if (g_group) irdm_group_destroy(g_group);
     else irdm_destroy(p);
     irdm_host_free(rd.buf[0]);

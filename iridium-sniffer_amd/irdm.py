@@ -128,6 +128,12 @@ class AcarsStats(C.Structure):
                                          "sbd_multi_frag", "sbd_broken", "acars_total", "acars_errors")]
 
 
+class FrontendConfig(C.Structure):
+    """irdm_frontend_config_t: the band-select front end (csrc/frontend.cpp)"""
+    _fields_ = [("device", C.c_int), ("in_rate", C.c_int), ("in_format", C.c_int), ("decim", C.c_int),
+                ("shift_hz", C.c_double)]
+
+
 ACARS_LINE_MAX = 8192
 RAW_LINE_MAX = 1280
 _lib = None
@@ -293,6 +299,26 @@ def lib():
                 getattr(L, name).restype = C.c_longlong
                 getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(rec), C.POINTER(ida), C.c_int, C.c_int,
                                              C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+        if hasattr(L, "irdm_frontend_create"):             # (csrc/frontend.cpp)
+            L.irdm_device_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.irdm_frontend_create.restype = C.c_void_p
+            L.irdm_frontend_create.argtypes = [C.POINTER(FrontendConfig)]
+            L.irdm_frontend_destroy.argtypes = [C.c_void_p]
+            L.irdm_frontend_destroy.restype = None
+            L.irdm_frontend_out_rate.argtypes = [C.c_void_p]
+            L.irdm_frontend_applied_shift_hz.argtypes = [C.c_void_p]
+            L.irdm_frontend_applied_shift_hz.restype = C.c_double
+            L.irdm_frontend_ntaps.argtypes = [C.c_void_p]
+            L.irdm_frontend_taps.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+            L.irdm_frontend_run_device.restype = C.c_longlong
+            L.irdm_frontend_run_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.irdm_frontend_finish_device.restype = C.c_longlong
+            L.irdm_frontend_finish_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.irdm_frontend_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.irdm_frontend_feed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+            L.irdm_frontend_flush.argtypes = [C.c_void_p, C.c_void_p]
+            L.irdm_frontend_wait_input.argtypes = [C.c_void_p]
+            L.irdm_frontend_kernel_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
         _lib = L
     return _lib
 
@@ -323,6 +349,12 @@ def device_buffer(array, device=0):
         L.irdm_device_free(ptr)
         raise RuntimeError("irdm_device_upload failed")
     return ptr
+
+
+def device_download(array, ptr):
+    """Copy array.nbytes from the device address ptr into the (contiguous) numpy array (irdm_device_download)."""
+    if lib().irdm_device_download(array.ctypes.data_as(C.c_void_p), C.c_void_p(ptr), array.nbytes) != 0:
+        raise RuntimeError("irdm_device_download failed")
 
 
 def device_free(ptr):
@@ -685,6 +717,70 @@ class Pipeline:
     def close(self):
         if self.h:
             self.L.irdm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Frontend:
+    """irdm_frontend_*: band select in front of a Pipeline -- shift by shift_hz, low-pass, decimate by decim.  The pipeline
+    behind it is a cf32 context at out_rate, centred at the capture centre + applied_shift_hz."""
+
+    def __init__(self, in_rate, fmt, decim, shift_hz=0.0, device=0):
+        self.L = lib()
+        self.cfg = FrontendConfig(device, int(in_rate), fmt, int(decim), float(shift_hz))
+        self.h = self.L.irdm_frontend_create(C.byref(self.cfg))
+        if not self.h:
+            raise RuntimeError("irdm_frontend_create failed (no GPU, or bad config)")
+        self.fmt = fmt
+        self.out_rate = self.L.irdm_frontend_out_rate(self.h)
+        self.applied_shift_hz = self.L.irdm_frontend_applied_shift_hz(self.h)
+        self.ntaps = self.L.irdm_frontend_ntaps(self.h)
+
+    def taps(self):
+        out = np.empty(self.ntaps, np.float32)
+        if self.L.irdm_frontend_taps(self.h, _fp(out), self.ntaps) != self.ntaps:
+            raise RuntimeError("irdm_frontend_taps failed")
+        return out
+
+    def feed_host(self, pipeline, x):
+        x = np.ascontiguousarray(x)
+        n = len(x) if self.fmt == FMT_CF32 else len(x) // 2
+        rc = self.L.irdm_frontend_feed_host(self.h, pipeline.h, x.ctypes.data_as(C.c_void_p), n)
+        if rc < 0:
+            raise RuntimeError("irdm_frontend_feed_host failed")
+        return rc
+
+    def feed_device(self, pipeline, ptr, n_samples, stream=None):
+        rc = self.L.irdm_frontend_feed_device(self.h, pipeline.h, C.c_void_p(ptr), n_samples, C.c_void_p(stream or 0))
+        if rc < 0:
+            raise RuntimeError("irdm_frontend_feed_device failed")
+        return rc
+
+    def wait_input(self):
+        if self.L.irdm_frontend_wait_input(self.h) != 0:
+            raise RuntimeError("irdm_frontend_wait_input failed")
+
+    def flush(self, pipeline):
+        rc = self.L.irdm_frontend_flush(self.h, pipeline.h)
+        if rc < 0:
+            raise RuntimeError("irdm_frontend_flush failed")
+        return rc
+
+    def kernel_clock(self, reset=False):
+        """(sum of K0's device spans in ms, launches) since the last reset"""
+        sm, n = C.c_double(0), C.c_uint64(0)
+        if self.L.irdm_frontend_kernel_clock(self.h, C.byref(sm), C.byref(n), 1 if reset else 0) != 0:
+            raise RuntimeError("irdm_frontend_kernel_clock failed")
+        return sm.value, int(n.value)
+
+    def close(self):
+        if self.h:
+            self.L.irdm_frontend_destroy(self.h)
             self.h = None
 
     def __del__(self):
