@@ -310,6 +310,20 @@ int irdm_flush(irdm_pipeline_t *p);
  * emitted, -1 on error.  (No reference counterpart: burst_downmix / qpsk_demod run on their own threads there,
  * main.c:667-694.) */
 int irdm_advance(irdm_pipeline_t *p);
+/* Another stream through the same context (no reference counterpart: burst_detector_destroy + _create cost microseconds
+ * there; here irdm_create builds hundreds of MB of device state).  Ends whatever stream the context carried and leaves it
+ * indistinguishable, in every result it will produce, from a context just returned by irdm_create with the same
+ * irdm_config_t -- but this centre frequency and start time (0 -> now, as in irdm_create) -- and the same options set:
+ * burst ids, sample indices, the detector's 512-frame priming, timestamps, irdm_tagged_bursts, irdm_sample_count,
+ * irdm_detector_stats and irdm_export_state all start over.  May be called after irdm_flush, or mid-stream: the scan and
+ * the per-burst chains in flight are then waited for and abandoned, and EVERY record queue is emptied, polled or not.
+ * What depends only on rate, format and options is kept and nothing is allocated: filters and tables, the rotator
+ * checkpoint rows, scratch that has grown, streams and events.  The "stat" counters of irdm_get_stat and the
+ * irdm_kernel_clock sums are diagnostics of the context, not of a stream: they run on ("resets" counts these calls).
+ * Waits for the context's own streams, not for the device.  0 ok; -1 and nothing changed when a chunk handed over with
+ * irdm_feed_begin still waits for its irdm_feed_end, when a scan waits for a history import (irdm_expect_history), or for
+ * a member of a group (a group is not reset: destroy and create it). */
+int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t start_time_ns);
 /* Pinned (page-locked) host memory for feed buffers, for hosts without HIP headers.  NULL on failure. */
 void *irdm_host_alloc(size_t bytes);
 void irdm_host_free(void *ptr);
@@ -505,7 +519,7 @@ int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max);
 uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
 
 /* Options (irdm_set_option; every one a field of THIS context -- two contexts of a process may differ in all of them; set them
- * before the first feed unless noted).  Twenty keys:
+ * before the first feed unless noted; irdm_reset keeps them all).  Twenty-one keys:
  *
  *   what a caller chooses
  *   "keep_frame_samples"  0/1, default 0: irdm_poll_frames returns metadata only
@@ -541,6 +555,7 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         0.07 / 1.3 / 3.2 GB at 2 / 10 / 12 MHz) instead of by the chains that first meet the bin; only
  *                         before the first burst
  *   "kernel_clock"        0/1, default 0: see irdm_kernel_clock
+ *   "group_member"        0/1, default 0: set by irdm_group_create on its members; irdm_reset refuses such a context
  *
  *   diagnostic
  *   "band_timeline"       0/1: the band scan's passes stamp a device timeline (stats "tl_dur_i" / "tl_gap_i" / "tl_n_i")
@@ -558,7 +573,7 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *   "scratch_outputs"     n = the decimated / low-passed scratch of every batch context with room for n outputs to begin with
  *
  * Stats (irdm_get_stat): "scan_fast_chunks", "scan_fallbacks", "scan_dense_frames", "band_chunks", "band_rounds",
- * "band_retries", "band_aborts", "band_extra", "band_last_flags", "k1_lists", "scan_chained", "scan_chain_undone", "spec_passes",
+ * "band_retries", "band_aborts", "band_extra", "band_last_flags", "k1_lists", "resets", "scan_chained", "scan_chain_undone", "spec_passes",
  * "spec_scans", "sum_restarts", "host_us_0".."host_us_9", "rot_rows", "rot_prebuilt_runs",
  * "rot_rows_cap", "rot_blocks", "rot_blocks_cap", "rot_builds", "rot_runs", "rot_ckpts", "rot_grows" (rotator checkpoints:
  * centre bins with a row / runs per bin prebuilt / the arena in whole rows / blocks of 2048 checkpoints in use / allocated /
@@ -779,6 +794,11 @@ int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const voi
 int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in);
 /* the end of the stream: the zero-padded rest, the held-back remainder as the pipeline's last chunk, then irdm_flush(p) */
 int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p);
+/* Another capture through the same front end (with irdm_reset of the pipeline behind it): back to its state after
+ * irdm_frontend_create -- no carried tail, stream position and output count zero (and with them the rotator's phase index),
+ * nothing held back by the feeder, not finished.  Taps, tables and the applied shift stay; nothing is allocated.  Waits for
+ * the front end's stream.  0 ok, -1 error. */
+int irdm_frontend_reset(irdm_frontend_t *fe);
 /* host wait until everything enqueued so far has read its input buffer */
 int irdm_frontend_wait_input(irdm_frontend_t *fe);
 /* irdm_kernel_clock for K0 (always on): the kernel's own spans on the device summed since the last reset.  Waits for the

@@ -14,6 +14,7 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     if (!strcmp(key, "parsed_records")) { p->parsed_records = value; return 0; }
     if (!strcmp(key, "frame_records")) { p->frame_records = value; return 0; }
     if (!strcmp(key, "chunk_marks")) { p->chunk_marks = value ? 1 : 0; if (!value) p->q_marks.clear(); return 0; }
+    if (!strcmp(key, "group_member")) { p->in_group = value != 0; return 0; }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
     if (!strcmp(key, "detect_only")) { p->detect_only = value; return 0; }
@@ -68,6 +69,7 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
 extern "C" int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key)
 {
     if (!p || !key) return -1;
+    if (!strcmp(key, "resets")) return (int64_t)p->stat_resets;
     if (!strcmp(key, "scan_fast_chunks")) return (int64_t)p->stat_fast_chunks;
     if (!strcmp(key, "scan_fallbacks")) return (int64_t)p->stat_fallbacks;
     if (!strncmp(key, "host_us_", 8) && key[8] >= '0' && key[8] <= '9') return (int64_t)p->host_us[key[8] - '0'];

@@ -969,4 +969,25 @@ int launch_detect_scan(const DetParams &P, DetState *st, float *sum, float *hist
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// irdm_reset: the detector's small carried blocks (DetState, the running sums, the band scan's markers and its speculation
+// state: a few tens of KB in all) back to zero in ONE launch instead of a memset per block; block r is zeroed by the
+// workgroups of row r of the grid, a word per lane and store.  The 512-frame history (16-32 MiB) goes by hipMemsetAsync
+// beside it.
+__global__ __launch_bounds__(256) void zero_regions_kernel(ZeroRegions z)
+{
+    const int r = (int)blockIdx.y;
+    if (r >= z.n) return;
+    uint32_t *__restrict__ dst = z.ptr[r];
+    const uint32_t n = z.words[r];
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) dst[i] = 0u;
+}
+
+int launch_zero_regions(const ZeroRegions &z, hipStream_t stream)
+{
+    if (z.n <= 0) return 0;
+    if (z.n > ZeroRegions::kMax) return -1;
+    hipLaunchKernelGGL(zero_regions_kernel, dim3(8, (unsigned)z.n), dim3(256), 0, stream, z);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 }  // namespace irdm

@@ -1,4 +1,4 @@
-// feed.cpp -- the feeding calls (irdm_feed_begin / _end / _device / _host, irdm_flush, irdm_advance), the polls, and the
+// feed.cpp -- the feeding calls (irdm_feed_begin / _end / _device / _host, irdm_flush, irdm_advance), irdm_reset, the polls, and the
 // buffer helpers for hosts without HIP headers.
 #include "pipeline.hpp"
 
@@ -66,6 +66,115 @@ extern "C" int irdm_advance(irdm_pipeline_t *p)
         if (deferred_enqueue(p) != 0) return -1;
     }
     return emitted;
+}
+
+// The context back to what irdm_create returned, for another stream at the same rate, format and options (DESIGN.md
+// section 4 sorts every field of irdm_pipeline into configuration, cache and stream state; this function is the list of the
+// third kind).  The old stream is abandoned where it stands: the scan and the chains in flight are waited for -- stream by
+// stream, the device as a whole is not -- and what they produced is dropped with the queues.  The history ring keeps its
+// contents: no reader takes a slot of an absolute index the NEW stream has not written (burst_src.hpp: a sample at or past
+// avail_end comes from index a - ref_ring, zero below ref_ring; K1 reads the chunk it is handed, in place or not).
+extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t start_time_ns)
+{
+    if (!p || p->in_group) return -1;
+    if (p->begin_no != p->end_no) return -1;        // a chunk handed over with irdm_feed_begin still waits for its irdm_feed_end
+    if (p->gate_open_pending) {
+        fprintf(stderr, "irdm_hip: irdm_reset while a scan waits for a history import (irdm_expect_history)\n");
+        return -1;
+    }
+    pipeline_enter(p);
+    // 1. whatever the old stream still has on the device: K1 and ring copies, the scan (and a speculation pass beside it),
+    //    the per-burst chains with their host step
+    IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
+    if (p->stream != p->fstream) IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
+    if (p->stream_spec) IRDM_HIP_CHECK(hipStreamSynchronize(p->stream_spec));
+    for (int i = 0; i < p->n_bc; i++) {
+        BatchCtx &b = p->bc[i];
+        IRDM_HIP_CHECK(hipStreamSynchronize(b.stream));
+        p->rot_done_gen[i] = p->rot_gen[i];         // (its rotator checkpoint builds are complete: the rows are kept)
+        b.n = 0;                                    // only now: the helper thread reads it while the chain is in flight
+        b.hp_flag[1] = 0;
+        b.chunk_no = 0;
+        b.ring_lo = b.ring_hi = 0;
+        b.recs.clear();
+    }
+    // 2. device side, on the detector's stream: the detector state, the running sums and the 512-frame history as
+    //    irdm_create leaves them; the band scan's commit / void markers and the speculation workspace's carried state.
+    //    (K1's candidate lists are rebuilt by every irdm_feed_begin and marked per feed slot below; every other scan
+    //    buffer is written before it is read.)  The first scan of the new stream is enqueued behind this on the same
+    //    stream; K1 reads the sums only once the host has seen a scan prime the detector.
+    const DetParams &P = p->P;
+    IRDM_HIP_CHECK(hipMemsetAsync(p->d_hist, 0, sizeof(float) * (size_t)kHistory * P.n, p->stream));
+    ZeroRegions z;
+    bool ok = z.add(p->d_state, sizeof(DetState)) && z.add(p->d_sum, sizeof(float) * (size_t)P.n);
+    if (p->band_ok) ok = ok && z.add(p->band.bar, 256);
+    if (p->d_band_spec)
+        ok = ok && z.add(p->band_spec.ctl, sizeof(BandCtl)) && z.add(p->band_spec.bar, 256) &&
+             z.add(p->band_spec.rec_count, 4 * 64) && z.add(p->band_spec.flags, 256) && z.add(p->d_state_spec, sizeof(DetState));
+    if (!ok || launch_zero_regions(z, p->stream) != 0) return -1;
+    // 3. host side
+    p->cfg.center_frequency = center_frequency;
+    p->start_time_ns = start_time_ns;
+    if (p->start_time_ns == 0) {
+        struct timespec ts;
+        clock_gettime(CLOCK_REALTIME, &ts);
+        p->start_time_ns = ts.tv_sec * 1000000000ULL + ts.tv_nsec;
+    }
+    p->total_samples = p->begun_samples = 0;
+    p->begin_no = p->end_no = 0;
+    p->chunk_no = 0;
+    p->tagged = 0;
+    p->stream_closed = false;
+    p->peak_signal_db = 0;
+    p->host_primed = 0;
+    p->host_hist_idx = 0;
+    for (auto &f : p->fs) {
+        f.iq = nullptr;
+        f.c0 = f.c1 = 0;
+        f.mag = nullptr;
+        f.frames = 0;
+        f.in_ring = f.lists = false;
+    }
+    // (the scan in flight, the one chained behind it, the bursts waiting for a batch context)
+    p->fl_active = p->fl_sparse = p->fl_band_ran = false;
+    p->fl_mode = p->fl_done = p->fl_frames = 0;
+    p->fl_mag = p->d_mag_last = nullptr;
+    p->fl_c0 = p->fl_c1 = p->fl_no = 0;
+    p->fl_feed = nullptr;
+    p->fl_seq = p->chain_seq = p->seq_counter = 0;
+    p->chain_pending = false;
+    p->chain_no = 0;
+    p->chain_sel = 0;
+    p->settle_clean = true;
+    scan_select_outputs(p, 0);
+    for (int s = 0; s < 2; s++) memset(p->h_pin_set[s], 0, sizeof(int) * 128);
+    p->spec_for_no = ~0ull;
+    p->spec_frames = 0;
+    p->has_pending = false;
+    p->pend_gone.clear();
+    p->pend_c1 = p->pend_no = 0;
+    p->deferred_emitted = 0;
+    p->caller_ordered = false;
+    p->gate_armed = false;
+    p->gate_src = nullptr;
+    // (the probes of the last chunk)
+    p->last_frames = 0;
+    p->last_chunk = nullptr;
+    p->last_chunk_start = p->last_chunk_end = 0;
+    p->last_bursts.clear();
+    for (float &ms : p->last_ms) ms = 0.0f;
+    p->q_bursts.clear();
+    p->q_frames.clear();
+    p->q_frame_samples.clear();
+    p->q_demods.clear();
+    p->q_packed.clear();
+    p->q_ida_packed.clear();
+    p->q_frame_packed.clear();
+    p->q_ida.clear();
+    p->q_decoded.clear();
+    p->q_marks.clear();
+    p->stat_resets++;
+    return 0;
 }
 
 // A feed in two halves.  irdm_feed_begin: everything that does not depend on the detector state -- K1 of the chunk and

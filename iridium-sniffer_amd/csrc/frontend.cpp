@@ -331,6 +331,23 @@ extern "C" int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p)
     return rc < 0 ? -1 : bursts + rc;
 }
 
+// Back to irdm_frontend_create's state for another capture: no carried tail, stream position and output count (the NCO's
+// phase index with them) zero, nothing held back by the feeder.  Taps, tables, the applied shift, the scratch chunk and the
+// staging buffer stay.  (The tail buffers keep their bytes: with n_tail 0 the kernel reads none of them.)
+extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
+{
+    if (!fe) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));      // (launches in flight read the tail and the staging buffer)
+    fe->cur = 0;
+    fe->n_tail = 0;
+    fe->total = fe->n_out = 0;
+    fe->finished = false;
+    fe->base = nullptr;
+    fe->room = fe->pend = 0;
+    return 0;
+}
+
 extern "C" int irdm_frontend_wait_input(irdm_frontend_t *fe)
 {
     if (!fe) return -1;

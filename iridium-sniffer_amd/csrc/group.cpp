@@ -582,7 +582,8 @@ static int group_build(irdm_group *g, const irdm_config_t *cfg, const int *devic
         if (r > 0) c.start_time_ns = irdm_start_time_ns(g->m[0].p);
         mb.p = irdm_create(&c);
         if (!mb.p) return -1;
-        if (irdm_set_option(mb.p, "chunk_marks", 1) != 0) return -1;
+        // ("group_member": irdm_reset refuses the context -- the group's own bookkeeping would not follow)
+        if (irdm_set_option(mb.p, "chunk_marks", 1) != 0 || irdm_set_option(mb.p, "group_member", 1) != 0) return -1;
         GRP_HIP(hipSetDevice(mb.dev));
         GRP_HIP(hipStreamCreateWithFlags(&mb.xs, hipStreamNonBlocking));
         GRP_HIP(hipStreamCreateWithFlags(&mb.hs, hipStreamNonBlocking));

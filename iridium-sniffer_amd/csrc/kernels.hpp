@@ -19,6 +19,22 @@ int launch_detect_scan(const DetParams &P, DetState *st, float *sum, float *hist
                        int n_frames, GoneBurst *gone, int gone_cap, PeakCand *cand_a,
                        PeakCand *cand_b, hipStream_t stream);
 
+// irdm_reset: up to kMax blocks of device memory (whole 32-bit words each) zeroed by one launch (zero_regions_kernel)
+struct ZeroRegions {
+    static constexpr int kMax = 8;
+    uint32_t *ptr[kMax];
+    uint32_t words[kMax];
+    int n = 0;
+    bool add(void *p, size_t bytes)
+    {
+        if (!p || n >= kMax || bytes % 4 != 0 || bytes / 4 > 0xffffffffull) return false;
+        ptr[n] = static_cast<uint32_t *>(p);
+        words[n++] = (uint32_t)(bytes / 4);
+        return true;
+    }
+};
+int launch_zero_regions(const ZeroRegions &z, hipStream_t stream);
+
 // scan_fast.hip
 int launch_prefilter(const float *sum, float thr, float *pre, const float *mag, int n,
                      unsigned *counts, ListEntry *entries, unsigned *goff, ListEntry *compact,

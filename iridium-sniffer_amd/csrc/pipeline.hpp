@@ -6,7 +6,7 @@
 //   create.cpp      irdm_create / irdm_destroy, the small getters
 //   chain.cpp       the per-burst chain of a chunk (K4 .. K7): rotator checkpoint arena, enqueue, records
 //   scan_host.cpp   the detector scan of a chunk from the host's side: launch, chaining, speculation pass, settle, fallbacks
-//   feed.cpp        irdm_feed_* / irdm_flush / irdm_advance, the polls, buffers for hosts without HIP headers
+//   feed.cpp        irdm_feed_* / irdm_flush / irdm_advance / irdm_reset, the polls, buffers for hosts without HIP headers
 //   state.cpp       detector-state export / import (time-chunk sharding), the stage-level batch calls
 //   api.cpp         options, statistics, kernel clock, RAW line formatting, --save-bursts
 #pragma once
@@ -362,6 +362,9 @@ struct irdm_pipeline {
     unsigned long long *kclk_rec(int i) const { return kernel_clock && d_kclk ? d_kclk + (size_t)i * kKClkWords : nullptr; }
     // (the decimator of batch context c: records 0..2, and 6.. for the contexts beyond the third)
     unsigned long long *kclk_fir(int c) const { return kclk_rec(c < 3 ? c : 3 + c); }
+    // irdm_reset (feed.cpp)
+    bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
+    uint64_t stat_resets = 0;   // irdm_reset calls that went through
 };
 
 // The rotator checkpoints (rotator.h:36-46 restated: the phase of the float recurrence every 16 samples -- a whole row for

@@ -6,6 +6,7 @@
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
  *                         [--band-center HZ --decimate D]
+ *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -19,8 +20,18 @@
  * around HZ is shifted to the centre, low-passed and decimated by D (2 .. 16) on the GPU in front of the detector
  * (irdm_frontend_*): a 50 MS/s capture with --decimate 5 runs as a 10 MS/s stream centred at HZ (at the nearest multiple
  * of RATE / 65536 from -c, printed with -v).  --chunk stays in samples of the decimated stream.
+ * Several recordings in one run: -f more than once and / or --files-from LIST (one "PATH" or "PATH START_SEC[.NNNNNNNNN]"
+ * per line).  They go, in the order given, through ONE context, one front end and one pair of pinned buffers, with
+ * irdm_reset / irdm_frontend_reset between them: what is paid once per process -- the HIP runtime, the context's device
+ * buffers, its filters and rotator rows, the pinned allocations -- is paid once per run.  Every option holds for all of them;
+ * each prints exactly what a run of its own prints (its lines, its "tagged N bursts total", its own ACARS and position
+ * state and closing lines), to stdout one after the other or, with --out-dir DIR, to DIR/<basename>.out.
+ * --start-time is the capture time of the first recording (instead of the wall clock at start: the timestamps, and with
+ * them the whole output, then depend on the file alone); a later one starts at the time its list entry carries, else
+ * at the wall clock.  A recording that cannot be opened or fails mid-way is reported and the others still run (exit 1).
  */
 #include <err.h>
+#include <errno.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -42,6 +53,8 @@ static const char *ext_of(const char *p)
 
 /* print every finished frame (frame_output_print, frame_output.c:160-199) and discard the other record queues */
 static const char *g_save_dir;
+/* where the lines of the recording at hand go: stdout, or with --out-dir its own file */
+static FILE *g_out;
 
 /* file reader thread: fills the two pinned buffers alternately.  A regular file is read by `n_slices` helper threads,
  * each with pread() on its own slice of the chunk (one thread copying out of the page cache moves 5-7 GB/s; the H2D copy
@@ -184,7 +197,7 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
                 if (irdm_poll_ida_packed(p, ip, n) != n) { fprintf(stderr, "--acars: IDA records out of step\n"); exit(1); }
                 len = irdm_format_acars_packed_batch(g_reasm, g_acars, dp, ip, n, g_parsed, t0, g_acars_line, sizeof g_acars_line);
                 if (len < 0) { fprintf(stderr, "--acars: formatting failed\n"); exit(1); }
-                if (len > 0) fwrite(g_acars_line, 1, (size_t)len, stdout);
+                if (len > 0) fwrite(g_acars_line, 1, (size_t)len, g_out);
                 continue;
             } else if (g_parsed) {
                 /* one compact IDA record per compact frame record, decoded on the GPU (option parsed_records) */
@@ -193,7 +206,7 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
             } else {
                 len = irdm_format_raw_packed_batch(dp, n, file_info, t0, line, cap);   /* one write per batch */
             }
-            if (len > 0) fwrite(line, 1, (size_t)len, stdout);
+            if (len > 0) fwrite(line, 1, (size_t)len, g_out);
         }
     }
     static irdm_ida_t ida[256];
@@ -209,7 +222,7 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
             if (irdm_poll_ida(p, ida, n) != n) { fprintf(stderr, "--acars: IDA records out of step\n"); exit(1); }
             len = irdm_format_acars_batch(g_reasm, g_acars, d, ida, n, g_parsed, t0, g_acars_line, sizeof g_acars_line);
             if (len < 0) { fprintf(stderr, "--acars: formatting failed\n"); exit(1); }
-            if (len > 0) fwrite(g_acars_line, 1, (size_t)len, stdout);
+            if (len > 0) fwrite(g_acars_line, 1, (size_t)len, g_out);
             continue;
         } else if (g_parsed) {
             /* the full-record path (--save-bursts): option decode_ida, one irdm_ida_t per frame record */
@@ -222,7 +235,7 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         } else {
             len = irdm_format_raw_batch(d, n, file_info, t0, line, cap);     /* one write per batch */
         }
-        if (len > 0) fwrite(line, 1, (size_t)len, stdout);
+        if (len > 0) fwrite(line, 1, (size_t)len, g_out);
     }
     irdm_burst_t tmp[256];
     while (irdm_poll_bursts(p, tmp, 256) > 0) {}
@@ -246,12 +259,90 @@ static double now_s(void)
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
+/* SEC[.NNNNNNNNN] -> nanoseconds; 0 ok, -1 malformed */
+static int parse_time(const char *v, long long *sec, long long *nsec)
+{
+    char *end;
+    *sec = strtoll(v, &end, 10);
+    *nsec = 0;
+    if (end == v) return -1;
+    if (*end == '.') {
+        int digits = 0;
+        for (end++; *end >= '0' && *end <= '9' && digits < 9; end++, digits++) *nsec = *nsec * 10 + (*end - '0');
+        for (; digits < 9; digits++) *nsec *= 10;
+    }
+    return *end ? -1 : 0;
+}
+
+/* the recordings of a run, in the order given */
+typedef struct {
+    char *path;
+    uint64_t start_ns;          /* capture time (--start-time for the first, the list's second column); 0: the wall clock */
+} input_t;
+static input_t *g_in;
+static int g_n_in;
+
+static void add_input(const char *path, uint64_t start_ns)
+{
+    g_in = realloc(g_in, sizeof(*g_in) * (size_t)(g_n_in + 1));
+    if (!g_in || !(g_in[g_n_in].path = strdup(path))) errx(1, "out of memory");
+    g_in[g_n_in++].start_ns = start_ns;
+}
+
+/* --files-from LIST: one "PATH" or "PATH START_SEC[.NNNNNNNNN]" per line; empty lines are skipped */
+static int read_list(const char *list)
+{
+    FILE *lf = fopen(list, "r");
+    if (!lf) { perror(list); return -1; }
+    char ln[4352];
+    int no = 0;
+    while (fgets(ln, sizeof ln, lf)) {
+        no++;
+        size_t n = strlen(ln);
+        while (n && (ln[n - 1] == '\n' || ln[n - 1] == '\r' || ln[n - 1] == ' ' || ln[n - 1] == '\t')) ln[--n] = 0;
+        if (!n) continue;
+        uint64_t start_ns = 0;
+        char *sp = strrchr(ln, ' ');
+        long long sec, nsec;
+        /* (a last column that reads as a time is one; a path with blanks and no time stays a path) */
+        if (sp && sp[1] && parse_time(sp + 1, &sec, &nsec) == 0 && sec >= 0) {
+            start_ns = (uint64_t)sec * 1000000000ULL + (uint64_t)nsec;
+            while (sp > ln && (sp[-1] == ' ' || sp[-1] == '\t')) sp--;
+            *sp = 0;
+        }
+        if (!ln[0]) { fprintf(stderr, "%s:%d: no path\n", list, no); fclose(lf); return -1; }
+        add_input(ln, start_ns);
+    }
+    fclose(lf);
+    return 0;
+}
+
+/* the sample format of a recording: --format, else its extension (options.c:533-544); -1: --format names none */
+static int format_of(const char *format, const char *path, size_t *bps)
+{
+    const int given = format != NULL;
+    if (!format) format = ext_of(path);
+    *bps = 2;
+    if (!strcmp(format, "cf32") || !strcmp(format, "fc32") || !strcmp(format, "cfile")) { *bps = 8; return IRDM_FMT_CF32; }
+    if (!strcmp(format, "ci16") || !strcmp(format, "cs16")) { *bps = 4; return IRDM_FMT_CI16; }
+    /* full-precision int16 (the reference's SoapySDR CS16 and bladeRF live conversions): by --format only, the extension
+     * autodetect above is the reference's */
+    if (given && !strcmp(format, "ci16-full")) { *bps = 4; return IRDM_FMT_CI16_FULL; }
+    if (given && !strcmp(format, "sc16q11")) { *bps = 4; return IRDM_FMT_SC16Q11; }
+    return IRDM_FMT_CI8;
+}
+
+static const char *base_of(const char *p)
+{
+    const char *s = strrchr(p, '/');
+    return s ? s + 1 : p;
+}
+
 int main(int argc, char **argv)
 {
     const double t_main = now_s();
     int timing = 0;
-    unsigned long long fed = 0;
-    const char *file = NULL, *file_info = NULL, *format = NULL;
+    const char *file_info = NULL, *format = NULL, *out_dir = NULL;
     double rate = 0, freq = 1622000000.0, db = 0;
     int gardner = 1, verbose = 0, no_simd = 0;
     size_t chunk = (size_t)16 << 20;
@@ -263,6 +354,7 @@ int main(int argc, char **argv)
     int acars = 0, acars_json = 0, has_origin = 0;
     const char *station = NULL;
     long long origin_sec = 0, origin_nsec = 0;
+    uint64_t start_ns = 0;      /* --start-time: the capture time of the first recording (0: the wall clock) */
     int position = 0;
     double position_height = 0;
     int decimate = 0, band_given = 0;      /* --band-center / --decimate: the band-select front end */
@@ -270,7 +362,15 @@ int main(int argc, char **argv)
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
-        if (!strcmp(a, "-f") || !strcmp(a, "--file")) file = NEXT();
+        if (!strcmp(a, "-f") || !strcmp(a, "--file")) add_input(NEXT(), 0);      /* more than once: the recordings in this order */
+        else if (!strcmp(a, "--files-from")) { if (read_list(NEXT()) != 0) return 2; }
+        else if (!strcmp(a, "--out-dir")) out_dir = NEXT();
+        else if (!strcmp(a, "--start-time")) {
+            const char *v = NEXT();
+            long long sec, nsec;
+            if (parse_time(v, &sec, &nsec) != 0 || sec < 0) { fprintf(stderr, "--start-time %s: expected SEC[.NNNNNNNNN]\n", v); return 2; }
+            start_ns = (uint64_t)sec * 1000000000ULL + (uint64_t)nsec;
+        }
         else if (!strcmp(a, "-r") || !strcmp(a, "--sample-rate")) rate = atof(NEXT());
         else if (!strcmp(a, "-c") || !strcmp(a, "--center-freq")) freq = atof(NEXT());
         else if (!strcmp(a, "-d") || !strcmp(a, "--threshold")) db = atof(NEXT());
@@ -299,14 +399,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--acars-origin")) {
             /* test aid: SEC[.NNNNNNNNN] is the wall clock of the first printed ACARS message instead of CLOCK_REALTIME */
             const char *v = NEXT();
-            char *end;
-            origin_sec = strtoll(v, &end, 10);
-            if (*end == '.') {
-                int digits = 0;
-                for (end++; *end >= '0' && *end <= '9' && digits < 9; end++, digits++) origin_nsec = origin_nsec * 10 + (*end - '0');
-                for (; digits < 9; digits++) origin_nsec *= 10;
-            }
-            if (*end) { fprintf(stderr, "--acars-origin %s: expected SEC[.NNNNNNNNN]\n", v); return 2; }
+            if (parse_time(v, &origin_sec, &origin_nsec) != 0) { fprintf(stderr, "--acars-origin %s: expected SEC[.NNNNNNNNN]\n", v); return 2; }
             has_origin = 1;
         }
         else if (!strcmp(a, "--acars-udp") || !strncmp(a, "--acars-udp=", 12) || !strcmp(a, "--feed") || !strncmp(a, "--feed=", 7) ||
@@ -329,8 +422,8 @@ int main(int argc, char **argv)
             return 2;
         }
     }
-    if (!file || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D]\n", argv[0]);
+    if (!g_n_in || rate <= 0) {
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]\n", argv[0]);
         return 2;
     }
     if (band_given != (decimate != 0)) {
@@ -342,16 +435,33 @@ int main(int argc, char **argv)
         return 2;
     }
     if (decimate) gpus = 0;
-    const int format_given = format != NULL;
-    if (!format) format = ext_of(file);              /* autodetect by extension, options.c:533-544 */
-    int fmt = IRDM_FMT_CI8;
+    /* several recordings: everything that can be refused is refused before anything is processed */
+    if (g_n_in > 1 && gpus > 1) {
+        fprintf(stderr, "%d recordings: one GPU only (--gpus %d); a group is not reset between recordings\n", g_n_in, gpus);
+        return 2;
+    }
+    if (g_n_in > 1) gpus = 0;
     size_t bps = 2;
-    if (!strcmp(format, "cf32") || !strcmp(format, "fc32") || !strcmp(format, "cfile")) { fmt = IRDM_FMT_CF32; bps = 8; }
-    else if (!strcmp(format, "ci16") || !strcmp(format, "cs16")) { fmt = IRDM_FMT_CI16; bps = 4; }
-    /* full-precision int16 (the reference's SoapySDR CS16 and bladeRF live conversions): by --format only, the extension
-     * autodetect above is the reference's */
-    else if (format_given && !strcmp(format, "ci16-full")) { fmt = IRDM_FMT_CI16_FULL; bps = 4; }
-    else if (format_given && !strcmp(format, "sc16q11")) { fmt = IRDM_FMT_SC16Q11; bps = 4; }
+    const int fmt = format_of(format, g_in[0].path, &bps);
+    for (int k = 0; k < g_n_in; k++) {
+        size_t b;
+        if (g_n_in > 1 && !strcmp(g_in[k].path, "-")) {
+            fprintf(stderr, "-f -: stdin only as the sole input (%d recordings given)\n", g_n_in);
+            return 2;
+        }
+        if (format_of(format, g_in[k].path, &b) != fmt) {
+            fprintf(stderr, "%s and %s resolve to different sample formats: one context takes one format (give --format, or run them apart)\n",
+                    g_in[0].path, g_in[k].path);
+            return 2;
+        }
+        for (int j = 0; out_dir && j < k; j++)
+            if (!strcmp(base_of(g_in[j].path), base_of(g_in[k].path))) {
+                fprintf(stderr, "--out-dir: %s and %s would share %s/%s.out\n", g_in[j].path, g_in[k].path, out_dir, base_of(g_in[k].path));
+                return 2;
+            }
+    }
+    if (g_in[0].start_ns == 0) g_in[0].start_ns = start_ns;
+    g_out = stdout;
 
     /* the front end first: the context behind it runs at its output rate, centred where the applied shift puts it */
     irdm_frontend_t *fe = NULL;
@@ -376,6 +486,7 @@ int main(int argc, char **argv)
     c.format = fe ? IRDM_FMT_CF32 : fmt;
     c.feed_block = 32768;
     c.use_gardner = gardner;
+    c.start_time_ns = g_in[0].start_ns;
     /* (several GPUs: a chunk must hold the samples a member is given from in front of its chunk -- 2 s of signal, the
      * reference's ring -- so the default grows with the rate) */
     if (gpus > 1 && !chunk_given) chunk = (size_t)(2.75 * rate);
@@ -420,136 +531,184 @@ int main(int argc, char **argv)
         fprintf(stderr, "%s: the library refused the IDA decoder\n", g_parsed ? "--parsed" : "--acars");
         return 1;
     }
-    if (acars) {
-        irdm_acars_config_t ac;
-        memset(&ac, 0, sizeof(ac));
-        ac.json = acars_json;
-        ac.station = station;
-        ac.fixed_origin = has_origin;
-        ac.origin_sec = origin_sec;
-        ac.origin_nsec = origin_nsec;
-        g_reasm = irdm_ida_reasm_create();
-        g_acars = irdm_acars_create(&ac);
-        if (!g_reasm || !g_acars) { fprintf(stderr, "--acars: out of memory\n"); return 1; }
-        /* main.c:617-629, without the network endpoints this binary does not build */
-        fprintf(stderr, "ACARS: enabled (%s output%s)\n", acars_json ? "JSON" : "text", station ? ", station set" : "");
-    }
-    if (position) {
-        if (SET_OPTION(save_dir ? "decode_frames" : "frame_records", 1) != 0) {
-            fprintf(stderr, "--position: the library refused the frame decoder\n");
-            return 1;
-        }
-        g_dop = irdm_doppler_create(position_height);
-        if (!g_dop) { fprintf(stderr, "--position: out of memory\n"); return 1; }
-        /* stream time: the frames' timestamps count from the context's start time */
-        irdm_doppler_set_origin(g_dop, irdm_start_time_ns(p));
-        fprintf(stderr, "Doppler positioning: enabled (height aiding: %.0f m)\n", position_height);     /* main.c:597-605 */
+    if (position && SET_OPTION(save_dir ? "decode_frames" : "frame_records", 1) != 0) {
+        fprintf(stderr, "--position: the library refused the frame decoder\n");
+        return 1;
     }
     g_save_dir = save_dir;
-    if (verbose) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
-                         gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");
-    if (verbose && fe)
-        fprintf(stderr, "front end: %d -> %d samples/s, %d taps, shift %.3f Hz applied (%.3f asked), centre %.3f Hz\n", (int)rate,
-                irdm_frontend_out_rate(fe), irdm_frontend_ntaps(fe), irdm_frontend_applied_shift_hz(fe), band_center - freq,
-                c.center_frequency);
     /* a group is fed a super-step at a time: one chunk per member */
     /* (behind a front end the reader's chunk is D pipeline chunks of capture samples) */
     const size_t step = chunk * (size_t)(gpus > 0 ? gpus : 1) * (size_t)(fe ? decimate : 1);
+    if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { perror(out_dir); return 1; }
 
-    FILE *f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
-    if (!f) { perror(file); return 1; }
-    /* Two pinned read buffers and a reader thread (the reference's spewer thread, main.c:223-284): the file read of
-     * chunk k+1 overlaps the H2D copy and GPU work of chunk k; the H2D copy itself is DMA that overlaps chunk k-1's
-     * detector scan. */
-    reader_t rd;
-    memset(&rd, 0, sizeof(rd));
-    rd.f = f;
-    rd.bps = bps;
-    rd.chunk = step;
+    /* Two pinned read buffers and a reader thread per recording (the reference's spewer thread, main.c:223-284): the file
+     * read of chunk k+1 overlaps the H2D copy and GPU work of chunk k; the H2D copy itself is DMA that overlaps chunk
+     * k-1's detector scan.  The buffers serve every recording of the run. */
+    void *pinned[2];
     for (int i = 0; i < 2; i++) {
-        rd.buf[i] = irdm_host_alloc(step * bps);
-        if (!rd.buf[i]) { fprintf(stderr, "irdm_host_alloc failed\n"); return 1; }
+        pinned[i] = irdm_host_alloc(step * bps);
+        if (!pinned[i]) { fprintf(stderr, "irdm_host_alloc failed\n"); return 1; }
     }
-    sem_init(&rd.filled, 0, 0);
-    sem_init(&rd.empty, 0, 2);
-    {
-        struct stat sb;
-        if (f != stdin && read_threads > 0 && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
-            rd.n_slices = read_threads > MAX_SLICES ? MAX_SLICES : read_threads;
-            rd.size = sb.st_size - sb.st_size % (off_t)bps;
-            for (int i = 0; i < rd.n_slices; i++) {
-                rd.sl[i].fd = fileno(f);
-                sem_init(&rd.sl[i].go, 0, 0);
-                sem_init(&rd.sl[i].done, 0, 0);
-                if (pthread_create(&rd.sl[i].th, NULL, slice_main, &rd.sl[i]) != 0) { rd.n_slices = i; break; }
-            }
-        }
-    }
-    pthread_t th;
-    if (pthread_create(&th, NULL, reader_main, &rd) != 0) { fprintf(stderr, "pthread_create failed\n"); return 1; }
-    const double t_ready = now_s();
     irdm_demod_t *d = malloc(sizeof(*d) * 256);
     static char line[256 * IRDM_RAW_LINE_MAX];
-    uint64_t t0 = 0;
-    int rc = 0;
-    for (int k = 0;; k ^= 1) {
-        sem_wait(&rd.filled);
-        const size_t r = rd.n[k];
-        if (r == 0) break;                          /* end of file */
-        if (rc == 0 && (fe ? irdm_frontend_feed_host(fe, p, rd.buf[k], r)
-                           : g_group ? irdm_group_feed_host(g_group, rd.buf[k], r) : irdm_feed_host(p, rd.buf[k], r)) < 0) {
-            fprintf(stderr, "burst_detect: GPU processing failed\n");
-            rc = 1;
+    int rc_all = 0;
+    FILE *f = NULL;
+    double t_down = 0;
+    for (int fi = 0; fi < g_n_in; fi++) {
+        const char *file = g_in[fi].path;
+        const double t_file = now_s();
+        double reset_ms = 0;
+        int rc = 0;
+        unsigned long long fed = 0;
+        f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
+        if (!f) { perror(file); rc_all = 1; continue; }
+        if (fi > 0) {
+            /* the context and the front end as they were created, for this recording's centre frequency and capture time */
+            if ((fe && irdm_frontend_reset(fe) != 0) || irdm_reset(p, c.center_frequency, g_in[fi].start_ns) != 0) {
+                fprintf(stderr, "%s: the context could not be reset\n", file);
+                fclose(f);
+                rc_all = 1;
+                break;
+            }
+            reset_ms = (now_s() - t_file) * 1e3;
+            if (verbose) fprintf(stderr, "%s: context reset in %.3f ms\n", file, reset_ms);
         }
-        fed += r;
-        sem_post(&rd.empty);                        /* irdm_feed_host has consumed the buffer when it returns */
-        if (rc == 0) drain(p, d, file_info, &t0, line, sizeof line);
-        if (r < step) { rd.stop = 1; sem_post(&rd.empty); break; }    /* ragged last chunk = end of stream */
+        if (out_dir) {
+            char path[4608];
+            snprintf(path, sizeof path, "%s/%s.out", out_dir, base_of(file));
+            g_out = fopen(path, "w");
+            if (!g_out) { perror(path); fclose(f); g_out = stdout; rc_all = 1; continue; }
+        }
+        /* the host-side objects of a recording: its line printer's t0, its IDA reassembly and ACARS state, its solver */
+        if (acars) {
+            irdm_acars_config_t ac;
+            memset(&ac, 0, sizeof(ac));
+            ac.json = acars_json;
+            ac.station = station;
+            ac.fixed_origin = has_origin;
+            ac.origin_sec = origin_sec;
+            ac.origin_nsec = origin_nsec;
+            g_reasm = irdm_ida_reasm_create();
+            g_acars = irdm_acars_create(&ac);
+            if (!g_reasm || !g_acars) { fprintf(stderr, "--acars: out of memory\n"); return 1; }
+            /* main.c:617-629, without the network endpoints this binary does not build */
+            fprintf(stderr, "ACARS: enabled (%s output%s)\n", acars_json ? "JSON" : "text", station ? ", station set" : "");
+        }
+        if (position) {
+            g_dop = irdm_doppler_create(position_height);
+            if (!g_dop) { fprintf(stderr, "--position: out of memory\n"); return 1; }
+            /* stream time: the frames' timestamps count from the context's start time */
+            irdm_doppler_set_origin(g_dop, irdm_start_time_ns(p));
+            fprintf(stderr, "Doppler positioning: enabled (height aiding: %.0f m)\n", position_height);     /* main.c:597-605 */
+        }
+        if (verbose && fi == 0) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
+                             gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");
+        if (verbose && fi == 0 && fe)
+        fprintf(stderr, "front end: %d -> %d samples/s, %d taps, shift %.3f Hz applied (%.3f asked), centre %.3f Hz\n", (int)rate,
+                    irdm_frontend_out_rate(fe), irdm_frontend_ntaps(fe), irdm_frontend_applied_shift_hz(fe), band_center - freq,
+                    c.center_frequency);
+        reader_t rd;
+        memset(&rd, 0, sizeof(rd));
+        rd.f = f;
+        rd.bps = bps;
+        rd.chunk = step;
+        rd.buf[0] = pinned[0];
+        rd.buf[1] = pinned[1];
+        sem_init(&rd.filled, 0, 0);
+        sem_init(&rd.empty, 0, 2);
+        {
+            struct stat sb;
+            if (f != stdin && read_threads > 0 && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
+                rd.n_slices = read_threads > MAX_SLICES ? MAX_SLICES : read_threads;
+                rd.size = sb.st_size - sb.st_size % (off_t)bps;
+                for (int i = 0; i < rd.n_slices; i++) {
+                    rd.sl[i].fd = fileno(f);
+                    sem_init(&rd.sl[i].go, 0, 0);
+                    sem_init(&rd.sl[i].done, 0, 0);
+                    if (pthread_create(&rd.sl[i].th, NULL, slice_main, &rd.sl[i]) != 0) { rd.n_slices = i; break; }
+                }
+            }
+        }
+        pthread_t th;
+        if (pthread_create(&th, NULL, reader_main, &rd) != 0) { fprintf(stderr, "pthread_create failed\n"); return 1; }
+        const double t_ready = now_s();
+        uint64_t t0 = 0;
+        for (int k = 0;; k ^= 1) {
+            sem_wait(&rd.filled);
+            const size_t r = rd.n[k];
+            if (r == 0) break;                          /* end of file */
+            if (rc == 0 && (fe ? irdm_frontend_feed_host(fe, p, rd.buf[k], r)
+                               : g_group ? irdm_group_feed_host(g_group, rd.buf[k], r) : irdm_feed_host(p, rd.buf[k], r)) < 0) {
+                fprintf(stderr, "burst_detect: GPU processing failed\n");
+                rc = 1;
+            }
+            fed += r;
+            sem_post(&rd.empty);                        /* irdm_feed_host has consumed the buffer when it returns */
+            if (rc == 0) drain(p, d, file_info, &t0, line, sizeof line);
+            if (r < step) { rd.stop = 1; sem_post(&rd.empty); break; }    /* ragged last chunk = end of stream */
+        }
+        rd.stop = 1;
+        sem_post(&rd.empty);
+        pthread_join(th, NULL);
+        for (int i = 0; i < rd.n_slices; i++) {
+            rd.sl[i].quit = 1;
+            sem_post(&rd.sl[i].go);
+            pthread_join(rd.sl[i].th, NULL);
+        }
+        if (rc == 0 && (fe ? irdm_frontend_flush(fe, p) : g_group ? irdm_group_flush(g_group) : irdm_flush(p)) < 0) { fprintf(stderr, "burst_detect: GPU processing failed\n"); rc = 1; }
+        drain(p, d, file_info, &t0, line, sizeof line);
+        fflush(g_out);
+        if (g_dop && rc == 0)          /* the ticks up to the stream's end (samples / rate), then the final solve */
+            position_out(irdm_doppler_finish(g_dop, irdm_start_time_ns(p) + (uint64_t)((double)fed / rate * 1e9), g_dop_text,
+                                             sizeof g_dop_text));
+        if (timing) {
+            const double t_done = now_s();
+            if (fi == 0)
+                fprintf(stderr, "irdm timing: startup %.3f s (HIP initialisation + device context), stream %.3f s for %llu samples = %.1f Msamples/s\n",
+                        t_ready - t_main, t_done - t_ready, fed, t_done > t_ready ? fed / (t_done - t_ready) / 1e6 : 0.0);
+            else
+                fprintf(stderr, "irdm timing: %s: reset %.3f ms (context and front end back to their created state), stream %.3f s for %llu samples = %.1f Msamples/s\n",
+                        file, reset_ms, t_done - t_ready, fed, t_done > t_ready ? fed / (t_done - t_ready) / 1e6 : 0.0);
+        }
+        fprintf(stderr, "burst_detect: tagged %lu bursts total\n",
+                (unsigned long)(g_group ? (uint64_t)irdm_group_get_stat(g_group, "tagged") : irdm_tagged_bursts(p)));
+        if (g_acars) {
+            char st[512];
+            if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */
+        }
+        if (rc) rc_all = 1;
+        if (fi + 1 == g_n_in) break;        /* (the last recording's objects go with the process, below) */
+        if (out_dir) { fclose(g_out); g_out = stdout; }
+        irdm_acars_destroy(g_acars);
+        irdm_ida_reasm_destroy(g_reasm);
+        irdm_doppler_destroy(g_dop);
+        g_acars = NULL;
+        g_reasm = NULL;
+        g_dop = NULL;
+        if (f != stdin) fclose(f);
+        f = NULL;
     }
-    rd.stop = 1;
-    sem_post(&rd.empty);
-    pthread_join(th, NULL);
-    for (int i = 0; i < rd.n_slices; i++) {
-        rd.sl[i].quit = 1;
-        sem_post(&rd.sl[i].go);
-        pthread_join(rd.sl[i].th, NULL);
-    }
-    if (rc == 0 && (fe ? irdm_frontend_flush(fe, p) : g_group ? irdm_group_flush(g_group) : irdm_flush(p)) < 0) { fprintf(stderr, "burst_detect: GPU processing failed\n"); rc = 1; }
-    drain(p, d, file_info, &t0, line, sizeof line);
-    fflush(stdout);
-    if (g_dop && rc == 0)          /* the ticks up to the stream's end (samples / rate), then the final solve */
-        position_out(irdm_doppler_finish(g_dop, irdm_start_time_ns(p) + (uint64_t)((double)fed / rate * 1e9), g_dop_text,
-                                         sizeof g_dop_text));
-    if (timing) {
-        const double t_done = now_s();
-        fprintf(stderr, "irdm timing: startup %.3f s (HIP initialisation + device context), stream %.3f s for %llu samples = %.1f Msamples/s\n",
-                t_ready - t_main, t_done - t_ready, fed, t_done > t_ready ? fed / (t_done - t_ready) / 1e6 : 0.0);
-    }
-    fprintf(stderr, "burst_detect: tagged %lu bursts total\n",
-            (unsigned long)(g_group ? (uint64_t)irdm_group_get_stat(g_group, "tagged") : irdm_tagged_bursts(p)));
-    if (g_acars) {
-        char st[512];
-        if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */
-    }
+    fflush(g_out);
     /* Everything is printed and flushed.  Giving 5-9 GB of device memory, the pinned buffers and the HIP runtime back piece
      * by piece took 0.2 s of a 0.77 s run; the process is about to end and the kernel reclaims all of it at once, so the
      * binary leaves here unless IRDM_CLEAN_EXIT=1 asks for the orderly teardown (leak checkers, embedding tests). */
     const char *ce = getenv("IRDM_CLEAN_EXIT");
     if (!(ce && ce[0] == '1')) {
         fflush(stderr);
-        _exit(rc);
+        _exit(rc_all);
     }
-    const double t_down = now_s();
+    t_down = now_s();
     irdm_frontend_destroy(fe);
     if (g_group) irdm_group_destroy(g_group);
     else irdm_destroy(p);
-    irdm_host_free(rd.buf[0]);
-    irdm_host_free(rd.buf[1]);
+    irdm_host_free(pinned[0]);
+    irdm_host_free(pinned[1]);
     free(d);
     irdm_acars_destroy(g_acars);
     irdm_ida_reasm_destroy(g_reasm);
     irdm_doppler_destroy(g_dop);
-    if (f != stdin) fclose(f);
+    if (f && f != stdin) fclose(f);
+    if (g_out && g_out != stdout) fclose(g_out);
     if (timing) fprintf(stderr, "irdm timing: teardown %.3f s\n", now_s() - t_down);
-    return rc;
+    return rc_all;
 }

@@ -164,6 +164,8 @@ def lib():
         L.irdm_feed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.irdm_feed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.irdm_flush.argtypes = [C.c_void_p]
+        if hasattr(L, "irdm_reset"):                       # (IRDM_LIB may name an older build, for A/B timing)
+            L.irdm_reset.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
         if hasattr(L, "irdm_advance"):
             L.irdm_advance.argtypes = [C.c_void_p]
         L.irdm_host_alloc.argtypes = [C.c_size_t]
@@ -318,6 +320,8 @@ def lib():
             L.irdm_frontend_feed_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
             L.irdm_frontend_flush.argtypes = [C.c_void_p, C.c_void_p]
             L.irdm_frontend_wait_input.argtypes = [C.c_void_p]
+            if hasattr(L, "irdm_frontend_reset"):
+                L.irdm_frontend_reset.argtypes = [C.c_void_p]
             L.irdm_frontend_kernel_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
         _lib = L
     return _lib
@@ -546,6 +550,14 @@ class Pipeline:
             raise RuntimeError("irdm_flush failed")
         return rc
 
+    def reset(self, center_frequency=None, start_time_ns=None):
+        """irdm_reset: the context as irdm_create returned it, for another stream (defaults: the centre frequency and
+        start time this Pipeline was made with; start_time_ns 0 = now).  Every queue is emptied."""
+        cf = self.cfg.center_frequency if center_frequency is None else float(center_frequency)
+        t0 = self.cfg.start_time_ns if start_time_ns is None else int(start_time_ns)
+        if self.L.irdm_reset(self.h, cf, t0) != 0:
+            raise RuntimeError("irdm_reset refused (a feed begun and not ended, or a member of a group)")
+
     def advance(self):
         """irdm_flush without the waiting: the scan in flight settled, its bursts' chain enqueued, finished records out"""
         rc = self.L.irdm_advance(self.h)
@@ -764,6 +776,11 @@ class Frontend:
     def wait_input(self):
         if self.L.irdm_frontend_wait_input(self.h) != 0:
             raise RuntimeError("irdm_frontend_wait_input failed")
+
+    def reset(self):
+        """irdm_frontend_reset: back to the state after creation, for another capture (taps, tables and shift stay)"""
+        if self.L.irdm_frontend_reset(self.h) != 0:
+            raise RuntimeError("irdm_frontend_reset failed")
 
     def flush(self, pipeline):
         rc = self.L.irdm_frontend_flush(self.h, pipeline.h)
