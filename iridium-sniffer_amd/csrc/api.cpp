@@ -13,7 +13,7 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     if (!strcmp(key, "packed_records")) { p->packed_records = value; return 0; }
     if (!strcmp(key, "parsed_records")) { p->parsed_records = value; return 0; }
     if (!strcmp(key, "frame_records")) { p->frame_records = value; return 0; }
-    if (!strcmp(key, "chunk_marks")) { p->chunk_marks = value ? 1 : 0; if (!value) p->q_marks.clear(); return 0; }
+    if (!strcmp(key, "chunk_marks")) { p->chunk_marks = value ? 1 : 0; if (!value) p->st.q_marks.clear(); return 0; }
     if (!strcmp(key, "group_member")) { p->in_group = value != 0; return 0; }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
@@ -48,7 +48,7 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         // only while no batch is in flight
         if (value < 16) return -1;
         for (int i = 0; i < p->n_bc; i++)
-            if (p->bc[i].n != 0) return -1;
+            if (p->bc[i].st.n != 0) return -1;
         IRDM_HIP_CHECK(hipDeviceSynchronize());
         for (int i = 0; i < p->n_bc; i++) {
             BatchCtx &b = p->bc[i];
@@ -146,7 +146,7 @@ extern "C" int irdm_kernel_clock(irdm_pipeline_t *p, int which, double *sum_ms, 
 extern "C" int irdm_last_timings(const irdm_pipeline_t *p, float *ms_out, int n)
 {
     if (!p || !ms_out) return -1;
-    for (int i = 0; i < n && i < 6; i++) ms_out[i] = p->last_ms[i];
+    for (int i = 0; i < n && i < 6; i++) ms_out[i] = p->st.last_ms[i];
     return n < 6 ? n : 6;
 }
 

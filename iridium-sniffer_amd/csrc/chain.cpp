@@ -29,11 +29,11 @@ int ring_guard(irdm_pipeline *p, uint64_t a0, uint64_t a1, hipStream_t st)
     if (a1 <= a0 || L == 0) return 0;
     for (int i = 0; i < p->n_bc; i++) {
         const BatchCtx &b = p->bc[i];
-        if (b.n <= 0 || b.ring_hi <= b.ring_lo) continue;
-        bool hit = a1 - a0 >= L || b.ring_hi - b.ring_lo >= L;
+        if (b.st.n <= 0 || b.st.ring_hi <= b.st.ring_lo) continue;
+        bool hit = a1 - a0 >= L || b.st.ring_hi - b.st.ring_lo >= L;
         if (!hit) {
-            const uint64_t x0 = a0 % L, y0 = b.ring_lo % L;
-            hit = (y0 + L - x0) % L < a1 - a0 || (x0 + L - y0) % L < b.ring_hi - b.ring_lo;
+            const uint64_t x0 = a0 % L, y0 = b.st.ring_lo % L;
+            hit = (y0 + L - x0) % L < a1 - a0 || (x0 + L - y0) % L < b.st.ring_hi - b.st.ring_lo;
         }
         if (hit) {
             IRDM_HIP_CHECK(hipStreamWaitEvent(st, b.ev[1], 0));
@@ -192,7 +192,7 @@ void cfreq_from_records(BatchCtx &b)
     irdm_pipeline *p = b.owner;
     const DetParams &P = p->P;
     const int fs = p->cfg.sample_rate;
-    for (int i = 0; i < b.n; i++) {
+    for (int i = 0; i < b.st.n; i++) {
         const BurstWork &w = b.hp_work[i];
         const float rel = (w.center_bin - P.n / 2) / (float)P.n;
         double cf = p->cfg.center_frequency;
@@ -207,7 +207,7 @@ void fine_cfo_host(BatchCtx &b)
     irdm_pipeline *p = b.owner;
     const DetParams &P = p->P;
     const int fs = p->cfg.sample_rate;
-    for (int i = 0; i < b.n; i++) {
+    for (int i = 0; i < b.st.n; i++) {
         BurstWork &w = b.hp_work[i];
         const float rel = (w.center_bin - P.n / 2) / (float)P.n;
         double cf = p->cfg.center_frequency;
@@ -409,8 +409,8 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 {
     const DetParams &P = p->P;
     const int fs = p->cfg.sample_rate;
-    b.n = nb;
-    b.recs.assign(nb, irdm_burst_t());
+    b.st.n = nb;
+    b.st.recs.assign(nb, irdm_burst_t());
     size_t n_tiles = 0, dec_need = 0;
     int max_dec_len = 0;         // the longest decimated burst of the batch: the tile grid of post_tiles_kernel
     // (the register-resident decimator also needs the chunk to start at a multiple of 8 samples: a caller's burst window
@@ -419,13 +419,13 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
     const int tile_out = fir_tile_out(p->decim, fir_aligned, p->fir_generic, p->fir_order);
     for (int i = 0; i < nb; i++) {
         const GoneBurst &g = gone_list[i];
-        irdm_burst_t &r = b.recs[i];
+        irdm_burst_t &r = b.st.recs[i];
         r.id = g.id; r.start = g.start; r.stop = g.stop; r.last_active = g.last_active;
         r.center_bin = g.center_bin;
         r.peak_rel = g.peak_rel; r.base_sum = g.base_sum;
         // burst_detect.c:572, :583-586 with the host libm
         r.magnitude = 10.0f * log10f(g.peak_rel * kHistory * 1.72f);
-        if (r.magnitude > p->peak_signal_db) p->peak_signal_db = r.magnitude;      // burst_detect.c:575-576
+        if (r.magnitude > p->st.peak_signal_db) p->st.peak_signal_db = r.magnitude;      // burst_detect.c:575-576
         r.noise = 10.0f * log10f(g.base_sum / kHistory / ((float)P.n * P.n) / 1.72f /
                                  ((float)fs / P.n));
         r.num_samples = g.stop + (uint64_t)P.pre_len - g.start;          // burst_detect.c:708-712
@@ -462,7 +462,7 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
             dec_need += ((size_t)w.dec_len + 15) & ~(size_t)15;           // rows start on 128-byte lines
         }
     }
-    b.ring_lo = b.ring_hi = 0;
+    b.st.ring_lo = b.st.ring_hi = 0;
     if (p->detect_only || nb == 0) return 0;      // stage A alone: burst records, no downmix / demod
     {
         uint64_t lo = ~0ull, hi = 0;
@@ -474,7 +474,7 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
             lo = std::min(lo, w.start > back ? w.start - back : 0);
             hi = std::max(hi, w.start + (uint64_t)w.n);
         }
-        if (lo < hi) { b.ring_lo = lo; b.ring_hi = hi; }
+        if (lo < hi) { b.st.ring_lo = lo; b.st.ring_hi = hi; }
     }
     if (dec_need > p->stat_scratch_peak) p->stat_scratch_peak = dec_need;
     if (dec_need > b.dec_cap) {
@@ -609,34 +609,25 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 // returns the number of bursts whose records were emitted, -1 on error
 int bursts_finish(irdm_pipeline *p, BatchCtx &b)
 {
-    if (!p->chunk_marks || b.n == 0) return bursts_finish_records(p, b);
-    const size_t before[6] = { p->q_bursts.size(), p->q_frames.size(), p->q_demods.size(), p->q_packed.size(),
-                               p->q_decoded.size(), p->q_ida.size() };
-    const uint64_t chunk = b.chunk_no;
+    if (!p->chunk_marks || b.st.n == 0) return bursts_finish_records(p, b);
+    const irdm_chunk_mark_t before = p->st.q.counts();
+    const uint64_t chunk = b.st.chunk_no;
     const int rc = bursts_finish_records(p, b);
     if (rc < 0) return rc;
-    irdm_chunk_mark_t m;
-    m.chunk = chunk;
-    m.n_bursts = (uint32_t)(p->q_bursts.size() - before[0]);
-    m.n_frames = (uint32_t)(p->q_frames.size() - before[1]);
-    m.n_demods = (uint32_t)(p->q_demods.size() - before[2]);
-    m.n_packed = (uint32_t)(p->q_packed.size() - before[3]);
-    m.n_decoded = (uint32_t)(p->q_decoded.size() - before[4]);
-    m.n_ida = (uint32_t)(p->q_ida.size() - before[5]);
-    p->q_marks.push_back(m);
+    p->st.q_marks.push_back(mark_between(chunk, before, p->st.q.counts()));
     return rc;
 }
 
 int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
 {
-    const int nb = b.n;
+    const int nb = b.st.n;
     const int fs = p->cfg.sample_rate;
     if (nb == 0) return 0;
     if (p->detect_only) {
-        b.n = 0;
+        b.st.n = 0;
         for (int i = 0; i < nb; i++) {
-            p->q_bursts.push_back(b.recs[i]);
-            p->last_bursts.push_back(b.recs[i]);
+            p->st.q.bursts.push_back(b.st.recs[i]);
+            p->st.last_bursts.push_back(b.st.recs[i]);
         }
         return nb;
     }
@@ -646,7 +637,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
     clock_gettime(CLOCK_MONOTONIC, &ts_);
     const double t_rec0 = ts_.tv_sec * 1e6 + ts_.tv_nsec * 1e-3;
     if (b.cfo_on_device) cfreq_from_records(b);
-    b.n = 0;                     // only now: the helper thread reads it while the chain is in flight
+    b.st.n = 0;                     // only now: the helper thread reads it while the chain is in flight
     if (b.hp_flag[1]) {
         fprintf(stderr, "irdm_hip: the host step of the per-burst chain did not answer\n");
         return -1;
@@ -655,7 +646,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
     b.ms[0] = hipEventElapsedTime(&ms, b.ev[0], b.ev[1]) == hipSuccess ? ms : -1.0f;
     b.ms[1] = hipEventElapsedTime(&ms, b.ev[1], b.ev[2]) == hipSuccess ? ms : -1.0f;
     b.ms[2] = hipEventElapsedTime(&ms, b.ev[2], b.ev[3]) == hipSuccess ? ms : -1.0f;
-    for (int i = 0; i < 3; i++) p->last_ms[2 + i] = b.ms[i];
+    for (int i = 0; i < 3; i++) p->st.last_ms[2 + i] = b.ms[i];
     if (p->decode_frames) {
         p->h_decoded.resize(nb);
         IRDM_HIP_CHECK(hipMemcpyAsync(p->h_decoded.data(), b.d_decoded, sizeof(DecodedOut) * nb, hipMemcpyDeviceToHost, b.stream));
@@ -676,15 +667,15 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
         // (qpsk_demod.c:521-527)
         for (int i = 0; i < nb; i++) {
             const BurstWork &w = b.hp_work[i];
-            const irdm_burst_t &r = b.recs[i];
-            p->q_bursts.push_back(r);
-            p->last_bursts.push_back(r);
+            const irdm_burst_t &r = b.st.recs[i];
+            p->st.q.bursts.push_back(r);
+            p->st.last_bursts.push_back(r);
             const DemodPacked &d = b.hp_packed[i];
             if (w.drop_reason != 0 || !d.ok) continue;
-            uint64_t timestamp = p->start_time_ns + (uint64_t)((double)r.start / fs * 1e9);
+            uint64_t timestamp = p->st.start_time_ns + (uint64_t)((double)r.start / fs * 1e9);
             if (w.dec_len > 0) timestamp += (uint64_t)((p->in_ntaps / 2) * 1000000000ULL / fs);
-            p->q_packed.emplace_back();
-            irdm_demod_packed_t &o = p->q_packed.back();
+            p->st.q.packed.emplace_back();
+            irdm_demod_packed_t &o = p->st.q.packed.back();
             o.id = r.id;
             o.timestamp = timestamp + (uint64_t)((double)w.start_idx / p->out_rate * 1e9);
             o.direction = d.direction;
@@ -700,13 +691,13 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             memcpy(o.bits, d.bits, sizeof(o.bits));
             if (b.parsed) {
                 static_assert(sizeof(irdm_ida_packed_t) == sizeof(IdaPacked), "the device record is the public one");
-                p->q_ida_packed.emplace_back();
-                memcpy(&p->q_ida_packed.back(), &b.hp_ida[i], sizeof(IdaPacked));
+                p->st.q.ida_packed.emplace_back();
+                memcpy(&p->st.q.ida_packed.back(), &b.hp_ida[i], sizeof(IdaPacked));
             }
             if (b.framed) {
                 static_assert(sizeof(irdm_frame_packed_t) == sizeof(FramePacked), "the device record is the public one");
-                p->q_frame_packed.emplace_back();
-                memcpy(&p->q_frame_packed.back(), &b.hp_frame[i], sizeof(FramePacked));
+                p->st.q.frame_packed.emplace_back();
+                memcpy(&p->st.q.frame_packed.back(), &b.hp_frame[i], sizeof(FramePacked));
             }
             if (d.n_symbols > 0) {
                 const double duration = (double)d.n_symbols / 25000;
@@ -721,16 +712,16 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
     }
     for (int i = 0; i < nb; i++) {
         const BurstWork &w = b.hp_work[i];
-        irdm_burst_t &r = b.recs[i];
-        p->q_bursts.push_back(r);
-        p->last_bursts.push_back(r);
+        irdm_burst_t &r = b.st.recs[i];
+        p->st.q.bursts.push_back(r);
+        p->st.last_bursts.push_back(r);
 
         irdm_frame_info_t f;
         memset(&f, 0, sizeof(f));
         f.id = r.id;
         f.drop_reason = w.drop_reason;
         f.dec_len = w.dec_len;
-        uint64_t timestamp = p->start_time_ns + (uint64_t)((double)r.start / fs * 1e9);   // :659-660
+        uint64_t timestamp = p->st.start_time_ns + (uint64_t)((double)r.start / fs * 1e9);   // :659-660
         if (w.dec_len > 0) timestamp += (uint64_t)((p->in_ntaps / 2) * 1000000000ULL / fs); // :431-433
         if (w.drop_reason == 0 || w.drop_reason >= 3) f.start = w.start_idx;
         if (w.drop_reason == 0 || w.drop_reason >= 4) {
@@ -754,21 +745,21 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             f.demod_ok = b.hp_demod[i].ok ? 1 : 0;
             f.demod_direction = b.hp_demod[i].ok ? b.hp_demod[i].direction : 0;      // DIR_UNDEF, qpsk_demod.c:444
         }
-        p->q_frames.push_back(f);
+        p->st.q.frames.push_back(f);
         {
             // always one entry per frame record, so that the two queues stay paired whatever keep_frame_samples does
             std::vector<float> sv;
             if (p->keep_frame_samples && w.drop_reason == 0)
                 sv.assign(p->h_frames.begin() + (size_t)i * kMaxFrameSamples * 2,
                           p->h_frames.begin() + (size_t)i * kMaxFrameSamples * 2 + 2 * (size_t)w.num_samples);
-            p->q_frame_samples.push_back(std::move(sv));
+            p->st.q.frame_samples.push_back(std::move(sv));
         }
         if (w.drop_reason == 0 && b.hp_demod[i].ok) {
             const DemodOut &d = b.hp_demod[i];
             // built in place in the queue, and only the symbols the frame has are copied (a record is 4.5 KB; 667 of
             // them filled, copied and copied again cost the feeding thread 0.5 ms per chunk)
-            p->q_demods.emplace_back();
-            irdm_demod_t &o = p->q_demods.back();
+            p->st.q.demods.emplace_back();
+            irdm_demod_t &o = p->st.q.demods.back();
             const size_t nbits = std::min<size_t>(sizeof(o.bits) / sizeof(o.bits[0]), (size_t)(d.n_symbols > 0 ? 2 * d.n_symbols : 0));
             memset(&o, 0, offsetof(irdm_demod_t, bits));
             o.id = r.id;
@@ -793,8 +784,8 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             } else {
                 o.center_frequency = f.center_frequency;
             }
-            if (p->decode_frames) p->q_decoded.push_back(finish_decoded(p->h_decoded[i], o.id, o.timestamp, o.center_frequency));
-            if (p->decode_ida) p->q_ida.push_back(finish_ida(p->h_ida[i], o));
+            if (p->decode_frames) p->st.q.decoded.push_back(finish_decoded(p->h_decoded[i], o.id, o.timestamp, o.center_frequency));
+            if (p->decode_ida) p->st.q.ida.push_back(finish_ida(p->h_ida[i], o));
         }
     }
     clock_gettime(CLOCK_MONOTONIC, &ts_);

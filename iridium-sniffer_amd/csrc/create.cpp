@@ -182,11 +182,11 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
     p->max_chunk = (p->max_chunk + p->feed_block - 1) / p->feed_block * p->feed_block;
     p->burst_cap = cfg->max_bursts_per_chunk > 0 ? cfg->max_bursts_per_chunk : 4096;
     p->gone_cap = p->burst_cap;
-    p->start_time_ns = cfg->start_time_ns;
-    if (p->start_time_ns == 0) {
+    p->st.start_time_ns = cfg->start_time_ns;
+    if (p->st.start_time_ns == 0) {
         struct timespec ts;
         clock_gettime(CLOCK_REALTIME, &ts);
-        p->start_time_ns = ts.tv_sec * 1000000000ULL + ts.tv_nsec;
+        p->st.start_time_ns = ts.tv_sec * 1000000000ULL + ts.tv_nsec;
     }
 
     // reference ring size (burst_detect.c:292-296)
@@ -269,9 +269,6 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
     p->sstream = p->stream;
     p->bstream_prio = prio_lo;
     p->ev_scan_in = p->ev_scan_out = nullptr;
-    p->has_pending = false;
-    p->pend_c1 = 0;
-    p->h_pin = nullptr;
     for (int s = 0; s < 2; s++) {
         p->h_pin_set[s] = nullptr;
         p->hp_gone_set[s] = nullptr;
@@ -281,13 +278,6 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
         ok = ok && hipHostMalloc(reinterpret_cast<void **>(&p->h_pin_set[s]), sizeof(int) * 128, hipHostMallocDefault) == hipSuccess;
         if (ok) memset(p->h_pin_set[s], 0, sizeof(int) * 128);
     }
-    p->out_sel = 0;
-    p->chain_pending = false;
-    p->settle_clean = true;
-    p->h_pin = p->h_pin_set[0];
-    p->ev_sk[0] = p->ev_sk_set[0][0];
-    p->ev_sk[1] = p->ev_sk_set[0][1];
-    p->ev_end = p->ev_end_set[0];
     for (auto &e : p->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
 #define UP(dst, vec) ok = ok && ((dst = reinterpret_cast<decltype(dst)>(dev_upload((vec).data(), (vec).size()))) != nullptr)
 #define AL(dst, T, count) ok = ok && ((dst = dev_alloc<T>(count)) != nullptr)
@@ -442,7 +432,6 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
     for (int i = 0; i < p->n_bc && ok; i++) {
         BatchCtx &b = p->bc[i];
         b.owner = p;
-        b.n = 0;
         b.cfo_seq = 0;
         b.owns_buffers = i > 0;
         b.tiles_cap = p->tiles_cap;
@@ -487,12 +476,10 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
     p->hp_gone_cap = p->gone_cap;
     for (int s = 0; s < 2; s++)
         ok = ok && hipHostMalloc(reinterpret_cast<void **>(&p->hp_gone_set[s]), sizeof(GoneBurst) * (size_t)p->hp_gone_cap, hipHostMallocDefault) == hipSuccess;
-    p->hp_gone = p->hp_gone_set[0];
     ok = ok && hipEventCreateWithFlags(&p->ev_ring, hipEventDisableTiming) == hipSuccess;
     for (auto &f : p->fs)
         ok = ok && hipEventCreate(&f.ev_start) == hipSuccess && hipEventCreate(&f.ev_k1) == hipSuccess &&
              hipEventCreateWithFlags(&f.ev_copy, hipEventDisableTiming) == hipSuccess;
-    p->chunk_no = 0;
 #undef UP
 #undef AL
     if (!ok) {
@@ -533,12 +520,6 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
         return nullptr;
     }
     p->h_gone.resize(p->gone_cap);
-    p->total_samples = p->begun_samples = 0;
-    p->begin_no = p->end_no = 0;
-    p->tagged = 0;
-    p->stream_closed = false;
-    p->last_frames = 0;
-    p->last_chunk = nullptr;
     p->keep_frame_samples = 0;
     p->chunk_marks = 0;
     p->scan_mode = 0;
@@ -552,10 +533,6 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
     p->stat_fast_chunks = p->stat_fallbacks = p->stat_dense_frames = 0;
     p->stat_band_chunks = p->stat_band_rounds = p->stat_band_retries = p->stat_band_aborts = 0;
     p->last_band_flags = 0;
-    p->fl_mode = 0;
-    p->fl_done = 0;
-    p->host_primed = 0;
-    p->host_hist_idx = 0;
     // Does libm_port.hpp reproduce THIS host's cexpf?  (Every float of the step's range is compared by
     // tools/check_sincosf.cpp; this is the same question asked of the running process on a probe set: 2^18 offsets
     // across [-0.26, 0.26], the neighbourhoods of the quadrant boundaries, zero and the tiny-argument branch.)
@@ -601,7 +578,7 @@ extern "C" int irdm_sincosf_probe(int device, const float *x, size_t n, float *r
     return rc;
 }
 
-extern "C" uint64_t irdm_tagged_bursts(const irdm_pipeline_t *p) { return p ? p->tagged : 0; }
+extern "C" uint64_t irdm_tagged_bursts(const irdm_pipeline_t *p) { return p ? p->st.tagged : 0; }
 extern "C" size_t irdm_max_chunk_samples(const irdm_pipeline_t *p) { return p ? p->max_chunk : 0; }
 extern "C" size_t irdm_bytes_per_sample(const irdm_pipeline_t *p) { return p ? p->bps : 0; }
 // Samples a context that takes over a stream at some position must be given from in front of it (irdm_seed_history*): the
@@ -621,17 +598,17 @@ extern "C" int irdm_wait_ingest(irdm_pipeline_t *p)
     IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
     return 0;
 }
-extern "C" uint64_t irdm_sample_count(const irdm_pipeline_t *p) { return p ? p->total_samples : 0; }
+extern "C" uint64_t irdm_sample_count(const irdm_pipeline_t *p) { return p ? p->st.total_samples : 0; }
 extern "C" int irdm_fft_size(const irdm_pipeline_t *p) { return p ? p->P.n : -1; }
-extern "C" uint64_t irdm_start_time_ns(const irdm_pipeline_t *p) { return p ? p->start_time_ns : 0; }
+extern "C" uint64_t irdm_start_time_ns(const irdm_pipeline_t *p) { return p ? p->st.start_time_ns : 0; }
 
 // The stream a stage-level call (irdm_downmix_burst) belongs to: its centre frequency and the wall-clock time of its
 // sample 0 (burst_data_t carries both per burst, burst_detect.h:40-48).  Host fields only; not while a feed is begun.
 extern "C" int irdm_set_stream_origin(irdm_pipeline_t *p, double center_frequency, uint64_t start_time_ns)
 {
-    if (!p || p->begin_no != p->end_no) return -1;
+    if (!p || p->st.begin_no != p->st.end_no) return -1;
     p->cfg.center_frequency = center_frequency;
-    if (start_time_ns) p->start_time_ns = start_time_ns;
+    if (start_time_ns) p->st.start_time_ns = start_time_ns;
     return 0;
 }
 

@@ -8,7 +8,7 @@ extern "C" int irdm_flush(irdm_pipeline_t *p)
 {
     if (!p) return -1;
     if (!p->depth) return 0;
-    if (p->begin_no != p->end_no) return -1;        // a chunk handed over with irdm_feed_begin is still pending
+    if (p->st.begin_no != p->st.end_no) return -1;        // a chunk handed over with irdm_feed_begin is still pending
     pipeline_enter(p);
     if (settle(p) != 0) return -1;
     int emitted = 0;
@@ -16,14 +16,14 @@ extern "C" int irdm_flush(irdm_pipeline_t *p)
     for (;;) {
         BatchCtx *oldest = nullptr;
         for (int i = 0; i < p->n_bc; i++)
-            if (p->bc[i].n > 0 && (!oldest || p->bc[i].chunk_no < oldest->chunk_no)) oldest = &p->bc[i];
+            if (p->bc[i].st.n > 0 && (!oldest || p->bc[i].st.chunk_no < oldest->st.chunk_no)) oldest = &p->bc[i];
         if (!oldest) break;
         const int e = deferred_finish(p, *oldest);
         if (e < 0) return -1;
         emitted += e;
     }
-    if (p->has_pending) {
-        BatchCtx &b = p->bc[p->pend_no % p->n_bc];
+    if (p->st.has_pending) {
+        BatchCtx &b = p->bc[p->st.pend_no % p->n_bc];
         if (deferred_enqueue(p) != 0) return -1;
         const int e = deferred_finish(p, b);
         if (e < 0) return -1;
@@ -41,14 +41,14 @@ extern "C" int irdm_advance(irdm_pipeline_t *p)
 {
     if (!p) return -1;
     if (!p->depth) return 0;
-    if (p->begin_no != p->end_no) return -1;
+    if (p->st.begin_no != p->st.end_no) return -1;
     pipeline_enter(p);
     if (settle(p) != 0) return -1;
     int emitted = 0;
     auto oldest_of = [&]() -> BatchCtx * {
         BatchCtx *o = nullptr;
         for (int i = 0; i < p->n_bc; i++)
-            if (p->bc[i].n > 0 && (!o || p->bc[i].chunk_no < o->chunk_no)) o = &p->bc[i];
+            if (p->bc[i].st.n > 0 && (!o || p->bc[i].st.chunk_no < o->st.chunk_no)) o = &p->bc[i];
         return o;
     };
     for (BatchCtx *o; (o = oldest_of()) != nullptr && (p->detect_only || hipStreamQuery(o->stream) == hipSuccess);) {
@@ -56,9 +56,9 @@ extern "C" int irdm_advance(irdm_pipeline_t *p)
         if (e < 0) return -1;
         emitted += e;
     }
-    if (p->has_pending) {
-        BatchCtx &b = p->bc[p->pend_no % p->n_bc];
-        while (b.n > 0) {            // (records leave in chunk order: everything older than the batch in the way goes first)
+    if (p->st.has_pending) {
+        BatchCtx &b = p->bc[p->st.pend_no % p->n_bc];
+        while (b.st.n > 0) {            // (records leave in chunk order: everything older than the batch in the way goes first)
             const int e = deferred_finish(p, *oldest_of());
             if (e < 0) return -1;
             emitted += e;
@@ -69,16 +69,17 @@ extern "C" int irdm_advance(irdm_pipeline_t *p)
 }
 
 // The context back to what irdm_create returned, for another stream at the same rate, format and options (DESIGN.md
-// section 4 sorts every field of irdm_pipeline into configuration, cache and stream state; this function is the list of the
-// third kind).  The old stream is abandoned where it stands: the scan and the chains in flight are waited for -- stream by
-// stream, the device as a whole is not -- and what they produced is dropped with the queues.  The history ring keeps its
-// contents: no reader takes a slot of an absolute index the NEW stream has not written (burst_src.hpp: a sample at or past
-// avail_end comes from index a - ref_ring, zero below ref_ring; K1 reads the chunk it is handed, in place or not).
+// section 4 sorts every field of irdm_pipeline into configuration, cache and stream state; the third kind is StreamState,
+// BatchCtx::State and FeedSlot::State of pipeline.hpp, and this function assigns fresh ones).  The old stream is abandoned
+// where it stands: the scan and the chains in flight are waited for -- stream by stream, the device as a whole is not --
+// and what they produced is dropped with the queues.  The history ring keeps its contents: no reader takes a slot of an
+// absolute index the NEW stream has not written (burst_src.hpp: a sample at or past avail_end comes from index
+// a - ref_ring, zero below ref_ring; K1 reads the chunk it is handed, in place or not).
 extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t start_time_ns)
 {
     if (!p || p->in_group) return -1;
-    if (p->begin_no != p->end_no) return -1;        // a chunk handed over with irdm_feed_begin still waits for its irdm_feed_end
-    if (p->gate_open_pending) {
+    if (p->st.begin_no != p->st.end_no) return -1;  // a chunk handed over with irdm_feed_begin still waits for its irdm_feed_end
+    if (p->st.gate_open_pending) {
         fprintf(stderr, "irdm_hip: irdm_reset while a scan waits for a history import (irdm_expect_history)\n");
         return -1;
     }
@@ -92,11 +93,8 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
         BatchCtx &b = p->bc[i];
         IRDM_HIP_CHECK(hipStreamSynchronize(b.stream));
         p->rot_done_gen[i] = p->rot_gen[i];         // (its rotator checkpoint builds are complete: the rows are kept)
-        b.n = 0;                                    // only now: the helper thread reads it while the chain is in flight
+        b.st = BatchCtx::State{};                   // only now: the helper thread reads st.n while the chain is in flight
         b.hp_flag[1] = 0;
-        b.chunk_no = 0;
-        b.ring_lo = b.ring_hi = 0;
-        b.recs.clear();
     }
     // 2. device side, on the detector's stream: the detector state, the running sums and the 512-frame history as
     //    irdm_create leaves them; the band scan's commit / void markers and the speculation workspace's carried state.
@@ -112,67 +110,17 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
         ok = ok && z.add(p->band_spec.ctl, sizeof(BandCtl)) && z.add(p->band_spec.bar, 256) &&
              z.add(p->band_spec.rec_count, 4 * 64) && z.add(p->band_spec.flags, 256) && z.add(p->d_state_spec, sizeof(DetState));
     if (!ok || launch_zero_regions(z, p->stream) != 0) return -1;
-    // 3. host side
+    // 3. host side: a fresh stream state (the types say which fields that is), the pinned words the scans export to
+    p->st = StreamState{};
+    for (auto &f : p->fs) f.st = FeedSlot::State{};
+    for (int s = 0; s < 2; s++) memset(p->h_pin_set[s], 0, sizeof(int) * 128);
     p->cfg.center_frequency = center_frequency;
-    p->start_time_ns = start_time_ns;
-    if (p->start_time_ns == 0) {
+    p->st.start_time_ns = start_time_ns;
+    if (p->st.start_time_ns == 0) {
         struct timespec ts;
         clock_gettime(CLOCK_REALTIME, &ts);
-        p->start_time_ns = ts.tv_sec * 1000000000ULL + ts.tv_nsec;
+        p->st.start_time_ns = ts.tv_sec * 1000000000ULL + ts.tv_nsec;
     }
-    p->total_samples = p->begun_samples = 0;
-    p->begin_no = p->end_no = 0;
-    p->chunk_no = 0;
-    p->tagged = 0;
-    p->stream_closed = false;
-    p->peak_signal_db = 0;
-    p->host_primed = 0;
-    p->host_hist_idx = 0;
-    for (auto &f : p->fs) {
-        f.iq = nullptr;
-        f.c0 = f.c1 = 0;
-        f.mag = nullptr;
-        f.frames = 0;
-        f.in_ring = f.lists = false;
-    }
-    // (the scan in flight, the one chained behind it, the bursts waiting for a batch context)
-    p->fl_active = p->fl_sparse = p->fl_band_ran = false;
-    p->fl_mode = p->fl_done = p->fl_frames = 0;
-    p->fl_mag = p->d_mag_last = nullptr;
-    p->fl_c0 = p->fl_c1 = p->fl_no = 0;
-    p->fl_feed = nullptr;
-    p->fl_seq = p->chain_seq = p->seq_counter = 0;
-    p->chain_pending = false;
-    p->chain_no = 0;
-    p->chain_sel = 0;
-    p->settle_clean = true;
-    scan_select_outputs(p, 0);
-    for (int s = 0; s < 2; s++) memset(p->h_pin_set[s], 0, sizeof(int) * 128);
-    p->spec_for_no = ~0ull;
-    p->spec_frames = 0;
-    p->has_pending = false;
-    p->pend_gone.clear();
-    p->pend_c1 = p->pend_no = 0;
-    p->deferred_emitted = 0;
-    p->caller_ordered = false;
-    p->gate_armed = false;
-    p->gate_src = nullptr;
-    // (the probes of the last chunk)
-    p->last_frames = 0;
-    p->last_chunk = nullptr;
-    p->last_chunk_start = p->last_chunk_end = 0;
-    p->last_bursts.clear();
-    for (float &ms : p->last_ms) ms = 0.0f;
-    p->q_bursts.clear();
-    p->q_frames.clear();
-    p->q_frame_samples.clear();
-    p->q_demods.clear();
-    p->q_packed.clear();
-    p->q_ida_packed.clear();
-    p->q_frame_packed.clear();
-    p->q_ida.clear();
-    p->q_decoded.clear();
-    p->q_marks.clear();
     p->stat_resets++;
     return 0;
 }
@@ -184,8 +132,8 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
 extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, void *stream_v)
 {
     if (!p || (!d_iq && n_samples)) return -1;
-    if (p->begin_no - p->end_no > (p->depth ? kLookAhead : 0u)) return -1;      // two chunks of look-ahead, pipeline_depth >= 1 only
-    if (p->stream_closed) {
+    if (p->st.begin_no - p->st.end_no > (p->depth ? kLookAhead : 0u)) return -1;    // two chunks of look-ahead, pipeline_depth >= 1 only
+    if (p->st.stream_closed) {
         fprintf(stderr, "irdm_hip: stream already ended by a chunk that was not a multiple of feed_block\n");
         return -1;
     }
@@ -193,7 +141,7 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
         fprintf(stderr, "irdm_hip: chunk of %zu samples exceeds max_chunk_samples %zu\n", n_samples, p->max_chunk);
         return -1;
     }
-    if (n_samples % p->feed_block != 0) p->stream_closed = true;     // last, ragged chunk of the stream
+    if (n_samples % p->feed_block != 0) p->st.stream_closed = true;     // last, ragged chunk of the stream
     pipeline_enter(p);
     // order after the caller's stream (the producer of d_iq)
     hipStream_t caller = static_cast<hipStream_t>(stream_v);
@@ -201,20 +149,19 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     // which would wait for every other stream including the detector scan in flight; and no event on a foreign stream
     // when it is not needed: streams share hardware queues, and an event recorded on a stream that shares one with the
     // detector's sits behind the scan -- measured: K1 of the next chunk then started only after the scan had ended.)
-    p->caller_ordered = caller != nullptr;
-    if (p->caller_ordered) {
+    if (caller) {
         IRDM_HIP_CHECK(hipEventRecord(p->ev[8], caller));
         if (caller != p->fstream) IRDM_HIP_CHECK(hipStreamWaitEvent(p->fstream, p->ev[8], 0));
     }
     const DetParams &P = p->P;
-    const uint64_t c0 = p->begun_samples, c1 = c0 + n_samples;
+    const uint64_t c0 = p->st.begun_samples, c1 = c0 + n_samples;
     const int n_frames = (int)(n_samples / (size_t)P.n);
 
     // K1 of this chunk.  pipeline_depth 1: on its own stream and into the other magnitude buffer, while the detector
     // scan of the previous chunk may still be running
-    irdm_pipeline::FeedSlot &f = p->fs[p->begin_no % kFeedSlots];
+    FeedSlot &f = p->fs[p->st.begin_no % kFeedSlots];
     float *const mags[kFeedSlots] = { p->d_mag, p->d_mag2, p->d_mag3 };
-    float *mag = p->depth ? mags[p->begin_no % kFeedSlots] : p->d_mag;
+    float *mag = p->depth ? mags[p->st.begin_no % kFeedSlots] : p->d_mag;
     // written in place (irdm_ingest_ptr)?  Then the ring already holds the chunk.
     const uint64_t pos = c0 % p->ring_len;
     const bool in_ring = p->depth && n_samples > 0 && pos + n_samples <= p->ring_len &&
@@ -224,17 +171,17 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     // sums as they are NOW (the previous chunk's scan may still be at work on them -- any levels do, the scan checks the
     // lists against the ones they were built with, scan_band.hip band_sum_kernel); not before the detector is primed
     // (no sums yet: every bin would be listed)
-    const int ls = p->depth ? (int)(p->begin_no % kFeedSlots) : 0;       // (pipeline_depth 0: one chunk at a time, one set)
-    f.lists = false;
-    if (p->k1_lists && p->host_primed && scan_pick(p) == 2 && p->k1_pre[ls] && n_frames > 0) {
+    const int ls = p->depth ? (int)(p->st.begin_no % kFeedSlots) : 0;       // (pipeline_depth 0: one chunk at a time, one set)
+    f.st.lists = false;
+    if (p->k1_lists && p->st.host_primed && scan_pick(p) == 2 && p->k1_pre[ls] && n_frames > 0) {
         if (launch_prefilter_threshold(p->d_sum, P.threshold, p->k1_pre[ls], P.n, p->fstream) != 0) return -1;
         const int rc = launch_fft_mag_lists(P.log_n, p->dev_fmt, d_iq, p->d_window, p->d_tw, mag, n_frames, p->k1_pre[ls],
                                             p->k1_counts[ls], p->k1_entries[ls], band_list_cap(P.n), p->fstream,
                                             p->kclk_rec(3 + ls % 3), p->fir_order);
         if (rc < 0) return -1;
-        f.lists = rc == 0;
+        f.st.lists = rc == 0;
     }
-    if (!f.lists && launch_fft_mag(P.log_n, p->dev_fmt, d_iq, p->d_window, p->d_tw, mag, n_frames, p->fstream,
+    if (!f.st.lists && launch_fft_mag(P.log_n, p->dev_fmt, d_iq, p->d_window, p->d_tw, mag, n_frames, p->fstream,
                                    p->kclk_rec(3 + ls % 3), p->fir_order) != 0)
         return -1;
     IRDM_HIP_CHECK(hipEventRecord(f.ev_k1, p->fstream));
@@ -243,37 +190,37 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     // flight still read: the copy never overwrites them)
     if (p->depth && !in_ring && (ring_guard(p, c0, c1, p->fstream) != 0 || ring_update(p, d_iq, c0, c1, p->fstream) != 0)) return -1;
     IRDM_HIP_CHECK(hipEventRecord(f.ev_copy, p->fstream));
-    f.iq = d_iq;
-    f.c0 = c0;
-    f.c1 = c1;
-    f.mag = mag;
-    f.frames = n_frames;
-    f.in_ring = in_ring;
-    p->begun_samples = c1;
-    p->begin_no++;
+    f.st.iq = d_iq;
+    f.st.c0 = c0;
+    f.st.c1 = c1;
+    f.st.mag = mag;
+    f.st.frames = n_frames;
+    f.st.in_ring = in_ring;
+    p->st.begun_samples = c1;
+    p->st.begin_no++;
     return 0;
 }
 
 extern "C" int irdm_feed_end(irdm_pipeline_t *p)
 {
-    if (!p || p->begin_no == p->end_no) return -1;
+    if (!p || p->st.begin_no == p->st.end_no) return -1;
     pipeline_enter(p);
-    irdm_pipeline::FeedSlot &f = p->fs[p->end_no % kFeedSlots];
-    const void *d_iq = f.iq;
-    const uint64_t c0 = f.c0, c1 = f.c1;
-    float *mag = f.mag;
-    const int n_frames = f.frames;
+    FeedSlot &f = p->fs[p->st.end_no % kFeedSlots];
+    const void *d_iq = f.st.iq;
+    const uint64_t c0 = f.st.c0, c1 = f.st.c1;
+    float *mag = f.st.mag;
+    const int n_frames = f.st.frames;
     float ms = 0;
 
     int emitted = 0;
     if (!p->depth) {
         int n_gone = 0;
-        p->fl_feed = &f;
+        p->st.fl_feed = &f;
         if (scan_launch(p, mag, n_frames, c1) != 0 || scan_finish(p, &n_gone) != 0) return -1;
-        p->last_bursts.clear();
-        p->last_chunk = d_iq;
-        p->last_chunk_start = c0;
-        p->last_chunk_end = c1;
+        p->st.last_bursts.clear();
+        p->st.last_chunk = d_iq;
+        p->st.last_chunk_start = c0;
+        p->st.last_chunk_end = c1;
         const SampleSource src = make_source(p, d_iq, c0, c1);
         // record the stage events once so an empty chunk has valid timings
         for (int i = 0; i < 4; i++) IRDM_HIP_CHECK(hipEventRecord(p->bc[0].ev[i], p->bc[0].stream));
@@ -291,12 +238,12 @@ extern "C" int irdm_feed_end(irdm_pipeline_t *p)
         double t0 = now_us(), t1;
 #define IRDM_HOST_PHASE(i) do { t1 = now_us(); p->host_us[i] += t1 - t0; t0 = t1; } while (0)
         IRDM_HOST_PHASE(0);
-        p->last_bursts.clear();
+        p->st.last_bursts.clear();
         // 0. if the oldest chain has already finished, its records are built NOW, while the previous chunk's detector
         //    scan is still running (0.3 ms of host work that would otherwise follow the wait for the scan)
-        BatchCtx &oldest = p->bc[p->chunk_no % p->n_bc];
+        BatchCtx &oldest = p->bc[p->st.chunk_no % p->n_bc];
         bool finished_early = false;
-        if (oldest.n > 0 && !p->detect_only && p->fl_active && hipStreamQuery(oldest.stream) == hipSuccess) {
+        if (oldest.st.n > 0 && !p->detect_only && p->st.fl_active && hipStreamQuery(oldest.stream) == hipSuccess) {
             emitted = deferred_finish(p, oldest);
             if (emitted < 0) return -1;
             finished_early = true;
@@ -305,19 +252,19 @@ extern "C" int irdm_feed_end(irdm_pipeline_t *p)
         // 1. this chunk's band scan goes behind the previous chunk's (scan_chain_try), then the previous chunk's is
         //    settled and its bursts collected
         // (already chained at the end of the previous feed -- scan_chain_early, below -- unless that could not be done)
-        if (!(p->chain_pending && p->chain_no == p->chunk_no) && scan_chain_try(p, f, p->chunk_no) != 0) return -1;
+        if (!(p->st.chain_pending && p->st.chain_no == p->st.chunk_no) && scan_chain_try(p, f, p->st.chunk_no) != 0) return -1;
         if (settle(p) != 0) return -1;
-        if (p->chain_pending && !p->settle_clean) {
+        if (p->st.chain_pending && !p->st.settle_clean) {
             // the scan in front did not commit on its own: the chained launch has declined itself (nothing written)
             IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-            p->chain_pending = false;
+            p->st.chain_pending = false;
             p->stat_chain_undone++;
         }
         IRDM_HOST_PHASE(1);
         // 2. this chunk's detector (needs K1's output) goes first: the next chunk's scan can only start when this one
         //    has ended, so every microsecond before its launch is added to the period
         IRDM_HIP_CHECK(hipStreamWaitEvent(p->stream, f.ev_k1, 0));
-        p->fl_feed = &f;
+        p->st.fl_feed = &f;
         if (scan_launch(p, mag, n_frames, c1) != 0) return -1;
         IRDM_HOST_PHASE(3);
         // 3. the per-burst stages of the chunk just settled: enqueued on the idle batch context, nothing waits.  (The
@@ -325,15 +272,15 @@ extern "C" int irdm_feed_end(irdm_pipeline_t *p)
         if (deferred_enqueue(p) != 0) return -1;
         IRDM_HOST_PHASE(2);
         // 3b. the next chunk, if its feed has begun (look-ahead): its round 0 as a speculation pass beside this chunk's scan
-        if (p->begin_no > p->end_no + 1 && p->fl_mode == 2 && p->fl_band_ran &&
-            spec_enqueue(p, p->fs[(p->end_no + 1) % kFeedSlots], p->chunk_no + 1) != 0)
+        if (p->st.begin_no > p->st.end_no + 1 && p->st.fl_mode == 2 && p->st.fl_band_ran &&
+            spec_enqueue(p, p->fs[(p->st.end_no + 1) % kFeedSlots], p->st.chunk_no + 1) != 0)
             return -1;
         // 3c. ... and its scan, chained behind this chunk's, NOW: what follows -- the wait for the oldest chain, the records,
         //     the caller's polls and its next irdm_feed_begin -- took 0.4-0.8 ms, during which the scan's stream ran dry
         //     after every scan: the period was (that host time + a scan) / 2, not a scan.
         //     The same launch the next irdm_feed_end would make first thing -- it finds it done.
-        if (p->begin_no > p->end_no + 1 && !p->chain_pending &&
-            scan_chain_try(p, p->fs[(p->end_no + 1) % kFeedSlots], p->chunk_no + 1) != 0)
+        if (p->st.begin_no > p->st.end_no + 1 && !p->st.chain_pending &&
+            scan_chain_try(p, p->fs[(p->st.end_no + 1) % kFeedSlots], p->st.chunk_no + 1) != 0)
             return -1;
         // 4. results of the older batch: its context is the one the NEXT chunk's bursts will use
         if (!finished_early) {
@@ -343,17 +290,17 @@ extern "C" int irdm_feed_end(irdm_pipeline_t *p)
         IRDM_HOST_PHASE(4);
         // 5. the caller may overwrite d_iq once we return: K1 and the ring copy are done with it.  (A chunk written in
         //    place stays where it is; K1 is waited for only so that its time can be read.)
-        IRDM_HIP_CHECK(hipEventSynchronize(f.in_ring ? f.ev_k1 : f.ev_copy));
+        IRDM_HIP_CHECK(hipEventSynchronize(f.st.in_ring ? f.ev_k1 : f.ev_copy));
         IRDM_HOST_PHASE(5);
 #undef IRDM_HOST_PHASE
     }
-    p->chunk_no++;
-    p->end_no++;
-    p->total_samples = c1;
+    p->st.chunk_no++;
+    p->st.end_no++;
+    p->st.total_samples = c1;
 
     // [0] K1, [5] the whole call on the detector side; [1] is set by scan_finish, [2..4] by bursts_finish
-    p->last_ms[0] = hipEventElapsedTime(&ms, f.ev_start, f.ev_k1) == hipSuccess ? ms : -1.0f;
-    p->last_ms[5] = !p->depth && hipEventElapsedTime(&ms, f.ev_start, p->ev[7]) == hipSuccess ? ms : -1.0f;
+    p->st.last_ms[0] = hipEventElapsedTime(&ms, f.ev_start, f.ev_k1) == hipSuccess ? ms : -1.0f;
+    p->st.last_ms[5] = !p->depth && hipEventElapsedTime(&ms, f.ev_start, p->ev[7]) == hipSuccess ? ms : -1.0f;
     return emitted;
 }
 
@@ -371,7 +318,7 @@ extern "C" int irdm_feed_device(irdm_pipeline_t *p, const void *d_iq, size_t n_s
 extern "C" void *irdm_ingest_ptr(irdm_pipeline_t *p, size_t n_samples)
 {
     if (!p || !p->depth || n_samples == 0 || n_samples > p->max_chunk) return nullptr;
-    const uint64_t pos = p->begun_samples % p->ring_len;
+    const uint64_t pos = p->st.begun_samples % p->ring_len;
     if (pos + n_samples > p->ring_len) return nullptr;
     return static_cast<char *>(p->d_ring) + pos * p->bps;
 }
@@ -456,7 +403,7 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
 extern "C" int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_marks, out, max);
+    return drain(p->st.q_marks, out, max);
 }
 
 // chunks (in the order fed, counted from 0) below this number have all their records in the queues: nothing of theirs is
@@ -464,51 +411,51 @@ extern "C" int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out,
 extern "C" uint64_t irdm_chunks_complete(const irdm_pipeline_t *p)
 {
     if (!p) return 0;
-    uint64_t w = p->chunk_no;
-    if (p->fl_active) w = std::min<uint64_t>(w, p->fl_no);
-    if (p->has_pending) w = std::min<uint64_t>(w, p->pend_no);
+    uint64_t w = p->st.chunk_no;
+    if (p->st.fl_active) w = std::min<uint64_t>(w, p->st.fl_no);
+    if (p->st.has_pending) w = std::min<uint64_t>(w, p->st.pend_no);
     for (int i = 0; i < p->n_bc; i++)
-        if (p->bc[i].n > 0) w = std::min<uint64_t>(w, p->bc[i].chunk_no);
+        if (p->bc[i].st.n > 0) w = std::min<uint64_t>(w, p->bc[i].st.chunk_no);
     return w;
 }
 
 extern "C" int irdm_poll_demods_packed(irdm_pipeline_t *p, irdm_demod_packed_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_packed, out, max);
+    return drain(p->st.q.packed, out, max);
 }
 
 extern "C" int irdm_poll_ida_packed(irdm_pipeline_t *p, irdm_ida_packed_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_ida_packed, out, max);
+    return drain(p->st.q.ida_packed, out, max);
 }
 
 extern "C" int irdm_poll_frame_packed(irdm_pipeline_t *p, irdm_frame_packed_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_frame_packed, out, max);
+    return drain(p->st.q.frame_packed, out, max);
 }
 
 extern "C" int irdm_poll_bursts(irdm_pipeline_t *p, irdm_burst_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_bursts, out, max);
+    return drain(p->st.q.bursts, out, max);
 }
 
 extern "C" int irdm_poll_frames(irdm_pipeline_t *p, irdm_frame_info_t *out, float *samples_out, int max)
 {
     if (!p || !out || max < 0) return -1;
     int n = 0;
-    while (n < max && !p->q_frames.empty()) {
-        out[n] = p->q_frames.front();
-        p->q_frames.pop_front();
-        if (!p->q_frame_samples.empty()) {
+    while (n < max && !p->st.q.frames.empty()) {
+        out[n] = p->st.q.frames.front();
+        p->st.q.frames.pop_front();
+        if (!p->st.q.frame_samples.empty()) {
             if (samples_out) {
-                const std::vector<float> &s = p->q_frame_samples.front();
+                const std::vector<float> &s = p->st.q.frame_samples.front();
                 memcpy(samples_out + (size_t)n * 2 * IRDM_MAX_FRAME_SAMPLES, s.data(), s.size() * sizeof(float));
             }
-            p->q_frame_samples.pop_front();
+            p->st.q.frame_samples.pop_front();
         }
         n++;
     }
@@ -518,16 +465,16 @@ extern "C" int irdm_poll_frames(irdm_pipeline_t *p, irdm_frame_info_t *out, floa
 extern "C" int irdm_poll_demods(irdm_pipeline_t *p, irdm_demod_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_demods, out, max);
+    return drain(p->st.q.demods, out, max);
 }
 
 extern "C" int irdm_last_magnitudes(irdm_pipeline_t *p, float *out, size_t max_frames)
 {
     if (!p || !out) return -1;
     if (quiesce(p) != 0) return -1;
-    const size_t nf = std::min<size_t>(max_frames, (size_t)p->last_frames);
+    const size_t nf = std::min<size_t>(max_frames, (size_t)p->st.last_frames);
     if (!nf) return 0;
-    IRDM_HIP_CHECK(hipMemcpy(out, p->d_mag_last, nf * p->P.n * sizeof(float), hipMemcpyDeviceToHost));
+    IRDM_HIP_CHECK(hipMemcpy(out, p->st.d_mag_last, nf * p->P.n * sizeof(float), hipMemcpyDeviceToHost));
     return (int)nf;
 }
 
@@ -553,7 +500,7 @@ extern "C" int irdm_detector_stats(irdm_pipeline_t *p, irdm_detector_stats_t *ou
     const float bin_width = (float)p->cfg.sample_rate / P.n;
     out->noise_floor_dbfs_hz = (avg > 0 && bin_width > 0) ? 10.0f * log10f(avg / bin_width) : -120.0f;
     // burst_detect.c:572-576: the running maximum of the magnitude a burst is created with
-    float peak = p->peak_signal_db;
+    float peak = p->st.peak_signal_db;
     for (const ActiveBurst &a : act) {
         const float m = 10.0f * log10f(a.peak_rel * kHistory * 1.72f);
         if (m > peak) peak = m;
@@ -571,13 +518,13 @@ extern "C" int irdm_baseline_sum(irdm_pipeline_t *p, float *out)
 
 extern "C" int irdm_burst_samples(irdm_pipeline_t *p, int burst_in_chunk, float *out, size_t max_samples)
 {
-    if (!p || !out || burst_in_chunk < 0 || burst_in_chunk >= (int)p->last_bursts.size() || (!p->depth && !p->last_chunk))
+    if (!p || !out || burst_in_chunk < 0 || burst_in_chunk >= (int)p->st.last_bursts.size() || (!p->depth && !p->st.last_chunk))
         return -1;
-    const irdm_burst_t &r = p->last_bursts[burst_in_chunk];
+    const irdm_burst_t &r = p->st.last_bursts[burst_in_chunk];
     const size_t n = std::min<size_t>(std::min<size_t>(max_samples, r.num_samples), p->l_cap);
     // NOTE: valid only until the next feed (the chunk pointer and ring are read again)
     SampleSource src = p->depth ? make_source(p, nullptr, 0, r.avail_end)
-                                : make_source(p, p->last_chunk, p->last_chunk_start, p->last_chunk_end);
+                                : make_source(p, p->st.last_chunk, p->st.last_chunk_start, p->st.last_chunk_end);
     // the ring already holds the chunk tail; reading through the chunk pointer is equivalent
     if (launch_gather_burst(src, r.start, r.avail_end, (int)n, p->d_probe, p->stream) != 0) return -1;
     IRDM_HIP_CHECK(hipMemcpyAsync(out, p->d_probe, n * sizeof(float2), hipMemcpyDeviceToHost, p->stream));

@@ -16,16 +16,20 @@ struct irdm_frontend {
     float *d_hr = nullptr, *d_G = nullptr;
     float2 *d_T = nullptr;
     void *d_tail[2] = { nullptr, nullptr };
-    int cur = 0;
-    long long n_tail = 0;
-    uint64_t total = 0, n_out = 0;
-    bool finished = false;
+    // stream state (irdm_frontend_reset assigns a fresh one)
+    struct State {
+        int cur = 0;                // which of d_tail holds the carried tail
+        long long n_tail = 0;
+        uint64_t total = 0, n_out = 0;
+        bool finished = false;
+        // the feeder: outputs written but not fed yet lie at base[0 .. pend)
+        float2 *base = nullptr;
+        size_t room = 0, pend = 0;
+    } st;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;
-    // the feeder: outputs written but not fed yet lie at base[0 .. pend)
-    float2 *base = nullptr, *d_scratch = nullptr;
-    size_t room = 0, pend = 0;
+    float2 *d_scratch = nullptr;
     void *d_stage = nullptr;
     size_t stage_bytes = 0;
 };
@@ -149,17 +153,17 @@ static uint64_t fe_outputs(const irdm_frontend *fe, uint64_t total, bool flush)
     return total > (uint64_t)fe->c ? (total - 1 - (uint64_t)fe->c) / (uint64_t)fe->D + 1 : 0;
 }
 
-// outputs [fe->n_out, m1) of [tail | d_in] into out
+// outputs [fe->st.n_out, m1) of [tail | d_in] into out
 static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1, float2 *out, hipStream_t s)
 {
-    if (m1 <= fe->n_out) return 0;
+    if (m1 <= fe->st.n_out) return 0;
     FrontendArgs a;
-    a.tail = fe->d_tail[fe->cur];
+    a.tail = fe->d_tail[fe->st.cur];
     a.in = d_in;
-    a.n_tail = fe->n_tail;
+    a.n_tail = fe->st.n_tail;
     a.n_in = (long long)n_in;
-    a.pos0 = (long long)fe->total - fe->n_tail;
-    a.m0 = (long long)fe->n_out;
+    a.pos0 = (long long)fe->st.total - fe->st.n_tail;
+    a.m0 = (long long)fe->st.n_out;
     a.m1 = (long long)m1;
     a.out = out;
     a.q16 = (unsigned)(fe->q & 0xffff);
@@ -167,34 +171,34 @@ static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1
     a.fmt = fe->fmt;
     if (launch_frontend(fe->D, a, fe->d_hr, fe->d_G, fe->d_T, s, fe->d_kclk) != 0) return -1;
     if (launch_kclk_fold(fe->d_kclk, s) != 0) return -1;
-    fe->n_out = m1;
+    fe->st.n_out = m1;
     return 0;
 }
 
 // the chunk has been consumed: keep what later outputs need, advance the stream position
 static int fe_commit(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream_t s)
 {
-    const uint64_t total = fe->total + n_in;
-    const long long need = (long long)(fe->n_out * (uint64_t)fe->D) - fe->c;       // first sample still needed
+    const uint64_t total = fe->st.total + n_in;
+    const long long need = (long long)(fe->st.n_out * (uint64_t)fe->D) - fe->c;       // first sample still needed
     const long long start = std::min<long long>(std::max<long long>(need, 0), (long long)total);
-    const long long pos0 = (long long)fe->total - fe->n_tail;
+    const long long pos0 = (long long)fe->st.total - fe->st.n_tail;
     const int n_new = (int)((long long)total - start);
     if (n_new > fe->ntaps + fe->D + 16) return -1;                                 // (cannot happen: see the header comment)
-    if (launch_frontend_tail(fe->d_tail[fe->cur], fe->n_tail, d_in, (long long)n_in, start - pos0, n_new, fe->bps,
-                             fe->d_tail[fe->cur ^ 1], s) != 0)
+    if (launch_frontend_tail(fe->d_tail[fe->st.cur], fe->st.n_tail, d_in, (long long)n_in, start - pos0, n_new, fe->bps,
+                             fe->d_tail[fe->st.cur ^ 1], s) != 0)
         return -1;
-    fe->cur ^= 1;
-    fe->n_tail = n_new;
-    fe->total = total;
+    fe->st.cur ^= 1;
+    fe->st.n_tail = n_new;
+    fe->st.total = total;
     return 0;
 }
 
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
-    if (!fe || fe->finished || (!d_in && n_in) || !d_out) return -1;
-    const uint64_t m1 = fe_outputs(fe, fe->total + n_in, false);
-    const uint64_t n = m1 - fe->n_out;
+    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out) return -1;
+    const uint64_t m1 = fe_outputs(fe, fe->st.total + n_in, false);
+    const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
     (void)hipSetDevice(fe->cfg.device);
     hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : fe->stream;
@@ -207,14 +211,14 @@ extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d
 
 extern "C" long long irdm_frontend_finish_device(irdm_frontend_t *fe, void *d_out, size_t out_cap, void *stream_v)
 {
-    if (!fe || fe->finished || !d_out) return -1;
-    const uint64_t m1 = fe_outputs(fe, fe->total, true);
-    const uint64_t n = m1 - fe->n_out;
+    if (!fe || fe->st.finished || !d_out) return -1;
+    const uint64_t m1 = fe_outputs(fe, fe->st.total, true);
+    const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
     (void)hipSetDevice(fe->cfg.device);
     hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : fe->stream;
     if (fe_emit(fe, nullptr, 0, m1, static_cast<float2 *>(d_out), s) != 0) return -1;
-    fe->finished = true;
+    fe->st.finished = true;
     if (!stream_v) IRDM_HIP_CHECK(hipStreamSynchronize(s));
     return (long long)n;
 }
@@ -226,7 +230,7 @@ extern "C" long long irdm_frontend_finish_device(irdm_frontend_t *fe, void *d_ou
 static int fe_acquire(irdm_frontend *fe, irdm_pipeline *p)
 {
     size_t room = p->max_chunk;
-    if (p->depth) room = (size_t)std::min<uint64_t>(room, p->ring_len - p->begun_samples % p->ring_len);
+    if (p->depth) room = (size_t)std::min<uint64_t>(room, p->ring_len - p->st.begun_samples % p->ring_len);
     room = room / (size_t)p->feed_block * (size_t)p->feed_block;
     void *slot = room ? irdm_ingest_ptr(p, room) : nullptr;
     if (!slot) {
@@ -234,8 +238,8 @@ static int fe_acquire(irdm_frontend *fe, irdm_pipeline *p)
         slot = fe->d_scratch;
         room = p->max_chunk;
     }
-    fe->base = static_cast<float2 *>(slot);
-    fe->room = room;
+    fe->st.base = static_cast<float2 *>(slot);
+    fe->st.room = room;
     return 0;
 }
 
@@ -245,27 +249,27 @@ static int fe_pump(irdm_frontend *fe, irdm_pipeline *p, const void *d_in, size_t
 {
     int bursts = 0;
     for (;;) {
-        if (!fe->base && fe_acquire(fe, p) != 0) return -1;
-        const size_t take = (size_t)std::min<uint64_t>(fe->room - fe->pend, m1 - fe->n_out);
-        if (fe_emit(fe, d_in, n_in, fe->n_out + take, fe->base + fe->pend, fe->stream) != 0) return -1;
-        fe->pend += take;
-        const bool done = fe->n_out == m1;
-        size_t feedable = fe->pend / (size_t)p->feed_block * (size_t)p->feed_block;
-        if (last && done) feedable = fe->pend;
+        if (!fe->st.base && fe_acquire(fe, p) != 0) return -1;
+        const size_t take = (size_t)std::min<uint64_t>(fe->st.room - fe->st.pend, m1 - fe->st.n_out);
+        if (fe_emit(fe, d_in, n_in, fe->st.n_out + take, fe->st.base + fe->st.pend, fe->stream) != 0) return -1;
+        fe->st.pend += take;
+        const bool done = fe->st.n_out == m1;
+        size_t feedable = fe->st.pend / (size_t)p->feed_block * (size_t)p->feed_block;
+        if (last && done) feedable = fe->st.pend;
         if (feedable) {
-            const int rc = irdm_feed_device(p, fe->base, feedable, fe->stream);
+            const int rc = irdm_feed_device(p, fe->st.base, feedable, fe->stream);
             if (rc < 0) return -1;
             bursts += rc;
-            const float2 *rest = fe->base + feedable;
-            const size_t n_rest = fe->pend - feedable;
-            fe->base = nullptr;
-            fe->pend = 0;
+            const float2 *rest = fe->st.base + feedable;
+            const size_t n_rest = fe->st.pend - feedable;
+            fe->st.base = nullptr;
+            fe->st.pend = 0;
             if (n_rest) {
                 if (fe_acquire(fe, p) != 0) return -1;
                 // (in the ring the remainder already lies where the next slot begins, unless the ring wraps there)
-                if (fe->base != rest)
-                    IRDM_HIP_CHECK(hipMemcpyAsync(fe->base, rest, n_rest * sizeof(float2), hipMemcpyDeviceToDevice, fe->stream));
-                fe->pend = n_rest;
+                if (fe->st.base != rest)
+                    IRDM_HIP_CHECK(hipMemcpyAsync(fe->st.base, rest, n_rest * sizeof(float2), hipMemcpyDeviceToDevice, fe->stream));
+                fe->st.pend = n_rest;
             }
         }
         if (done) break;
@@ -275,7 +279,7 @@ static int fe_pump(irdm_frontend *fe, irdm_pipeline *p, const void *d_in, size_t
 
 static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
 {
-    if (!fe || !p || fe->finished) return -1;
+    if (!fe || !p || fe->st.finished) return -1;
     if (p->dev_fmt != IRDM_FMT_CF32 || p->cfg.sample_rate != fe->out_rate || p->cfg.device != fe->cfg.device) {
         fprintf(stderr, "irdm_hip: front end: the pipeline must be a cf32 context at %d samples/s on device %d\n", fe->out_rate,
                 fe->cfg.device);
@@ -292,7 +296,7 @@ extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
         IRDM_HIP_CHECK(hipStreamWaitEvent(fe->stream, fe->ev_caller, 0));
     }
-    const int bursts = fe_pump(fe, p, d_in, n_in, fe_outputs(fe, fe->total + n_in, false), false);
+    const int bursts = fe_pump(fe, p, d_in, n_in, fe_outputs(fe, fe->st.total + n_in, false), false);
     if (bursts < 0) return -1;
     if (fe_commit(fe, d_in, n_in, fe->stream) != 0) return -1;
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_in, fe->stream));
@@ -324,9 +328,9 @@ extern "C" int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p)
 {
     if (fe_check(fe, p) != 0) return -1;
     pipeline_enter(p);
-    int bursts = fe_pump(fe, p, nullptr, 0, fe_outputs(fe, fe->total, true), true);
+    int bursts = fe_pump(fe, p, nullptr, 0, fe_outputs(fe, fe->st.total, true), true);
     if (bursts < 0) return -1;
-    fe->finished = true;
+    fe->st.finished = true;
     const int rc = irdm_flush(p);
     return rc < 0 ? -1 : bursts + rc;
 }
@@ -339,12 +343,7 @@ extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
     if (!fe) return -1;
     (void)hipSetDevice(fe->cfg.device);
     IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));      // (launches in flight read the tail and the staging buffer)
-    fe->cur = 0;
-    fe->n_tail = 0;
-    fe->total = fe->n_out = 0;
-    fe->finished = false;
-    fe->base = nullptr;
-    fe->room = fe->pend = 0;
+    fe->st = irdm_frontend::State{};
     return 0;
 }
 

@@ -48,6 +48,7 @@
 
 #include "../../include/irdm_hip.h"
 #include "kernels.hpp"
+#include "record_queues.hpp"
 
 namespace {
 
@@ -118,19 +119,6 @@ Rccl *rccl()
         }                                                                                                    \
     } while (0)
 
-// the records of one chunk of the stream, in the order the member queued them
-struct ChunkRecords {
-    std::vector<irdm_burst_t> bursts;
-    std::vector<irdm_frame_info_t> frames;
-    std::vector<std::vector<float>> frame_samples;
-    std::vector<irdm_demod_t> demods;
-    std::vector<irdm_demod_packed_t> packed;
-    std::vector<irdm_ida_packed_t> ida_packed;          // parsed_records: one per packed record
-    std::vector<irdm_frame_packed_t> frame_packed;      // frame_records: one per packed record
-    std::vector<irdm_decoded_t> decoded;
-    std::vector<irdm_ida_t> ida;
-};
-
 struct Member {
     irdm_pipeline_t *p = nullptr;
     int dev = 0;
@@ -172,17 +160,9 @@ struct irdm_group {
                                          // may be ahead of what was fed -- every later stage / feed / flush call fails cleanly
     int loopback = 0, keep_samples = 0, parsed = 0, framed = 0;
     // merged output
-    std::map<uint64_t, ChunkRecords> store;
+    std::map<uint64_t, RecordQueues> store;     // the records of a chunk of the stream, in the order its member queued them
     uint64_t next_emit = 0;
-    std::deque<irdm_burst_t> q_bursts;
-    std::deque<irdm_frame_info_t> q_frames;
-    std::deque<std::vector<float>> q_frame_samples;
-    std::deque<irdm_demod_t> q_demods;
-    std::deque<irdm_demod_packed_t> q_packed;
-    std::deque<irdm_ida_packed_t> q_ida_packed;
-    std::deque<irdm_frame_packed_t> q_frame_packed;
-    std::deque<irdm_decoded_t> q_decoded;
-    std::deque<irdm_ida_t> q_ida;
+    RecordQueues q;
     uint64_t st_hops = 0, st_hop_bytes = 0, st_scatter_bytes = 0, st_overlap_bytes = 0, st_late = 0;
     std::vector<float> tmp_samples;
 };
@@ -220,6 +200,17 @@ int transfer(irdm_group *g, std::vector<ncclComm_t> &comms, int src, const void 
     return 0;
 }
 
+// n records of one kind from a member (through its poll: the C-ABI is the boundary) to the back of a chunk's queue
+template <typename T>
+int pull(irdm_pipeline_t *p, int (*poll)(irdm_pipeline_t *, T *, int), uint32_t n, std::deque<T> &to)
+{
+    if (!n) return 0;
+    std::vector<T> got(n);
+    if (poll(p, got.data(), (int)n) != (int)n) return -1;
+    to.insert(to.end(), got.begin(), got.end());
+    return 0;
+}
+
 // a member's queues -> the store, mark by mark
 int drain_member(irdm_group *g, int r)
 {
@@ -230,11 +221,8 @@ int drain_member(irdm_group *g, int r)
         for (int i = 0; i < k; i++) {
             const irdm_chunk_mark_t &mk = marks[i];
             // member-local chunk c of member r is chunk c * N + r of the stream
-            ChunkRecords &cr = g->store[mk.chunk * (uint64_t)g->n + (uint64_t)r];
-            size_t at;
-            at = cr.bursts.size();
-            cr.bursts.resize(at + mk.n_bursts);
-            if (mk.n_bursts && irdm_poll_bursts(mb.p, cr.bursts.data() + at, (int)mk.n_bursts) != (int)mk.n_bursts) return -1;
+            RecordQueues &cr = g->store[mk.chunk * (uint64_t)g->n + (uint64_t)r];
+            if (pull(mb.p, irdm_poll_bursts, mk.n_bursts, cr.bursts) != 0) return -1;
             for (uint32_t j = 0; j < mk.n_frames; j++) {
                 irdm_frame_info_t fi;
                 if (g->keep_samples) {
@@ -248,31 +236,12 @@ int drain_member(irdm_group *g, int r)
                 }
                 cr.frames.push_back(fi);
             }
-            at = cr.demods.size();
-            cr.demods.resize(at + mk.n_demods);
-            if (mk.n_demods && irdm_poll_demods(mb.p, cr.demods.data() + at, (int)mk.n_demods) != (int)mk.n_demods) return -1;
-            at = cr.packed.size();
-            cr.packed.resize(at + mk.n_packed);
-            if (mk.n_packed && irdm_poll_demods_packed(mb.p, cr.packed.data() + at, (int)mk.n_packed) != (int)mk.n_packed) return -1;
-            if (g->parsed) {
-                at = cr.ida_packed.size();
-                cr.ida_packed.resize(at + mk.n_packed);
-                if (mk.n_packed && irdm_poll_ida_packed(mb.p, cr.ida_packed.data() + at, (int)mk.n_packed) != (int)mk.n_packed)
-                    return -1;
-            }
-            if (g->framed) {
-                at = cr.frame_packed.size();
-                cr.frame_packed.resize(at + mk.n_packed);
-                if (mk.n_packed &&
-                    irdm_poll_frame_packed(mb.p, cr.frame_packed.data() + at, (int)mk.n_packed) != (int)mk.n_packed)
-                    return -1;
-            }
-            at = cr.decoded.size();
-            cr.decoded.resize(at + mk.n_decoded);
-            if (mk.n_decoded && irdm_poll_decoded(mb.p, cr.decoded.data() + at, (int)mk.n_decoded) != (int)mk.n_decoded) return -1;
-            at = cr.ida.size();
-            cr.ida.resize(at + mk.n_ida);
-            if (mk.n_ida && irdm_poll_ida(mb.p, cr.ida.data() + at, (int)mk.n_ida) != (int)mk.n_ida) return -1;
+            if (pull(mb.p, irdm_poll_demods, mk.n_demods, cr.demods) != 0 ||
+                pull(mb.p, irdm_poll_demods_packed, mk.n_packed, cr.packed) != 0 ||
+                (g->parsed && pull(mb.p, irdm_poll_ida_packed, mk.n_packed, cr.ida_packed) != 0) ||
+                (g->framed && pull(mb.p, irdm_poll_frame_packed, mk.n_packed, cr.frame_packed) != 0) ||
+                pull(mb.p, irdm_poll_decoded, mk.n_decoded, cr.decoded) != 0 || pull(mb.p, irdm_poll_ida, mk.n_ida, cr.ida) != 0)
+                return -1;
         }
     }
     return k < 0 ? -1 : 0;
@@ -288,16 +257,7 @@ void emit_ready(irdm_group *g)
         if (local >= irdm_chunks_complete(g->m[r].p)) return;
         auto it = g->store.find(g->next_emit);
         if (it != g->store.end()) {
-            ChunkRecords &cr = it->second;
-            g->q_bursts.insert(g->q_bursts.end(), cr.bursts.begin(), cr.bursts.end());
-            g->q_frames.insert(g->q_frames.end(), cr.frames.begin(), cr.frames.end());
-            for (auto &v : cr.frame_samples) g->q_frame_samples.push_back(std::move(v));
-            g->q_demods.insert(g->q_demods.end(), cr.demods.begin(), cr.demods.end());
-            g->q_packed.insert(g->q_packed.end(), cr.packed.begin(), cr.packed.end());
-            g->q_ida_packed.insert(g->q_ida_packed.end(), cr.ida_packed.begin(), cr.ida_packed.end());
-            g->q_frame_packed.insert(g->q_frame_packed.end(), cr.frame_packed.begin(), cr.frame_packed.end());
-            g->q_decoded.insert(g->q_decoded.end(), cr.decoded.begin(), cr.decoded.end());
-            g->q_ida.insert(g->q_ida.end(), cr.ida.begin(), cr.ida.end());
+            g->q.append(std::move(it->second));
             g->store.erase(it);
         }
         g->next_emit++;
@@ -517,17 +477,6 @@ int feed(irdm_group *g, const void *src, size_t n_samples, bool host)
     }
     if (g->staged.empty()) return 0;
     return run_super_step(g);
-}
-
-template <typename T>
-int drain(std::deque<T> &q, T *out, int max)
-{
-    int n = 0;
-    while (n < max && !q.empty()) {
-        out[n++] = q.front();
-        q.pop_front();
-    }
-    return n;
 }
 
 } // namespace
@@ -755,23 +704,23 @@ extern "C" int irdm_group_flush(irdm_group_t *g)
 extern "C" int irdm_group_poll_bursts(irdm_group_t *g, irdm_burst_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_bursts, out, max);
+    return drain(g->q.bursts, out, max);
 }
 
 extern "C" int irdm_group_poll_frames(irdm_group_t *g, irdm_frame_info_t *out, float *samples_out, int max)
 {
     if (!g || !out || max < 0) return -1;
     int n = 0;
-    while (n < max && !g->q_frames.empty()) {
-        out[n] = g->q_frames.front();
-        g->q_frames.pop_front();
-        std::vector<float> &sv = g->q_frame_samples.front();
+    while (n < max && !g->q.frames.empty()) {
+        out[n] = g->q.frames.front();
+        g->q.frames.pop_front();
+        std::vector<float> &sv = g->q.frame_samples.front();
         if (samples_out) {
             float *dst = samples_out + (size_t)n * 2 * IRDM_MAX_FRAME_SAMPLES;
             memset(dst, 0, sizeof(float) * 2 * IRDM_MAX_FRAME_SAMPLES);
             if (!sv.empty()) memcpy(dst, sv.data(), sizeof(float) * sv.size());
         }
-        g->q_frame_samples.pop_front();
+        g->q.frame_samples.pop_front();
         n++;
     }
     return n;
@@ -780,35 +729,35 @@ extern "C" int irdm_group_poll_frames(irdm_group_t *g, irdm_frame_info_t *out, f
 extern "C" int irdm_group_poll_demods(irdm_group_t *g, irdm_demod_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_demods, out, max);
+    return drain(g->q.demods, out, max);
 }
 
 extern "C" int irdm_group_poll_demods_packed(irdm_group_t *g, irdm_demod_packed_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_packed, out, max);
+    return drain(g->q.packed, out, max);
 }
 
 extern "C" int irdm_group_poll_ida_packed(irdm_group_t *g, irdm_ida_packed_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_ida_packed, out, max);
+    return drain(g->q.ida_packed, out, max);
 }
 
 extern "C" int irdm_group_poll_frame_packed(irdm_group_t *g, irdm_frame_packed_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_frame_packed, out, max);
+    return drain(g->q.frame_packed, out, max);
 }
 
 extern "C" int irdm_group_poll_decoded(irdm_group_t *g, irdm_decoded_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_decoded, out, max);
+    return drain(g->q.decoded, out, max);
 }
 
 extern "C" int irdm_group_poll_ida(irdm_group_t *g, irdm_ida_t *out, int max)
 {
     if (!g || !out || max < 0) return -1;
-    return drain(g->q_ida, out, max);
+    return drain(g->q.ida, out, max);
 }

@@ -9,6 +9,11 @@
 //   feed.cpp        irdm_feed_* / irdm_flush / irdm_advance / irdm_reset, the polls, buffers for hosts without HIP headers
 //   state.cpp       detector-state export / import (time-chunk sharding), the stage-level batch calls
 //   api.cpp         options, statistics, kernel clock, RAW line formatting, --save-bursts
+//
+// Every field of a context is configuration, cache or stream state.  The third kind lives in types of
+// its own -- StreamState (irdm_pipeline::st), BatchCtx::State, FeedSlot::State, with the record queues of record_queues.hpp
+// inside -- so that `p->st.` marks it where it is used and irdm_reset clears it by assigning fresh values.  A new field
+// goes into the struct of its kind; one that belongs to the stream needs no line in irdm_create or irdm_reset.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -30,6 +35,7 @@
 #include "libm_port.hpp"
 #include "band_core.hpp"
 #include "types.hpp"
+#include "record_queues.hpp"
 
 using namespace irdm;
 
@@ -119,23 +125,91 @@ struct BatchCtx {
     bool framed;                 // ... and FramePacked records
     bool cfo_on_device;          // this batch's libm step ran on the device: h_cfreq is filled from the returned records
     std::vector<double> h_cfreq;
-    std::vector<irdm_burst_t> recs;
-    int n;                       // bursts in flight (0: idle)
-    uint64_t chunk_no;           // the chunk they come from
-    uint64_t ring_lo = 0, ring_hi = 0;   // absolute sample range this batch's decimator may read from the history ring (incl. the
-                                 // stale slots one reference ring length back); it reads nothing behind ev[1]
+    // stream state (irdm_reset assigns a fresh one): the batch in flight
+    struct State {
+        int n = 0;                   // bursts in flight (0: idle)
+        uint64_t chunk_no = 0;       // the chunk they come from
+        uint64_t ring_lo = 0, ring_hi = 0;   // absolute sample range this batch's decimator may read from the history ring (incl.
+                                     // the stale slots one reference ring length back); it reads nothing behind ev[1]
+        std::vector<irdm_burst_t> recs;
+    } st;
     bool owns_buffers;           // context 1 allocates its own device scratch; context 0 aliases the pipeline's
     float ms[3];                 // fir, post, demod of the last finished batch
 };
 
+// A chunk between irdm_feed_begin and the settling of its scan (kFeedSlots above).
+struct FeedSlot {
+    // stream state (irdm_reset assigns a fresh one): the chunk the slot holds
+    struct State {
+        const void *iq = nullptr;
+        uint64_t c0 = 0, c1 = 0;
+        float *mag = nullptr;
+        int frames = 0;
+        bool in_ring = false;       // the caller wrote the chunk where irdm_ingest_ptr() said: no copy into the ring
+        bool lists = false;         // K1 wrote the band scan's candidate lists of the chunk (k1_pre / k1_counts / k1_entries)
+    } st;
+    hipEvent_t ev_start, ev_k1, ev_copy;
+};
+
+// Everything on the host side of a context that belongs to the STREAM it carries (a field is
+// configuration, cache or stream state).  irdm_create leaves it as `StreamState{}` (but start_time_ns), irdm_reset assigns
+// `StreamState{}`: a field whose fresh value is not zero says so here, and a field added here needs no line anywhere else.
+// The per-element stream state of the batch contexts and feed slots: BatchCtx::State, FeedSlot::State.
+struct StreamState {
+    uint64_t total_samples = 0, tagged = 0, start_time_ns = 0;
+    uint64_t begun_samples = 0;     // absolute index the next irdm_feed_begin starts at
+    uint64_t begin_no = 0, end_no = 0;  // feeds begun / ended; slot = number % kFeedSlots
+    uint64_t chunk_no = 0;          // chunks fed so far
+    int host_primed = 0, host_hist_idx = 0;
+    float peak_signal_db = 0;       // burst_detector_peak_signal over the finished bursts (starts at 0 like the reference's calloc)
+    bool stream_closed = false;
+    // detector scan in flight (scan_launch .. scan_finish)
+    bool fl_active = false;
+    bool fl_band_ran = false;       // the band scan's control block on the device belongs to the scan in flight
+    int fl_mode = 0;                // 0 dense, 1 sparse (leader/updaters), 2 band
+    int fl_done = 0;                // frames the dense scan primed before the in-flight scan proper
+    int fl_frames = 0, fl_band_first = 0;
+    const float *fl_mag = nullptr, *d_mag_last = nullptr;
+    uint64_t fl_c1 = 0, fl_c0 = 0, fl_no = 0;
+    const FeedSlot *fl_feed = nullptr;      // feed slot of the scan in flight
+    int out_sel = 0;                // which set of export targets (h_pin_set ...) the scan that scan_finish settles next writes
+    // the chained launch (scan_chain_try), taken over by scan_launch
+    bool chain_pending = false;     // feed_end has enqueued this chunk's scan behind the previous one
+    int chain_sel = 0, chain_band_first = 0;
+    uint64_t chain_no = 0;          // the chunk the chained launch in flight scans
+    bool settle_clean = true;       // the scan settled last committed on its own (no continuation, retry or fallback)
+    // the speculation pass
+    uint64_t spec_for_no = ~0ull;   // the chunk the speculation workspace holds a pass for (~0: none)
+    int spec_frames = 0;            // ... and its frames
+    // pipeline_depth >= 1: bursts of the last scanned chunk, processed during the next feed / irdm_flush
+    bool has_pending = false;
+    std::vector<GoneBurst> pend_gone;
+    uint64_t pend_c1 = 0, pend_no = 0;
+    // time-chunk sharding (hp_gate below)
+    bool gate_armed = false;        // the next band scan enqueued from frame 0 waits for gate_seq before its first history read
+    bool gate_open_pending = false; // a scan in flight waits for the history to arrive in gate_src
+    const void *gate_src = nullptr; // the caller's receive buffer (device memory) the scan copies the history from
+    // last chunk (probes)
+    int last_frames = 0;
+    const void *last_chunk = nullptr;
+    uint64_t last_chunk_start = 0, last_chunk_end = 0;
+    std::vector<irdm_burst_t> last_bursts;
+    float last_ms[6] = {};
+    // result queues; option "chunk_marks": one mark per batch of records pushed to them -- which chunk (in the order fed)
+    // they belong to and how many records went to each queue -- for a caller that merges the records of several contexts
+    // in stream order (group.cpp)
+    RecordQueues q;
+    std::deque<irdm_chunk_mark_t> q_marks;
+};
+
 struct irdm_pipeline {
     irdm_config_t cfg;
+    StreamState st;
     DetParams P;
     int dev_fmt;                // device sample format == cfg.format: 0 ci8, 1 ci16 (narrowed in the load stage,
                                 // main.c:245-246), 2 cf32, 3 ci16 full precision, 4 SC16Q11 (common.hpp load_iq)
     size_t bps;                 // bytes per device sample
     int feed_block, decim, out_rate;
-    float peak_signal_db;    // burst_detector_peak_signal over the finished bursts (starts at 0 like the reference's calloc)
     bool dev_cfo;            // the fine-CFO libm step runs on the device (the port reproduces this host's cexpf)
     bool dev_cfo_ok;         // irdm_create's self-check: libm_port.hpp reproduces THIS host's cexpf (option host_cfo cannot override a failed check)
     float sps;
@@ -162,18 +236,11 @@ struct irdm_pipeline {
     hipStream_t stream_spec = nullptr;
     hipEvent_t ev_sums1 = nullptr;          // behind the first sums pass of the latest band-scan launch (its sum_new: the pass's sums)
     hipEvent_t ev_spec_done = nullptr;      // behind the latest speculation pass
-    uint64_t spec_for_no = ~0ull;           // the chunk the speculation workspace holds a pass for (~0: none)
-    int spec_frames = 0;                    // ... and its frames
     uint64_t stat_spec_passes = 0, stat_spec_scans = 0, stat_sum_restarts = 0;
-    uint32_t seq_counter = 0;               // scans numbered so far (HistJob::seq; never 0)
-    uint32_t fl_seq = 0;                    // number of the scan in flight
-    uint32_t chain_seq = 0;                 // ... of the chained launch (scan_chain_try), taken over by scan_launch
-    uint64_t chain_no = 0;                  // the chunk the chained launch in flight (chain_pending) scans
     int fir_order = 1;       // option fir_order / simd_order: 1 simd_avx2.c's operation order, 0 simd_generic.c's (--no-simd); per pipeline
     int fir_generic = 0;     // test hook fir_generic: 1 = always the any-M decimator (what 2 / 4 MHz streams take)
     int post_generic = 0;    // test hook post_generic: 1 = the runtime-tap-count instances of post_tiles / post_cfo / post2
     irdm::BandTune band_tune;   // options band_selfcheck / band_timeline / band_sum_restart
-    hipEvent_t ev_sk[2];     // bracket the scan kernel itself on sstream (last_timings[1], bench.py's roofline)
     hipEvent_t ev[10];   // 0 start,1 fft,2 scan,3 pre-fir,4 fir,5 post,6 demod,7 end,8 caller sync
 
     float *d_window, *d_hist, *d_sum, *d_mag;
@@ -197,9 +264,7 @@ struct irdm_pipeline {
     int2 *d_syn_da, *d_syn_l1, *d_syn_l2, *d_syn_l3;
     int *d_dirs;
     std::vector<IdaOut> h_ida;
-    std::deque<irdm_ida_t> q_ida;
     std::vector<DecodedOut> h_decoded;
-    std::deque<irdm_decoded_t> q_decoded;
     // sparse scan (scan_fast.hip): prefilter lists, status word, pre-chunk snapshot for the dense fallback
     unsigned *d_counts, *d_goff;
     ListEntry *d_entries, *d_compact;
@@ -213,37 +278,19 @@ struct irdm_pipeline {
     int scan_mode;              // 0 auto (sparse multi-CU where the device has the CUs, dense fallback), 1 dense only,
                                 // 2 sparse on one CU, 3 sparse multi-CU
     uint64_t stat_fast_chunks, stat_fallbacks, stat_dense_frames;
-    int host_primed, host_hist_idx;
     // band-parallel speculative scan (scan_band.hip): the default where band_scan_supported()
     void *d_band;               // one allocation, carved into `band`
     BandWork band;
     float *d_smin;              // smallest sum every bin went through in the last band scan (stale-list retry)
     bool band_ok;
-    int fl_mode;                // scan in flight: 0 dense, 1 sparse (leader/updaters), 2 band
-    int fl_done;                // frames the dense scan primed before the in-flight scan proper
     uint64_t stat_plan_tp[16] = {};
     uint64_t stat_tl_dur[32] = {}, stat_tl_gap[32] = {}, stat_tl_n[32] = {};
     uint64_t stat_band_chunks, stat_band_rounds, stat_band_retries, stat_band_aborts, stat_band_extra, stat_chain_undone, stat_chained;
     uint32_t last_band_flags;
 
     std::vector<GoneBurst> h_gone;
-    // pipeline_depth 1: bursts of the last fed chunk, processed during the next feed / irdm_flush
-    std::vector<GoneBurst> pend_gone;
-    bool has_pending;
-    uint64_t pend_c1, pend_no, fl_no;
     int depth;
-    int *h_pin;              // pinned host words: [0..63] scan status, [64..65] n_gone/overflow, [66..67] hist_idx/primed.
-                             // (a D2H copy into pageable memory blocks the host until the stream drains -- that would
-                             // serialise pipeline_depth 1's deferred work behind the detector scan)
-    int deferred_emitted;
-    bool caller_ordered;     // the current chunk was handed over on a stream (ev[8] recorded)
     int k1_first;            // per-burst chains start behind K1 (1) / K1 + ring copy (2) of the chunk just fed
-    // detector scan in flight (scan_launch .. scan_finish)
-    bool fl_active, fl_sparse;
-    bool fl_band_ran;        // the band scan's control block on the device belongs to the scan in flight
-    const float *fl_mag, *d_mag_last;
-    int fl_frames;
-    uint64_t fl_c1, fl_c0;
     hipStream_t fstream;     // K1 (== stream unless pipeline_depth 1)
     float *d_mag2;           // pipeline_depth 1: second magnitude buffer
     std::vector<BurstWork> h_work;
@@ -255,31 +302,23 @@ struct irdm_pipeline {
     std::condition_variable cfo_cv;
     std::deque<BatchCtx *> cfo_jobs;
     bool cfo_quit;
-    GoneBurst *hp_gone;         // pinned copy of the finished-burst records of a scan
     int hp_gone_cap;
-    // Two sets of the scan's export targets (pinned words, pinned records, timing events): a band scan launched BEHIND
-    // the one still in flight (scan_chain) exports into the other set.  h_pin / hp_gone / ev_sk / ev_end alias the set of
-    // the scan that scan_finish settles next.
-    int *h_pin_set[2];
-    GoneBurst *hp_gone_set[2];
-    hipEvent_t ev_sk_set[2][2], ev_end_set[2], ev_end;
-    int out_sel;
-    bool chain_pending;         // feed_end has enqueued this chunk's scan behind the previous one
-    int chain_sel, chain_band_first;
-    bool settle_clean;          // the scan settled last committed on its own (no continuation, retry or fallback)
+    // Two sets of the scan's export targets: a band scan launched BEHIND the one still in flight (scan_chain) exports into
+    // the other set.  st.out_sel is the set of the scan that scan_finish settles next: h_pin() .. ev_end() are its targets.
+    int *h_pin_set[2];          // pinned host words: [0..63] scan status, [64..65] n_gone/overflow, [66..67] hist_idx/primed.
+                                // (a D2H copy into pageable memory blocks the host until the stream drains -- that would
+                                // serialise pipeline_depth 1's deferred work behind the detector scan)
+    GoneBurst *hp_gone_set[2];  // pinned copy of the finished-burst records of a scan
+    hipEvent_t ev_sk_set[2][2]; // bracket the scan kernel itself on sstream (last_timings[1], bench.py's roofline)
+    hipEvent_t ev_end_set[2];
+    int *h_pin() const { return h_pin_set[st.out_sel]; }
+    GoneBurst *hp_gone() const { return hp_gone_set[st.out_sel]; }
+    hipEvent_t ev_sk(int i) const { return ev_sk_set[st.out_sel][i]; }
+    hipEvent_t ev_end() const { return ev_end_set[st.out_sel]; }
     hipEvent_t ev_ring;         // pipeline_depth >= 1: the history-ring copy of the last fed chunk
-    uint64_t chunk_no;          // chunks fed so far
     // chunks between irdm_feed_begin and irdm_feed_end: at most one at pipeline_depth 0, two (one chunk of look-ahead:
     // K1 of chunk N+1 is on the GPU before the host waits for the scan of chunk N-1) otherwise
-    struct FeedSlot {
-        const void *iq;
-        uint64_t c0, c1;
-        float *mag;
-        int frames;
-        bool in_ring;           // the caller wrote the chunk where irdm_ingest_ptr() said: no copy into the ring
-        bool lists;             // K1 wrote the band scan's candidate lists of the chunk (k1_pre / k1_counts / k1_entries)
-        hipEvent_t ev_start, ev_k1, ev_copy;
-    } fs[kFeedSlots];
+    FeedSlot fs[kFeedSlots];
     // candidate lists written by K1 (fft_mag_r16_kernel<.., LISTS>), one set per feed slot: the reference levels the
     // lists were built against, the per-frame counts and entries
     float *k1_pre[kFeedSlots];
@@ -288,42 +327,17 @@ struct irdm_pipeline {
     int k1_lists;               // option: 1 = let K1 build the lists where it can
     int band_first;             // band-scan rounds enqueued up front: 0 = as many as the previous chunk needed (at least
                                 // 2, kBandFirst to begin with), n = always n (test hook)
-    int band_auto, fl_band_first;
-    const FeedSlot *fl_feed;    // feed slot of the scan in flight
+    int band_auto;
     uint64_t stat_k1_lists;
-    uint64_t begin_no, end_no;  // feeds begun / ended; slot = number % kFeedSlots
-    uint64_t begun_samples;     // absolute index the next irdm_feed_begin starts at
     float *d_mag3;
     double host_us[10];         // pipeline_depth >= 1, accumulated host time: K1+ring enqueue, settle, chain enqueue, scan enqueue, wait for the older chain, final sync
-    std::vector<FirTile> h_tiles;
     std::vector<DemodOut> h_demod;
     std::vector<float> h_frames;
 
-    // result queues
-    std::deque<irdm_burst_t> q_bursts;
-    std::deque<irdm_frame_info_t> q_frames;
-    std::deque<std::vector<float>> q_frame_samples;
-    std::deque<irdm_demod_t> q_demods;
-    std::deque<irdm_demod_packed_t> q_packed;
     int packed_records;         // option: queue irdm_demod_packed_t records only
     int parsed_records;         // option: packed_records, and one irdm_ida_packed_t per irdm_demod_packed_t
-    std::deque<irdm_ida_packed_t> q_ida_packed;
     int frame_records;          // option: packed_records, and one irdm_frame_packed_t per irdm_demod_packed_t
-    std::deque<irdm_frame_packed_t> q_frame_packed;
-    // option "chunk_marks": one mark per batch of records pushed to the queues above -- which chunk (in the order fed)
-    // they belong to and how many records went to each queue -- for a caller that merges the records of several contexts
-    // in stream order (group.cpp)
-    std::deque<irdm_chunk_mark_t> q_marks;
-    int chunk_marks;
-
-    uint64_t total_samples, tagged, start_time_ns;
-    bool stream_closed;
-    // last chunk (probes)
-    int last_frames;
-    const void *last_chunk;
-    uint64_t last_chunk_start, last_chunk_end;
-    std::vector<irdm_burst_t> last_bursts;
-    float last_ms[6];
+    int chunk_marks;            // option: StreamState::q_marks
     int keep_frame_samples;
     // rotator checkpoint rows on demand (rot_rows_prepare)
     int *d_rot_slot = nullptr;              // [n][rot_runs] centre bin, run -> block of d_rot_table, -1: none yet (written by the kernel that builds the run)
@@ -353,9 +367,6 @@ struct irdm_pipeline {
     // flag of the waiting kernel, in mapped pinned memory; the import's copies run on gstream
     uint32_t *hp_gate = nullptr, *hp_gate_dev = nullptr;
     uint32_t gate_seq = 0;
-    bool gate_armed = false;        // the next band scan enqueued from frame 0 waits for gate_seq before its first history read
-    bool gate_open_pending = false; // a scan in flight waits for the history to arrive in gate_src
-    const void *gate_src = nullptr; // the caller's receive buffer (device memory) the scan copies the history from
     // kernel clock (option "kernel_clock", common.hpp): records 0..2 the decimator of bc[0..2], 3..5 K1 of feed slot 0..2
     unsigned long long *d_kclk = nullptr;
     int kernel_clock = 0;
@@ -383,17 +394,6 @@ static inline void pipeline_enter(const irdm_pipeline *p) { (void)hipSetDevice(p
 namespace irdmh {
 bool rate_supported(int fs, int *fft_size);      // create.cpp: a sample rate irdm_create takes
 
-template <typename T>
-static int drain(std::deque<T> &q, T *out, int max)
-{
-    int n = 0;
-    while (n < max && !q.empty()) {
-        out[n++] = q.front();
-        q.pop_front();
-    }
-    return n;
-}
-
 // create.cpp
 void pipeline_free(irdm_pipeline *p);
 bool chain_stream_create(irdm_pipeline *, hipStream_t *out, int prio);
@@ -418,8 +418,6 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b);
 int process_bursts(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const GoneBurst *gone_list, int n_gone);
 
 // scan_host.cpp
-int hist_fence(irdm_pipeline *);
-uint32_t next_scan_seq(irdm_pipeline *p);
 int scan_hop_in(irdm_pipeline *p);
 int scan_hop_out(irdm_pipeline *p);
 int scan_dense(irdm_pipeline *p, const float *mag, int n_frames, bool timed);
@@ -427,14 +425,12 @@ int scan_pick(const irdm_pipeline *p);
 int scan_snapshot(irdm_pipeline *p);
 int scan_restore(irdm_pipeline *p);
 int scan_band_enqueue_at(irdm_pipeline *p, const float *mag, int n_frames, int done, int retry, bool more_rounds,
-                                uint64_t c0, const irdm_pipeline::FeedSlot *feed, int sel, int first, int chained,
-                                uint32_t seq, uint64_t chunk_no, bool use_spec = false);
+                                uint64_t c0, const FeedSlot *feed, int sel, int first, int chained, bool use_spec = false);
 int scan_band_enqueue(irdm_pipeline *p, const float *mag, int n_frames, int done, int retry, bool more_rounds = false);
 int scan_legacy_enqueue(irdm_pipeline *p, const float *mag, int n_frames, int done, bool sparse);
 int scan_export(irdm_pipeline *p);
-void scan_select_outputs(irdm_pipeline *p, int sel);
-int scan_chain_try(irdm_pipeline *p, irdm_pipeline::FeedSlot &f, uint64_t no);
-int spec_enqueue(irdm_pipeline *p, irdm_pipeline::FeedSlot &nx, uint64_t no);
+int scan_chain_try(irdm_pipeline *p, FeedSlot &f, uint64_t no);
+int spec_enqueue(irdm_pipeline *p, FeedSlot &nx, uint64_t no);
 int scan_launch(irdm_pipeline *p, const float *mag, int n_frames, uint64_t c1);
 int scan_finish(irdm_pipeline *p, int *n_gone_out);
 int settle(irdm_pipeline *p);

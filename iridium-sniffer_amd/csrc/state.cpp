@@ -22,8 +22,8 @@ extern "C" long long irdm_export_state(irdm_pipeline_t *p, void *buf, size_t cap
     if (!p || !buf || cap < irdm_state_bytes(p) || quiesce(p) != 0) return -1;
     pipeline_enter(p);
     char *o = static_cast<char *>(buf);
-    StateHeader h = { 0x4952444d53544154ull, (uint64_t)p->P.n, (uint64_t)kHistory, p->total_samples, p->tagged,
-                      p->start_time_ns, p->host_primed, p->host_hist_idx };
+    StateHeader h = { 0x4952444d53544154ull, (uint64_t)p->P.n, (uint64_t)kHistory, p->st.total_samples, p->st.tagged,
+                      p->st.start_time_ns, p->st.host_primed, p->st.host_hist_idx };
     memcpy(o, &h, sizeof(h));
     o += sizeof(h);
     IRDM_HIP_CHECK(hipMemcpy(o, p->d_state, sizeof(DetState), hipMemcpyDeviceToHost));
@@ -38,7 +38,7 @@ extern "C" long long irdm_export_state(irdm_pipeline_t *p, void *buf, size_t cap
 // ahead, or with the next chunk's scan already chained behind the one in flight (scan_chain_early), that scan has read -- or
 // committed against -- the state the import is about to overwrite, and irdm_feed_end would book its results as the
 // imported stream's.  The time-sharded callers begin one chunk ahead at most and import before its irdm_feed_end.
-static inline bool import_allowed(const irdm_pipeline *p) { return !p->chain_pending && p->begin_no <= p->end_no + 1; }
+static inline bool import_allowed(const irdm_pipeline *p) { return !p->st.chain_pending && p->st.begin_no <= p->st.end_no + 1; }
 
 extern "C" int irdm_import_state(irdm_pipeline_t *p, const void *buf, size_t n)
 {
@@ -54,11 +54,12 @@ extern "C" int irdm_import_state(irdm_pipeline_t *p, const void *buf, size_t n)
     IRDM_HIP_CHECK(hipMemcpy(p->d_sum, i, sizeof(float) * p->P.n, hipMemcpyHostToDevice));
     i += sizeof(float) * p->P.n;
     IRDM_HIP_CHECK(hipMemcpy(p->d_hist, i, sizeof(float) * (size_t)kHistory * p->P.n, hipMemcpyHostToDevice));
-    if (p->begin_no == p->end_no) p->total_samples = p->begun_samples = h.total_samples;     // (a feed already begun has fixed its own position)
-    p->tagged = h.tagged;
-    p->start_time_ns = h.start_time_ns;
-    p->host_primed = h.host_primed;
-    p->host_hist_idx = h.host_hist_idx;
+    // (a feed already begun has fixed its own position)
+    if (p->st.begin_no == p->st.end_no) p->st.total_samples = p->st.begun_samples = h.total_samples;
+    p->st.tagged = h.tagged;
+    p->st.start_time_ns = h.start_time_ns;
+    p->st.host_primed = h.host_primed;
+    p->st.host_hist_idx = h.host_hist_idx;
     return 0;
 }
 
@@ -69,10 +70,10 @@ extern "C" long long irdm_export_state_device(irdm_pipeline_t *p, void *d_buf, s
 {
     if (!p || !d_buf || cap < irdm_state_bytes(p)) return -1;
     pipeline_enter(p);
-    if (settle(p) != 0 || hist_fence(p) != 0) return -1;
+    if (settle(p) != 0) return -1;
     char *o = static_cast<char *>(d_buf);
-    const StateHeader h = { 0x4952444d53544154ull, (uint64_t)p->P.n, (uint64_t)kHistory, p->total_samples, p->tagged,
-                            p->start_time_ns, p->host_primed, p->host_hist_idx };
+    const StateHeader h = { 0x4952444d53544154ull, (uint64_t)p->P.n, (uint64_t)kHistory, p->st.total_samples, p->st.tagged,
+                            p->st.start_time_ns, p->st.host_primed, p->st.host_hist_idx };
     IRDM_HIP_CHECK(hipMemcpyAsync(o, &h, sizeof(h), hipMemcpyHostToDevice, p->stream));
     o += sizeof(h);
     IRDM_HIP_CHECK(hipMemcpyAsync(o, p->d_state, sizeof(DetState), hipMemcpyDeviceToDevice, p->stream));
@@ -88,7 +89,7 @@ extern "C" int irdm_import_state_device(irdm_pipeline_t *p, const void *d_buf, s
 {
     if (!p || !d_buf || n < irdm_state_bytes(p) || !import_allowed(p)) return -1;
     pipeline_enter(p);
-    if (settle(p) != 0 || hist_fence(p) != 0) return -1;
+    if (settle(p) != 0) return -1;
     const char *i = static_cast<const char *>(d_buf);
     StateHeader h;
     IRDM_HIP_CHECK(hipMemcpyAsync(&h, i, sizeof(h), hipMemcpyDeviceToHost, p->stream));
@@ -101,11 +102,12 @@ extern "C" int irdm_import_state_device(irdm_pipeline_t *p, const void *d_buf, s
     i += sizeof(float) * p->P.n;
     IRDM_HIP_CHECK(hipMemcpyAsync(p->d_hist, i, sizeof(float) * (size_t)kHistory * p->P.n, hipMemcpyDeviceToDevice, p->stream));
     IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-    if (p->begin_no == p->end_no) p->total_samples = p->begun_samples = h.total_samples;     // (a feed already begun has fixed its own position)
-    p->tagged = h.tagged;
-    p->start_time_ns = h.start_time_ns;
-    p->host_primed = h.host_primed;
-    p->host_hist_idx = h.host_hist_idx;
+    // (a feed already begun has fixed its own position)
+    if (p->st.begin_no == p->st.end_no) p->st.total_samples = p->st.begun_samples = h.total_samples;
+    p->st.tagged = h.tagged;
+    p->st.start_time_ns = h.start_time_ns;
+    p->st.host_primed = h.host_primed;
+    p->st.host_hist_idx = h.host_hist_idx;
     return 0;
 }
 
@@ -134,11 +136,11 @@ extern "C" int irdm_import_state_head_device(irdm_pipeline_t *p, const void *d_b
     i += sizeof(DetState);
     IRDM_HIP_CHECK(hipMemcpyAsync(p->d_sum, i, sizeof(float) * p->P.n, hipMemcpyDeviceToDevice, p->stream));
     IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-    if (p->begin_no == p->end_no) p->total_samples = p->begun_samples = h.total_samples;
-    p->tagged = h.tagged;
-    p->start_time_ns = h.start_time_ns;
-    p->host_primed = h.host_primed;
-    p->host_hist_idx = h.host_hist_idx;
+    if (p->st.begin_no == p->st.end_no) p->st.total_samples = p->st.begun_samples = h.total_samples;
+    p->st.tagged = h.tagged;
+    p->st.start_time_ns = h.start_time_ns;
+    p->st.host_primed = h.host_primed;
+    p->st.host_hist_idx = h.host_hist_idx;
     return 0;
 }
 
@@ -150,14 +152,14 @@ extern "C" int irdm_import_state_head_device(irdm_pipeline_t *p, const void *d_b
 // detector that is not primed, a scan other than the band scan): import the history before irdm_feed_end.
 extern "C" int irdm_expect_history(irdm_pipeline_t *p, const void *d_hist_buf)
 {
-    if (!p || !d_hist_buf || !p->hp_gate_dev || !p->depth || !p->host_primed || scan_pick(p) != 2 || p->begin_no == p->end_no)
+    if (!p || !d_hist_buf || !p->hp_gate_dev || !p->depth || !p->st.host_primed || scan_pick(p) != 2 || p->st.begin_no == p->st.end_no)
         return 0;
     // (test hook band_first 1: the launch ends with round 0's verdict, before the pass the gate sits in front of -- the
     // continuation would run on a history that was never copied in)
     if (p->band_first == 1) return 0;
     p->gate_seq++;
-    p->gate_src = d_hist_buf;
-    p->gate_armed = true;
+    p->st.gate_src = d_hist_buf;
+    p->st.gate_armed = true;
     return 1;
 }
 
@@ -168,15 +170,15 @@ extern "C" int irdm_import_state_history_device(irdm_pipeline_t *p, const void *
     const size_t bytes = p ? sizeof(float) * (size_t)kHistory * p->P.n : 0;
     if (!p || !d_hist_buf || n < bytes) return -1;
     pipeline_enter(p);
-    if (p->gate_open_pending) {
+    if (p->st.gate_open_pending) {
         // a scan is waiting for it: the word it polls is written by the HOST (no GPU work of ours that could queue up
         // behind the waiting kernel); the scan's stream copies the history in and goes on
-        if (d_hist_buf != p->gate_src) return -1;
+        if (d_hist_buf != p->st.gate_src) return -1;
         __atomic_store_n(&p->hp_gate[0], p->gate_seq, __ATOMIC_RELEASE);
         return 0;
     }
-    p->gate_armed = false;               // (announced, but the scan was never enqueued: the ordinary import)
-    if (settle(p) != 0 || hist_fence(p) != 0) return -1;
+    p->st.gate_armed = false;               // (announced, but the scan was never enqueued: the ordinary import)
+    if (settle(p) != 0) return -1;
     IRDM_HIP_CHECK(hipMemcpyAsync(p->d_hist, d_hist_buf, bytes, hipMemcpyDeviceToDevice, p->stream));
     IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     return 0;
@@ -185,7 +187,7 @@ extern "C" int irdm_import_state_history_device(irdm_pipeline_t *p, const void *
 // the preceding samples from DEVICE memory (a chunk overlap received from the previous rank)
 extern "C" int irdm_seed_history_device(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, uint64_t abs_start)
 {
-    if (!p || (!d_iq && n_samples) || n_samples > abs_start || p->begin_no != p->end_no) return -1;
+    if (!p || (!d_iq && n_samples) || n_samples > abs_start || p->st.begin_no != p->st.end_no) return -1;
     pipeline_enter(p);
     if (n_samples > p->ring_len) {
         d_iq = static_cast<const char *>(d_iq) + (n_samples - p->ring_len) * p->bps;
@@ -197,13 +199,13 @@ extern "C" int irdm_seed_history_device(irdm_pipeline_t *p, const void *d_iq, si
     if (ring_update(p, d_iq, abs_start - n_samples, abs_start, p->fstream) != 0) return -1;
     IRDM_HIP_CHECK(hipEventRecord(p->ev_ring, p->fstream));
     IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
-    p->total_samples = p->begun_samples = abs_start;
+    p->st.total_samples = p->st.begun_samples = abs_start;
     return 0;
 }
 
 extern "C" int irdm_seed_history(irdm_pipeline_t *p, const void *h_iq, size_t n_samples, uint64_t abs_start)
 {
-    if (!p || (!h_iq && n_samples) || n_samples > abs_start || p->begin_no != p->end_no) return -1;
+    if (!p || (!h_iq && n_samples) || n_samples > abs_start || p->st.begin_no != p->st.end_no) return -1;
     if (quiesce(p) != 0) return -1;
     if (n_samples > p->ring_len) {       // only the most recent ring_len samples can matter
         h_iq = static_cast<const char *>(h_iq) + (n_samples - p->ring_len) * p->bps;
@@ -219,7 +221,7 @@ extern "C" int irdm_seed_history(irdm_pipeline_t *p, const void *h_iq, size_t n_
                                  hipMemcpyHostToDevice));
         done += run;
     }
-    p->total_samples = p->begun_samples = abs_start;
+    p->st.total_samples = p->st.begun_samples = abs_start;
     return 0;
 }
 
@@ -241,37 +243,36 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     g.center_bin = info->center_bin;
     g.peak_rel = info->peak_rel;
     g.base_sum = info->base_sum;
-    // keep the result queues of the stream untouched: run on private queues
-    std::deque<irdm_burst_t> qb; std::deque<irdm_frame_info_t> qf; std::deque<std::vector<float>> qs;
-    std::deque<irdm_demod_t> qd;
-    qb.swap(p->q_bursts); qf.swap(p->q_frames); qs.swap(p->q_frame_samples); qd.swap(p->q_demods);
+    // keep the result queues of the stream untouched: they stand aside while the call runs on empty ones
+    RecordQueues stream_q;
+    std::swap(stream_q, p->st.q);
     const int keep = p->keep_frame_samples, dec = p->decode_frames, dec_ida = p->decode_ida, det = p->detect_only;
     p->decode_frames = 0;
     p->decode_ida = 0;
     p->detect_only = 0;          // a stage-B call on a detect-only context still runs stage B
     const int marks = p->chunk_marks;
     p->chunk_marks = 0;          // (the records go to private queues: no chunk mark for them)
-    const uint64_t tagged = p->tagged;
-    std::vector<irdm_burst_t> last; last.swap(p->last_bursts);
+    const uint64_t tagged = p->st.tagged;
+    std::vector<irdm_burst_t> last; last.swap(p->st.last_bursts);
     p->keep_frame_samples = 1;
     const int rc = process_bursts(p, p->bc[0], src, &g, 1);
     int ret = -1;
-    if (rc == 0 && !p->q_frames.empty()) {
-        *frame = p->q_frames.front();
+    if (rc == 0 && !p->st.q.frames.empty()) {
+        *frame = p->st.q.frames.front();
         frame->magnitude = info->magnitude;
         frame->noise = info->noise;
-        if (frame->drop_reason == 0 && frame_samples && !p->q_frame_samples.empty())
-            memcpy(frame_samples, p->q_frame_samples.front().data(), p->q_frame_samples.front().size() * sizeof(float));
+        if (frame->drop_reason == 0 && frame_samples && !p->st.q.frame_samples.empty())
+            memcpy(frame_samples, p->st.q.frame_samples.front().data(), p->st.q.frame_samples.front().size() * sizeof(float));
         ret = frame->drop_reason == 0 ? 1 : 0;
     }
-    p->q_bursts.swap(qb); p->q_frames.swap(qf); p->q_frame_samples.swap(qs); p->q_demods.swap(qd);
+    std::swap(stream_q, p->st.q);
     p->keep_frame_samples = keep;
     p->chunk_marks = marks;
     p->detect_only = det;
     p->decode_frames = dec;
     p->decode_ida = dec_ida;
-    p->tagged = tagged;
-    p->last_bursts.swap(last);
+    p->st.tagged = tagged;
+    p->st.last_bursts.swap(last);
     return ret;
 }
 
@@ -321,7 +322,7 @@ extern "C" int irdm_qpsk_demod_batch(irdm_pipeline_t *p, const float *samples, c
 extern "C" int irdm_poll_decoded(irdm_pipeline_t *p, irdm_decoded_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_decoded, out, max);
+    return drain(p->st.q.decoded, out, max);
 }
 
 extern "C" int irdm_frame_decode_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, int use_llr, irdm_decoded_t *out)
@@ -361,7 +362,7 @@ extern "C" int irdm_frame_decode_batch(irdm_pipeline_t *p, const irdm_demod_t *i
 extern "C" int irdm_poll_ida(irdm_pipeline_t *p, irdm_ida_t *out, int max)
 {
     if (!p || !out || max < 0) return -1;
-    return drain(p->q_ida, out, max);
+    return drain(p->st.q.ida, out, max);
 }
 
 extern "C" int irdm_ida_decode_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, int use_llr, irdm_ida_t *out)
