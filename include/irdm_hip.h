@@ -805,6 +805,38 @@ int irdm_frontend_wait_input(irdm_frontend_t *fe);
  * front end's stream. */
 int irdm_frontend_kernel_clock(irdm_frontend_t *fe, double *sum_ms, uint64_t *launches, int reset);
 
+/* The rational mode (K0r): output rate = in_rate * L / M, L / M = out_rate / in_rate in lowest terms, for captures whose
+ * rate is no integer multiple of a rate the pipeline demodulates at (the pipeline wants a multiple of 250 kHz: 10 samples per
+ * symbol after its own integer decimation).
+ *
+ *   y[m] = sum_n P[m M + C - n L] r[n]   (terms with 0 <= m M + C - n L < Np),  C = (Np - 1) / 2,  r[n] as above
+ *
+ *   P  the same low-pass design at the rate L * in_rate with gain L: cut-off 0.5 f_min, transition parameter 0.09 f_min,
+ *      f_min = min(in_rate, out_rate); Np odd.  For L = 1 these are K0's taps at D = M.  (The design takes the rate as a
+ *      float: L * in_rate is formed exactly and rounded once to nearest; exact for the rates the README names.)
+ * Output m sits at capture time m M / L input samples: no delay.  A stream of n samples gives ceil(n L / M) outputs.  One
+ * accumulator per component from +0, one fused multiply-add per term in ascending n, the zero samples outside the stream
+ * included (tests/resample_model.c restates it in plain C, bit for bit).
+ * Limits: L <= 125, M <= 768, 24/25 <= M / L <= 16, M != L; out_rate one irdm_create takes; format and shift as above.
+ * When in_rate / out_rate is an integer D in 2 .. 16 the object is irdm_frontend_create's: K0's output, bit for bit.
+ * Every irdm_frontend_* call above works on the object unchanged in meaning (irdm_frontend_taps returns P). */
+typedef struct {
+    int device;                /* HIP device ordinal (the pipeline's) */
+    int in_rate;               /* capture sample rate, Hz */
+    int in_format;             /* IRDM_FMT_* of the capture */
+    int out_rate;              /* the rate handed to the pipeline, Hz */
+    double shift_hz;           /* band centre - capture centre; |shift_hz| <= in_rate / 2 */
+} irdm_frontend_rational_config_t;
+/* NULL (message on stderr) for a ratio outside the limits, an unknown format, a shift beyond half the capture rate, or an
+ * output rate irdm_create would refuse. */
+irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_rational_config_t *cfg);
+/* The ratio out_rate / in_rate in lowest terms and the limits above on it, without a device: 0 when
+ * irdm_frontend_create_rational would take the pair of rates as far as the ratio goes (an integer ratio 2 .. 16 included),
+ * -1 with the create call's message on stderr otherwise.  L, M (either may be NULL) are set whenever both rates are positive. */
+int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L, int *M);
+/* the ratio in lowest terms: output rate = capture rate * L / M (1 / D for irdm_frontend_create's object).  0 ok, -1 error. */
+int irdm_frontend_ratio(const irdm_frontend_t *fe, int *L, int *M);
+
 /* The fine-CFO step's cexpf(i x) (burst_downmix.c:716-717) as the device evaluates it -- glibc's sincosf restated,
  * csrc/libm_port.hpp -- for n arbitrary arguments (test / audit surface: tests/test_gpu_libm.py,
  * tools/check_sincosf_gpu.c compare it with the host's libm).  0 ok, -1 error; NaN where |x| >= 120. */

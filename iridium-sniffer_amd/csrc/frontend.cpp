@@ -1,53 +1,57 @@
 // frontend.cpp -- irdm_frontend_*: the band-select front end's object (K0, frontend.hip): taps, tables, the carried tail,
 // and the feeder that converts a wideband capture into the pipeline's ingest slot.
 //
-// Stream bookkeeping.  total = capture samples received, n_out = outputs produced.  Output m reads the inputs
-// m D - c .. m D + c, so after `total` samples the outputs below floor((total - 1 - c) / D) + 1 are complete, and the samples
-// from n_out D - c on are still needed: they are kept, raw, in a device tail buffer (at most ntaps - 1 + D of them) and the
-// kernel reads [tail | chunk] as one sequence.  The flush treats everything behind the last sample as zero and brings
-// the count to ceil(total / D).
+// Stream bookkeeping, for the ratio L / M (K0: 1 / D; K0r, resample.hip: any).  total = capture samples received, n_out =
+// outputs produced.  Output m reads the inputs n with 0 <= m M + c - n L < ntaps, that is floor((m M - c - 1) / L) + 1 ..
+// floor((m M + c) / L) (K0: m D - c .. m D + c), so after `total` samples the outputs below floor((total L - 1 - c) / M) + 1
+// are complete, and the samples from floor((n_out M - c - 1) / L) + 1 on are still needed: they are kept, raw, in a device
+// tail buffer (at most ntaps / L + 1 of them) and the kernel reads [tail | chunk] as one sequence.  The flush treats
+// everything behind the last sample as zero and brings the count to ceil(total L / M).
 #include "pipeline.hpp"
-
-struct irdm_frontend {
-    irdm_frontend_config_t cfg;
-    int D, fmt, bps, ntaps, c, out_rate;
-    long long q;
-    std::vector<float> taps;
-    float *d_hr = nullptr, *d_G = nullptr;
-    float2 *d_T = nullptr;
-    void *d_tail[2] = { nullptr, nullptr };
-    // stream state (irdm_frontend_reset assigns a fresh one)
-    struct State {
-        int cur = 0;                // which of d_tail holds the carried tail
-        long long n_tail = 0;
-        uint64_t total = 0, n_out = 0;
-        bool finished = false;
-        // the feeder: outputs written but not fed yet lie at base[0 .. pend)
-        float2 *base = nullptr;
-        size_t room = 0, pend = 0;
-    } st;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr, ev_caller = nullptr;
-    unsigned long long *d_kclk = nullptr;
-    float2 *d_scratch = nullptr;
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
-};
+#include "frontend_obj.hpp"
 
 namespace irdmh {
 
-static void fe_free(irdm_frontend *fe)
+void fe_free(irdm_frontend *fe)
 {
     if (!fe) return;
     (void)hipSetDevice(fe->cfg.device);
     if (fe->stream) (void)hipStreamSynchronize(fe->stream);
-    void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage };
+    void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     if (fe->ev_in) (void)hipEventDestroy(fe->ev_in);
     if (fe->ev_caller) (void)hipEventDestroy(fe->ev_caller);
     if (fe->stream) (void)hipStreamDestroy(fe->stream);
     delete fe;
+}
+
+bool fe_alloc_common(irdm_frontend *fe, size_t tail_samples)
+{
+    // the rotation table (built in double)
+    std::vector<float2> T(65536);
+    for (int i = 0; i < 65536; i++) {
+        const double a = -2.0 * M_PI * (double)i / 65536.0;
+        T[i] = make_float2((float)cos(a), (float)sin(a));
+    }
+    int prio_lo = 0, prio_hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    const int prio_k1 = prio_hi < prio_lo - 1 ? prio_hi + 1 : prio_hi;          // K1's class (create.cpp)
+    const size_t tail_bytes = tail_samples * 8;
+    std::vector<unsigned long long> kinit(kKClkWords, 0ull);
+    for (int i = 0; i < 64; i++) kinit[i] = ~0ull;
+    bool ok = (fe->d_T = dev_upload(T.data(), T.size())) != nullptr;
+    ok = ok && (fe->d_kclk = dev_upload(kinit.data(), kinit.size())) != nullptr;
+    ok = ok && hipMalloc(&fe->d_tail[0], tail_bytes) == hipSuccess && hipMalloc(&fe->d_tail[1], tail_bytes) == hipSuccess;
+    ok = ok && hipStreamCreateWithPriority(&fe->stream, hipStreamNonBlocking, prio_k1) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&fe->ev_in, hipEventDisableTiming) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&fe->ev_caller, hipEventDisableTiming) == hipSuccess;
+    return ok;
+}
+
+static int fe_launch_k0(irdm_frontend *fe, const FrontendArgs &a, hipStream_t s)
+{
+    return launch_frontend(fe->D, a, fe->d_hr, fe->d_G, fe->d_T, s, fe->d_kclk);
 }
 
 extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *cfg)
@@ -87,6 +91,9 @@ extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *c
     if (!fe) return nullptr;
     fe->cfg = *cfg;
     fe->D = cfg->decim;
+    fe->L = 1;
+    fe->M = cfg->decim;
+    fe->launch = fe_launch_k0;
     fe->fmt = cfg->in_format;
     fe->bps = fe->fmt == IRDM_FMT_CF32 ? 8 : (fe->fmt == IRDM_FMT_CI8 ? 2 : 4);
     fe->out_rate = out_rate;
@@ -100,30 +107,14 @@ extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *c
         delete fe;
         return nullptr;
     }
-    // reversed taps (ascending input order), the table of the full steps, the rotation table (built in double)
+    // reversed taps (ascending input order), the table of the full steps
     std::vector<float> hr(nt), G((size_t)(nt - (R - 1) * D) * R);
     for (int j = 0; j < nt; j++) hr[j] = fe->taps[nt - 1 - j];
     for (int i = (R - 1) * D; i < nt; i++)
         for (int r = 0; r < R; r++) G[(size_t)(i - (R - 1) * D) * R + r] = hr[i - r * D];
-    std::vector<float2> T(65536);
-    for (int i = 0; i < 65536; i++) {
-        const double a = -2.0 * M_PI * (double)i / 65536.0;
-        T[i] = make_float2((float)cos(a), (float)sin(a));
-    }
-    int prio_lo = 0, prio_hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    const int prio_k1 = prio_hi < prio_lo - 1 ? prio_hi + 1 : prio_hi;          // K1's class (create.cpp)
-    const size_t tail_bytes = (size_t)(nt + D + 16) * 8;
-    std::vector<unsigned long long> kinit(kKClkWords, 0ull);
-    for (int i = 0; i < 64; i++) kinit[i] = ~0ull;
     bool ok = (fe->d_hr = dev_upload(hr.data(), hr.size())) != nullptr;
     ok = ok && (fe->d_G = dev_upload(G.data(), G.size())) != nullptr;
-    ok = ok && (fe->d_T = dev_upload(T.data(), T.size())) != nullptr;
-    ok = ok && (fe->d_kclk = dev_upload(kinit.data(), kinit.size())) != nullptr;
-    ok = ok && hipMalloc(&fe->d_tail[0], tail_bytes) == hipSuccess && hipMalloc(&fe->d_tail[1], tail_bytes) == hipSuccess;
-    ok = ok && hipStreamCreateWithPriority(&fe->stream, hipStreamNonBlocking, prio_k1) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&fe->ev_in, hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&fe->ev_caller, hipEventDisableTiming) == hipSuccess;
+    ok = ok && fe_alloc_common(fe, (size_t)(nt + D + 16));
     if (!ok) {
         fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
         fe_free(fe);
@@ -138,6 +129,13 @@ extern "C" double irdm_frontend_applied_shift_hz(const irdm_frontend_t *fe)
 {
     return fe ? (double)fe->q * (double)fe->cfg.in_rate / 65536.0 : 0.0;
 }
+extern "C" int irdm_frontend_ratio(const irdm_frontend_t *fe, int *L, int *M)
+{
+    if (!fe) return -1;
+    if (L) *L = fe->L;
+    if (M) *M = fe->M;
+    return 0;
+}
 extern "C" int irdm_frontend_ntaps(const irdm_frontend_t *fe) { return fe ? fe->ntaps : -1; }
 extern "C" int irdm_frontend_taps(const irdm_frontend_t *fe, float *out, int max)
 {
@@ -149,8 +147,9 @@ extern "C" int irdm_frontend_taps(const irdm_frontend_t *fe, float *out, int max
 // outputs complete once `total` samples are in (flush: with zeros behind them)
 static uint64_t fe_outputs(const irdm_frontend *fe, uint64_t total, bool flush)
 {
-    if (flush) return (total + (uint64_t)fe->D - 1) / (uint64_t)fe->D;
-    return total > (uint64_t)fe->c ? (total - 1 - (uint64_t)fe->c) / (uint64_t)fe->D + 1 : 0;
+    const uint64_t L = (uint64_t)fe->L, M = (uint64_t)fe->M;
+    if (flush) return (total * L + M - 1) / M;
+    return total * L > (uint64_t)fe->c ? (total * L - 1 - (uint64_t)fe->c) / M + 1 : 0;
 }
 
 // outputs [fe->st.n_out, m1) of [tail | d_in] into out
@@ -169,7 +168,7 @@ static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1
     a.q16 = (unsigned)(fe->q & 0xffff);
     a.ntaps = fe->ntaps;
     a.fmt = fe->fmt;
-    if (launch_frontend(fe->D, a, fe->d_hr, fe->d_G, fe->d_T, s, fe->d_kclk) != 0) return -1;
+    if (fe->launch(fe, a, s) != 0) return -1;
     if (launch_kclk_fold(fe->d_kclk, s) != 0) return -1;
     fe->st.n_out = m1;
     return 0;
@@ -179,11 +178,12 @@ static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1
 static int fe_commit(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream_t s)
 {
     const uint64_t total = fe->st.total + n_in;
-    const long long need = (long long)(fe->st.n_out * (uint64_t)fe->D) - fe->c;       // first sample still needed
+    const long long edge = (long long)(fe->st.n_out * (uint64_t)fe->M) - fe->c - 1;
+    const long long need = (edge >= 0 ? edge / fe->L : -((-edge + fe->L - 1) / fe->L)) + 1;     // first sample still needed
     const long long start = std::min<long long>(std::max<long long>(need, 0), (long long)total);
     const long long pos0 = (long long)fe->st.total - fe->st.n_tail;
     const int n_new = (int)((long long)total - start);
-    if (n_new > fe->ntaps + fe->D + 16) return -1;                                 // (cannot happen: see the header comment)
+    if (n_new > fe->ntaps / fe->L + fe->M + 16) return -1;                                 // (cannot happen: see the header comment)
     if (launch_frontend_tail(fe->d_tail[fe->st.cur], fe->st.n_tail, d_in, (long long)n_in, start - pos0, n_new, fe->bps,
                              fe->d_tail[fe->st.cur ^ 1], s) != 0)
         return -1;

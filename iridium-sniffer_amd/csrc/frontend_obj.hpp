@@ -1,0 +1,45 @@
+// frontend_obj.hpp -- the front end's object, shared by its two makers: irdm_frontend_create (frontend.cpp: K0, integer
+// decimation) and irdm_frontend_create_rational (resample.cpp: K0r, L / M).  Everything behind creation -- the stream
+// bookkeeping, the feeder, reset -- is frontend.cpp's and works on the ratio L / M (1 / D for K0); the object carries its
+// kernel's launch function, so frontend.cpp refers to neither kernel file by name beyond K0's.
+#pragma once
+#include "pipeline.hpp"
+
+struct irdm_frontend {
+    irdm_frontend_config_t cfg;      // (rational mode: device, in_rate, in_format, shift_hz; decim 0)
+    int D, fmt, bps, ntaps, c, out_rate;
+    int L = 1, M = 0;                // output rate = input rate * L / M; K0: 1 / D
+    long long q;
+    std::vector<float> taps;
+    float *d_hr = nullptr, *d_G = nullptr;
+    float2 *d_T = nullptr;
+    void *d_tail[2] = { nullptr, nullptr };
+    // outputs [a.m0, a.m1) of [tail | chunk] on stream s: K0 (frontend.cpp) or K0r (resample.cpp)
+    int (*launch)(irdm_frontend *fe, const irdm::FrontendArgs &a, hipStream_t s) = nullptr;
+    // K0r: the launch geometry and the phase blocks' descriptors (d_G holds their tap rows)
+    irdm::ResampleGeom geom{};
+    int *d_desc = nullptr;
+    // stream state (irdm_frontend_reset assigns a fresh one)
+    struct State {
+        int cur = 0;                // which of d_tail holds the carried tail
+        long long n_tail = 0;
+        uint64_t total = 0, n_out = 0;
+        bool finished = false;
+        // the feeder: outputs written but not fed yet lie at base[0 .. pend)
+        float2 *base = nullptr;
+        size_t room = 0, pend = 0;
+    } st;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_in = nullptr, ev_caller = nullptr;
+    unsigned long long *d_kclk = nullptr;
+    float2 *d_scratch = nullptr;
+    void *d_stage = nullptr;
+    size_t stage_bytes = 0;
+};
+
+namespace irdmh {
+void fe_free(irdm_frontend *fe);
+// what both modes allocate: the rotation table, the kernel clock record, the two tail buffers (tail_samples each, 8 bytes
+// per sample), the stream in K1's priority class and the events.  fe->cfg.device is current.  false: allocation failed.
+bool fe_alloc_common(irdm_frontend *fe, size_t tail_samples);
+}  // namespace irdmh

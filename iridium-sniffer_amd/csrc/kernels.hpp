@@ -1,6 +1,7 @@
 // kernels.hpp -- host-callable launchers of the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <vector>
 #include "types.hpp"
 
 namespace irdm {
@@ -213,5 +214,28 @@ int launch_frontend(int D, const FrontendArgs &a, const float *hr, const float *
                     unsigned long long *kclk);
 int launch_frontend_tail(const void *tail, long long n_tail, const void *in, long long n_in, long long from, int n_new, int bps,
                          void *out, hipStream_t stream);
+
+// resample.hip (K0r): the front end's rational mode, out = in * L / M.  The geometry of a launch and the host-laid tables
+// (resample_plan): per phase block a descriptor of kRsDesc ints and the rows of its tap table (kRsRow floats per step).
+constexpr int kRsDesc = 32, kRsRow = 8;
+struct ResampleGeom {
+    int L, M;                    // the ratio in lowest terms
+    int R;                       // outputs (consecutive phases) per lane: 5 .. 8
+    int nper;                    // periods (of L outputs, M inputs) per tile
+    int nblk;                    // phase blocks per period, ceil(L / R)
+    int lo_min;                  // first input of a period's first output, relative to the period's p M (<= 0)
+    int cnt;                     // staged samples per tile
+    int pad;                     // 1: a row of M staged samples is followed by a pad sample (M even)
+    unsigned magic;              // floor(2^32 / M) + 1: g / M = (g * magic) >> 32 for every staged index g
+    int out_off;                 // LDS index (in samples) of the tile's outputs
+    long long p_first;           // the launch's first period, floor(m0 / L) (set by launch_resample)
+};
+// taps: the prototype P (ntaps, odd).  Fills the geometry, the descriptors and the tap rows; false when the ratio does not
+// fit the kernel.
+bool resample_plan(int L, int M, const float *taps, int ntaps, ResampleGeom *g, std::vector<int> *desc, std::vector<float> *G);
+size_t resample_lds_bytes(const ResampleGeom &g);
+// outputs [a.m0, a.m1) of the rational front end into a.out (a.ntaps = the prototype's length)
+int launch_resample(const ResampleGeom &g, const FrontendArgs &a, const int *desc, const float *G, const float2 *T,
+                    hipStream_t stream, unsigned long long *kclk);
 
 }  // namespace irdm

@@ -1,0 +1,128 @@
+// resample.cpp -- irdm_frontend_create_rational: the front end's rational mode (K0r, resample.hip), output rate = input rate
+// * L / M.  It makes the same object irdm_frontend_create makes (frontend_obj.hpp); everything behind creation is
+// frontend.cpp's.  An integer ratio 2 .. 16 is handed to irdm_frontend_create: K0, bit for bit.
+//
+// The prototype P is the pipeline's own low-pass design at the rate L * in_rate with gain L, cut-off 0.5 f_min and
+// transition parameter 0.09 f_min, f_min = min(in_rate, out_rate).  design_lpf takes the rate as a float: L * in_rate is
+// formed exactly (64-bit) and converted with one rounding to nearest.  For every ratio the limits admit from a capture rate
+// that is a multiple of 2^k Hz with L * in_rate / 2^k below 2^24 the conversion is exact -- all the rates the README names
+// (tests/test_resample_emul.py asserts them).
+#include "frontend_obj.hpp"
+
+namespace irdmh {
+
+static int fe_launch_k0r(irdm_frontend *fe, const FrontendArgs &a, hipStream_t s)
+{
+    return launch_resample(fe->geom, a, fe->d_desc, fe->d_G, fe->d_T, s, fe->d_kclk);
+}
+
+static long long gcd_ll(long long a, long long b)
+{
+    while (b) {
+        const long long t = a % b;
+        a = b;
+        b = t;
+    }
+    return a;
+}
+
+// the ratio in lowest terms and the limits on it, for the create call and for callers that must refuse before they start
+// (the binary): 0 within the limits (an integer ratio 2 .. 16 included), -1 with a message otherwise.  Needs no device.
+extern "C" int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L_out, int *M_out)
+{
+    if (in_rate <= 0 || out_rate <= 0) {
+        fprintf(stderr, "irdm_hip: front end: sample rates %d -> %d\n", in_rate, out_rate);
+        return -1;
+    }
+    const long long gd = gcd_ll(in_rate, out_rate);
+    const long long L = out_rate / gd, M = in_rate / gd;
+    if (L_out) *L_out = (int)L;
+    if (M_out) *M_out = (int)M;
+    if (L > 125 || M > 768) {
+        fprintf(stderr, "irdm_hip: front end: %d -> %d samples/s is the ratio %lld/%lld; L <= 125 and M <= 768 are built\n",
+                in_rate, out_rate, L, M);
+        return -1;
+    }
+    if (L == M || 25 * M < 24 * L || M > 16 * L) {
+        fprintf(stderr, "irdm_hip: front end: %d -> %d samples/s (ratio %lld/%lld): M / L must lie in 24/25 .. 16 and differ from 1\n",
+                in_rate, out_rate, L, M);
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_rational_config_t *cfg)
+{
+    if (!cfg) return nullptr;
+    int Li = 0, Mi = 0;
+    if (irdm_frontend_rational_ratio(cfg->in_rate, cfg->out_rate, &Li, &Mi) != 0) return nullptr;
+    const long long L = Li, M = Mi;
+    if (L == 1 && M >= 2 && M <= 16) {
+        irdm_frontend_config_t ic;
+        memset(&ic, 0, sizeof(ic));
+        ic.device = cfg->device;
+        ic.in_rate = cfg->in_rate;
+        ic.in_format = cfg->in_format;
+        ic.decim = (int)M;
+        ic.shift_hz = cfg->shift_hz;
+        return irdm_frontend_create(&ic);
+    }
+    if (cfg->in_format < IRDM_FMT_CI8 || cfg->in_format > IRDM_FMT_SC16Q11) {
+        fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
+        return nullptr;
+    }
+    int fft = 0;
+    if (!rate_supported(cfg->out_rate, &fft)) {
+        fprintf(stderr, "irdm_hip: front end: output rate %d (%d * %lld / %lld) is not one the pipeline takes (fft_size %d)\n",
+                cfg->out_rate, cfg->in_rate, L, M, fft);
+        return nullptr;
+    }
+    const long long q = llround(cfg->shift_hz * 65536.0 / (double)cfg->in_rate);
+    if (q < -32768 || q > 32768) {
+        fprintf(stderr, "irdm_hip: front end: shift %.1f Hz is beyond half the capture rate %d\n", cfg->shift_hz, cfg->in_rate);
+        return nullptr;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
+        fprintf(stderr, "irdm_hip: no HIP device -- there is no CPU fallback in this library\n");
+        return nullptr;
+    }
+    if (hipSetDevice(cfg->device) != hipSuccess) return nullptr;
+    irdm_frontend *fe = new (std::nothrow) irdm_frontend();
+    if (!fe) return nullptr;
+    memset(&fe->cfg, 0, sizeof(fe->cfg));
+    fe->cfg.device = cfg->device;
+    fe->cfg.in_rate = cfg->in_rate;
+    fe->cfg.in_format = cfg->in_format;
+    fe->cfg.shift_hz = cfg->shift_hz;
+    fe->D = 0;
+    fe->L = (int)L;
+    fe->M = (int)M;
+    fe->launch = fe_launch_k0r;
+    fe->fmt = cfg->in_format;
+    fe->bps = fe->fmt == IRDM_FMT_CF32 ? 8 : (fe->fmt == IRDM_FMT_CI8 ? 2 : 4);
+    fe->out_rate = cfg->out_rate;
+    fe->q = q;
+    const float f_min = (float)std::min(cfg->in_rate, cfg->out_rate);
+    fe->taps = design_lpf((float)L, (float)(L * (long long)cfg->in_rate), 0.5f * f_min, 0.09f * f_min);
+    fe->ntaps = (int)fe->taps.size();
+    fe->c = (fe->ntaps - 1) / 2;
+    std::vector<int> desc;
+    std::vector<float> G;
+    if (!resample_plan(fe->L, fe->M, fe->taps.data(), fe->ntaps, &fe->geom, &desc, &G)) {
+        fprintf(stderr, "irdm_hip: front end: %d taps at the ratio %lld/%lld do not fit the kernel\n", fe->ntaps, L, M);
+        delete fe;
+        return nullptr;
+    }
+    bool ok = (fe->d_desc = dev_upload(desc.data(), desc.size())) != nullptr;
+    ok = ok && (fe->d_G = dev_upload(G.data(), G.size())) != nullptr;
+    ok = ok && fe_alloc_common(fe, (size_t)(fe->ntaps / fe->L + fe->M + 16));
+    if (!ok) {
+        fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
+        fe_free(fe);
+        return nullptr;
+    }
+    return fe;
+}
+
+}  // namespace irdmh

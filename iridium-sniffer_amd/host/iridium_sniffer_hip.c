@@ -5,7 +5,7 @@
  *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
- *                         [--band-center HZ --decimate D]
+ *                         [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]]
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
@@ -20,6 +20,11 @@
  * around HZ is shifted to the centre, low-passed and decimated by D (2 .. 16) on the GPU in front of the detector
  * (irdm_frontend_*): a 50 MS/s capture with --decimate 5 runs as a 10 MS/s stream centred at HZ (at the nearest multiple
  * of RATE / 65536 from -c, printed with -v).  --chunk stays in samples of the decimated stream.
+ * --resample-to HZ: the same front end in its rational mode (irdm_frontend_create_rational) -- the capture, described by -r
+ * and -c, is resampled on the GPU to HZ = RATE * L / M (L <= 125, M <= 768, 24/25 <= M / L <= 16) in front of the detector:
+ * for captures whose rate is no multiple of 250 kHz (2.4 MS/s, 11.2 MS/s, 61.44 MS/s ...), which the demodulator cannot
+ * follow to the end of a frame.  --band-center is optional with it (without: no shift); --decimate, --gpus N > 1 and HZ =
+ * RATE are refused.  --chunk counts samples of the resampled stream.
  * Several recordings in one run: -f more than once and / or --files-from LIST (one "PATH" or "PATH START_SEC[.NNNNNNNNN]"
  * per line).  They go, in the order given, through ONE context, one front end and one pair of pinned buffers, with
  * irdm_reset / irdm_frontend_reset between them: what is paid once per process -- the HIP runtime, the context's device
@@ -359,6 +364,8 @@ int main(int argc, char **argv)
     double position_height = 0;
     int decimate = 0, band_given = 0;      /* --band-center / --decimate: the band-select front end */
     double band_center = 0;
+    int resample_to = 0;                   /* --resample-to: the front end's rational mode */
+    int rs_l = 0, rs_m = 0;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -409,6 +416,10 @@ int main(int argc, char **argv)
         }
         else if (!strcmp(a, "--band-center")) { band_center = atof(NEXT()); band_given = 1; }
         else if (!strcmp(a, "--decimate")) decimate = atoi(NEXT());
+        else if (!strcmp(a, "--resample-to")) {
+            resample_to = atoi(NEXT());
+            if (resample_to <= 0) { fprintf(stderr, "--resample-to: a rate in Hz\n"); return 2; }
+        }
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -423,12 +434,33 @@ int main(int argc, char **argv)
         }
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]\n", argv[0]);
         return 2;
     }
-    if (band_given != (decimate != 0)) {
+    if (resample_to && decimate) {
+        fprintf(stderr, "--resample-to and --decimate: one or the other (--resample-to takes integer ratios as well)\n");
+        return 2;
+    }
+    if (!resample_to && band_given != (decimate != 0)) {
         fprintf(stderr, "--band-center and --decimate go together\n");
         return 2;
+    }
+    if (resample_to) {
+        if (gpus > 1) {
+            fprintf(stderr, "--resample-to: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if ((double)(int)rate != rate) {
+            fprintf(stderr, "--resample-to: -r %.3f is no whole number of samples per second\n", rate);
+            return 2;
+        }
+        if ((int)rate == resample_to) {
+            fprintf(stderr, "--resample-to %d: that is the capture's rate; leave the flag out\n", resample_to);
+            return 2;
+        }
+        /* the library's own check of the ratio (its message), before anything is started */
+        if (irdm_frontend_rational_ratio((int)rate, resample_to, &rs_l, &rs_m) != 0) return 2;
+        gpus = 0;
     }
     if (decimate && gpus > 1) {
         fprintf(stderr, "--band-center / --decimate: one GPU only (--gpus %d)\n", gpus);
@@ -475,6 +507,18 @@ int main(int argc, char **argv)
         fe = irdm_frontend_create(&fc);
         if (!fe) {
             fprintf(stderr, "irdm_frontend_create failed (no MI355X / bad parameters)\n");
+            return 1;
+        }
+    } else if (resample_to) {
+        irdm_frontend_rational_config_t fc;
+        memset(&fc, 0, sizeof(fc));
+        fc.in_rate = (int)rate;
+        fc.in_format = fmt;
+        fc.out_rate = resample_to;
+        fc.shift_hz = band_given ? band_center - freq : 0.0;
+        fe = irdm_frontend_create_rational(&fc);
+        if (!fe) {
+            fprintf(stderr, "irdm_frontend_create_rational failed (no MI355X / bad parameters)\n");
             return 1;
         }
     }
@@ -537,8 +581,9 @@ int main(int argc, char **argv)
     }
     g_save_dir = save_dir;
     /* a group is fed a super-step at a time: one chunk per member */
-    /* (behind a front end the reader's chunk is D pipeline chunks of capture samples) */
-    const size_t step = chunk * (size_t)(gpus > 0 ? gpus : 1) * (size_t)(fe ? decimate : 1);
+    /* (behind a front end the reader's chunk is D -- or M / L -- pipeline chunks of capture samples) */
+    const size_t step = resample_to ? (chunk * (size_t)rs_m + (size_t)rs_l - 1) / (size_t)rs_l
+                                    : chunk * (size_t)(gpus > 0 ? gpus : 1) * (size_t)(fe ? decimate : 1);
     if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { perror(out_dir); return 1; }
 
     /* Two pinned read buffers and a reader thread per recording (the reference's spewer thread, main.c:223-284): the file
@@ -603,7 +648,11 @@ int main(int argc, char **argv)
         }
         if (verbose && fi == 0) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
                              gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");
-        if (verbose && fi == 0 && fe)
+        if (verbose && fi == 0 && fe && resample_to)
+            fprintf(stderr, "front end: %d -> %d samples/s (%d/%d), %d taps, shift %.3f Hz applied (%.3f asked), centre %.3f Hz\n", (int)rate,
+                    irdm_frontend_out_rate(fe), rs_l, rs_m, irdm_frontend_ntaps(fe), irdm_frontend_applied_shift_hz(fe),
+                    band_given ? band_center - freq : 0.0, c.center_frequency);
+        else if (verbose && fi == 0 && fe)
         fprintf(stderr, "front end: %d -> %d samples/s, %d taps, shift %.3f Hz applied (%.3f asked), centre %.3f Hz\n", (int)rate,
                     irdm_frontend_out_rate(fe), irdm_frontend_ntaps(fe), irdm_frontend_applied_shift_hz(fe), band_center - freq,
                     c.center_frequency);

@@ -134,6 +134,12 @@ class FrontendConfig(C.Structure):
                 ("shift_hz", C.c_double)]
 
 
+class FrontendRationalConfig(C.Structure):
+    """irdm_frontend_rational_config_t: the front end's rational mode (csrc/resample.cpp)"""
+    _fields_ = [("device", C.c_int), ("in_rate", C.c_int), ("in_format", C.c_int), ("out_rate", C.c_int),
+                ("shift_hz", C.c_double)]
+
+
 ACARS_LINE_MAX = 8192
 RAW_LINE_MAX = 1280
 _lib = None
@@ -323,6 +329,11 @@ def lib():
             if hasattr(L, "irdm_frontend_reset"):
                 L.irdm_frontend_reset.argtypes = [C.c_void_p]
             L.irdm_frontend_kernel_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
+            if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
+                L.irdm_frontend_create_rational.restype = C.c_void_p
+                L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
+                L.irdm_frontend_ratio.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+                L.irdm_frontend_rational_ratio.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -742,16 +753,34 @@ class Frontend:
     """irdm_frontend_*: band select in front of a Pipeline -- shift by shift_hz, low-pass, decimate by decim.  The pipeline
     behind it is a cf32 context at out_rate, centred at the capture centre + applied_shift_hz."""
 
-    def __init__(self, in_rate, fmt, decim, shift_hz=0.0, device=0):
+    def __init__(self, in_rate, fmt, decim, shift_hz=0.0, device=0, out_rate=None):
         self.L = lib()
-        self.cfg = FrontendConfig(device, int(in_rate), fmt, int(decim), float(shift_hz))
-        self.h = self.L.irdm_frontend_create(C.byref(self.cfg))
+        if out_rate is None:
+            self.cfg = FrontendConfig(device, int(in_rate), fmt, int(decim), float(shift_hz))
+            self.h = self.L.irdm_frontend_create(C.byref(self.cfg))
+        else:
+            self.cfg = FrontendRationalConfig(device, int(in_rate), fmt, int(out_rate), float(shift_hz))
+            self.h = self.L.irdm_frontend_create_rational(C.byref(self.cfg))
         if not self.h:
-            raise RuntimeError("irdm_frontend_create failed (no GPU, or bad config)")
+            raise RuntimeError("irdm_frontend_create%s failed (no GPU, or bad config)" % ("" if out_rate is None else "_rational"))
         self.fmt = fmt
         self.out_rate = self.L.irdm_frontend_out_rate(self.h)
         self.applied_shift_hz = self.L.irdm_frontend_applied_shift_hz(self.h)
         self.ntaps = self.L.irdm_frontend_ntaps(self.h)
+
+    @classmethod
+    def rational(cls, in_rate, fmt, out_rate, shift_hz=0.0, device=0):
+        """irdm_frontend_create_rational: resample to out_rate = in_rate * L / M (an integer ratio 2 .. 16 gives the
+        integer front end)"""
+        return cls(in_rate, fmt, None, shift_hz, device, out_rate=out_rate)
+
+    @property
+    def ratio(self):
+        """(L, M): output rate = capture rate * L / M; (1, D) for the integer front end"""
+        l, m = C.c_int(0), C.c_int(0)
+        if self.L.irdm_frontend_ratio(self.h, C.byref(l), C.byref(m)) != 0:
+            raise RuntimeError("irdm_frontend_ratio failed")
+        return l.value, m.value
 
     def taps(self):
         out = np.empty(self.ntaps, np.float32)
