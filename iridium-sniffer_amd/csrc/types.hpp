@@ -5,7 +5,9 @@
 namespace irdm {
 
 constexpr int kHistory = 512;            // iridium.h:46
-constexpr int kMaxActive = 1024;         // max_bursts (<= 240) + bursts one frame can add before the squelch check
+constexpr int kMaxActive = 1024;         // max_bursts + bursts one frame can add before the squelch check (n / width) + 8:
+                                         // rate_supported() in create.cpp refuses a rate that needs more, so max_bursts
+                                         // <= 452 (22.6 MHz: 452 + 564 + 8 = 1024)
 constexpr int kScanThreads = 1024;
 constexpr int kFirTaps = 801;            // lpf_taps(.., 1e7, 1e5, 5e4), burst_downmix.c:251-261
 constexpr int kRotSeg = 16;              // rotator checkpoint spacing (samples)

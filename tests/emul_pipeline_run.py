@@ -1,7 +1,7 @@
 """TEST INFRASTRUCTURE: runs the product end to end on the CPU emulation (tests/_build/libirdm_emul.so, built by
 tests/emul_build.py from the product's own sources) and compares every record with the oracle, exactly as the -m gpu
 parity tests do on the real library (tests/parity.py).  Started by tests/test_pipeline_emul.py in a process of its own with
-IRDM_LIB pointing at the emulated build.  Usage: python emul_pipeline_run.py <case>"""
+IRDM_LIB pointing at the emulated build.  Usage: python emul_pipeline_run.py <case> [sample rates of the rate cases]"""
 import json
 import os
 import sys
@@ -15,6 +15,7 @@ import numpy as np      # noqa: E402
 import irdm             # noqa: E402
 import orc              # noqa: E402
 import parity           # noqa: E402
+import rates            # noqa: E402
 import scenes           # noqa: E402
 import siggen           # noqa: E402
 
@@ -168,6 +169,51 @@ def main():
         got = parity.run_group(iq[:cut], fs, n_gpus=2, chunk=chunk, staged_ahead=True)
         res["two_members_ragged_end"] = parity.compare(got, ref_cut)
         assert got["stats"]["chunks"] == 4 and got["stats"]["hops"] == 4, got["stats"]
+    elif case == "rates":
+        # every class of sample rate irdm_create accepts (tests/rates.py): FFT sizes 1024 .. 16384, burst widths 28 .. 56 bins,
+        # the any-M decimator at M = 3 .. 80 (odd M, M that does not divide 16), the dense scan below 2048 points, the band
+        # scan with 128- and 256-bin bands, and from 16 MHz the wave walk of scan_fast.hip as the default scan.  Each stream
+        # whole and in chunks at pipeline_depth 2 fed in place with look-ahead; the scan the rules name must have run.
+        for fs in [int(a) for a in sys.argv[2:]] or rates.EMUL_RATES:
+            d = rates.describe(fs)
+            iq = rates.stream(fs)
+            ref = orc.run_stream(iq, fs)
+            got = parity.run_gpu(iq, fs)
+            s = parity.compare(got, ref)
+            rates.check_counts(s)
+            rates.check_scan(got["stats"], fs)
+            parts = 3 + (fs // 1000) % 3
+            got2 = parity.run_gpu(iq, fs, chunks=rates.chunks_of(len(iq), parts), depth=2, feed="ingest_lookahead")
+            s2 = parity.compare(got2, ref)
+            rates.check_counts(s2)
+            rates.check_scan(got2["stats"], fs)
+            assert s2 == s
+            res[str(fs)] = dict(s, n=d["n"], scan=d["scan"], decim=d["decim"], chunks=parts,
+                                band_chunks=got2["stats"]["band_chunks"], scan_fast_chunks=got2["stats"]["scan_fast_chunks"])
+    elif case == "rates_random":
+        # randomised emitters (scenes.random_scene) at rates of the band scan's two band widths and of the wave walk, in
+        # chunks at pipeline_depth 1
+        secs = {2_500_000: 1.0, 6_250_000: 1.3, 12_500_000: 1.2, 16_000_000: 1.0}
+        for fs in [int(a) for a in sys.argv[2:]] or sorted(secs):
+            _, iq = scenes.random_scene(fs // 100_000, fs=fs, secs=secs[fs])
+            ref = orc.run_stream(iq, fs)
+            got = parity.run_gpu(iq, fs, chunks=rates.chunks_of(len(iq), 4), depth=1)
+            s = parity.compare(got, ref)
+            rates.check_counts(s, min_bursts=10)
+            rates.check_scan(got["stats"], fs)
+            res[str(fs)] = dict(s, scan=rates.describe(fs)["scan"])
+    elif case == "scan_forms":
+        # the wave walk of scan_fast.hip on one workgroup (scan_mode 2) and with updater workgroups (3) at 2 MHz, where the
+        # band scan is the default
+        fs = 2_000_000
+        iq = scene(fs, 1.3, 7, 3)
+        ref = orc.run_stream(iq, fs)
+        for mode in (2, 3):
+            got = parity.run_gpu(iq, fs, chunks=chunks_of(len(iq), 3), depth=1, scan_mode=mode)
+            s = parity.compare(got, ref)
+            rates.check_counts(s)
+            rates.check_scan(got["stats"], fs, scan="wave")
+            res["scan_mode_%d" % mode] = s
     else:
         raise SystemExit("unknown case")
     print("RESULT " + json.dumps(res))

@@ -228,28 +228,45 @@ SCENE = dict(fs_in=50_000_000, D=5, shift_hz=11_000_000.0, secs=0.75, seed=50, n
              inband_channels=(-90, -55, -20, 15, 50, 85),          # +-3.75 MHz: inside 0.42 fs_out of the band centre
              outband_hz=(6.5e6, -7.0e6, 8.2e6))                    # 0.65 / 0.70 / 0.82 fs_out from the band centre
 
+# ... and two whose output rate is not 10 MHz (optional keys: fmt, default ci8; start0 / step, the first in-band burst's
+# start and the spacing in seconds, default 0.45 / 0.045 -- the first burst lies behind the 530 priming frames AT THE OUTPUT
+# RATE: 0.424 s at 10.24 MHz, 0.695 s at 12.5 MHz).  In-band channels within 0.42 fs_out of the band centre, the strong
+# out-of-band carriers 0.65 / 0.70 / 0.82 fs_out from it.
+SCENE_61M44_D6 = dict(fs_in=61_440_000, D=6, shift_hz=9_000_000.0, secs=0.70, seed=61, n_inband=7, fmt=irdm.FMT_CI16,
+                      start0=0.44, step=0.035,
+                      inband_channels=(-100, -65, -30, 5, 40, 75, 100),       # +-4.17 MHz of 4.30 MHz
+                      outband_hz=(6.656e6, -7.168e6, 8.397e6))
+SCENE_50M_D4 = dict(fs_in=50_000_000, D=4, shift_hz=-8_000_000.0, secs=0.98, seed=54, n_inband=6, fmt=irdm.FMT_CI8,
+                    start0=0.71, step=0.04,
+                    inband_channels=(-120, -75, -30, 15, 60, 120),            # +-5.0 MHz of 5.25 MHz
+                    outband_hz=(8.125e6, -8.75e6, 10.25e6))
 
-def wideband_scene():
-    """(ci8 capture, expected hard bits per in-band burst in time order, q).  Every strong out-of-band burst lies on top
-    of an in-band one in time and would alias into the band without the filter."""
+
+def wideband_scene(scene=None):
+    """(capture in the scene's format, expected hard bits per in-band burst in time order, q).  Every strong out-of-band
+    burst lies on top of an in-band one in time and would alias into the band without the filter.  Without a scene:
+    SCENE, the same bytes as ever (tests/test_frontend_emul.py pins their digest)."""
     import siggen
-    s = SCENE
+    s = SCENE if scene is None else scene
     fs = s["fs_in"]
     n = int(s["secs"] * fs) // 32768 * 32768
     q = quantise(s["shift_hz"], fs)
     applied = q * fs / 65536.0
     rng = np.random.default_rng(s["seed"])
+    start0, step = s.get("start0", 0.45), s.get("step", 0.045)
     bursts, expect = [], []
     for k, ch in enumerate(s["inband_channels"]):
         payload = list(rng.integers(0, 4, 150))
-        start = int((0.45 + 0.045 * k) * fs)
+        start = int((start0 + step * k) * fs)
         bursts.append(dict(start=start, freq_hz=applied + siggen.channel_freq(ch), payload=payload, amp=0.05))
         expect.append(siggen.quadrants_to_bits(siggen.frame_quadrants(payload)[16:]))
     for k, off in enumerate(s["outband_hz"]):
         bursts.append(dict(start=bursts[2 * k]["start"] + 5000, freq_hz=applied + off + 1234.0,
                            payload=list(rng.integers(0, 4, 150)), amp=0.2))
     iq, _ = siggen.make_stream(fs, n, bursts, seed=s["seed"])
-    return siggen.to_ci8(iq), expect, q
+    fmt = s.get("fmt", irdm.FMT_CI8)
+    assert fmt in (irdm.FMT_CI8, irdm.FMT_CI16)
+    return (siggen.to_ci8(iq) if fmt == irdm.FMT_CI8 else siggen.to_ci16(iq)), expect, q
 
 
 def check_scene_demods(demods, expect):

@@ -323,6 +323,10 @@ inline int update_dpp(int old, int src, int ctrl, int, int, bool)
         if ((l & 15) >= n) r = (int)(uint32_t)m.box[base + l - n];
     } else if (ctrl == 0x138) {                           // wave_shr:1
         if (l >= 1) r = (int)(uint32_t)m.box[base + l - 1];
+    } else if (ctrl == 0x142) {                           // row_bcast:15: lane 15 of each row to every lane of the next row
+        if (l >= 16) r = (int)(uint32_t)m.box[base + (l & ~15) - 1];
+    } else if (ctrl == 0x143) {                           // row_bcast:31: lane 31 to every lane of rows 2 and 3
+        if (l >= 32) r = (int)(uint32_t)m.box[base + 31];
     } else {
         fprintf(stderr, "hip_emul: DPP control 0x%x is not emulated\n", ctrl);
         abort();

@@ -4,6 +4,7 @@ C restatement of the arithmetic contract (tests/frontend_model.c) bit for bit; t
 of a float64 evaluation; the taps meet the stated response; the feeder composes with the pipeline."""
 import ctypes as C
 import json
+import math
 import os
 import re
 import subprocess
@@ -98,11 +99,39 @@ def test_wideband_scene_model_then_oracle():
     """Scene selection for the GPU signal test (tests/test_gpu_frontend.py), on the CPU: a 50 MHz ci8 capture, the band 11 MHz
     above its centre, D = 5; six in-band bursts and three strong ones 0.65-0.82 fs_out from the band centre.  Model ->
     oracle at 10 MHz gives all six payloads and nothing from out of band."""
+    import hashlib
     import orc
     x, expect, q = fm.wideband_scene()
     s = fm.SCENE
+    # the default capture is the bytes it was before wideband_scene() took a scene
+    assert (q, len(x)) == (14418, 74973184)
+    assert hashlib.sha256(x.tobytes()).hexdigest() == "b5d430bcef80c6759616fe96bbab86f4b35b9811024a426b4098ced89802d623"
+    assert hashlib.sha256(json.dumps(expect).encode()).hexdigest() == "ee12d86885208dc5d47f31e4011c902c54c7c688237a823dad41599251b5c936"
     taps = fm.design_taps(s["fs_in"], s["D"])
     y = fm.run(x, irdm.FMT_CI8, s["D"], q, taps)
     ref = orc.run_stream(y, s["fs_in"] // s["D"], center_frequency=1622000000.0 + q * s["fs_in"] / 65536.0)
     assert len(expect) == s["n_inband"] == 6
     fm.check_scene_demods(ref.demods, expect)
+
+
+@pytest.mark.parametrize("scene,out_rate", [(fm.SCENE_61M44_D6, 10_240_000), (fm.SCENE_50M_D4, 12_500_000)],
+                         ids=["61.44M_by_6", "50M_by_4"])
+def test_wideband_scenes_at_other_output_rates_model_then_oracle(scene, out_rate):
+    """Scene selection for tests/test_gpu_rates.py, on the CPU: 61.44 MS/s ci16 by 6 -> 10.24 MHz and 50 MS/s ci8 by 4 ->
+    12.5 MHz.  Model -> oracle gives at least 5 frames at both; at 12.5 MHz (a multiple of 250 kHz) every in-band payload
+    whole and nothing from out of band.  (At 10.24 MHz the oracle decodes every payload of this scene too, but the margin
+    of a decimation by 40.96 rounded to 41 is not measured, so the GPU test asserts no payloads there.)"""
+    import orc
+    s = scene
+    assert s["fs_in"] // s["D"] == out_rate and s["fs_in"] % s["D"] == 0
+    assert max(abs(c) for c in s["inband_channels"]) * (1e6 / 24.0) + 1234.0 <= 0.42 * out_rate
+    assert min(abs(f) for f in s["outband_hz"]) >= 0.65 * out_rate
+    assert s["start0"] * out_rate > 530 * (1 << int(round(math.log2(out_rate / 1000.0))))       # behind the priming frames
+    x, expect, q = fm.wideband_scene(s)
+    taps = fm.design_taps(s["fs_in"], s["D"])
+    y = fm.run(x, s["fmt"], s["D"], q, taps)
+    ref = orc.run_stream(y, out_rate, center_frequency=1622000000.0 + q * s["fs_in"] / 65536.0)
+    assert len(expect) == s["n_inband"]
+    assert sum(1 for f in ref.frames if f.drop_reason == 0) >= 5 and len(ref.demods) >= 5
+    if out_rate % 250_000 == 0:
+        fm.check_scene_demods(ref.demods, expect)

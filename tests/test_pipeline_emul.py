@@ -12,6 +12,7 @@ import sys
 import pytest
 
 import emul_build
+import rates
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -21,12 +22,12 @@ def emul_lib():
     return emul_build.build()
 
 
-def run_case(lib, case, timeout=900, order=None):
+def run_case(lib, case, timeout=900, order=None, args=()):
     env = dict(os.environ, IRDM_LIB=lib)
     if order:
         env["HIP_EMUL_ORDER"] = order
-    p = subprocess.run([sys.executable, os.path.join(HERE, "emul_pipeline_run.py"), case], env=env, capture_output=True,
-                       text=True, timeout=timeout)
+    p = subprocess.run([sys.executable, os.path.join(HERE, "emul_pipeline_run.py"), case] + [str(a) for a in args], env=env,
+                       capture_output=True, text=True, timeout=timeout)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("RESULT ")][-1]
     return json.loads(line[7:])
@@ -88,3 +89,41 @@ def test_group_of_members_equals_one_context(emul_lib):
                         "one_member", "two_members_ragged_end"}
     for name, s in res.items():
         assert s["bursts"] >= 36 and s["demods"] >= 30, (name, s)
+
+
+@pytest.mark.parametrize("fs", rates.EMUL_RATES)
+def test_every_class_of_sample_rate(emul_lib, fs):
+    """A context at each class of rate irdm_create accepts, not only 1 / 2 / 4 / 10 / 12 MHz: the front ends' output rates
+    (12.5, 10.24, 6.25, 5 MHz), the lowest rate, FFT sizes 1024 .. 16384, the any-M decimator at M = 3 .. 80, and from 16 MHz
+    the wave walk of scan_fast.hip as the DEFAULT scan (the band scan declines 128 bands).  Six bursts behind the priming
+    frames, whole and in 3-5 chunks at pipeline_depth 2 fed in place with look-ahead; the runner asserts parity with the
+    oracle, at least 5 bursts and 4 demodulated frames, no fallback, and that the scan the dispatch rules name ran."""
+    res = run_case(emul_lib, "rates", args=[fs])[str(fs)]
+    d = rates.describe(fs)
+    assert d["supported"] and res["n"] == d["n"] and res["scan"] == d["scan"], (res, d)
+    assert res["bursts"] >= 5 and res["demods"] >= 4 and res["frames"] >= 4, res
+    if d["scan"] == "band":
+        assert res["band_chunks"] >= 1, res
+    elif d["scan"] == "wave":
+        assert fs >= 16_000_000 and res["band_chunks"] == 0 and res["scan_fast_chunks"] >= 1, res
+    else:
+        assert d["n"] < 2048 and res["band_chunks"] == 0 and res["scan_fast_chunks"] == 0, res
+
+
+def test_random_scenes_at_other_rates(emul_lib):
+    """scenes.random_scene at 2.5, 6.25, 12.5 and 16 MHz in four chunks at pipeline_depth 1: at least 10 bursts and 4
+    demodulated frames each, the expected scan, no fallback (asserted in the runner)"""
+    res = run_case(emul_lib, "rates_random")
+    assert set(res) == {"2500000", "6250000", "12500000", "16000000"}
+    for fs, s in res.items():
+        assert s["bursts"] >= 10 and s["demods"] >= 4, (fs, s)
+    assert res["16000000"]["scan"] == "wave" and res["12500000"]["scan"] == "band"
+
+
+def test_wave_walk_forms_2mhz(emul_lib):
+    """scan_mode 2 and 3 (the wave walk on one workgroup / with updater workgroups) at 2 MHz: its wavefront reductions
+    need the DPP controls row_bcast:15 / row_bcast:31 of the emulation (tests/test_dpp_emul.py)"""
+    res = run_case(emul_lib, "scan_forms")
+    assert set(res) == {"scan_mode_2", "scan_mode_3"}
+    for name, s in res.items():
+        assert s["bursts"] >= 5 and s["demods"] >= 4, (name, s)
