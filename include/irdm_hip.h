@@ -260,6 +260,15 @@ typedef struct {
     uint32_t n_bursts, n_frames, n_demods, n_packed, n_decoded, n_ida;
 } irdm_chunk_mark_t;
 
+/* option "spectrum_frames": one row of the waterfall (irdm_poll_spectrum) */
+typedef struct {
+    uint64_t row;              /* rows of a stream counted from 0 */
+    uint64_t first_frame;      /* absolute frame the row starts at: frame f holds samples f * n_bins .. f * n_bins + n_bins - 1 */
+    uint64_t timestamp_ns;     /* of that frame's first sample: irdm_start_time_ns + sample offset at the context's rate */
+    uint32_t n_frames;         /* frames in the row: R, or fewer in the row irdm_flush closed */
+    uint32_t n_bins;           /* irdm_spectrum_bins */
+} irdm_spectrum_row_t;
+
 typedef struct irdm_pipeline irdm_pipeline_t;
 
 /* burst_detector_create + burst_downmix_create (burst_detect.c:174, burst_downmix.c:223):
@@ -382,6 +391,26 @@ typedef struct {
 int irdm_detector_stats(irdm_pipeline_t *p, irdm_detector_stats_t *out);
 
 int irdm_last_magnitudes(irdm_pipeline_t *p, float *out, size_t max_frames);
+/* Band survey (option "spectrum_frames" = R, 1 <= R <= 2^20; 0 = off, the default): the windowed, fft-shifted |X|^2 plane the
+ * detector's FFT kernel writes for every frame of every chunk, reduced on the device to a waterfall.  Row r covers the R
+ * consecutive frames r R .. r R + R - 1 of the stream, whatever chunks they came in; per bin (bin 0 is -fs/2, values are
+ * linear |X|^2, as in the plane)
+ *   mean = (sum of the row's frames) / n_frames, in fp32        peak = the largest of them.
+ * Summation order: the row's frames are taken in groups of min(R, 64), counted from the row's first frame; a group's frames
+ * are added one after the other in frame order, starting from 0, and the groups' sums one after the other in group order,
+ * starting from 0 (a last group of fewer frames likewise); then the one division.  The order depends on a frame's place in
+ * its row alone: a stream yields the same bytes however it is cut into chunks, at every pipeline_depth.  For R = 1 mean and
+ * peak are the plane itself.
+ * irdm_feed_begin enqueues the reduction behind the chunk's FFT kernel; the trailing samples of a ragged last chunk that do
+ * not fill a frame belong to no row.  irdm_flush closes the open row -- n_frames < R, the mean over those frames -- and
+ * waits for every row; should the stream go on after that, the next row starts at the next frame.
+ * irdm_poll_spectrum returns up to max finished rows in stream order -- rows whose kernels and copies have completed, after
+ * irdm_flush all of them --: hdr[i], mean[i * n_bins ..], peak[i * n_bins ..] (max * n_bins floats each).  Unpolled rows
+ * queue on the host without bound, like the records.  irdm_reset drops them and starts at row 0 again; it allocates
+ * nothing.  The open row's sums live on the device and are NOT part of irdm_export_state: a context that takes a stream
+ * over from another starts a row of its own.  Returns rows written, or -1. */
+int irdm_spectrum_bins(const irdm_pipeline_t *p);      /* bins per row = irdm_fft_size */
+int irdm_poll_spectrum(irdm_pipeline_t *p, irdm_spectrum_row_t *hdr, float *mean, float *peak, int max);
 int irdm_baseline_sum(irdm_pipeline_t *p, float *out);
 /* burst_data_t.samples of the i-th burst emitted by the LAST chunk (re-gathered) */
 int irdm_burst_samples(irdm_pipeline_t *p, int burst_in_chunk, float *out, size_t max_samples);
@@ -519,7 +548,7 @@ int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max);
 uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
 
 /* Options (irdm_set_option; every one a field of THIS context -- two contexts of a process may differ in all of them; set them
- * before the first feed unless noted; irdm_reset keeps them all).  Twenty-one keys:
+ * before the first feed unless noted; irdm_reset keeps them all).  Twenty-two keys:
  *
  *   what a caller chooses
  *   "keep_frame_samples"  0/1, default 0: irdm_poll_frames returns metadata only
@@ -538,6 +567,11 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         (both kernels run on the same frames).  "decode_frames", "decode_ida" and "keep_frame_samples"
  *                         win as for "parsed_records".
  *   "chunk_marks"         0/1, default 0: see irdm_chunk_mark_t (what a group merges its members' records with)
+ *   "spectrum_frames"     R, default 0 = off; 1 .. 2^20: mean and peak-hold spectra over rows of R frames, see irdm_poll_spectrum.
+ *                         The workspace (two planes per min(R, 64) frames of max_chunk_samples), the rows of one
+ *                         chunk and three pinned buffers of that size are allocated when the option is first set to a non-zero
+ *                         value, never before.  -1 for a value out of range, for a member of a group (and so through
+ *                         irdm_group_set_option), and between a stream's first irdm_feed_begin and irdm_reset
  *   "decode_frames" / "decode_ida"   0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
  *   "fir_order" (alias "simd_order")   default 1 = the arithmetic of the reference's AVX2 kernels, simd_avx2.c -- what

@@ -15,6 +15,11 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     if (!strcmp(key, "frame_records")) { p->frame_records = value; return 0; }
     if (!strcmp(key, "chunk_marks")) { p->chunk_marks = value ? 1 : 0; if (!value) p->st.q_marks.clear(); return 0; }
     if (!strcmp(key, "group_member")) { p->in_group = value != 0; return 0; }
+    if (!strcmp(key, "spectrum_frames")) {
+        // rows of `value` frames (0: off); not for a member of a group, and not between a stream's first feed and irdm_reset
+        if (value < 0 || value > (1 << 20) || p->in_group || p->st.begin_no != 0) return -1;
+        return spectrum_configure(p, value);
+    }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
     if (!strcmp(key, "detect_only")) { p->detect_only = value; return 0; }

@@ -64,6 +64,12 @@ void pipeline_free(irdm_pipeline *p)
         if (f.ev_copy) (void)hipEventDestroy(f.ev_copy);
     }
     if (p->hp_gate) (void)hipHostFree(p->hp_gate);
+    for (void *q : { (void *)p->d_spec_carry, (void *)p->d_spec_ws, (void *)p->d_spec_out })
+        if (q) (void)hipFree(q);
+    for (auto &h : p->hp_spec)
+        if (h) (void)hipHostFree(h);
+    for (auto &e : p->ev_spec)
+        if (e) (void)hipEventDestroy(e);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);
     for (float2 *q : p->rot_retired) (void)hipFree(q);
     for (float2 *q : p->scratch_retired) (void)hipFree(q);

@@ -990,4 +990,154 @@ int launch_zero_regions(const ZeroRegions &z, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---------------------------------------------------------------------------
+// KS: mean and peak-hold spectra of K1's plane (option "spectrum_frames", include/irdm_hip.h).  Row rho of the stream
+// covers R consecutive frames; within a row the frames are summed in GROUPS of `grp` frames counted from the row's first
+// frame: a group's frames one after the other, the groups' sums one after the other.  Both orders are functions of a
+// frame's place in its row, never of where a chunk ends: the open row's sum of whole groups, the open group's sum and
+// the row's maximum are carried from chunk to chunk (SpectrumCarry, three planes of n floats), and a group a chunk
+// boundary cuts is continued from the carried sum with the very additions the uncut group would take.
+//
+// The plane is read once, memory-bound, by spectrum_partial_kernel: a workgroup takes one CELL -- the part of one group
+// that lies in this chunk -- of 1024 bins, a lane four consecutive bins with 16-byte non-temporal loads, eight frames
+// in flight; the cell's sum and maximum go to a workspace of two planes per cell (1/32 of the chunk's plane each at
+// grp = 64: 8192 frames of 8192 bins in groups of 64 are 1024 workgroups).  spectrum_rows_kernel then walks the cells
+// of one row per workgroup and writes the rows this chunk completes, or the carry of the row it leaves open; the
+// carry is double-buffered (in / out) because its reader and its writer are different workgroups of one launch.
+// No float atomics anywhere: they would make the order a matter of timing.
+//
+// Places are counted from the first frame of the row open at the chunk's start: the chunk's frame j stands at
+// x = fill + j (fill < R frames of that row came with earlier chunks), row rho = x / R, group g = (x % R) / grp.
+// ---------------------------------------------------------------------------
+struct SpectrumGeom {
+    int n, frames, R, grp, fill;
+    __host__ __device__ int gpr() const { return (R + grp - 1) / grp; }                     // groups per row
+    __host__ __device__ int cell_of(int x) const { return (x / R) * gpr() + (x % R) / grp; }
+    __host__ __device__ int cells() const { return frames > 0 ? cell_of(fill + frames - 1) - cell_of(fill) + 1 : 0; }
+    __host__ __device__ int rows_touched() const { return (fill + frames) / R + 1; }        // the last one stays open (it may be empty)
+    // the places [xa, xb) of cell c that lie in this chunk; end: where the whole group ends
+    __host__ __device__ void cell_range(int c, int &xa, int &xb, int &end) const
+    {
+        const int row = c / gpr(), g = c % gpr();
+        const int begin = row * R + g * grp;
+        end = begin + grp < (row + 1) * R ? begin + grp : (row + 1) * R;
+        xa = begin > fill ? begin : fill;
+        xb = end < fill + frames ? end : fill + frames;
+    }
+};
+
+__device__ __forceinline__ v4f spec_load4(const float *p) { return __builtin_nontemporal_load(reinterpret_cast<const v4f *>(p)); }
+
+__global__ __launch_bounds__(256) void spectrum_partial_kernel(SpectrumGeom G, const float *__restrict__ mag,
+                                                               const float *__restrict__ carry_grp,
+                                                               float *__restrict__ ws_sum, float *__restrict__ ws_peak)
+{
+    const int s = (int)blockIdx.x;                      // cell of this chunk, in stream order
+    const int col = 4 * ((int)blockIdx.y * (int)blockDim.x + (int)threadIdx.x);
+    if (s >= G.cells() || col >= G.n) return;
+    int xa, xb, end;
+    G.cell_range(G.cell_of(G.fill) + s, xa, xb, end);
+    // the first cell continues the group the previous chunk left open (a plane of zeros when it left none)
+    v4f sum = s == 0 ? *reinterpret_cast<const v4f *>(carry_grp + col) : v4f{ 0.0f, 0.0f, 0.0f, 0.0f };
+    v4f pk = v4f{ 0.0f, 0.0f, 0.0f, 0.0f };
+    const float *src = mag + (size_t)(xa - G.fill) * (size_t)G.n + col;
+    auto take = [&](const v4f &m) {
+        sum.x = sum.x + m.x; sum.y = sum.y + m.y; sum.z = sum.z + m.z; sum.w = sum.w + m.w;
+        pk.x = fmaxf(pk.x, m.x); pk.y = fmaxf(pk.y, m.y); pk.z = fmaxf(pk.z, m.z); pk.w = fmaxf(pk.w, m.w);
+    };
+    int x = xa;
+    for (; x + 8 <= xb; x += 8, src += (size_t)8 * G.n) {
+        v4f m[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) m[k] = spec_load4(src + (size_t)k * G.n);
+#pragma unroll
+        for (int k = 0; k < 8; k++) take(m[k]);
+    }
+    for (; x < xb; x++, src += G.n) take(spec_load4(src));
+    *reinterpret_cast<v4f *>(ws_sum + (size_t)s * G.n + col) = sum;
+    *reinterpret_cast<v4f *>(ws_peak + (size_t)s * G.n + col) = pk;
+}
+
+__global__ __launch_bounds__(256) void spectrum_rows_kernel(SpectrumGeom G, const float *__restrict__ ws_sum,
+                                                            const float *__restrict__ ws_peak, SpectrumCarry cin,
+                                                            SpectrumCarry cout, float *__restrict__ out)
+{
+    const int rho = (int)blockIdx.x;
+    const int col = (int)blockIdx.y * (int)blockDim.x + (int)threadIdx.x;
+    if (rho >= G.rows_touched() || col >= G.n) return;
+    const int x_end = G.fill + G.frames;
+    float acc = rho == 0 ? cin.acc[col] : 0.0f, pk = rho == 0 ? cin.peak[col] : 0.0f, open = 0.0f;
+    const int xa = rho * G.R > G.fill ? rho * G.R : G.fill, xb = (rho + 1) * G.R < x_end ? (rho + 1) * G.R : x_end;
+    if (xa < xb) {
+        const int c0 = G.cell_of(G.fill);
+        for (int c = G.cell_of(xa); c <= G.cell_of(xb - 1); c++) {
+            int ca, cb, end;
+            G.cell_range(c, ca, cb, end);
+            const float s = ws_sum[(size_t)(c - c0) * G.n + col];
+            pk = fmaxf(pk, ws_peak[(size_t)(c - c0) * G.n + col]);
+            if (end <= x_end) acc = acc + s;            // the group is whole: it joins the row's sum, in order
+            else open = s;                              // cut by the chunk's end: the next chunk continues it
+        }
+    }
+    if ((rho + 1) * G.R <= x_end) {
+        float *row = out + (size_t)rho * 2 * G.n;
+        row[col] = acc / (float)G.R;
+        row[G.n + col] = pk;
+    } else {
+        cout.acc[col] = acc;
+        cout.grp[col] = open;
+        cout.peak[col] = pk;
+    }
+}
+
+// irdm_flush: the open row as it stands -- its whole groups, then the open group -- over the `fill` frames it has
+__global__ __launch_bounds__(256) void spectrum_close_kernel(int n, int fill, SpectrumCarry c, float *__restrict__ out)
+{
+    const int col = (int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x;
+    if (col >= n) return;
+    out[col] = (c.acc[col] + c.grp[col]) / (float)fill;
+    out[n + col] = c.peak[col];
+    c.acc[col] = c.grp[col] = c.peak[col] = 0.0f;
+}
+
+static int spectrum_group(int R) { return R < 64 ? R : 64; }      // frames per summation group
+
+static SpectrumGeom spectrum_geom(int n, int frames, int R, int fill)
+{
+    SpectrumGeom G;
+    G.n = n; G.frames = frames; G.R = R; G.grp = spectrum_group(R); G.fill = fill;
+    return G;
+}
+
+int spectrum_cells_max(int max_frames, int R)
+{
+    // every group of every row the chunk touches, the rows at both ends counted whole; a cell holds at least one frame
+    const long long by_rows = ((long long)max_frames / R + 2) * spectrum_geom(4, max_frames, R, 0).gpr();
+    return (int)(by_rows < max_frames ? by_rows : max_frames);
+}
+
+int launch_spectrum(const float *mag, int n, int frames, int R, int fill, const SpectrumCarry &cin, const SpectrumCarry &cout,
+                    float *ws, size_t ws_cells, float *out, size_t out_rows, hipStream_t stream)
+{
+    if (frames <= 0) return 0;
+    if (n % 4 != 0 || R < 1 || fill < 0 || fill >= R) return -1;
+    const SpectrumGeom G = spectrum_geom(n, frames, R, fill);
+    const int cells = G.cells(), rows = G.rows_touched();
+    if ((size_t)cells > ws_cells || (size_t)(rows - 1) > out_rows) return -1;
+    float *ws_sum = ws, *ws_peak = ws + ws_cells * (size_t)n;
+    const int lanes = n / 4 < 256 ? n / 4 : 256;
+    hipLaunchKernelGGL(spectrum_partial_kernel, dim3((unsigned)cells, (unsigned)((n / 4 + lanes - 1) / lanes)), dim3(lanes), 0,
+                       stream, G, mag, cin.grp, ws_sum, ws_peak);
+    hipLaunchKernelGGL(spectrum_rows_kernel, dim3((unsigned)rows, (unsigned)((n + 255) / 256)), dim3(256), 0, stream, G, ws_sum,
+                       ws_peak, cin, cout, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int launch_spectrum_close(int n, int fill, const SpectrumCarry &c, float *out, hipStream_t stream)
+{
+    if (fill <= 0) return 0;
+    hipLaunchKernelGGL(spectrum_close_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, fill, c, out);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 }  // namespace irdm

@@ -4,9 +4,154 @@
 
 namespace irdmh {
 
+// ---- option "spectrum_frames": mean and peak-hold spectra of K1's plane (detect.hip, KS) ----
+
+// Buffers for rows of R frames, made when the option is first set (and again should a later R need larger ones): the two
+// carry sets, the workspace of a chunk's cells, the device rows of one chunk and the pinned buffers they are copied to.
+int spectrum_configure(irdm_pipeline *p, int R)
+{
+    if (R == 0) {
+        p->spectrum_R = 0;
+        return 0;
+    }
+    pipeline_enter(p);
+    const size_t n = (size_t)p->P.n, max_frames = p->max_chunk / n;
+    const size_t cells = (size_t)spectrum_cells_max((int)max_frames, R), rows = max_frames / (size_t)R + 1;
+    if (!p->d_spec_carry) {
+        if (!(p->d_spec_carry = dev_alloc<float>(6 * n))) return -1;
+        IRDM_HIP_CHECK(hipMemset(p->d_spec_carry, 0, sizeof(float) * 6 * n));
+        for (auto &e : p->ev_spec) IRDM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (cells > p->spec_ws_cells || rows > p->spec_out_rows) {
+        IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));     // (nothing of a stream is in flight: the option is refused then)
+        if (p->d_spec_ws) (void)hipFree(p->d_spec_ws);
+        if (p->d_spec_out) (void)hipFree(p->d_spec_out);
+        for (auto &h : p->hp_spec)
+            if (h) (void)hipHostFree(h);
+        p->d_spec_ws = p->d_spec_out = nullptr;
+        for (auto &h : p->hp_spec) h = nullptr;
+        p->spec_ws_cells = std::max(cells, p->spec_ws_cells);
+        p->spec_out_rows = std::max(rows, p->spec_out_rows);
+        p->d_spec_ws = dev_alloc<float>(2 * p->spec_ws_cells * n);
+        p->d_spec_out = dev_alloc<float>(2 * p->spec_out_rows * n);
+        bool ok = p->d_spec_ws && p->d_spec_out;
+        for (auto &h : p->hp_spec)
+            ok = ok && hipHostMalloc(reinterpret_cast<void **>(&h), sizeof(float) * 2 * p->spec_out_rows * n, hipHostMallocDefault) == hipSuccess;
+        if (!ok) {
+            p->spec_ws_cells = p->spec_out_rows = 0;
+            p->spectrum_R = 0;
+            return -1;
+        }
+    }
+    p->spectrum_R = R;
+    return 0;
+}
+
+// Batches whose copy has completed move from their pinned buffer to the row queue, oldest first.  wait_slot >= 0: the
+// batch that holds that pinned buffer (and every older one) is waited for -- it was enqueued kSpecSlots feeds ago;
+// wait_slot == kSpecSlots: all of them.
+static int spectrum_harvest(irdm_pipeline *p, int wait_slot)
+{
+    StreamState &s = p->st;
+    const size_t n = (size_t)p->P.n;
+    while (!s.spec_pending.empty()) {
+        const SpecBatch b = s.spec_pending.front();
+        bool must = wait_slot == kSpecSlots;
+        for (const SpecBatch &o : s.spec_pending) must = must || o.slot == wait_slot;
+        if (must) IRDM_HIP_CHECK(hipEventSynchronize(p->ev_spec[b.slot]));
+        else if (hipEventQuery(p->ev_spec[b.slot]) != hipSuccess) break;
+        for (int i = 0; i < b.rows; i++) {
+            SpecRow r;
+            r.hdr.row = b.row0 + (uint64_t)i;
+            r.hdr.first_frame = b.frame0 + (uint64_t)i * (uint64_t)p->spectrum_R;
+            r.hdr.timestamp_ns = s.start_time_ns + (uint64_t)((double)(r.hdr.first_frame * n) / (double)p->cfg.sample_rate * 1e9);
+            r.hdr.n_frames = (uint32_t)b.n_frames;
+            r.hdr.n_bins = (uint32_t)n;
+            const float *src = p->hp_spec[b.slot] + (size_t)i * 2 * n;
+            r.data.assign(src, src + 2 * n);
+            s.spec_q.push_back(std::move(r));
+        }
+        s.spec_pending.pop_front();
+    }
+    return 0;
+}
+
+// `rows` rows of n_frames frames in d_spec_out, behind the launch that writes them on K1's stream: on their way to a pinned buffer
+static int spectrum_send(irdm_pipeline *p, int rows, int n_frames)
+{
+    StreamState &s = p->st;
+    const int slot = (int)(s.spec_batches % kSpecSlots);
+    IRDM_HIP_CHECK(hipMemcpyAsync(p->hp_spec[slot], p->d_spec_out, sizeof(float) * 2 * (size_t)rows * (size_t)p->P.n, hipMemcpyDeviceToHost, p->fstream));
+    IRDM_HIP_CHECK(hipEventRecord(p->ev_spec[slot], p->fstream));
+    s.spec_pending.push_back(SpecBatch{ slot, rows, n_frames, s.spec_row, s.spec_row_frame });
+    s.spec_batches++;
+    s.spec_row += (uint64_t)rows;
+    s.spec_row_frame += (uint64_t)rows * (uint64_t)n_frames;
+    return 0;
+}
+
+// The reduction of a chunk's plane, behind its K1 on K1's stream: `mag` is written again by the K1 of a later feed on that
+// same stream, so stream order alone keeps the plane until it has been read.
+static int spectrum_enqueue(irdm_pipeline *p, const float *mag, int n_frames, uint64_t c0)
+{
+    StreamState &s = p->st;
+    const int R = p->spectrum_R;
+    if (!s.spec_started) {
+        s.spec_started = true;
+        s.spec_row_frame = c0 / (uint64_t)p->P.n;
+    }
+    if (spectrum_harvest(p, (int)(s.spec_batches % kSpecSlots)) != 0) return -1;
+    if (launch_spectrum(mag, p->P.n, n_frames, R, s.spec_fill, p->spec_carry(s.spec_sel), p->spec_carry(s.spec_sel ^ 1), p->d_spec_ws,
+                        p->spec_ws_cells, p->d_spec_out, p->spec_out_rows, p->fstream) != 0)
+        return -1;
+    const int rows = (s.spec_fill + n_frames) / R;
+    s.spec_sel ^= 1;
+    s.spec_fill = (s.spec_fill + n_frames) % R;
+    return rows > 0 ? spectrum_send(p, rows, R) : 0;
+}
+
+// irdm_flush: the open row leaves with the frames it has, and every row enqueued so far arrives
+static int spectrum_flush(irdm_pipeline *p)
+{
+    StreamState &s = p->st;
+    if (s.spec_fill > 0) {
+        if (spectrum_harvest(p, (int)(s.spec_batches % kSpecSlots)) != 0) return -1;
+        if (launch_spectrum_close(p->P.n, s.spec_fill, p->spec_carry(s.spec_sel), p->d_spec_out, p->fstream) != 0) return -1;
+        const int fill = s.spec_fill;
+        s.spec_fill = 0;
+        if (spectrum_send(p, 1, fill) != 0) return -1;
+    }
+    return spectrum_harvest(p, kSpecSlots);
+}
+
+extern "C" int irdm_spectrum_bins(const irdm_pipeline_t *p) { return p ? p->P.n : -1; }
+
+extern "C" int irdm_poll_spectrum(irdm_pipeline_t *p, irdm_spectrum_row_t *hdr, float *mean, float *peak, int max)
+{
+    if (!p || !hdr || !mean || !peak || max < 0) return -1;
+    if (!p->st.spec_pending.empty()) {
+        pipeline_enter(p);
+        if (spectrum_harvest(p, -1) != 0) return -1;
+    }
+    const size_t n = (size_t)p->P.n;
+    int k = 0;
+    for (; k < max && !p->st.spec_q.empty(); k++) {
+        const SpecRow &r = p->st.spec_q.front();
+        hdr[k] = r.hdr;
+        memcpy(mean + (size_t)k * n, r.data.data(), sizeof(float) * n);
+        memcpy(peak + (size_t)k * n, r.data.data() + n, sizeof(float) * n);
+        p->st.spec_q.pop_front();
+    }
+    return k;
+}
+
 extern "C" int irdm_flush(irdm_pipeline_t *p)
 {
     if (!p) return -1;
+    if (p->spectrum_R && p->st.begin_no == p->st.end_no) {
+        pipeline_enter(p);
+        if (spectrum_flush(p) != 0) return -1;
+    }
     if (!p->depth) return 0;
     if (p->st.begin_no != p->st.end_no) return -1;        // a chunk handed over with irdm_feed_begin is still pending
     pipeline_enter(p);
@@ -110,6 +255,8 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
         ok = ok && z.add(p->band_spec.ctl, sizeof(BandCtl)) && z.add(p->band_spec.bar, 256) &&
              z.add(p->band_spec.rec_count, 4 * 64) && z.add(p->band_spec.flags, 256) && z.add(p->d_state_spec, sizeof(DetState));
     if (!ok || launch_zero_regions(z, p->stream) != 0) return -1;
+    // (option "spectrum_frames": both carry sets, on the stream the next reduction runs on)
+    if (p->d_spec_carry) IRDM_HIP_CHECK(hipMemsetAsync(p->d_spec_carry, 0, sizeof(float) * 6 * (size_t)P.n, p->fstream));
     // 3. host side: a fresh stream state (the types say which fields that is), the pinned words the scans export to
     p->st = StreamState{};
     for (auto &f : p->fs) f.st = FeedSlot::State{};
@@ -190,6 +337,8 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     // flight still read: the copy never overwrites them)
     if (p->depth && !in_ring && (ring_guard(p, c0, c1, p->fstream) != 0 || ring_update(p, d_iq, c0, c1, p->fstream) != 0)) return -1;
     IRDM_HIP_CHECK(hipEventRecord(f.ev_copy, p->fstream));
+    // option "spectrum_frames": the plane's reduction, behind everything a feed waits for
+    if (p->spectrum_R && n_frames > 0 && spectrum_enqueue(p, mag, n_frames, c0) != 0) return -1;
     f.st.iq = d_iq;
     f.st.c0 = c0;
     f.st.c1 = c1;

@@ -36,6 +36,22 @@ struct ZeroRegions {
 };
 int launch_zero_regions(const ZeroRegions &z, hipStream_t stream);
 
+// KS (option "spectrum_frames"): mean and peak-hold spectra of K1's plane, rows of R frames that may straddle chunks.
+// What a chunk leaves of the row still open, three planes of n floats: the sum of its whole groups, the sum of the group
+// the chunk's end cut, its maximum.  All zero: no row open.
+struct SpectrumCarry {
+    float *acc, *grp, *peak;
+};
+// workspace cells (one per summation group of min(R, 64) frames, cut at the chunk's ends) a chunk of at most max_frames
+// frames takes, whatever part of a row came before it
+int spectrum_cells_max(int max_frames, int R);
+// mag[frames][n] behind `fill` (< R) frames of the open row: the (fill + frames) / R rows the chunk completes go to
+// out[row][2][n] (mean, peak), what it leaves open to `cout` (never the same planes as `cin`).  ws: 2 * ws_cells * n floats.
+int launch_spectrum(const float *mag, int n, int frames, int R, int fill, const SpectrumCarry &cin, const SpectrumCarry &cout,
+                    float *ws, size_t ws_cells, float *out, size_t out_rows, hipStream_t stream);
+// the open row of `fill` (> 0) frames to out[2][n]; the carry back to zero
+int launch_spectrum_close(int n, int fill, const SpectrumCarry &c, float *out, hipStream_t stream);
+
 // scan_fast.hip
 int launch_prefilter(const float *sum, float thr, float *pre, const float *mag, int n,
                      unsigned *counts, ListEntry *entries, unsigned *goff, ListEntry *compact,

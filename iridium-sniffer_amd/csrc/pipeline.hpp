@@ -93,6 +93,20 @@ static inline float *box_of(float2 *lpf, size_t cap) { return reinterpret_cast<f
 // buffer, K1's candidate lists with the levels they were built against, and the events of its K1 and ring copy.
 constexpr int kFeedSlots = 3;
 constexpr unsigned kLookAhead = 1;
+// option "spectrum_frames": pinned buffers the finished rows of a chunk land in, taken in turn -- the one a feed takes was
+// filled three feeds earlier
+constexpr int kSpecSlots = 3;
+
+// Rows of one launch of the spectrum reduction on their way to the host: `rows` rows of n_frames frames each, the first
+// one row number `row0`, starting at absolute frame `frame0`, in pinned buffer `slot` once its event has completed
+struct SpecBatch {
+    int slot, rows, n_frames;
+    uint64_t row0, frame0;
+};
+struct SpecRow {
+    irdm_spectrum_row_t hdr;
+    std::vector<float> data;        // mean[n], peak[n]
+};
 
 // One batch of finished bursts on its way through the per-burst stages K4..K7.  pipeline_depth 0 uses one context on the
 // detector's stream; pipeline_depth >= 1 alternates between two, each on a stream of its own, so that the FIR of one
@@ -200,6 +214,15 @@ struct StreamState {
     // in stream order (group.cpp)
     RecordQueues q;
     std::deque<irdm_chunk_mark_t> q_marks;
+    // option "spectrum_frames": the row still open -- its number, the absolute frame it starts at, the frames it holds and
+    // which of the two carry sets on the device holds its sums (the reset zeroes both) --, the batches of finished rows
+    // in flight and the rows that have arrived, until they are polled
+    bool spec_started = false;
+    uint64_t spec_row = 0, spec_row_frame = 0;
+    int spec_fill = 0, spec_sel = 0;
+    uint64_t spec_batches = 0;      // batches enqueued; pinned buffer = number % kSpecSlots
+    std::deque<SpecBatch> spec_pending;
+    std::deque<SpecRow> spec_q;
 };
 
 struct irdm_pipeline {
@@ -373,6 +396,19 @@ struct irdm_pipeline {
     unsigned long long *kclk_rec(int i) const { return kernel_clock && d_kclk ? d_kclk + (size_t)i * kKClkWords : nullptr; }
     // (the decimator of batch context c: records 0..2, and 6.. for the contexts beyond the third)
     unsigned long long *kclk_fir(int c) const { return kclk_rec(c < 3 ? c : 3 + c); }
+    // option "spectrum_frames" (feed.cpp): R frames per row, 0 = off (configuration); the carry sets, the workspace, the
+    // device rows of one chunk and the pinned buffers they are copied to (cache: allocated when the option is first set)
+    int spectrum_R = 0;
+    float *d_spec_carry = nullptr;          // [2 sets][3 planes][n]
+    float *d_spec_ws = nullptr, *d_spec_out = nullptr;
+    size_t spec_ws_cells = 0, spec_out_rows = 0;
+    float *hp_spec[kSpecSlots] = {};
+    hipEvent_t ev_spec[kSpecSlots] = {};
+    SpectrumCarry spec_carry(int sel) const
+    {
+        float *b = d_spec_carry + (size_t)sel * 3 * (size_t)P.n;
+        return SpectrumCarry{ b, b + P.n, b + 2 * (size_t)P.n };
+    }
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -416,6 +452,9 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 int bursts_finish(irdm_pipeline *p, BatchCtx &b);
 int bursts_finish_records(irdm_pipeline *p, BatchCtx &b);
 int process_bursts(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const GoneBurst *gone_list, int n_gone);
+
+// feed.cpp
+int spectrum_configure(irdm_pipeline *p, int R);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

@@ -7,6 +7,7 @@
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
  *                         [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]]
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
+ *                         [--spectrum FILE [--spectrum-frames R]]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -34,6 +35,14 @@
  * --start-time is the capture time of the first recording (instead of the wall clock at start: the timestamps, and with
  * them the whole output, then depend on the file alone); a later one starts at the time its list entry carries, else
  * at the wall clock.  A recording that cannot be opened or fails mid-way is reported and the others still run (exit 1).
+ * --spectrum FILE: a band survey beside the lines -- the mean and the peak-hold spectrum of every R consecutive FFT frames of
+ * the stream the detector sees (behind the front end: of the selected band), reduced on the GPU (option "spectrum_frames",
+ * irdm_poll_spectrum), written to FILE: a 64-byte little-endian header -- "IRDMSPEC", u32 version 1, u32 n_bins, u32 R, u32
+ * rate, f64 centre frequency, u64 start time in ns, 24 bytes of zeros; rate and centre are the context's, behind a front end
+ * the band's -- then per row an irdm_spectrum_row_t (32 bytes), n_bins floats of mean, n_bins floats of peak (bin 0 = -rate / 2,
+ * linear |X|^2).  --spectrum-frames R: frames per row, default round(rate / fft_size), about a second, at least 1.  stdout and
+ * stderr are what they are without the flag.  With several recordings FILE must be `auto` and --out-dir given: each recording
+ * leaves DIR/<basename>.spec.  --gpus N > 1 is refused.
  */
 #include <err.h>
 #include <errno.h>
@@ -58,6 +67,41 @@ static const char *ext_of(const char *p)
 
 /* print every finished frame (frame_output_print, frame_output.c:160-199) and discard the other record queues */
 static const char *g_save_dir;
+
+/* --spectrum: the rows finished so far to the recording's .spec file */
+static FILE *g_spec;
+static float *g_spec_rows;
+#define SPEC_POLL 8
+static int spectrum_drain(irdm_pipeline_t *p)
+{
+    if (!g_spec) return 0;
+    irdm_spectrum_row_t hdr[SPEC_POLL];
+    const size_t n = (size_t)irdm_spectrum_bins(p);
+    for (;;) {
+        const int k = irdm_poll_spectrum(p, hdr, g_spec_rows, g_spec_rows + SPEC_POLL * n, SPEC_POLL);
+        if (k < 0) return -1;
+        if (k == 0) return 0;
+        for (int i = 0; i < k; i++)
+            if (fwrite(&hdr[i], sizeof hdr[i], 1, g_spec) != 1 || fwrite(g_spec_rows + (size_t)i * n, sizeof(float), n, g_spec) != n ||
+                fwrite(g_spec_rows + (SPEC_POLL + (size_t)i) * n, sizeof(float), n, g_spec) != n)
+                return -1;
+    }
+}
+
+static int spectrum_open(const char *path, irdm_pipeline_t *p, int R, int rate, double centre)
+{
+    unsigned char h[64];
+    const uint32_t w[4] = { 1u, (uint32_t)irdm_spectrum_bins(p), (uint32_t)R, (uint32_t)rate };
+    const uint64_t t0 = irdm_start_time_ns(p);
+    memset(h, 0, sizeof h);
+    memcpy(h, "IRDMSPEC", 8);
+    memcpy(h + 8, w, 16);
+    memcpy(h + 24, &centre, 8);
+    memcpy(h + 32, &t0, 8);
+    g_spec = fopen(path, "wb");
+    if (!g_spec) { perror(path); return -1; }
+    return fwrite(h, sizeof h, 1, g_spec) == 1 ? 0 : -1;
+}
 /* where the lines of the recording at hand go: stdout, or with --out-dir its own file */
 static FILE *g_out;
 
@@ -366,6 +410,8 @@ int main(int argc, char **argv)
     double band_center = 0;
     int resample_to = 0;                   /* --resample-to: the front end's rational mode */
     int rs_l = 0, rs_m = 0;
+    const char *spectrum = NULL;           /* --spectrum FILE | auto */
+    int spectrum_frames = 0;               /* --spectrum-frames R (0: about a second) */
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -420,6 +466,11 @@ int main(int argc, char **argv)
             resample_to = atoi(NEXT());
             if (resample_to <= 0) { fprintf(stderr, "--resample-to: a rate in Hz\n"); return 2; }
         }
+        else if (!strcmp(a, "--spectrum")) spectrum = NEXT();
+        else if (!strcmp(a, "--spectrum-frames")) {
+            spectrum_frames = atoi(NEXT());
+            if (spectrum_frames < 1 || spectrum_frames > (1 << 20)) { fprintf(stderr, "--spectrum-frames: 1 .. 1048576 frames per row\n"); return 2; }
+        }
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -434,7 +485,7 @@ int main(int argc, char **argv)
         }
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -473,6 +524,20 @@ int main(int argc, char **argv)
         return 2;
     }
     if (g_n_in > 1) gpus = 0;
+    if (spectrum) {
+        if (gpus > 1) {
+            fprintf(stderr, "--spectrum: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if ((g_n_in > 1 || !strcmp(spectrum, "auto")) && (strcmp(spectrum, "auto") != 0 || !out_dir)) {
+            fprintf(stderr, "--spectrum with several recordings: give --spectrum auto and --out-dir DIR (DIR/<basename>.spec each)\n");
+            return 2;
+        }
+        gpus = 0;
+    } else if (spectrum_frames) {
+        fprintf(stderr, "--spectrum-frames goes with --spectrum FILE\n");
+        return 2;
+    }
     size_t bps = 2;
     const int fmt = format_of(format, g_in[0].path, &bps);
     for (int k = 0; k < g_n_in; k++) {
@@ -579,6 +644,17 @@ int main(int argc, char **argv)
         fprintf(stderr, "--position: the library refused the frame decoder\n");
         return 1;
     }
+    if (spectrum) {
+        if (!spectrum_frames) {
+            spectrum_frames = (int)((double)c.sample_rate / (double)irdm_fft_size(p) + 0.5);
+            if (spectrum_frames < 1) spectrum_frames = 1;
+        }
+        g_spec_rows = malloc(sizeof(float) * 2 * SPEC_POLL * (size_t)irdm_spectrum_bins(p));
+        if (!g_spec_rows || irdm_set_option(p, "spectrum_frames", spectrum_frames) != 0) {
+            fprintf(stderr, "--spectrum: the library refused %d frames per row\n", spectrum_frames);
+            return 1;
+        }
+    }
     g_save_dir = save_dir;
     /* a group is fed a super-step at a time: one chunk per member */
     /* (behind a front end the reader's chunk is D -- or M / L -- pipeline chunks of capture samples) */
@@ -623,6 +699,19 @@ int main(int argc, char **argv)
             snprintf(path, sizeof path, "%s/%s.out", out_dir, base_of(file));
             g_out = fopen(path, "w");
             if (!g_out) { perror(path); fclose(f); g_out = stdout; rc_all = 1; continue; }
+        }
+        if (spectrum) {
+            char path[4608];
+            if (!strcmp(spectrum, "auto")) snprintf(path, sizeof path, "%s/%s.spec", out_dir, base_of(file));
+            else snprintf(path, sizeof path, "%s", spectrum);
+            if (spectrum_open(path, p, spectrum_frames, c.sample_rate, c.center_frequency) != 0) {
+                if (g_spec) fclose(g_spec);
+                g_spec = NULL;
+                if (out_dir) { fclose(g_out); g_out = stdout; }
+                fclose(f);
+                rc_all = 1;
+                continue;
+            }
         }
         /* the host-side objects of a recording: its line printer's t0, its IDA reassembly and ACARS state, its solver */
         if (acars) {
@@ -694,6 +783,7 @@ int main(int argc, char **argv)
             fed += r;
             sem_post(&rd.empty);                        /* irdm_feed_host has consumed the buffer when it returns */
             if (rc == 0) drain(p, d, file_info, &t0, line, sizeof line);
+            if (rc == 0 && spectrum_drain(p) != 0) { fprintf(stderr, "--spectrum: writing the rows failed\n"); rc = 1; }
             if (r < step) { rd.stop = 1; sem_post(&rd.empty); break; }    /* ragged last chunk = end of stream */
         }
         rd.stop = 1;
@@ -707,6 +797,11 @@ int main(int argc, char **argv)
         if (rc == 0 && (fe ? irdm_frontend_flush(fe, p) : g_group ? irdm_group_flush(g_group) : irdm_flush(p)) < 0) { fprintf(stderr, "burst_detect: GPU processing failed\n"); rc = 1; }
         drain(p, d, file_info, &t0, line, sizeof line);
         fflush(g_out);
+        if (g_spec) {
+            if (rc == 0 && spectrum_drain(p) != 0) { fprintf(stderr, "--spectrum: writing the rows failed\n"); rc = 1; }
+            if (fclose(g_spec) != 0) { fprintf(stderr, "--spectrum: writing the rows failed\n"); rc = 1; }
+            g_spec = NULL;
+        }
         if (g_dop && rc == 0)          /* the ticks up to the stream's end (samples / rate), then the final solve */
             position_out(irdm_doppler_finish(g_dop, irdm_start_time_ns(p) + (uint64_t)((double)fed / rate * 1e9), g_dop_text,
                                              sizeof g_dop_text));

@@ -106,6 +106,12 @@ class FramePacked(C.Structure):
                 ("page_msc", C.c_uint8 * 12)]
 
 
+class SpectrumRow(C.Structure):
+    """irdm_spectrum_row_t: header of one row of the waterfall (option spectrum_frames)"""
+    _fields_ = [("row", C.c_uint64), ("first_frame", C.c_uint64), ("timestamp_ns", C.c_uint64), ("n_frames", C.c_uint32),
+                ("n_bins", C.c_uint32)]
+
+
 class Position(C.Structure):
     """irdm_position_t: doppler_solution_t"""
     _fields_ = [("lat", C.c_double), ("lon", C.c_double), ("alt", C.c_double), ("hdop", C.c_double),
@@ -174,6 +180,9 @@ def lib():
             L.irdm_reset.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
         if hasattr(L, "irdm_advance"):
             L.irdm_advance.argtypes = [C.c_void_p]
+        if hasattr(L, "irdm_poll_spectrum"):
+            L.irdm_spectrum_bins.argtypes = [C.c_void_p]
+            L.irdm_poll_spectrum.argtypes = [C.c_void_p, C.POINTER(SpectrumRow), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
         L.irdm_host_alloc.argtypes = [C.c_size_t]
         L.irdm_host_alloc.restype = C.c_void_p
         L.irdm_host_free.argtypes = [C.c_void_p]
@@ -620,6 +629,24 @@ class Pipeline:
     def poll_frame_packed(self):
         """option frame_records 1: one FramePacked per polled DemodPacked, in the same order"""
         return self._poll(self.L.irdm_poll_frame_packed, FramePacked)
+
+    def poll_spectrum(self, chunk=64):
+        """option spectrum_frames: (headers, mean, peak) of the rows finished so far -- a list of SpectrumRow and two float32
+        arrays [rows][n_bins], bin 0 at -fs/2, linear |X|^2"""
+        n = self.L.irdm_spectrum_bins(self.h)
+        hdr = (SpectrumRow * chunk)()
+        mean, peak = np.empty((chunk, n), np.float32), np.empty((chunk, n), np.float32)
+        hs, ms, ps = [], [np.empty((0, n), np.float32)], [np.empty((0, n), np.float32)]
+        while True:
+            k = self.L.irdm_poll_spectrum(self.h, hdr, _fp(mean), _fp(peak), chunk)
+            if k < 0:
+                raise RuntimeError("irdm_poll_spectrum failed")
+            if k == 0:
+                break
+            hs += [SpectrumRow.from_buffer_copy(hdr[i]) for i in range(k)]
+            ms.append(mean[:k].copy())
+            ps.append(peak[:k].copy())
+        return hs, np.concatenate(ms), np.concatenate(ps)
 
     def drop_frames(self, chunk=4096):
         """Discard queued frame records (metadata only path)."""
