@@ -871,6 +871,41 @@ int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L, int *M);
 /* the ratio in lowest terms: output rate = capture rate * L / M (1 / D for irdm_frontend_create's object).  0 ok, -1 error. */
 int irdm_frontend_ratio(const irdm_frontend_t *fe, int *L, int *M);
 
+/* Saving the band: the front end's output stream -- every sample it produces, in order, in either mode, through the
+ * stage-level entries and the feeder alike -- handed to a callback as a ci8 / ci16 / cf32 recording at
+ * irdm_frontend_out_rate, centred at the capture centre + irdm_frontend_applied_shift_hz.  Per float component x of the
+ * cf32 band, with S = 128 (ci8) or 32768 (ci16) and k = (float)gain * S formed once in float:
+ *
+ *   v = rintf(x * k)   (one rounded product; to nearest, ties to even)     q = clamp(v, -S, S - 1)
+ *   NaN -> 0; +-Inf -> the rail of its sign
+ *
+ * written as interleaved I, Q little-endian int8 / int16.  ci16 holds all 16 bits: such a file is read back as
+ * IRDM_FMT_CI16_FULL (IRDM_FMT_CI16 narrows by >> 8 as the reference does).  cf32: the bytes as they are, gain 1.
+ * The sink runs on the calling thread, inside irdm_frontend_* calls, in stream order, with at most slot_samples samples at
+ * a time; irdm_frontend_flush and irdm_frontend_finish_device deliver everything outstanding before they return.  The bytes
+ * delivered are ceil(n_in_total * L / M) samples and do not depend on how the input was cut into feeds, on slot_samples, or
+ * on the pipeline behind the feeder.  irdm_frontend_reset drops what has not been delivered and zeroes the statistics; the
+ * sink stays installed and nothing is allocated. */
+typedef int (*irdm_band_sink_t)(void *user, const void *bytes, size_t n_bytes);   /* non-zero = stop: the call in progress returns -1 */
+typedef struct {
+    int format;               /* IRDM_FMT_CI8, IRDM_FMT_CI16 (full 16 bits, read back as IRDM_FMT_CI16_FULL) or IRDM_FMT_CF32 */
+    float gain;               /* > 0, finite; must be 1 for cf32 */
+    size_t slot_samples;      /* 0 = default (4 Mi samples); two pinned host slots of this size (and two on the device) */
+    irdm_band_sink_t sink;
+    void *user;
+} irdm_frontend_save_config_t;
+/* before the first sample; NULL cfg = off; -1 mid-stream or on a bad field */
+int irdm_frontend_save(irdm_frontend_t *fe, const irdm_frontend_save_config_t *cfg);
+/* n_samples: samples requantised (cf32: copied) since creation or the last reset; n_clipped: components whose v fell outside
+ * [-S, S - 1] or that were NaN; peak: max |x * k| / S over the finite components, the fraction of full scale before clipping
+ * (cf32: n_clipped 0, peak 0 -- no kernel looks at the samples). */
+typedef struct { uint64_t n_samples, n_clipped; float peak; } irdm_band_stats_t;
+int irdm_frontend_save_stats(irdm_frontend_t *fe, irdm_band_stats_t *out);              /* waits for the front end's streams */
+/* stage level: n cf32 samples in device memory (8-byte aligned) -> d_out (format as above; aligned to a sample of it), the
+ * statistics of this call alone (stats may be NULL); stream NULL = synchronous (an integer format waits for the stream in
+ * either case: the statistics are read back).  0 ok, -1 error. */
+int irdm_requantize_device(const void *d_in, size_t n, int format, float gain, void *d_out, irdm_band_stats_t *stats, int device, void *stream);
+
 /* The fine-CFO step's cexpf(i x) (burst_downmix.c:716-717) as the device evaluates it -- glibc's sincosf restated,
  * csrc/libm_port.hpp -- for n arbitrary arguments (test / audit surface: tests/test_gpu_libm.py,
  * tools/check_sincosf_gpu.c compare it with the host's libm).  0 ok, -1 error; NaN where |x| >= 120. */

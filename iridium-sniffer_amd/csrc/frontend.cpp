@@ -12,11 +12,29 @@
 
 namespace irdmh {
 
+// saving off: the slots, the copy stream and the statistics words go (nothing of a stream is in flight, or is waited for)
+static void fe_save_off(irdm_frontend *fe)
+{
+    irdm_frontend::Save &sv = fe->sv;
+    if (sv.copy) (void)hipStreamSynchronize(sv.copy);
+    for (int i = 0; i < 2; i++) {
+        if (sv.h[i]) (void)hipHostFree(sv.h[i]);
+        if (sv.d[i]) (void)hipFree(sv.d[i]);
+        if (sv.ev[i]) (void)hipEventDestroy(sv.ev[i]);
+        if (sv.ev_k[i]) (void)hipEventDestroy(sv.ev_k[i]);
+    }
+    if (sv.copy) (void)hipStreamDestroy(sv.copy);
+    if (sv.d_stats) (void)hipFree(sv.d_stats);
+    sv = irdm_frontend::Save{};
+    for (int i = 0; i < 2; i++) fe->st.sv_busy[i] = false;
+}
+
 void fe_free(irdm_frontend *fe)
 {
     if (!fe) return;
     (void)hipSetDevice(fe->cfg.device);
     if (fe->stream) (void)hipStreamSynchronize(fe->stream);
+    fe_save_off(fe);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
@@ -152,6 +170,59 @@ static uint64_t fe_outputs(const irdm_frontend *fe, uint64_t total, bool flush)
     return total * L > (uint64_t)fe->c ? (total * L - 1 - (uint64_t)fe->c) / M + 1 : 0;
 }
 
+// ---- saving the band (irdm_frontend_save): the tap behind fe_emit's kernel ----
+
+// slot i to the sink, once its bytes are in the pinned buffer
+static int fe_save_deliver(irdm_frontend *fe, int i)
+{
+    if (!fe->st.sv_busy[i]) return 0;
+    IRDM_HIP_CHECK(hipEventSynchronize(fe->sv.ev[i]));
+    fe->st.sv_busy[i] = false;
+    return fe->sv.sink(fe->sv.user, fe->sv.h[i], fe->st.sv_bytes[i]) == 0 ? 0 : -1;
+}
+
+// everything outstanding, in stream order (the slot to be filled next is the older one)
+static int fe_save_drain(irdm_frontend *fe)
+{
+    if (!fe->sv.sink) return 0;
+    if (fe_save_deliver(fe, fe->st.sv_next) != 0) return -1;
+    return fe_save_deliver(fe, fe->st.sv_next ^ 1);
+}
+
+// out[0 .. n) has just been written on stream s: requantised (cf32: copied) in pieces of at most slot_samples, each into
+// the slot whose turn it is.  s waits for no transfer: it runs the piece's kernel (cf32: a device copy) into staging and
+// the copy stream takes it from there; with `direct` the kernel's own stores (cf32: the copy) go to the pinned slot.
+static int fe_save_tap(irdm_frontend *fe, const float2 *out, size_t n, hipStream_t s)
+{
+    irdm_frontend::Save &sv = fe->sv;
+    const int bits = sv.format == IRDM_FMT_CI8 ? 8 : (sv.format == IRDM_FMT_CI16 ? 16 : 0);
+    for (size_t off = 0; off < n; off += sv.slot_samples) {
+        const size_t piece = std::min(sv.slot_samples, n - off);
+        const int i = fe->st.sv_next;
+        if (fe_save_deliver(fe, i) != 0) return -1;
+        const size_t bytes = piece * (size_t)sv.bytes_per_sample;
+        void *dst = sv.direct ? sv.h[i] : sv.d[i];
+        if (bits) {
+            if (launch_requant(bits, out + off, (long long)piece, sv.k, dst, sv.d_stats, s) != 0) return -1;
+        } else {
+            IRDM_HIP_CHECK(hipMemcpyAsync(dst, out + off, bytes, sv.direct ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, s));
+        }
+        if (sv.direct) {
+            IRDM_HIP_CHECK(hipEventRecord(sv.ev[i], s));
+        } else {
+            IRDM_HIP_CHECK(hipEventRecord(sv.ev_k[i], s));
+            IRDM_HIP_CHECK(hipStreamWaitEvent(sv.copy, sv.ev_k[i], 0));
+            IRDM_HIP_CHECK(hipMemcpyAsync(sv.h[i], sv.d[i], bytes, hipMemcpyDeviceToHost, sv.copy));
+            IRDM_HIP_CHECK(hipEventRecord(sv.ev[i], sv.copy));
+        }
+        fe->st.sv_busy[i] = true;
+        fe->st.sv_bytes[i] = bytes;
+        fe->st.sv_next = i ^ 1;
+        fe->st.sv_samples += piece;
+    }
+    return 0;
+}
+
 // outputs [fe->st.n_out, m1) of [tail | d_in] into out
 static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1, float2 *out, hipStream_t s)
 {
@@ -170,6 +241,7 @@ static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1
     a.fmt = fe->fmt;
     if (fe->launch(fe, a, s) != 0) return -1;
     if (launch_kclk_fold(fe->d_kclk, s) != 0) return -1;
+    if (fe->sv.sink && fe_save_tap(fe, out, (size_t)(m1 - fe->st.n_out), s) != 0) return -1;
     fe->st.n_out = m1;
     return 0;
 }
@@ -219,6 +291,7 @@ extern "C" long long irdm_frontend_finish_device(irdm_frontend_t *fe, void *d_ou
     hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : fe->stream;
     if (fe_emit(fe, nullptr, 0, m1, static_cast<float2 *>(d_out), s) != 0) return -1;
     fe->st.finished = true;
+    if (fe_save_drain(fe) != 0) return -1;
     if (!stream_v) IRDM_HIP_CHECK(hipStreamSynchronize(s));
     return (long long)n;
 }
@@ -331,6 +404,7 @@ extern "C" int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p)
     int bursts = fe_pump(fe, p, nullptr, 0, fe_outputs(fe, fe->st.total, true), true);
     if (bursts < 0) return -1;
     fe->st.finished = true;
+    if (fe_save_drain(fe) != 0) return -1;
     const int rc = irdm_flush(p);
     return rc < 0 ? -1 : bursts + rc;
 }
@@ -343,7 +417,113 @@ extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
     if (!fe) return -1;
     (void)hipSetDevice(fe->cfg.device);
     IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));      // (launches in flight read the tail and the staging buffer)
+    // saving: what the sink has not been given is dropped, the statistics start again; the sink and the slots stay
+    if (fe->sv.copy) IRDM_HIP_CHECK(hipStreamSynchronize(fe->sv.copy));
+    if (fe->sv.d_stats) IRDM_HIP_CHECK(hipMemset(fe->sv.d_stats, 0, 3 * sizeof(unsigned long long)));
     fe->st = irdm_frontend::State{};
+    return 0;
+}
+
+// ---- saving the band: the public calls ----
+
+static int save_scale(int format) { return format == IRDM_FMT_CI8 ? 128 : (format == IRDM_FMT_CI16 ? 32768 : 0); }
+
+static void save_stats_out(int format, const unsigned long long h[3], uint64_t n_samples, irdm_band_stats_t *out)
+{
+    const int S = save_scale(format);
+    out->n_samples = S ? h[0] / 2 : n_samples;
+    out->n_clipped = h[1];
+    float peak = 0.0f;
+    if (S) {
+        const uint32_t b = (uint32_t)h[2];
+        memcpy(&peak, &b, sizeof(peak));
+        peak = peak / (float)S;
+    }
+    out->peak = peak;
+}
+
+extern "C" int irdm_frontend_save(irdm_frontend_t *fe, const irdm_frontend_save_config_t *cfg)
+{
+    if (!fe || fe->st.total || fe->st.n_out || fe->st.finished) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+    if (!cfg) {
+        fe_save_off(fe);
+        return 0;
+    }
+    const int S = save_scale(cfg->format);
+    if ((!S && cfg->format != IRDM_FMT_CF32) || !cfg->sink || !(cfg->gain > 0.0f) || !std::isfinite(cfg->gain) ||
+        (!S && cfg->gain != 1.0f) || (S && !std::isfinite(cfg->gain * (float)S))) {
+        fprintf(stderr, "irdm_hip: front end: save: format ci8 / ci16 / cf32, a positive finite gain (1 for cf32) and a sink\n");
+        return -1;
+    }
+    fe_save_off(fe);
+    irdm_frontend::Save &sv = fe->sv;
+    sv.format = cfg->format;
+    sv.bytes_per_sample = S == 128 ? 2 : (S ? 4 : 8);
+    sv.gain = cfg->gain;
+    sv.k = S ? cfg->gain * (float)S : 0.0f;
+    sv.slot_samples = cfg->slot_samples ? cfg->slot_samples : (size_t)4 << 20;
+    sv.user = cfg->user;
+    // (measurement aid, tools/saveband_rate.py: IRDM_SAVE_DIRECT=1 lets the kernel store into the pinned slot itself)
+    const char *dm = getenv("IRDM_SAVE_DIRECT");
+    sv.direct = dm && dm[0] == '1';
+    const size_t slot_bytes = sv.slot_samples * (size_t)sv.bytes_per_sample;
+    bool ok = true;
+    for (int i = 0; i < 2 && ok; i++) {
+        ok = hipHostMalloc(&sv.h[i], slot_bytes, hipHostMallocDefault) == hipSuccess;
+        ok = ok && (sv.direct || hipMalloc(&sv.d[i], slot_bytes) == hipSuccess);
+        ok = ok && hipEventCreateWithFlags(&sv.ev[i], hipEventDisableTiming) == hipSuccess;
+        ok = ok && hipEventCreateWithFlags(&sv.ev_k[i], hipEventDisableTiming) == hipSuccess;
+    }
+    ok = ok && (sv.direct || hipStreamCreateWithFlags(&sv.copy, hipStreamNonBlocking) == hipSuccess);
+    ok = ok && hipMalloc(reinterpret_cast<void **>(&sv.d_stats), 3 * sizeof(unsigned long long)) == hipSuccess;
+    ok = ok && hipMemset(sv.d_stats, 0, 3 * sizeof(unsigned long long)) == hipSuccess;
+    if (!ok) {
+        fprintf(stderr, "irdm_hip: front end: save: allocating two slots of %zu bytes failed\n", slot_bytes);
+        fe_save_off(fe);
+        return -1;
+    }
+    sv.sink = cfg->sink;
+    return 0;
+}
+
+extern "C" int irdm_frontend_save_stats(irdm_frontend_t *fe, irdm_band_stats_t *out)
+{
+    if (!fe || !out || !fe->sv.sink) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+    if (fe->sv.copy) IRDM_HIP_CHECK(hipStreamSynchronize(fe->sv.copy));
+    unsigned long long h[3] = { 0, 0, 0 };
+    IRDM_HIP_CHECK(hipMemcpy(h, fe->sv.d_stats, sizeof(h), hipMemcpyDeviceToHost));
+    save_stats_out(fe->sv.format, h, fe->st.sv_samples, out);
+    return 0;
+}
+
+extern "C" int irdm_requantize_device(const void *d_in, size_t n, int format, float gain, void *d_out, irdm_band_stats_t *stats,
+                                      int device, void *stream_v)
+{
+    const int S = save_scale(format);
+    if ((!S && format != IRDM_FMT_CF32) || !(gain > 0.0f) || !std::isfinite(gain) || (!S && gain != 1.0f) ||
+        (S && !std::isfinite(gain * (float)S)) || (n && (!d_in || !d_out)))
+        return -1;
+    if (hipSetDevice(device) != hipSuccess) return -1;
+    hipStream_t s = static_cast<hipStream_t>(stream_v);
+    unsigned long long h[3] = { 0, 0, 0 };
+    if (n && !S) {
+        IRDM_HIP_CHECK(hipMemcpyAsync(d_out, d_in, n * sizeof(float2), hipMemcpyDeviceToDevice, s));
+    } else if (n) {
+        // (the statistics words of this call alone; read back, so the call waits for the stream whenever it has launched)
+        unsigned long long *d_stats = nullptr;
+        IRDM_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&d_stats), sizeof(h)));
+        int rc = hipMemsetAsync(d_stats, 0, sizeof(h), s) == hipSuccess ? 0 : -1;
+        if (rc == 0) rc = launch_requant(S == 128 ? 8 : 16, d_in, (long long)n, gain * (float)S, d_out, d_stats, s);
+        if (rc == 0) rc = hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h, d_stats, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+        (void)hipFree(d_stats);
+        if (rc != 0) return -1;
+    }
+    if (n && !S && !stream_v) IRDM_HIP_CHECK(hipStreamSynchronize(s));
+    if (stats) save_stats_out(format, h, n, stats);
     return 0;
 }
 

@@ -268,4 +268,138 @@ int launch_frontend_tail(const void *tail, long long n_tail, const void *in, lon
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---- the requantiser: the cf32 band as a ci8 / ci16 recording (irdm_frontend_save, irdm_requantize_device) ----
+//
+// Arithmetic contract, per float component x, k = (float)gain * S (S = 128 / 32768) formed once by the host:
+//   v = rintf(x * k)       one rounded product, rounded to nearest, ties to even
+//   q = clamp(v, -S, S - 1);  NaN -> 0;  +-Inf -> the rail of its sign
+// Statistics (three 64-bit words at `stats`, added to): [0] components, [1] clipped components (v outside [-S, S - 1], or
+// NaN), [2] the largest bit pattern of |x * k| over the components with x finite (a non-negative float's pattern orders as
+// the float does).  All three are independent of the order in which the workgroups arrive.
+//
+// Shape.  Memory-bound: 8 bytes in, 2 or 4 bytes out per sample.  A lane takes kRqV = 4 consecutive samples per step: two
+// 16-byte loads (four 8-byte ones when the input is only 8-byte aligned) and one 8- or 16-byte store; the lanes of a
+// wavefront are consecutive, the grid strides.  A piece may start at any sample: the `head` samples in front of the first
+// output address that is aligned for the wide store, and the fewer than kRqV behind the last whole step, are done one per
+// lane by workgroup 0.  The statistics are reduced per wavefront (shuffles), then per workgroup (LDS); lane 0 of the
+// workgroup issues one atomic per statistic.
+// Bounds: every index is below n (head <= n; quads * kRqV <= n - head); the launcher refuses a misaligned pointer.
+constexpr int kRqThreads = 256, kRqV = 4, kRqMaxBlocks = 2048;
+
+struct RqAcc { unsigned comps, clipped, peak; };
+
+template <int S>
+__device__ __forceinline__ int rq_one(float x, float k, RqAcc &a)
+{
+    const float p = x * k;
+    const float v = rintf(p);
+    if ((__float_as_uint(x) & 0x7fffffffu) < 0x7f800000u) a.peak = max(a.peak, __float_as_uint(p) & 0x7fffffffu);
+    a.comps++;
+    if (!(v >= (float)-S && v <= (float)(S - 1))) a.clipped++;            // (a NaN compares false: counted)
+    if (v != v) return 0;
+    return (int)fminf(fmaxf(v, (float)-S), (float)(S - 1));
+}
+
+template <int S, typename Q>
+__global__ __launch_bounds__(kRqThreads) void requant_kernel(const float2 *__restrict__ in, long long n, int head, int in16,
+                                                             float k, Q *__restrict__ out, unsigned long long *__restrict__ stats)
+{
+    __shared__ unsigned red[3 * (kRqThreads / 64)];
+    RqAcc a{ 0u, 0u, 0u };
+    const int tid = threadIdx.x;
+    const long long quads = (n - head) / kRqV;
+    const float2 *bin = in + head;
+    Q *bout = out + 2 * head;
+    for (long long g = (long long)blockIdx.x * kRqThreads + tid; g < quads; g += (long long)gridDim.x * kRqThreads) {
+        float c[2 * kRqV];
+        if (in16) {
+            const float4 *p = reinterpret_cast<const float4 *>(bin + g * kRqV);
+            const float4 u0 = p[0], u1 = p[1];
+            c[0] = u0.x; c[1] = u0.y; c[2] = u0.z; c[3] = u0.w;
+            c[4] = u1.x; c[5] = u1.y; c[6] = u1.z; c[7] = u1.w;
+        } else {
+            const float2 *p = bin + g * kRqV;
+#pragma unroll
+            for (int j = 0; j < kRqV; j++) {
+                const float2 u = p[j];
+                c[2 * j] = u.x;
+                c[2 * j + 1] = u.y;
+            }
+        }
+        unsigned q[2 * kRqV];
+#pragma unroll
+        for (int j = 0; j < 2 * kRqV; j++) q[j] = (unsigned)rq_one<S>(c[j], k, a);
+        if constexpr (sizeof(Q) == 1) {
+            uint2 w;
+            w.x = (q[0] & 0xffu) | (q[1] & 0xffu) << 8 | (q[2] & 0xffu) << 16 | q[3] << 24;
+            w.y = (q[4] & 0xffu) | (q[5] & 0xffu) << 8 | (q[6] & 0xffu) << 16 | q[7] << 24;
+            *reinterpret_cast<uint2 *>(bout + g * (2 * kRqV)) = w;
+        } else {
+            *reinterpret_cast<uint4 *>(bout + g * (2 * kRqV)) =
+                make_uint4((q[0] & 0xffffu) | q[1] << 16, (q[2] & 0xffffu) | q[3] << 16, (q[4] & 0xffffu) | q[5] << 16,
+                           (q[6] & 0xffffu) | q[7] << 16);
+        }
+    }
+    if (blockIdx.x == 0) {
+        // the scalar head and tail: at most kRqV - 1 samples each
+        const long long tail0 = head + quads * kRqV;
+        const long long i = tid < head ? tid : (tail0 + (tid - head) < n ? tail0 + (tid - head) : -1);
+        if (i >= 0) {
+            const float2 x = in[i];
+            out[2 * i] = (Q)rq_one<S>(x.x, k, a);
+            out[2 * i + 1] = (Q)rq_one<S>(x.y, k, a);
+        }
+    }
+    // the statistics: wavefront, workgroup, one atomic each
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        a.comps += __shfl_xor(a.comps, d);
+        a.clipped += __shfl_xor(a.clipped, d);
+        a.peak = max(a.peak, __shfl_xor(a.peak, d));
+    }
+    if ((tid & 63) == 0) {
+        red[3 * (tid >> 6)] = a.comps;
+        red[3 * (tid >> 6) + 1] = a.clipped;
+        red[3 * (tid >> 6) + 2] = a.peak;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long comps = 0, clipped = 0, peak = 0;
+        for (int w = 0; w < kRqThreads / 64; w++) {
+            comps += red[3 * w];
+            clipped += red[3 * w + 1];
+            if (red[3 * w + 2] > peak) peak = red[3 * w + 2];
+        }
+        if (comps) atomicAdd(&stats[0], comps);
+        if (clipped) atomicAdd(&stats[1], clipped);
+        if (peak) atomicMax(&stats[2], peak);
+    }
+}
+
+template <int S, typename Q>
+static int launch_requant_q(const float2 *in, long long n, float k, Q *out, unsigned long long *stats, hipStream_t stream)
+{
+    // the samples in front of the first output address aligned for a lane's store of kRqV samples
+    const uintptr_t A = (uintptr_t)(2 * kRqV) * sizeof(Q), sample = 2 * sizeof(Q);
+    const uintptr_t o = reinterpret_cast<uintptr_t>(out);
+    if (o % sample != 0 || reinterpret_cast<uintptr_t>(in) % sizeof(float2) != 0) return -1;
+    const int head = (int)std::min<long long>((long long)(((A - o % A) % A) / sample), n);
+    const long long quads = (n - head) / kRqV;
+    const int in16 = reinterpret_cast<uintptr_t>(in + head) % 16 == 0 ? 1 : 0;
+    const long long blocks = std::max<long long>(1, std::min<long long>((quads + kRqThreads - 1) / kRqThreads, kRqMaxBlocks));
+    hipLaunchKernelGGL((requant_kernel<S, Q>), dim3((unsigned)blocks), dim3(kRqThreads), 0, stream, in, n, head, in16, k, out, stats);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// n cf32 samples at `in` (8-byte aligned) -> interleaved int8 (bits 8; out 2-byte aligned) or int16 (bits 16; 4-byte aligned)
+// pairs at `out`, k = (float)gain * S; the statistics are added to stats[0 .. 3).  n = 0 launches nothing.
+int launch_requant(int bits, const void *in, long long n, float k, void *out, unsigned long long *stats, hipStream_t stream)
+{
+    if (n < 0 || (bits != 8 && bits != 16) || !(k > 0.0f) || k > 3.0e38f) return -1;
+    if (n == 0) return 0;
+    if (!in || !out || !stats) return -1;
+    if (bits == 8) return launch_requant_q<128>(static_cast<const float2 *>(in), n, k, static_cast<signed char *>(out), stats, stream);
+    return launch_requant_q<32768>(static_cast<const float2 *>(in), n, k, static_cast<short *>(out), stats, stream);
+}
+
 }  // namespace irdm

@@ -28,7 +28,28 @@ struct irdm_frontend {
         // the feeder: outputs written but not fed yet lie at base[0 .. pend)
         float2 *base = nullptr;
         size_t room = 0, pend = 0;
+        // saving the band: slot sv_next is filled next; a busy slot holds sv_bytes bytes not handed to the sink yet
+        int sv_next = 0;
+        bool sv_busy[2] = { false, false };
+        size_t sv_bytes[2] = { 0, 0 };
+        uint64_t sv_samples = 0;
     } st;
+    // Saving the band (irdm_frontend_save; off: sink == nullptr and nothing below exists).  fe_emit requantises what its
+    // kernel wrote in pieces of at most slot_samples, each into one of two slots: device staging d[i] copied to the pinned
+    // h[i] on the copy stream (ev_k[i]: the piece is in d[i]; ev[i]: it is in h[i]), or, with `direct`, written by the
+    // kernel into h[i] itself.  A slot is handed to the sink, after its event, before it is filled again.
+    struct Save {
+        int format = 0, bytes_per_sample = 0;
+        float gain = 1.0f, k = 0.0f;
+        size_t slot_samples = 0;
+        irdm_band_sink_t sink = nullptr;
+        void *user = nullptr;
+        bool direct = false;
+        void *h[2] = { nullptr, nullptr }, *d[2] = { nullptr, nullptr };
+        hipEvent_t ev[2] = { nullptr, nullptr }, ev_k[2] = { nullptr, nullptr };
+        hipStream_t copy = nullptr;
+        unsigned long long *d_stats = nullptr;      // launch_requant's three words
+    } sv;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

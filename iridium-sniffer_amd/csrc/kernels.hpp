@@ -230,6 +230,10 @@ int launch_frontend(int D, const FrontendArgs &a, const float *hr, const float *
                     unsigned long long *kclk);
 int launch_frontend_tail(const void *tail, long long n_tail, const void *in, long long n_in, long long from, int n_new, int bps,
                          void *out, hipStream_t stream);
+// the requantiser (requant_kernel): n cf32 samples -> interleaved int8 (bits 8) or int16 (bits 16) pairs, q = clamp(rintf(x k),
+// -S, S - 1), NaN -> 0; stats[0 .. 3) (64-bit words: components, clipped components, the largest bit pattern of |x k| over
+// finite x) are added to.  in 8-byte, out sample aligned; n = 0 launches nothing.
+int launch_requant(int bits, const void *in, long long n, float k, void *out, unsigned long long *stats, hipStream_t stream);
 
 // resample.hip (K0r): the front end's rational mode, out = in * L / M.  The geometry of a launch and the host-laid tables
 // (resample_plan): per phase block a descriptor of kRsDesc ints and the rows of its tap table (kRsRow floats per step).

@@ -8,6 +8,7 @@
  *                         [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]]
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
+ *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -43,6 +44,14 @@
  * linear |X|^2).  --spectrum-frames R: frames per row, default round(rate / fft_size), about a second, at least 1.  stdout and
  * stderr are what they are without the flag.  With several recordings FILE must be `auto` and --out-dir given: each recording
  * leaves DIR/<basename>.spec.  --gpus N > 1 is refused.
+ * --save-band FILE (with --decimate or --resample-to): the selected band, every sample the front end produces, written to FILE
+ * beside the normal run (irdm_frontend_save) as a recording at the front end's output rate.  --save-format ci8|ci16|cf32, default
+ * by FILE's extension (options.c:536-542: .cf32 .fc32 .cfile / .ci16 .cs16 / .ci8); ci8 and ci16 are round(x * G * 128) and
+ * round(x * G * 32768), clipped to the format's range, --save-gain G (default 1, positive; cf32 takes 1 only).  A ci16 file
+ * holds all 16 bits: read it back with --format ci16-full.  stdout and stderr are what they are without the flag, except, with
+ * -v, a closing "saved band: ..." line that names the -r, -c and --format to read the file with, and, without -v, a warning
+ * when components clipped.  --save-only: nothing but the file -- no context, no lines (irdm_frontend_run_device).  With several
+ * recordings FILE must be `auto`, --out-dir given and --save-format named: each leaves DIR/<basename>.band.<format>.
  */
 #include <err.h>
 #include <errno.h>
@@ -381,6 +390,91 @@ static int format_of(const char *format, const char *path, size_t *bps)
     return IRDM_FMT_CI8;
 }
 
+static const char *base_of(const char *p);
+
+/* --save-band: its format by name (--save-format) or by the file's extension (options.c:536-542); -1: neither names one */
+static int save_format_of(const char *name, const char *path)
+{
+    const char *f = name ? name : ext_of(path);
+    if (!strcmp(f, "cf32") || (!name && (!strcmp(f, "fc32") || !strcmp(f, "cfile")))) return IRDM_FMT_CF32;
+    if (!strcmp(f, "ci16") || (!name && !strcmp(f, "cs16"))) return IRDM_FMT_CI16;
+    if (!strcmp(f, "ci8")) return IRDM_FMT_CI8;
+    return -1;
+}
+
+/* --save-band: the front end's sink.  A short write is remembered, reported once the recording ends, and the rest of the
+ * recording's bytes are dropped; the run itself goes on. */
+static struct { FILE *f; int failed; } g_band;
+
+static int band_sink(void *user, const void *bytes, size_t n)
+{
+    (void)user;
+    if (g_band.f && !g_band.failed && fwrite(bytes, 1, n, g_band.f) != n) g_band.failed = 1;
+    return 0;
+}
+
+static const char *save_name(int fmt) { return fmt == IRDM_FMT_CF32 ? "cf32" : (fmt == IRDM_FMT_CI16 ? "ci16" : "ci8"); }
+
+static int band_open(const char *save_band, const char *out_dir, const char *file, int fmt)
+{
+    char path[4608];
+    if (!strcmp(save_band, "auto")) snprintf(path, sizeof path, "%s/%s.band.%s", out_dir, base_of(file), save_name(fmt));
+    else snprintf(path, sizeof path, "%s", save_band);
+    g_band.failed = 0;
+    g_band.f = fopen(path, "wb");
+    if (!g_band.f) { perror(path); return -1; }
+    return 0;
+}
+
+/* the recording is complete: close it, say what went wrong or, with -v, what was written.  0 ok, 1 the file is not whole */
+static int band_close(irdm_frontend_t *fe, const char *file, int fmt, float gain, int verbose, double centre)
+{
+    int rc = g_band.failed;
+    if (fclose(g_band.f) != 0) rc = 1;
+    g_band.f = NULL;
+    if (rc) fprintf(stderr, "--save-band: %s: writing the band failed\n", file);
+    irdm_band_stats_t st;
+    if (irdm_frontend_save_stats(fe, &st) != 0) { fprintf(stderr, "--save-band: %s: no statistics\n", file); return 1; }
+    if (verbose)
+        fprintf(stderr, "saved band: %llu samples %s gain %g, peak %.4f of full scale, %llu components clipped; read with -r %d -c %.17g --format %s\n",
+                (unsigned long long)st.n_samples, save_name(fmt), (double)gain, (double)st.peak, (unsigned long long)st.n_clipped,
+                irdm_frontend_out_rate(fe), centre, fmt == IRDM_FMT_CI16 ? "ci16-full" : save_name(fmt));
+    else if (st.n_clipped)
+        fprintf(stderr, "--save-band: %s: %llu of %llu components clipped at gain %g (peak %.4f of full scale)\n", file,
+                (unsigned long long)st.n_clipped, 2ULL * (unsigned long long)st.n_samples, (double)gain, (double)st.peak);
+    return rc;
+}
+
+/* --save-only: every recording through the stage-level entries -- no context, no lines.  step: capture samples per read,
+ * cap: the outputs a read can complete. */
+static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char *out_dir, int fmt, float gain, int verbose,
+                         double centre, size_t step, size_t bps, size_t cap)
+{
+    void *h_in = irdm_host_alloc(step * bps), *d_in = irdm_device_alloc(0, step * bps), *d_out = irdm_device_alloc(0, cap * 8);
+    int rc_all = 0;
+    if (!h_in || !d_in || !d_out) { fprintf(stderr, "--save-only: allocating the buffers failed\n"); return 1; }
+    for (int fi = 0; fi < g_n_in; fi++) {
+        const char *file = g_in[fi].path;
+        FILE *f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
+        int rc = 0;
+        if (!f) { perror(file); rc_all = 1; continue; }
+        if (fi > 0 && irdm_frontend_reset(fe) != 0) { fprintf(stderr, "%s: the front end could not be reset\n", file); rc_all = 1; break; }
+        if (band_open(save_band, out_dir, file, fmt) != 0) { if (f != stdin) fclose(f); rc_all = 1; continue; }
+        for (;;) {
+            const size_t r = fread(h_in, bps, step, f);
+            if (r == 0) break;
+            if (irdm_device_upload(d_in, h_in, r * bps) != 0 || irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
+            if (r < step) break;
+        }
+        if (rc == 0 && irdm_frontend_finish_device(fe, d_out, cap, NULL) < 0) rc = 1;
+        if (rc) fprintf(stderr, "%s: GPU processing failed\n", file);
+        if (band_close(fe, file, fmt, gain, verbose, centre) != 0) rc = 1;
+        if (f != stdin) fclose(f);
+        if (rc) rc_all = 1;
+    }
+    return rc_all;
+}
+
 static const char *base_of(const char *p)
 {
     const char *s = strrchr(p, '/');
@@ -412,6 +506,9 @@ int main(int argc, char **argv)
     int rs_l = 0, rs_m = 0;
     const char *spectrum = NULL;           /* --spectrum FILE | auto */
     int spectrum_frames = 0;               /* --spectrum-frames R (0: about a second) */
+    const char *save_band = NULL, *save_format = NULL;     /* --save-band FILE | auto, --save-format */
+    double save_gain = 1.0;
+    int save_gain_given = 0, save_only = 0, save_fmt = -1;
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -471,6 +568,19 @@ int main(int argc, char **argv)
             spectrum_frames = atoi(NEXT());
             if (spectrum_frames < 1 || spectrum_frames > (1 << 20)) { fprintf(stderr, "--spectrum-frames: 1 .. 1048576 frames per row\n"); return 2; }
         }
+        else if (!strcmp(a, "--save-band")) save_band = NEXT();
+        else if (!strcmp(a, "--save-format")) save_format = NEXT();
+        else if (!strcmp(a, "--save-gain")) {
+            char *end;
+            const char *v = NEXT();
+            save_gain = strtod(v, &end);
+            save_gain_given = 1;
+            if (end == v || *end || !(save_gain > 0) || !(save_gain <= 3.0e38) || !((float)save_gain > 0)) {
+                fprintf(stderr, "--save-gain %s: a positive finite number\n", v);
+                return 2;
+            }
+        }
+        else if (!strcmp(a, "--save-only")) save_only = 1;
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -485,7 +595,7 @@ int main(int argc, char **argv)
         }
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -536,6 +646,38 @@ int main(int argc, char **argv)
         gpus = 0;
     } else if (spectrum_frames) {
         fprintf(stderr, "--spectrum-frames goes with --spectrum FILE\n");
+        return 2;
+    }
+    if (save_band) {
+        if (!decimate && !resample_to) {
+            fprintf(stderr, "--save-band saves the band a front end selects: give --band-center / --decimate or --resample-to\n");
+            return 2;
+        }
+        const int many = g_n_in > 1 || !strcmp(save_band, "auto");
+        if (many && (strcmp(save_band, "auto") != 0 || !out_dir)) {
+            fprintf(stderr, "--save-band with several recordings: give --save-band auto and --out-dir DIR (DIR/<basename>.band.<format> each)\n");
+            return 2;
+        }
+        if (many && !save_format) {
+            fprintf(stderr, "--save-band auto: name the format with --save-format ci8|ci16|cf32\n");
+            return 2;
+        }
+        save_fmt = save_format_of(save_format, save_band);
+        if (save_fmt < 0) {
+            if (save_format) fprintf(stderr, "--save-format %s: ci8, ci16 or cf32\n", save_format);
+            else fprintf(stderr, "--save-band %s: the extension names no format (.ci8, .ci16, .cs16, .cf32, .fc32, .cfile); give --save-format\n", save_band);
+            return 2;
+        }
+        if (save_fmt == IRDM_FMT_CF32 && (float)save_gain != 1.0f) {
+            fprintf(stderr, "--save-gain %g: a cf32 recording holds the samples as they are (gain 1)\n", save_gain);
+            return 2;
+        }
+        if (save_fmt != IRDM_FMT_CF32 && !((float)save_gain * (save_fmt == IRDM_FMT_CI8 ? 128.0f : 32768.0f) <= 3.0e38f)) {
+            fprintf(stderr, "--save-gain %g: too large\n", save_gain);
+            return 2;
+        }
+    } else if (save_format || save_gain_given || save_only) {
+        fprintf(stderr, "--save-format, --save-gain and --save-only go with --save-band FILE\n");
         return 2;
     }
     size_t bps = 2;
@@ -604,6 +746,25 @@ int main(int argc, char **argv)
     c.max_chunk_samples = chunk;
     c.pipeline_depth = depth;
     if (gpus < 0 || gpus > 64) { fprintf(stderr, "--gpus %d\n", gpus); return 2; }
+    if (save_band) {
+        irdm_frontend_save_config_t sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.format = save_fmt;
+        sc.gain = (float)save_gain;
+        sc.sink = band_sink;
+        if (irdm_frontend_save(fe, &sc) != 0) {
+            fprintf(stderr, "--save-band: the library refused the recording\n");
+            return 1;
+        }
+    }
+    if (save_only) {
+        const size_t so_step = resample_to ? (chunk * (size_t)rs_m + (size_t)rs_l - 1) / (size_t)rs_l : chunk * (size_t)decimate;
+        if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { perror(out_dir); return 1; }
+        const int rc = save_only_run(fe, save_band, out_dir, save_fmt, (float)save_gain, verbose, c.center_frequency, so_step, bps,
+                                     chunk + (size_t)irdm_frontend_ntaps(fe) + 64);
+        fflush(stderr);
+        _exit(rc);
+    }
     if (gpus > irdm_device_count()) {
         fprintf(stderr, "--gpus %d: this host has %d GPU%s\n", gpus, irdm_device_count(), irdm_device_count() == 1 ? "" : "s");
         return 2;
@@ -713,6 +874,13 @@ int main(int argc, char **argv)
                 continue;
             }
         }
+        if (save_band && band_open(save_band, out_dir, file, save_fmt) != 0) {
+            if (g_spec) { fclose(g_spec); g_spec = NULL; }
+            if (out_dir) { fclose(g_out); g_out = stdout; }
+            fclose(f);
+            rc_all = 1;
+            continue;
+        }
         /* the host-side objects of a recording: its line printer's t0, its IDA reassembly and ACARS state, its solver */
         if (acars) {
             irdm_acars_config_t ac;
@@ -820,6 +988,7 @@ int main(int argc, char **argv)
             char st[512];
             if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */
         }
+        if (save_band && band_close(fe, file, save_fmt, (float)save_gain, verbose, c.center_frequency) != 0) rc = 1;
         if (rc) rc_all = 1;
         if (fi + 1 == g_n_in) break;        /* (the last recording's objects go with the process, below) */
         if (out_dir) { fclose(g_out); g_out = stdout; }

@@ -146,6 +146,20 @@ class FrontendRationalConfig(C.Structure):
                 ("shift_hz", C.c_double)]
 
 
+BAND_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
+
+
+class FrontendSaveConfig(C.Structure):
+    """irdm_frontend_save_config_t: the band as a recording (csrc/frontend.cpp)"""
+    _fields_ = [("format", C.c_int), ("gain", C.c_float), ("slot_samples", C.c_size_t), ("sink", BAND_SINK),
+                ("user", C.c_void_p)]
+
+
+class BandStats(C.Structure):
+    """irdm_band_stats_t"""
+    _fields_ = [("n_samples", C.c_uint64), ("n_clipped", C.c_uint64), ("peak", C.c_float)]
+
+
 ACARS_LINE_MAX = 8192
 RAW_LINE_MAX = 1280
 _lib = None
@@ -338,6 +352,11 @@ def lib():
             if hasattr(L, "irdm_frontend_reset"):
                 L.irdm_frontend_reset.argtypes = [C.c_void_p]
             L.irdm_frontend_kernel_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
+            if hasattr(L, "irdm_frontend_save"):
+                L.irdm_frontend_save.argtypes = [C.c_void_p, C.POINTER(FrontendSaveConfig)]
+                L.irdm_frontend_save_stats.argtypes = [C.c_void_p, C.POINTER(BandStats)]
+                L.irdm_requantize_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.POINTER(BandStats),
+                                                     C.c_int, C.c_void_p]
             if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
                 L.irdm_frontend_create_rational.restype = C.c_void_p
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
@@ -383,6 +402,16 @@ def device_download(array, ptr):
 
 def device_free(ptr):
     lib().irdm_device_free(ptr)
+
+
+def requantize_device(d_in, n, fmt, gain, d_out, device=0, stream=None):
+    """irdm_requantize_device: n cf32 samples at the device address d_in -> d_out as ci8 / ci16 (FMT_CI16: all 16 bits) / cf32;
+    returns (n_samples, n_clipped, peak) of this call"""
+    st = BandStats()
+    if lib().irdm_requantize_device(C.c_void_p(d_in), n, fmt, float(gain), C.c_void_p(d_out), C.byref(st), device,
+                                    C.c_void_p(stream or 0)) != 0:
+        raise RuntimeError("irdm_requantize_device failed")
+    return int(st.n_samples), int(st.n_clipped), np.float32(st.peak)
 
 
 def host_free(ptr):
@@ -843,6 +872,33 @@ class Frontend:
         if rc < 0:
             raise RuntimeError("irdm_frontend_flush failed")
         return rc
+
+    def save(self, fmt, sink=None, gain=1.0, slot_samples=0):
+        """irdm_frontend_save: the band as a ci8 / ci16 / cf32 recording.  sink(bytes) is called with each piece in stream
+        order (return a true value to stop); without one the pieces collect in self.saved.  fmt None: saving off."""
+        if fmt is None:
+            if self.L.irdm_frontend_save(self.h, None) != 0:
+                raise RuntimeError("irdm_frontend_save failed")
+            self._sink = None
+            return
+        saved = []
+        take = sink if sink is not None else saved.append
+
+        def call(user, ptr, n):
+            return 1 if take(C.string_at(ptr, n)) else 0
+        cb = BAND_SINK(call)
+        cfg = FrontendSaveConfig(fmt, float(gain), int(slot_samples), cb, None)
+        if self.L.irdm_frontend_save(self.h, C.byref(cfg)) != 0:
+            raise RuntimeError("irdm_frontend_save failed (mid-stream, or a bad field)")
+        self.saved = saved
+        self._sink = cb              # (the library calls it for as long as the front end lives)
+
+    def save_stats(self):
+        """irdm_frontend_save_stats: (n_samples, n_clipped, peak as a fraction of full scale)"""
+        st = BandStats()
+        if self.L.irdm_frontend_save_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_frontend_save_stats failed")
+        return int(st.n_samples), int(st.n_clipped), np.float32(st.peak)
 
     def kernel_clock(self, reset=False):
         """(sum of K0's device spans in ms, launches) since the last reset"""
