@@ -69,9 +69,19 @@ int gpu_burst_fft_process_device(gpu_burst_fft_t *g, const void *d_input, void *
  * Contract: a context in either format produces exactly -- bit for bit, not within a tolerance -- the records (bursts,
  * frames, demods with their LLRs, packed, parsed and frame records) of an IRDM_FMT_CF32 context fed the same samples
  * converted to float and multiplied by the scale: int16 -> float is exact, and the power-of-two scale keeps every
- * product exact and far from the subnormal range.  irdm_create refuses any format outside 0..4. */
+ * product exact and far from the subnormal range. */
 #define IRDM_FMT_CI16_FULL 3
 #define IRDM_FMT_SC16Q11   4
+/* rtl_sdr's files: unsigned 8-bit I/Q in offset binary, 2 bytes per sample, interleaved I, Q.
+ *   IRDM_FMT_CU8        ((float)u - 127.5f) / 128.0f = (2u - 255) / 256, every step exact
+ * 127.5 is the converter's mid-scale: with 128 every recording would carry a constant half-LSB DC term, which behind a band
+ * selected off centre is a tone inside the band.  The same contract as formats 3 and 4: a cu8 context produces, bit for
+ * bit, every record queue of an IRDM_FMT_CF32 context fed the converted samples.  The reference has no such input, so
+ * the reference-shaped burst_detector_feed of irdm_compat.h does not take it.
+ * The code is 6: irdm_create and both front ends refuse every format outside {0, 1, 2, 3, 4, 6}, and 5 and 7 in
+ * particular stay refused ("unknown sample format N") -- callers and tests rely on those two as the unknown formats
+ * next to the known ones. */
+#define IRDM_FMT_CU8       6
 
 typedef struct {
     double center_frequency;   /* -c, burst_config_t.center_frequency (burst_detect.h:52) */
@@ -268,6 +278,23 @@ typedef struct {
     uint32_t n_frames;         /* frames in the row: R, or fewer in the row irdm_flush closed */
     uint32_t n_bins;           /* irdm_spectrum_bins */
 } irdm_spectrum_row_t;
+
+/* option "input_stats": what the raw samples of the input say about the recording (irdm_input_stats).  x is the converted
+ * value, exactly as the pipeline's load stage gives it; a component "at a rail" holds the file code the converter clips to:
+ *   ci8 -128 / 127;  cu8 0 / 255;  ci16 and ci16-full -32768 / 32767;  sc16q11 v <= -2048 / v >= 2047;  cf32 x <= -1 / x >= 1.
+ * Plain ci16: rails and code_min / code_max are taken on the 16-bit code v, sum / sum_sq / abs_max on the narrowed value
+ * (v >> 8) / 128 the pipeline sees -- a 12-bit recording read as ci16 reports an RMS of a fraction of an LSB, which is true.
+ * Integer formats: x = c * 2^-k with an integer c; the sums of c and c^2 are kept as integers and sum / sum_sq formed from
+ * the totals with one rounding, so these fields and every count do not depend on how the stream was cut into chunks.
+ * cf32: sum / sum_sq are double sums of the exact x and x^2 over the finite components, reproducible for a given cut. */
+typedef struct {
+    uint64_t n_samples;
+    uint64_t n_rail_lo[2], n_rail_hi[2];  /* [0] = I, [1] = Q: components at the format's negative / positive rail */
+    uint64_t n_nonfinite[2];              /* cf32: NaN or Inf; left out of everything below */
+    int32_t  code_min[2], code_max[2];    /* integer formats: extreme file codes seen; 0 for cf32 */
+    double   sum[2], sum_sq[2];           /* of the converted value x, as load_iq gives it */
+    float    abs_max[2];                  /* max |x| over finite components */
+} irdm_input_stats_t;
 
 typedef struct irdm_pipeline irdm_pipeline_t;
 
@@ -572,6 +599,11 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         chunk and three pinned buffers of that size are allocated when the option is first set to a non-zero
  *                         value, never before.  -1 for a value out of range, for a member of a group (and so through
  *                         irdm_group_set_option), and between a stream's first irdm_feed_begin and irdm_reset
+ *   "input_stats"         0/1, default 0: one reduction pass over the raw samples of every chunk fed from then on, see
+ *                         irdm_input_stats.  A side stream, four small device blocks and their pinned copies are allocated
+ *                         when the option is first set to 1, never before.  -1 for a member of a group (and so through
+ *                         irdm_group_set_option) and while a chunk handed over with irdm_feed_begin waits for its
+ *                         irdm_feed_end
  *   "decode_frames" / "decode_ida"   0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
  *   "fir_order" (alias "simd_order")   default 1 = the arithmetic of the reference's AVX2 kernels, simd_avx2.c -- what
@@ -905,6 +937,20 @@ int irdm_frontend_save_stats(irdm_frontend_t *fe, irdm_band_stats_t *out);      
  * statistics of this call alone (stats may be NULL); stream NULL = synchronous (an integer format waits for the stream in
  * either case: the statistics are read back).  0 ok, -1 error. */
 int irdm_requantize_device(const void *d_in, size_t n, int format, float gain, void *d_out, irdm_band_stats_t *stats, int device, void *stream);
+
+/* ---- input statistics (irdm_input_stats_t above) ----
+ * irdm_set_option(p, "input_stats", 1): every chunk fed from then on is reduced by one extra pass on a side stream of the
+ * context (one read of the chunk, beside K1; no record changes).  irdm_input_stats: the statistics of the stream so far --
+ * what is in flight is settled first, like irdm_detector_stats.  irdm_reset starts them over; they are not part of
+ * irdm_export_state.  Returns 0, or -1 (the option is off included).
+ * The front end has the same switch and getter over the CAPTURE's samples in front of its kernel: clipping is a property of
+ * the recording, not of the selected band.  irdm_frontend_reset starts them over.
+ * Stage level: the statistics of the n samples of `format` at d_in (device memory, aligned to a sample) alone; the pass runs
+ * on `stream` (NULL: a stream of its own) and the call is synchronous on return. */
+int irdm_input_stats(irdm_pipeline_t *p, irdm_input_stats_t *out);
+int irdm_frontend_input_stats_enable(irdm_frontend_t *fe, int on);
+int irdm_frontend_input_stats(irdm_frontend_t *fe, irdm_input_stats_t *out);
+int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_stats_t *out, int device, void *stream);
 
 /* The fine-CFO step's cexpf(i x) (burst_downmix.c:716-717) as the device evaluates it -- glibc's sincosf restated,
  * csrc/libm_port.hpp -- for n arbitrary arguments (test / audit surface: tests/test_gpu_libm.py,

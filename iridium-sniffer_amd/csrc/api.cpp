@@ -8,6 +8,8 @@ namespace irdmh {
 extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
 {
     if (!p || !key) return -1;
+    // (several keys allocate or launch: on the context's device, whichever device the calling thread was on)
+    pipeline_enter(p);
     // ---- what a caller chooses (include/irdm_hip.h documents every key) ----
     if (!strcmp(key, "keep_frame_samples")) { p->keep_frame_samples = value; return 0; }
     if (!strcmp(key, "packed_records")) { p->packed_records = value; return 0; }
@@ -19,6 +21,12 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         // rows of `value` frames (0: off); not for a member of a group, and not between a stream's first feed and irdm_reset
         if (value < 0 || value > (1 << 20) || p->in_group || p->st.begin_no != 0) return -1;
         return spectrum_configure(p, value);
+    }
+    if (!strcmp(key, "input_stats")) {
+        // 0 / 1; not for a member of a group (it is fed its chunk with the overlap in front: those samples would count twice),
+        // and not while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
+        if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
+        return input_stats_configure(p, value);
     }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }

@@ -16,6 +16,7 @@ SampleSource make_source(const irdm_pipeline *p, const void *chunk, uint64_t c0,
     s.ring_len = p->ring_len;
     s.ref_ring = p->ref_ring;
     s.fmt = p->dev_fmt;
+    s.n_cu = p->n_cu;
     return s;
 }
 

@@ -207,22 +207,30 @@ __host__ __device__ __forceinline__ unsigned bitrev(unsigned v, int bits)
 //   fmt 1: ci16, narrowed to int8 by (int8_t)(v >> 8) (spewer_thread, main.c:245-246), then as ci8
 //   fmt 3: ci16 at full precision, int16 * (1.0f / 32768.0f) (the SoapySDR CS16 live path, soapysdr.c:213-216)
 //   fmt 4: bladeRF SC16Q11, int16 * (1.0f / 2048.0f) (the bladeRF live path, bladerf.c:93-96)
-// Formats 3 and 4 are exact: int16 -> float is, and a power-of-two scale keeps every product a normal float, so a
-// context in either format computes what a cf32 context computes on v.astype(np.float32) * scale, bit for bit.
+//   fmt 6: cu8 (rtl_sdr's files: offset binary, one unsigned byte each), ((float)u - 127.5f) / 128.0f = (2u - 255) / 256,
+//          exact in every step (the reference has no such input; 127.5 is the converter's mid-scale -- with 128 every
+//          recording would carry a constant half-LSB DC term, a tone inside a band selected off centre)
+// (5 and 7 are no formats: tests pin irdm_create refusing 5 and the rational front end refusing 7)
+// Formats 3, 4 and 6 are exact: int16 -> float is, and a power-of-two scale keeps every product a normal float, so a
+// context in one of them computes what a cf32 context computes on the converted samples, bit for bit.
 template <int FMT>       // (FMT 3 or 4)
 __host__ __device__ __forceinline__ float i16_full(int v)
 {
     return (float)v * (FMT == 3 ? 1.0f / 32768.0f : 1.0f / 2048.0f);
 }
 
+__host__ __device__ __forceinline__ float cu8_f(int u) { return ((float)u - 127.5f) / 128.0f; }
+
 // bytes per sample of a device format
 template <int FMT>
-constexpr int kFmtBytes = FMT == 2 ? 8 : (FMT == 0 ? 2 : 4);
+constexpr int kFmtBytes = FMT == 2 ? 8 : ((FMT == 0 || FMT == 6) ? 2 : 4);
+constexpr bool fmt_valid(int fmt) { return (fmt >= 0 && fmt <= 4) || fmt == 6; }
+constexpr int fmt_bytes(int fmt) { return fmt == 2 ? 8 : ((fmt == 0 || fmt == 6) ? 2 : 4); }
 
 template <int FMT>
 __device__ __forceinline__ float2 load_iq(const void *__restrict__ iq, size_t i)
 {
-    static_assert(FMT >= 0 && FMT <= 4, "device sample format");
+    static_assert(fmt_valid(FMT), "device sample format");
     if (FMT == 2) {
         return reinterpret_cast<const float2 *>(iq)[i];
     } else if (FMT == 1) {
@@ -231,12 +239,15 @@ __device__ __forceinline__ float2 load_iq(const void *__restrict__ iq, size_t i)
     } else if (FMT == 3 || FMT == 4) {
         const short2 v = reinterpret_cast<const short2 *>(iq)[i];
         return make_float2(i16_full<FMT>(v.x), i16_full<FMT>(v.y));
+    } else if (FMT == 6) {
+        const unsigned v = reinterpret_cast<const unsigned short *>(iq)[i];      // I in the low byte
+        return make_float2(cu8_f((int)(v & 0xff)), cu8_f((int)(v >> 8)));
     } else {
         const char2 v = reinterpret_cast<const char2 *>(iq)[i];
         return make_float2((float)v.x / 128.0f, (float)v.y / 128.0f);
     }
 }
-// (irdm_create admits formats 0..4 only; anything else reads as NaN rather than as some other format)
+// (irdm_create admits formats 0..4 and 6 only; anything else reads as NaN rather than as some other format)
 __device__ __forceinline__ float2 load_iq(int fmt, const void *__restrict__ iq, size_t i)
 {
     switch (fmt) {
@@ -245,6 +256,7 @@ __device__ __forceinline__ float2 load_iq(int fmt, const void *__restrict__ iq, 
     case 3: return load_iq<3>(iq, i);
     case 4: return load_iq<4>(iq, i);
     case 0: return load_iq<0>(iq, i);
+    case 6: return load_iq<6>(iq, i);
     default: return make_float2(__builtin_nanf(""), __builtin_nanf(""));
     }
 }

@@ -70,6 +70,7 @@ void pipeline_free(irdm_pipeline *p)
         if (h) (void)hipHostFree(h);
     for (auto &e : p->ev_spec)
         if (e) (void)hipEventDestroy(e);
+    input_stats_pass_free(p->in_stats);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);
     for (float2 *q : p->rot_retired) (void)hipFree(q);
     for (float2 *q : p->scratch_retired) (void)hipFree(q);
@@ -177,13 +178,13 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
         delete p;
         return nullptr;
     }
-    if (cfg->format < IRDM_FMT_CI8 || cfg->format > IRDM_FMT_SC16Q11) {
+    if (!fmt_valid(cfg->format)) {
         fprintf(stderr, "irdm_hip: unknown sample format %d\n", cfg->format);
         delete p;
         return nullptr;
     }
     p->dev_fmt = cfg->format;
-    p->bps = p->dev_fmt == IRDM_FMT_CF32 ? 8 : (p->dev_fmt == IRDM_FMT_CI8 ? 2 : 4);
+    p->bps = (size_t)fmt_bytes(p->dev_fmt);
     p->max_chunk = cfg->max_chunk_samples ? cfg->max_chunk_samples : ((size_t)64 << 20);
     p->max_chunk = (p->max_chunk + p->feed_block - 1) / p->feed_block * p->feed_block;
     p->burst_cap = cfg->max_bursts_per_chunk > 0 ? cfg->max_bursts_per_chunk : 4096;
@@ -535,6 +536,7 @@ extern "C" irdm_pipeline_t *irdm_create(const irdm_config_t *cfg)
         const bool have = hipGetDeviceProperties(&prop, cfg->device) == hipSuccess;
         p->mc_auto = have && prop.multiProcessorCount >= 64;
         if (p->scan_cus == 0) p->scan_cus = have ? prop.multiProcessorCount : 1;
+        p->n_cu = have && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     }
     p->stat_fast_chunks = p->stat_fallbacks = p->stat_dense_frames = 0;
     p->stat_band_chunks = p->stat_band_rounds = p->stat_band_retries = p->stat_band_aborts = 0;

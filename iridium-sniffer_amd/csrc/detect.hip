@@ -7,11 +7,11 @@
 namespace irdm {
 
 // ---------------------------------------------------------------------------
-// K1: load (ci8 | ci16 | cf32, load_iq) -> Blackman/0.42 window -> N-point pinned FFT in LDS ->
+// K1: load (ci8 | cu8 | ci16 | cf32, load_iq) -> Blackman/0.42 window -> N-point pinned FFT in LDS ->
 //     fftshift -> |.|^2  (simd_window_cf + fftwf_execute + simd_fftshift_mag,
 //     burst_detect.c:679-687; opencl/burst_fft.c:52-80 window_multiply /
 //     fftshift_magnitude).  One workgroup per frame, grid-stride.
-//     HBM: 8 B (cf32), 4 B (the int16 formats) or 2 B (ci8) read + 4 B written per sample.
+//     HBM: 8 B (cf32), 4 B (the int16 formats) or 2 B (ci8, cu8) read + 4 B written per sample.
 // ---------------------------------------------------------------------------
 template <int LOGN, int NT, int FMT>
 __global__ __launch_bounds__(NT) void fft_mag_kernel(const void *__restrict__ iq,
@@ -277,6 +277,10 @@ __device__ __forceinline__ void load_pair(__amdgpu_buffer_rsrc_t r, int lane, in
         const short r0 = (short)(v.x & 0xffff), i0 = (short)(v.x >> 16), r1 = (short)(v.y & 0xffff), i1 = (short)(v.y >> 16);
         x0 = v2f{ i16_full<FMT>(r0), i16_full<FMT>(i0) };                    // load_iq<3>, load_iq<4>
         x1 = v2f{ i16_full<FMT>(r1), i16_full<FMT>(i1) };
+    } else if (FMT == 6) {
+        const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(r, lane * 4, soff, 2);
+        x0 = v2f{ cu8_f((int)(v & 0xff)), cu8_f((int)((v >> 8) & 0xff)) };    // load_iq<6>
+        x1 = v2f{ cu8_f((int)((v >> 16) & 0xff)), cu8_f((int)(v >> 24)) };
     } else {
         const int v = __builtin_amdgcn_raw_buffer_load_b32(r, lane * 4, soff, 2);
         const signed char r0 = (signed char)(v & 0xff), i0 = (signed char)((v >> 8) & 0xff);
@@ -551,6 +555,7 @@ static int launch_p32(int fmt, const void *iq, const float *window, const float2
     else if (fmt == 3) IRDM_LAUNCH_P32(3);
     else if (fmt == 4) IRDM_LAUNCH_P32(4);
     else if (fmt == 0) IRDM_LAUNCH_P32(0);
+    else if (fmt == 6) IRDM_LAUNCH_P32(6);
     else return -1;
 #undef IRDM_LAUNCH_P32
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -577,6 +582,7 @@ static int launch_r16(int fmt, const void *iq, const float *window, const float2
     else if (fmt == 3) IRDM_LAUNCH_R16(3);
     else if (fmt == 4) IRDM_LAUNCH_R16(4);
     else if (fmt == 0) IRDM_LAUNCH_R16(0);
+    else if (fmt == 6) IRDM_LAUNCH_R16(6);
     else return -1;
 #undef IRDM_LAUNCH_R16
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -589,7 +595,7 @@ int launch_fft_mag_lists(int log_n, int fmt, const void *iq, const float *window
                          hipStream_t stream, unsigned long long *kclk, int order)
 {
     if (n_frames <= 0) return 0;
-    if (fmt < 0 || fmt > 4) return -1;
+    if (!fmt_valid(fmt)) return -1;
     if (log_n < 12 || log_n > 14) return 1;
     if (log_n == 13) return launch_p32<13, true>(fmt, iq, window, tw, mag, n_frames, pre, counts, entries, cap, kclk, stream, order);
     if (log_n == 14) return launch_p32<14, true>(fmt, iq, window, tw, mag, n_frames, pre, counts, entries, cap, kclk, stream, order);
@@ -602,7 +608,7 @@ int launch_fft_mag(int log_n, int fmt, const void *iq, const float *window, cons
     if (n_frames <= 0) return 0;
     const int grid = n_frames < 4096 ? n_frames : 4096;
     const int f = fmt;
-    if (f < 0 || f > 4) return -1;
+    if (!fmt_valid(f)) return -1;
     if (log_n == 13) return launch_p32<13, false>(fmt, iq, window, tw, mag, n_frames, nullptr, nullptr, nullptr, 0, kclk, stream, order);
     if (log_n == 14) return launch_p32<14, false>(fmt, iq, window, tw, mag, n_frames, nullptr, nullptr, nullptr, 0, kclk, stream, order);
     if (log_n == 12) return launch_r16<12, false>(fmt, iq, window, tw, mag, n_frames, nullptr, nullptr, nullptr, 0, stream, order);
@@ -621,6 +627,7 @@ int launch_fft_mag(int log_n, int fmt, const void *iq, const float *window, cons
         else if (f == 3) IRDM_LAUNCH_FFT_F(LOGN, NT, 3);                                       \
         else if (f == 4) IRDM_LAUNCH_FFT_F(LOGN, NT, 4);                                       \
         else if (f == 0) IRDM_LAUNCH_FFT_F(LOGN, NT, 0);                                       \
+        else if (f == 6) IRDM_LAUNCH_FFT_F(LOGN, NT, 6);                                       \
         else return -1;                                                                        \
     } while (0)
     switch (log_n) {

@@ -124,6 +124,55 @@ static int spectrum_flush(irdm_pipeline *p)
     return spectrum_harvest(p, kSpecSlots);
 }
 
+// ---- option "input_stats": one reduction pass over the raw samples of every chunk (input_stats.hpp) ----
+
+int input_stats_configure(irdm_pipeline *p, int on)
+{
+    if (on && input_stats_pass_alloc(p->in_stats) != 0) return -1;
+    p->in_stats.on = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_input_stats(irdm_pipeline_t *p, irdm_input_stats_t *out)
+{
+    if (!p || !out || !p->in_stats.stream) return -1;
+    pipeline_enter(p);
+    if (input_stats_settle(p->in_stats, p->st.in_stats, p->dev_fmt, ~0ull) != 0) return -1;
+    input_stats_result(p->st.in_stats.run, p->dev_fmt, out);
+    return 0;
+}
+
+extern "C" int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_stats_t *out, int device, void *stream_v)
+{
+    if (!out || (!d_in && n) || !fmt_valid(format) || (reinterpret_cast<uintptr_t>(d_in) % (size_t)fmt_bytes(format)) != 0) return -1;
+    IRDM_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
+    void *d_block = nullptr;
+    std::vector<unsigned char> h(kIsBlockBytes);
+    InputStatsRun run;
+    int rc = 0;
+    if (!s) {
+        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
+        s = own;
+    }
+    if (hipMalloc(&d_block, kIsBlockBytes) != hipSuccess) rc = -1;
+    const size_t bps = (size_t)fmt_bytes(format);
+    for (size_t off = 0; rc == 0 && off < n; off += kIsMaxLaunch) {
+        const size_t piece = std::min(kIsMaxLaunch, n - off);
+        const int grid = launch_input_stats(format, static_cast<const char *>(d_in) + off * bps, piece, d_block, s);
+        if (grid < 0 || hipMemcpyAsync(h.data(), d_block, kIsBlockBytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            rc = -1;
+            break;
+        }
+        input_stats_fold(run, format, h.data(), grid, piece);
+    }
+    if (d_block) (void)hipFree(d_block);
+    if (own) (void)hipStreamDestroy(own);
+    if (rc == 0) input_stats_result(run, format, out);
+    return rc;
+}
+
 extern "C" int irdm_spectrum_bins(const irdm_pipeline_t *p) { return p ? p->P.n : -1; }
 
 extern "C" int irdm_poll_spectrum(irdm_pipeline_t *p, irdm_spectrum_row_t *hdr, float *mean, float *peak, int max)
@@ -234,6 +283,7 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
     IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
     if (p->stream != p->fstream) IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     if (p->stream_spec) IRDM_HIP_CHECK(hipStreamSynchronize(p->stream_spec));
+    if (p->in_stats.stream) IRDM_HIP_CHECK(hipStreamSynchronize(p->in_stats.stream));   // (its totals go with the stream state)
     for (int i = 0; i < p->n_bc; i++) {
         BatchCtx &b = p->bc[i];
         IRDM_HIP_CHECK(hipStreamSynchronize(b.stream));
@@ -303,6 +353,11 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     const DetParams &P = p->P;
     const uint64_t c0 = p->st.begun_samples, c1 = c0 + n_samples;
     const int n_frames = (int)(n_samples / (size_t)P.n);
+    // option "input_stats": the chunk's pass, on its side stream behind the chunk's arrival (settled by this chunk's
+    // irdm_feed_end, before the caller may overwrite d_iq)
+    if (p->in_stats.on &&
+        input_stats_enqueue(p->in_stats, p->st.in_stats, p->dev_fmt, d_iq, n_samples, caller, p->st.begin_no) != 0)
+        return -1;
 
     // K1 of this chunk.  pipeline_depth 1: on its own stream and into the other magnitude buffer, while the detector
     // scan of the previous chunk may still be running
@@ -443,6 +498,9 @@ extern "C" int irdm_feed_end(irdm_pipeline_t *p)
         IRDM_HOST_PHASE(5);
 #undef IRDM_HOST_PHASE
     }
+    if (!p->st.in_stats.pending.empty() &&
+        input_stats_settle(p->in_stats, p->st.in_stats, p->dev_fmt, p->st.end_no) != 0)
+        return -1;
     p->st.chunk_no++;
     p->st.end_no++;
     p->st.total_samples = c1;

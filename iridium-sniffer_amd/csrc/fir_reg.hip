@@ -91,6 +91,14 @@ __device__ __forceinline__ void load_piece(const void *__restrict__ base, size_t
                 x[4 * u + k] = v2f{ i16_full<FMT>(re), i16_full<FMT>(im) };
             }
         }
+    } else if (FMT == 6) {
+        const int4 v = *reinterpret_cast<const int4 *>(reinterpret_cast<const unsigned short *>(base) + idx);   // 8 samples per 16 B
+        const unsigned w[4] = { (unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w };
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            x[2 * k] = v2f{ cu8_f((int)(w[k] & 0xff)), cu8_f((int)((w[k] >> 8) & 0xff)) };
+            x[2 * k + 1] = v2f{ cu8_f((int)((w[k] >> 16) & 0xff)), cu8_f((int)(w[k] >> 24)) };
+        }
     } else {
         const int4 v = *reinterpret_cast<const int4 *>(reinterpret_cast<const char2 *>(base) + idx);    // 8 samples per 16 B
         const int w[4] = { v.x, v.y, v.z, v.w };
@@ -522,19 +530,15 @@ static int launch_fir_f_fmt(const SampleSource &src, const FirGeom *geom, int n_
     // 0.55 -> 0.41 / 0.40 ms, the step 1.09 -> 1.06-1.09 / 1.08 ms against one workgroup per strip, whose short-lived waves
     // (40 000 per chunk) lose every freed slot to the higher-priority streams; five and six per CU again in round 6: 70.2 /
     // 72.7 against 74.1-74.4 Gsamples/s (profiles/r6_option_ab.json).
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu <= 0) n_cu = 256;
-    }
+    // (n_cu: the context's device, SampleSource::n_cu)
+    const int n_cu = src.n_cu > 0 ? src.n_cu : 256;
     const int grid = 7 * n_cu < n_tiles ? 7 * n_cu : n_tiles;
     if (src.fmt == 2) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 2>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 1) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 1>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 3) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 3>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 4) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 4>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 0) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 0>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 6) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 6>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -560,6 +564,7 @@ static int launch_fir_r_fmt(const SampleSource &src, const FirGeom *geom, int n_
     else if (src.fmt == 3) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 3>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 4) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 4>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 0) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 0>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 6) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 6>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -35,6 +35,7 @@ void fe_free(irdm_frontend *fe)
     (void)hipSetDevice(fe->cfg.device);
     if (fe->stream) (void)hipStreamSynchronize(fe->stream);
     fe_save_off(fe);
+    input_stats_pass_free(fe->is);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
@@ -83,7 +84,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *c
         fprintf(stderr, "irdm_hip: front end: sample rate %d is not a multiple of the decimation %d\n", cfg->in_rate, cfg->decim);
         return nullptr;
     }
-    if (cfg->in_format < IRDM_FMT_CI8 || cfg->in_format > IRDM_FMT_SC16Q11) {
+    if (!fmt_valid(cfg->in_format)) {
         fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
         return nullptr;
     }
@@ -113,7 +114,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *c
     fe->M = cfg->decim;
     fe->launch = fe_launch_k0;
     fe->fmt = cfg->in_format;
-    fe->bps = fe->fmt == IRDM_FMT_CF32 ? 8 : (fe->fmt == IRDM_FMT_CI8 ? 2 : 4);
+    fe->bps = fmt_bytes(fe->fmt);
     fe->out_rate = out_rate;
     fe->q = q;
     fe->taps = design_lpf(1.0f, (float)cfg->in_rate, 0.5f * (float)out_rate, 0.09f * (float)out_rate);
@@ -265,6 +266,41 @@ static int fe_commit(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream
     return 0;
 }
 
+// ---- input statistics: the capture's samples in front of the kernel ----
+
+// the pass over the chunk that has arrived on s, on the side stream
+static int fe_stats_enqueue(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream_t s)
+{
+    if (!fe->is.on || !n_in) return 0;
+    return input_stats_enqueue(fe->is, fe->st.is, fe->fmt, d_in, n_in, s, fe->st.is.launches);
+}
+
+// s goes on behind that pass: what s records or runs next may hand the chunk's memory back
+static int fe_stats_join(irdm_frontend *fe, size_t n_in, hipStream_t s)
+{
+    if (!fe->is.on || !n_in || fe->st.is.last_slot < 0) return 0;
+    IRDM_HIP_CHECK(hipStreamWaitEvent(s, fe->is.ev[fe->st.is.last_slot], 0));
+    return 0;
+}
+
+extern "C" int irdm_frontend_input_stats_enable(irdm_frontend_t *fe, int on)
+{
+    if (!fe) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (on && input_stats_pass_alloc(fe->is) != 0) return -1;
+    fe->is.on = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_frontend_input_stats(irdm_frontend_t *fe, irdm_input_stats_t *out)
+{
+    if (!fe || !out || !fe->is.stream) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (input_stats_settle(fe->is, fe->st.is, fe->fmt, ~0ull) != 0) return -1;
+    input_stats_result(fe->st.is.run, fe->fmt, out);
+    return 0;
+}
+
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
@@ -274,8 +310,10 @@ extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d
     if (n > out_cap) return -1;
     (void)hipSetDevice(fe->cfg.device);
     hipStream_t s = stream_v ? static_cast<hipStream_t>(stream_v) : fe->stream;
+    if (fe_stats_enqueue(fe, d_in, n_in, s) != 0) return -1;
     if (fe_emit(fe, d_in, n_in, m1, static_cast<float2 *>(d_out), s) != 0) return -1;
     if (fe_commit(fe, d_in, n_in, s) != 0) return -1;
+    if (fe_stats_join(fe, n_in, s) != 0) return -1;
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_in, s));
     if (!stream_v) IRDM_HIP_CHECK(hipStreamSynchronize(s));
     return (long long)n;
@@ -369,9 +407,11 @@ extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
         IRDM_HIP_CHECK(hipStreamWaitEvent(fe->stream, fe->ev_caller, 0));
     }
+    if (fe_stats_enqueue(fe, d_in, n_in, fe->stream) != 0) return -1;
     const int bursts = fe_pump(fe, p, d_in, n_in, fe_outputs(fe, fe->st.total + n_in, false), false);
     if (bursts < 0) return -1;
     if (fe_commit(fe, d_in, n_in, fe->stream) != 0) return -1;
+    if (fe_stats_join(fe, n_in, fe->stream) != 0) return -1;
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_in, fe->stream));
     return bursts;
 }
@@ -420,6 +460,7 @@ extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
     // saving: what the sink has not been given is dropped, the statistics start again; the sink and the slots stay
     if (fe->sv.copy) IRDM_HIP_CHECK(hipStreamSynchronize(fe->sv.copy));
     if (fe->sv.d_stats) IRDM_HIP_CHECK(hipMemset(fe->sv.d_stats, 0, 3 * sizeof(unsigned long long)));
+    if (fe->is.stream) IRDM_HIP_CHECK(hipStreamSynchronize(fe->is.stream));       // (the passes in flight are dropped with the state)
     fe->st = irdm_frontend::State{};
     return 0;
 }

@@ -118,6 +118,7 @@ __global__ __launch_bounds__(NT) void frontend_kernel(FrontendArgs a, const floa
         case 1: fe_stage_inside<1, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         case 3: fe_stage_inside<3, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         case 4: fe_stage_inside<4, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        case 6: fe_stage_inside<6, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         default: fe_stage_inside<0, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         }
     } else {
@@ -235,7 +236,7 @@ static int launch_frontend_d(const FrontendArgs &a, const float *hr, const float
 int launch_frontend(int D, const FrontendArgs &a, const float *hr, const float *G, const float2 *T, hipStream_t stream,
                     unsigned long long *kclk)
 {
-    if (a.ntaps < (kFeR - 1) * D + 1 || a.fmt < 0 || a.fmt > 4 || a.m1 < a.m0 || a.pos0 < 0) return -1;
+    if (a.ntaps < (kFeR - 1) * D + 1 || !fmt_valid(a.fmt) || a.m1 < a.m0 || a.pos0 < 0) return -1;
     switch (D) {
 #define FE_CASE(d) case d: return launch_frontend_d<d>(a, hr, G, T, stream, kclk);
     FE_CASE(2) FE_CASE(3) FE_CASE(4) FE_CASE(5) FE_CASE(6) FE_CASE(7) FE_CASE(8) FE_CASE(9) FE_CASE(10) FE_CASE(11)

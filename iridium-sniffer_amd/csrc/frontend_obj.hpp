@@ -33,6 +33,8 @@ struct irdm_frontend {
         bool sv_busy[2] = { false, false };
         size_t sv_bytes[2] = { 0, 0 };
         uint64_t sv_samples = 0;
+        // input statistics: the totals of the capture and the passes in flight (input_stats.hpp)
+        irdm::InputStatsStream is;
     } st;
     // Saving the band (irdm_frontend_save; off: sink == nullptr and nothing below exists).  fe_emit requantises what its
     // kernel wrote in pieces of at most slot_samples, each into one of two slots: device staging d[i] copied to the pinned
@@ -50,6 +52,8 @@ struct irdm_frontend {
         hipStream_t copy = nullptr;
         unsigned long long *d_stats = nullptr;      // launch_requant's three words
     } sv;
+    // irdm_frontend_input_stats_enable: the pass over the capture's samples in front of the kernel (cache; is.on the switch)
+    irdm::InputStatsPass is;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

@@ -138,6 +138,7 @@ struct SampleSource {
     uint64_t ring_len;
     uint64_t ref_ring;        // the REFERENCE's ring size (burst_detect.c:292-296): stale slot = a - ref_ring
     int fmt;                  // device sample format (IRDM_FMT_*, load_iq)
+    int n_cu;                 // compute units of the context's device (host side only: the resident decimator's grid)
 };
 
 // downmix.hip

@@ -36,6 +36,7 @@
 #include "band_core.hpp"
 #include "types.hpp"
 #include "record_queues.hpp"
+#include "input_stats.hpp"
 
 using namespace irdm;
 
@@ -223,6 +224,8 @@ struct StreamState {
     uint64_t spec_batches = 0;      // batches enqueued; pinned buffer = number % kSpecSlots
     std::deque<SpecBatch> spec_pending;
     std::deque<SpecRow> spec_q;
+    // option "input_stats": the totals of the stream's raw samples and the passes in flight (input_stats.hpp)
+    InputStatsStream in_stats;
 };
 
 struct irdm_pipeline {
@@ -230,7 +233,7 @@ struct irdm_pipeline {
     StreamState st;
     DetParams P;
     int dev_fmt;                // device sample format == cfg.format: 0 ci8, 1 ci16 (narrowed in the load stage,
-                                // main.c:245-246), 2 cf32, 3 ci16 full precision, 4 SC16Q11 (common.hpp load_iq)
+                                // main.c:245-246), 2 cf32, 3 ci16 full precision, 4 SC16Q11, 6 cu8 (common.hpp load_iq)
     size_t bps;                 // bytes per device sample
     int feed_block, decim, out_rate;
     bool dev_cfo;            // the fine-CFO libm step runs on the device (the port reproduces this host's cexpf)
@@ -298,6 +301,7 @@ struct irdm_pipeline {
     unsigned *d_mc_done;
     int mc_ops_cap, mc_updaters, mc_auto;
     int scan_cus;               // CUs the scan stream may use (its CU mask, or the whole device)
+    int n_cu = 0;               // compute units of cfg.device (the resident decimator's grid, fir_reg.hip)
     int scan_mode;              // 0 auto (sparse multi-CU where the device has the CUs, dense fallback), 1 dense only,
                                 // 2 sparse on one CU, 3 sparse multi-CU
     uint64_t stat_fast_chunks, stat_fallbacks, stat_dense_frames;
@@ -409,6 +413,9 @@ struct irdm_pipeline {
         float *b = d_spec_carry + (size_t)sel * 3 * (size_t)P.n;
         return SpectrumCarry{ b, b + P.n, b + 2 * (size_t)P.n };
     }
+    // option "input_stats" (feed.cpp, input_stats.hpp): the side stream and the blocks of the passes (cache: allocated when
+    // the option is first set); in_stats.on is the switch (configuration)
+    InputStatsPass in_stats;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -455,6 +462,7 @@ int process_bursts(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 
 // feed.cpp
 int spectrum_configure(irdm_pipeline *p, int R);
+int input_stats_configure(irdm_pipeline *p, int on);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

@@ -67,7 +67,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_ra
         ic.shift_hz = cfg->shift_hz;
         return irdm_frontend_create(&ic);
     }
-    if (cfg->in_format < IRDM_FMT_CI8 || cfg->in_format > IRDM_FMT_SC16Q11) {
+    if (!fmt_valid(cfg->in_format)) {
         fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
         return nullptr;
     }
@@ -100,7 +100,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_ra
     fe->M = (int)M;
     fe->launch = fe_launch_k0r;
     fe->fmt = cfg->in_format;
-    fe->bps = fe->fmt == IRDM_FMT_CF32 ? 8 : (fe->fmt == IRDM_FMT_CI8 ? 2 : 4);
+    fe->bps = fmt_bytes(fe->fmt);
     fe->out_rate = cfg->out_rate;
     fe->q = q;
     const float f_min = (float)std::min(cfg->in_rate, cfg->out_rate);

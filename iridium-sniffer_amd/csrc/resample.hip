@@ -206,6 +206,7 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
         case 1: rs_stage_inside<1>(a, g, v0, n_start, T, s, tid); break;
         case 3: rs_stage_inside<3>(a, g, v0, n_start, T, s, tid); break;
         case 4: rs_stage_inside<4>(a, g, v0, n_start, T, s, tid); break;
+        case 6: rs_stage_inside<6>(a, g, v0, n_start, T, s, tid); break;
         default: rs_stage_inside<0>(a, g, v0, n_start, T, s, tid); break;
         }
     } else {
@@ -344,7 +345,7 @@ static int launch_resample_r(const ResampleGeom &g, const FrontendArgs &a, const
 int launch_resample(const ResampleGeom &g0, const FrontendArgs &a, const int *desc, const float *G, const float2 *T,
                     hipStream_t stream, unsigned long long *kclk)
 {
-    if (a.fmt < 0 || a.fmt > 4 || a.m1 < a.m0 || a.m0 < 0 || a.pos0 < 0 || g0.L < 2 || g0.M < 2 || g0.nper < 1) return -1;
+    if (!fmt_valid(a.fmt) || a.m1 < a.m0 || a.m0 < 0 || a.pos0 < 0 || g0.L < 2 || g0.M < 2 || g0.nper < 1) return -1;
     if (a.m1 == a.m0) return 0;
     if (resample_lds_bytes(g0) > 160 * 1024) return -1;
     ResampleGeom g = g0;

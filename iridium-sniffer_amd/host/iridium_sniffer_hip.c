@@ -2,13 +2,14 @@
  * iridium_sniffer_hip.c -- file-mode command line over the MI355X hot path, plain C99.
  *
  * Mirrors the reference's file-mode surface (options.c:186-551, main.c:223-284, frame_output.c:160-199):
- *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB]
+ *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11] [-d DB]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
  *                         [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]]
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
+ *                         [--input-stats] [--diagnostic]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -17,7 +18,8 @@
  * path here (the reference's own --no-gpu binary is the CPU path).
  * --format ci16-full and --format sc16q11 read interleaved int16 at full precision, scaled as the reference's live
  * SoapySDR CS16 (v / 32768) and bladeRF SC16Q11 (v / 2048) paths scale it; ci16 (and a .ci16 / .cs16 file) is the
- * reference's file path, narrowed to 8 bits.
+ * reference's file path, narrowed to 8 bits.  --format cu8 (and a .cu8 / .u8 file) is rtl_sdr's unsigned 8-bit I/Q,
+ * (u - 127.5) / 128; the reference reads no such file.
  * --band-center HZ --decimate D (both or neither): the file is a wideband capture -- -r and -c describe it -- and the band
  * around HZ is shifted to the centre, low-passed and decimated by D (2 .. 16) on the GPU in front of the detector
  * (irdm_frontend_*): a 50 MS/s capture with --decimate 5 runs as a 10 MS/s stream centred at HZ (at the nearest multiple
@@ -52,9 +54,20 @@
  * -v, a closing "saved band: ..." line that names the -r, -c and --format to read the file with, and, without -v, a warning
  * when components clipped.  --save-only: nothing but the file -- no context, no lines (irdm_frontend_run_device).  With several
  * recordings FILE must be `auto`, --out-dir given and --save-format named: each leaves DIR/<basename>.band.<format>.
+ * --input-stats: one closing line per recording on stderr, after "tagged N bursts total" -- what the raw samples of the file
+ * say about the recording, reduced on the GPU (option "input_stats"; behind a front end: of the capture, not of the band):
+ *     input: N samples FMT; I dc %+.5f rms %.2f dBFS peak %.2f dBFS rails %llu (%.4f%%); Q ...; nonfinite %llu
+ * dBFS relative to |x| = 1, -inf where there is nothing to take a logarithm of; rails: components at the converter's
+ * negative or positive rail, and their share of N.  stdout and the rest of stderr are those of the run without the flag.
+ * --diagnostic: the reference's setup check (main.c:444-480) in file form.  Implies --input-stats, suppresses the RAW / IDA
+ * lines (frame_output.c:162, :205) and closes each recording with the reference's "Runtime: ... | Bursts: ... | Decoded: ...
+ * | Noise: ... | Peak: ..." line and its guidance clause; the elapsed time is the recording's stream time, samples / rate.
+ * Both work with --save-only (statistics without a context; no Runtime line: there is no detector) and are refused with
+ * --gpus N > 1.
  */
 #include <err.h>
 #include <errno.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -219,6 +232,55 @@ static irdm_group_t *g_group;
 #define irdm_poll_frame_packed(p, o, m) (g_group ? irdm_group_poll_frame_packed(g_group, o, m) : irdm_poll_frame_packed(p, o, m))
 #define irdm_poll_decoded(p, o, m) (g_group ? irdm_group_poll_decoded(g_group, o, m) : irdm_poll_decoded(p, o, m))
 
+/* --input-stats / --diagnostic */
+static int g_input_stats, g_diag;
+static unsigned long long g_n_demods;       /* frames the demodulator accepted, this recording */
+
+static const char *format_name(int fmt)
+{
+    switch (fmt) {
+    case IRDM_FMT_CF32: return "cf32";
+    case IRDM_FMT_CI16: return "ci16";
+    case IRDM_FMT_CI16_FULL: return "ci16-full";
+    case IRDM_FMT_SC16Q11: return "sc16q11";
+    case IRDM_FMT_CU8: return "cu8";
+    default: return "ci8";
+    }
+}
+
+/* the closing "input:" line of a recording */
+static void input_line(const irdm_input_stats_t *st, int fmt)
+{
+    const double n = (double)st->n_samples;
+    fprintf(stderr, "input: %llu samples %s;", (unsigned long long)st->n_samples, format_name(fmt));
+    for (int k = 0; k < 2; k++) {
+        const double fin = n - (double)st->n_nonfinite[k];
+        const double dc = fin > 0 ? st->sum[k] / fin : 0.0;
+        const double ms = fin > 0 ? st->sum_sq[k] / fin : 0.0;
+        const unsigned long long rails = (unsigned long long)(st->n_rail_lo[k] + st->n_rail_hi[k]);
+        fprintf(stderr, " %c dc %+.5f rms %.2f dBFS peak %.2f dBFS rails %llu (%.4f%%);", k ? 'Q' : 'I', dc,
+                ms > 0 ? 10.0 * log10(ms) : -INFINITY, st->abs_max[k] > 0 ? 20.0 * log10((double)st->abs_max[k]) : -INFINITY,
+                rails, n > 0 ? 100.0 * (double)rails / n : 0.0);
+    }
+    fprintf(stderr, " nonfinite %llu\n", (unsigned long long)(st->n_nonfinite[0] + st->n_nonfinite[1]));
+}
+
+/* --diagnostic: the reference's closing status line (main.c:444-480) over the recording's stream time */
+static void diagnostic_line(double elapsed, unsigned long det, unsigned long sub, float noise_floor, float peak_signal)
+{
+    const int runtime = (int)elapsed;
+    const double per_min = elapsed > 0 ? det * 60.0 / elapsed : 0;
+    const double ok_avg = det > 0 ? 100.0 * sub / det : 0;
+    fprintf(stderr, "Runtime: %02d:%02d:%02d  |  Bursts: %lu detected (%.1f/min)  |  Decoded: %lu (ok_avg: %.0f%%)  |  "
+                    "Noise: %.1f dBFS/Hz  |  Peak: %.1f dB  ",
+            runtime / 3600, runtime % 3600 / 60, runtime % 60, det, per_min, sub, ok_avg, noise_floor, peak_signal);
+    if (det == 0 && elapsed > 120) fprintf(stderr, "| No bursts detected - check antenna");
+    else if (ok_avg >= 70 && per_min >= 3) fprintf(stderr, "| Setup looks good (gap: %.1f dB)", peak_signal - noise_floor);
+    else if (ok_avg < 70 && det > 10) fprintf(stderr, "| Low decode rate - try adjusting gain");
+    else if (ok_avg >= 70 && per_min < 3 && elapsed > 60) fprintf(stderr, "| Good decode rate but low burst count");
+    fprintf(stderr, "\n");
+}
+
 /* --parsed (main.c:322-331): per frame the IDA line where ida_decode() succeeds, the RAW line otherwise */
 static int g_parsed;
 /* --acars / --acars-json (main.c:357-361): IDA reassembly, SBD and ACARS on the host for the whole stream; RAW lines are
@@ -246,6 +308,7 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         static irdm_frame_packed_t fp[256];
         while ((n = irdm_poll_demods_packed(p, dp, 256)) > 0) {
             long long len;
+            g_n_demods += (unsigned long long)n;
             if (g_dop) {
                 /* one compact frame_decode() record per compact frame record, decoded on the GPU (option frame_records) */
                 if (irdm_poll_frame_packed(p, fp, n) != n) { fprintf(stderr, "--position: frame records out of step\n"); exit(1); }
@@ -264,13 +327,14 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
             } else {
                 len = irdm_format_raw_packed_batch(dp, n, file_info, t0, line, cap);   /* one write per batch */
             }
-            if (len > 0) fwrite(line, 1, (size_t)len, g_out);
+            if (len > 0 && !g_diag) fwrite(line, 1, (size_t)len, g_out);
         }
     }
     static irdm_ida_t ida[256];
     static irdm_decoded_t dec[256];
     while ((n = irdm_poll_demods(p, d, 256)) > 0) {
         long long len = 0;
+        g_n_demods += (unsigned long long)n;
         if (g_dop) {
             /* the full-record path (--save-bursts): option decode_frames, one irdm_decoded_t per frame record */
             if (irdm_poll_decoded(p, dec, n) != n) { fprintf(stderr, "--position: frame records out of step\n"); exit(1); }
@@ -293,7 +357,7 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         } else {
             len = irdm_format_raw_batch(d, n, file_info, t0, line, cap);     /* one write per batch */
         }
-        if (len > 0) fwrite(line, 1, (size_t)len, g_out);
+        if (len > 0 && !g_diag) fwrite(line, 1, (size_t)len, g_out);
     }
     irdm_burst_t tmp[256];
     while (irdm_poll_bursts(p, tmp, 256) > 0) {}
@@ -387,6 +451,9 @@ static int format_of(const char *format, const char *path, size_t *bps)
      * autodetect above is the reference's */
     if (given && !strcmp(format, "ci16-full")) { *bps = 4; return IRDM_FMT_CI16_FULL; }
     if (given && !strcmp(format, "sc16q11")) { *bps = 4; return IRDM_FMT_SC16Q11; }
+    /* rtl_sdr's unsigned bytes: by --format, or by an extension the reference does not know (it would read such a file as
+     * ci8, which is never right) */
+    if (!strcmp(format, "cu8") || (!given && !strcmp(format, "u8"))) return IRDM_FMT_CU8;
     return IRDM_FMT_CI8;
 }
 
@@ -448,7 +515,7 @@ static int band_close(irdm_frontend_t *fe, const char *file, int fmt, float gain
 /* --save-only: every recording through the stage-level entries -- no context, no lines.  step: capture samples per read,
  * cap: the outputs a read can complete. */
 static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char *out_dir, int fmt, float gain, int verbose,
-                         double centre, size_t step, size_t bps, size_t cap)
+                         double centre, size_t step, size_t bps, size_t cap, int in_fmt)
 {
     void *h_in = irdm_host_alloc(step * bps), *d_in = irdm_device_alloc(0, step * bps), *d_out = irdm_device_alloc(0, cap * 8);
     int rc_all = 0;
@@ -469,6 +536,11 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
         if (rc == 0 && irdm_frontend_finish_device(fe, d_out, cap, NULL) < 0) rc = 1;
         if (rc) fprintf(stderr, "%s: GPU processing failed\n", file);
         if (band_close(fe, file, fmt, gain, verbose, centre) != 0) rc = 1;
+        if (g_input_stats) {
+            irdm_input_stats_t is;
+            if (irdm_frontend_input_stats(fe, &is) == 0) input_line(&is, in_fmt);
+            else { fprintf(stderr, "--input-stats: %s: no statistics\n", file); rc = 1; }
+        }
         if (f != stdin) fclose(f);
         if (rc) rc_all = 1;
     }
@@ -581,6 +653,8 @@ int main(int argc, char **argv)
             }
         }
         else if (!strcmp(a, "--save-only")) save_only = 1;
+        else if (!strcmp(a, "--input-stats")) g_input_stats = 1;
+        else if (!strcmp(a, "--diagnostic")) g_input_stats = g_diag = 1;     /* options.c:376 */
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -595,7 +669,7 @@ int main(int argc, char **argv)
         }
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -647,6 +721,13 @@ int main(int argc, char **argv)
     } else if (spectrum_frames) {
         fprintf(stderr, "--spectrum-frames goes with --spectrum FILE\n");
         return 2;
+    }
+    if (g_input_stats) {
+        if (gpus > 1) {
+            fprintf(stderr, "%s: one GPU only (--gpus %d)\n", g_diag ? "--diagnostic" : "--input-stats", gpus);
+            return 2;
+        }
+        gpus = 0;
     }
     if (save_band) {
         if (!decimate && !resample_to) {
@@ -757,11 +838,15 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    if (g_input_stats && fe && irdm_frontend_input_stats_enable(fe, 1) != 0) {
+        fprintf(stderr, "--input-stats: the library refused the statistics\n");
+        return 1;
+    }
     if (save_only) {
         const size_t so_step = resample_to ? (chunk * (size_t)rs_m + (size_t)rs_l - 1) / (size_t)rs_l : chunk * (size_t)decimate;
         if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { perror(out_dir); return 1; }
         const int rc = save_only_run(fe, save_band, out_dir, save_fmt, (float)save_gain, verbose, c.center_frequency, so_step, bps,
-                                     chunk + (size_t)irdm_frontend_ntaps(fe) + 64);
+                                     chunk + (size_t)irdm_frontend_ntaps(fe) + 64, fmt);
         fflush(stderr);
         _exit(rc);
     }
@@ -816,6 +901,10 @@ int main(int argc, char **argv)
             return 1;
         }
     }
+    if (g_input_stats && !fe && irdm_set_option(p, "input_stats", 1) != 0) {
+        fprintf(stderr, "--input-stats: the library refused the statistics\n");
+        return 1;
+    }
     g_save_dir = save_dir;
     /* a group is fed a super-step at a time: one chunk per member */
     /* (behind a front end the reader's chunk is D -- or M / L -- pipeline chunks of capture samples) */
@@ -842,6 +931,7 @@ int main(int argc, char **argv)
         double reset_ms = 0;
         int rc = 0;
         unsigned long long fed = 0;
+        g_n_demods = 0;
         f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
         if (!f) { perror(file); rc_all = 1; continue; }
         if (fi > 0) {
@@ -989,6 +1079,18 @@ int main(int argc, char **argv)
             if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */
         }
         if (save_band && band_close(fe, file, save_fmt, (float)save_gain, verbose, c.center_frequency) != 0) rc = 1;
+        if (g_input_stats) {
+            irdm_input_stats_t is;
+            if ((fe ? irdm_frontend_input_stats(fe, &is) : irdm_input_stats(p, &is)) == 0) input_line(&is, fmt);
+            else { fprintf(stderr, "--input-stats: %s: no statistics\n", file); rc = 1; }
+        }
+        if (g_diag) {
+            irdm_detector_stats_t ds;
+            if (irdm_detector_stats(p, &ds) == 0)
+                diagnostic_line((double)fed / rate, (unsigned long)irdm_tagged_bursts(p), (unsigned long)g_n_demods,
+                                ds.noise_floor_dbfs_hz, ds.peak_signal_db);
+            else { fprintf(stderr, "--diagnostic: %s: no detector statistics\n", file); rc = 1; }
+        }
         if (rc) rc_all = 1;
         if (fi + 1 == g_n_in) break;        /* (the last recording's objects go with the process, below) */
         if (out_dir) { fclose(g_out); g_out = stdout; }

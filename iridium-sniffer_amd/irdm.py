@@ -18,6 +18,15 @@ FMT_CI8, FMT_CI16, FMT_CF32 = 0, 1, 2
 # full-precision int16 I/Q (include/irdm_hip.h): records equal a cf32 context's on v.astype(np.float32) * FMT_SCALE[fmt]
 FMT_CI16_FULL, FMT_SC16Q11 = 3, 4
 FMT_SCALE = {FMT_CI16_FULL: 1.0 / 32768.0, FMT_SC16Q11: 1.0 / 2048.0}
+# rtl_sdr's unsigned 8-bit I/Q (offset binary): records equal a cf32 context's on convert_cu8(u)
+FMT_CU8 = 6
+
+
+def convert_cu8(u):
+    """interleaved uint8 I, Q -> complex64 as the load stage converts them: (u - 127.5) / 128 = (2u - 255) / 256, exact"""
+    u = np.ascontiguousarray(u, np.uint8)
+    x = (u.astype(np.float32) - np.float32(127.5)) / np.float32(128.0)
+    return x.view(np.complex64)
 MAX_FRAME_SAMPLES = 4440
 MAX_BITS = 896
 
@@ -160,6 +169,13 @@ class BandStats(C.Structure):
     _fields_ = [("n_samples", C.c_uint64), ("n_clipped", C.c_uint64), ("peak", C.c_float)]
 
 
+class InputStats(C.Structure):
+    """irdm_input_stats_t (option input_stats): [0] = I, [1] = Q"""
+    _fields_ = [("n_samples", C.c_uint64), ("n_rail_lo", C.c_uint64 * 2), ("n_rail_hi", C.c_uint64 * 2),
+                ("n_nonfinite", C.c_uint64 * 2), ("code_min", C.c_int32 * 2), ("code_max", C.c_int32 * 2),
+                ("sum", C.c_double * 2), ("sum_sq", C.c_double * 2), ("abs_max", C.c_float * 2)]
+
+
 ACARS_LINE_MAX = 8192
 RAW_LINE_MAX = 1280
 _lib = None
@@ -197,6 +213,9 @@ def lib():
         if hasattr(L, "irdm_poll_spectrum"):
             L.irdm_spectrum_bins.argtypes = [C.c_void_p]
             L.irdm_poll_spectrum.argtypes = [C.c_void_p, C.POINTER(SpectrumRow), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
+        if hasattr(L, "irdm_input_stats"):
+            L.irdm_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
+            L.irdm_input_stats_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(InputStats), C.c_int, C.c_void_p]
         L.irdm_host_alloc.argtypes = [C.c_size_t]
         L.irdm_host_alloc.restype = C.c_void_p
         L.irdm_host_free.argtypes = [C.c_void_p]
@@ -357,6 +376,9 @@ def lib():
                 L.irdm_frontend_save_stats.argtypes = [C.c_void_p, C.POINTER(BandStats)]
                 L.irdm_requantize_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_void_p, C.POINTER(BandStats),
                                                      C.c_int, C.c_void_p]
+            if hasattr(L, "irdm_frontend_input_stats"):
+                L.irdm_frontend_input_stats_enable.argtypes = [C.c_void_p, C.c_int]
+                L.irdm_frontend_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
             if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
                 L.irdm_frontend_create_rational.restype = C.c_void_p
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
@@ -412,6 +434,14 @@ def requantize_device(d_in, n, fmt, gain, d_out, device=0, stream=None):
                                     C.c_void_p(stream or 0)) != 0:
         raise RuntimeError("irdm_requantize_device failed")
     return int(st.n_samples), int(st.n_clipped), np.float32(st.peak)
+
+
+def input_stats_device(d_in, n, fmt, device=0, stream=None):
+    """irdm_input_stats_device: the InputStats of the n samples of format fmt at the device address d_in alone"""
+    st = InputStats()
+    if lib().irdm_input_stats_device(C.c_void_p(d_in), n, fmt, C.byref(st), device, C.c_void_p(stream or 0)) != 0:
+        raise RuntimeError("irdm_input_stats_device failed")
+    return st
 
 
 def host_free(ptr):
@@ -475,6 +505,13 @@ class Pipeline:
 
     def stat(self, key):
         return int(self.L.irdm_get_stat(self.h, key.encode()))
+
+    def input_stats(self):
+        """irdm_input_stats (option input_stats): the InputStats of the stream's raw samples so far"""
+        st = InputStats()
+        if self.L.irdm_input_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_input_stats failed (option input_stats never set?)")
+        return st
 
     def feed_host(self, iq):
         iq = np.ascontiguousarray(iq)
@@ -892,6 +929,18 @@ class Frontend:
             raise RuntimeError("irdm_frontend_save failed (mid-stream, or a bad field)")
         self.saved = saved
         self._sink = cb              # (the library calls it for as long as the front end lives)
+
+    def input_stats_enable(self, on=True):
+        """irdm_frontend_input_stats_enable: statistics of the capture's samples in front of the kernel"""
+        if self.L.irdm_frontend_input_stats_enable(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("irdm_frontend_input_stats_enable failed")
+
+    def input_stats(self):
+        """irdm_frontend_input_stats: the InputStats of the capture so far"""
+        st = InputStats()
+        if self.L.irdm_frontend_input_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_frontend_input_stats failed (never enabled?)")
+        return st
 
     def save_stats(self):
         """irdm_frontend_save_stats: (n_samples, n_clipped, peak as a fraction of full scale)"""
