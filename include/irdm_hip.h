@@ -82,6 +82,16 @@ int gpu_burst_fft_process_device(gpu_burst_fft_t *g, const void *d_input, void *
  * particular stay refused ("unknown sample format N") -- callers and tests rely on those two as the unknown formats
  * next to the known ones. */
 #define IRDM_FMT_CU8       6
+/* 32-bit integer I/Q: interleaved little-endian int32 I, Q, 8 bytes per sample.
+ *   IRDM_FMT_CI32       (float)v * 2^-31   SigMF ci32_le, 32-bit PCM WAV
+ *   IRDM_FMT_CI32_24    (float)v * 2^-23   24-bit samples held in int32 (SDRangel's .sdriq at sample size 24)
+ * (float)v rounds to nearest, ties to even -- v_cvt_f32_i32 on the device, numpy's astype(float32) on the host -- and the
+ * power-of-two product is exact: INT32_MAX converts to exactly 1.0f in format 8.  The contract of formats 3, 4 and 6: a
+ * context in either format produces, bit for bit, every record queue of an IRDM_FMT_CF32 context fed
+ * v.astype(np.float32) * np.float32(scale).  The reference-shaped burst_detector_feed of irdm_compat.h does not take them.
+ * irdm_create and both front ends refuse every format outside {0, 1, 2, 3, 4, 6, 8, 9}: 5, 7 and everything from 10 up. */
+#define IRDM_FMT_CI32      8
+#define IRDM_FMT_CI32_24   9
 
 typedef struct {
     double center_frequency;   /* -c, burst_config_t.center_frequency (burst_detect.h:52) */
@@ -281,11 +291,14 @@ typedef struct {
 
 /* option "input_stats": what the raw samples of the input say about the recording (irdm_input_stats).  x is the converted
  * value, exactly as the pipeline's load stage gives it; a component "at a rail" holds the file code the converter clips to:
- *   ci8 -128 / 127;  cu8 0 / 255;  ci16 and ci16-full -32768 / 32767;  sc16q11 v <= -2048 / v >= 2047;  cf32 x <= -1 / x >= 1.
+ *   ci8 -128 / 127;  cu8 0 / 255;  ci16 and ci16-full -32768 / 32767;  sc16q11 v <= -2048 / v >= 2047;  cf32 x <= -1 / x >= 1;
+ *   ci32 INT32_MIN / INT32_MAX;  24-bit in int32 v <= -2^23 / v >= 2^23 - 1.
  * Plain ci16: rails and code_min / code_max are taken on the 16-bit code v, sum / sum_sq / abs_max on the narrowed value
  * (v >> 8) / 128 the pipeline sees -- a 12-bit recording read as ci16 reports an RMS of a fraction of an LSB, which is true.
  * Integer formats: x = c * 2^-k with an integer c; the sums of c and c^2 are kept as integers and sum / sum_sq formed from
  * the totals with one rounding, so these fields and every count do not depend on how the stream was cut into chunks.
+ * (The int32 formats: c = v, k = 31 / 23; c^2 reaches 2^62, its sums are carried in two words on the device; abs_max is
+ * the converted value of the extreme code, rounded as the load stage rounds it.)
  * cf32: sum / sum_sq are double sums of the exact x and x^2 over the finite components, reproducible for a given cut. */
 typedef struct {
     uint64_t n_samples;
@@ -394,6 +407,7 @@ uint64_t irdm_tagged_bursts(const irdm_pipeline_t *p);
 uint64_t irdm_sample_count(const irdm_pipeline_t *p);
 size_t irdm_max_chunk_samples(const irdm_pipeline_t *p);      /* the configured value with its default resolved */
 size_t irdm_bytes_per_sample(const irdm_pipeline_t *p);       /* of the configured input format */
+size_t irdm_format_bytes(int format);                         /* bytes per sample of an IRDM_FMT_*; 0: no such format */
 /* samples in front of a stream position that a context taking over there must be given (irdm_seed_history*): the
  * reference's ring (stale-slot reads reach one ring length back, burst_detect.c:292-296, :401-422) + the longest burst window */
 size_t irdm_required_overlap(const irdm_pipeline_t *p);
@@ -951,6 +965,43 @@ int irdm_input_stats(irdm_pipeline_t *p, irdm_input_stats_t *out);
 int irdm_frontend_input_stats_enable(irdm_frontend_t *fe, int on);
 int irdm_frontend_input_stats(irdm_frontend_t *fe, irdm_input_stats_t *out);
 int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_stats_t *out, int device, void *stream);
+
+/* ---- self-describing recordings: WAV / RF64, SigMF, SDRangel .sdriq (csrc/recording.cpp) ----
+ * Host code only, no device call: works without a GPU.  irdm_recording_probe reads the header of `path` and says what the
+ * samples are and where they lie.  container: 0 = by the file's extension, compared without case (.wav / .wave / .rf64;
+ * .sigmf-meta / .sigmf-data; .sdriq), or one of IRDM_CONTAINER_* to force a kind.  File contents are never sniffed: a raw
+ * recording may begin with any bytes.  Returns 0: a container was recognised and *out is filled; 1: not a container (a
+ * raw file; *out untouched but for kind = 0); -1: malformed or unsupported, and err (err_cap bytes, may be NULL) says what
+ * and where.
+ *   WAV / RF64: RIFF..WAVE, or RF64 / BW64 with a ds64 chunk; fmt of 16, 18 or 40 bytes, tag 1 (PCM), 3 (float) or 0xFFFE
+ *     (the tag is the first two bytes of the sub-format GUID); two channels (I, Q); 8-bit PCM -> cu8, 16-bit PCM -> ci16-full
+ *     (v / 32768), 32-bit PCM -> ci32, 32-bit float -> cf32; anything else is refused with the bit depth in the message.  A
+ *     data size of 0 or 0xFFFFFFFF, or one past the end of the file, means "to the end of the file".  The binary auxi chunk
+ *     (two SYSTEMTIMEs, then a u32 centre frequency) gives start time and centre when its year lies in 1990..2100;
+ *     otherwise the centre comes from _<digits>Hz / _<digits>kHz in the file name.
+ *   SigMF: either file of the pair; global core:datatype cf32_le / ci16_le (-> ci16-full) / ci8 / cu8 / ci32_le,
+ *     core:sample_rate (a whole number), core:num_channels absent or 1, core:trailing_bytes, core:dataset; captures[0]
+ *     core:sample_start 0, core:frequency, core:datetime (ISO 8601 UTC, kept to the nanosecond), core:header_bytes.
+ *   .sdriq: a 32-byte header (u32 rate, u64 centre, u64 start in s or -- from 10^11 up -- ms, u32 sample size 16 / 24, u32 0,
+ *     u32 CRC-32 of the first 28 bytes); 16 -> ci16-full, 24 -> IRDM_FMT_CI32_24. */
+#define IRDM_CONTAINER_NONE  0
+#define IRDM_CONTAINER_WAV   1
+#define IRDM_CONTAINER_SIGMF 2
+#define IRDM_CONTAINER_SDRIQ 3
+typedef struct {
+    int      kind;                 /* IRDM_CONTAINER_* */
+    int      format;               /* IRDM_FMT_* of the samples */
+    int      sample_rate;          /* samples per second */
+    int      has_center;           /* center_frequency is from the file */
+    double   center_frequency;     /* Hz */
+    int      has_start;            /* start_time_ns is from the file */
+    int      n_captures;           /* SigMF: capture segments in the metadata (the first one's values are used); else 1 */
+    uint64_t start_time_ns;        /* UTC, ns since 1970 */
+    uint64_t data_offset;          /* the samples are [data_offset, data_offset + data_bytes) of data_path */
+    uint64_t data_bytes;           /* rounded down to whole samples */
+    char     data_path[4096];      /* the file that holds the samples */
+} irdm_recording_info_t;
+int irdm_recording_probe(const char *path, int container, irdm_recording_info_t *out, char *err, size_t err_cap);
 
 /* The fine-CFO step's cexpf(i x) (burst_downmix.c:716-717) as the device evaluates it -- glibc's sincosf restated,
  * csrc/libm_port.hpp -- for n arbitrary arguments (test / audit surface: tests/test_gpu_libm.py,

@@ -210,9 +210,16 @@ __host__ __device__ __forceinline__ unsigned bitrev(unsigned v, int bits)
 //   fmt 6: cu8 (rtl_sdr's files: offset binary, one unsigned byte each), ((float)u - 127.5f) / 128.0f = (2u - 255) / 256,
 //          exact in every step (the reference has no such input; 127.5 is the converter's mid-scale -- with 128 every
 //          recording would carry a constant half-LSB DC term, a tone inside a band selected off centre)
-// (5 and 7 are no formats: tests pin irdm_create refusing 5 and the rational front end refusing 7)
+//   fmt 8: ci32 (SigMF ci32_le, 32-bit PCM WAV), (float)v * 2^-31
+//   fmt 9: 24-bit samples held in int32 (SDRangel's .sdriq at sample size 24), (float)v * 2^-23
+//          Both: interleaved little-endian int32 I, Q, 8 bytes per sample -- cf32's geometry with a convert and a multiply
+//          behind each component.  (float)v rounds to nearest, ties to even (v_cvt_f32_i32; numpy's astype(float32)); the
+//          power-of-two product is exact (INT32_MAX -> 2^31 -> exactly 1.0f in format 8).
+// (5 and 7 are no formats: tests pin irdm_create refusing 5 and the rational front end refusing 7; everything from 10 up
+// is refused as well)
 // Formats 3, 4 and 6 are exact: int16 -> float is, and a power-of-two scale keeps every product a normal float, so a
-// context in one of them computes what a cf32 context computes on the converted samples, bit for bit.
+// context in one of them computes what a cf32 context computes on the converted samples, bit for bit.  Formats 8 and 9
+// keep the same contract against v.astype(np.float32) * np.float32(scale): one rounding, in the conversion.
 template <int FMT>       // (FMT 3 or 4)
 __host__ __device__ __forceinline__ float i16_full(int v)
 {
@@ -221,11 +228,17 @@ __host__ __device__ __forceinline__ float i16_full(int v)
 
 __host__ __device__ __forceinline__ float cu8_f(int u) { return ((float)u - 127.5f) / 128.0f; }
 
+template <int FMT>       // (FMT 8 or 9)
+__host__ __device__ __forceinline__ float i32_f(int v)
+{
+    return (float)v * (FMT == 8 ? 0x1p-31f : 0x1p-23f);
+}
+
 // bytes per sample of a device format
 template <int FMT>
-constexpr int kFmtBytes = FMT == 2 ? 8 : ((FMT == 0 || FMT == 6) ? 2 : 4);
-constexpr bool fmt_valid(int fmt) { return (fmt >= 0 && fmt <= 4) || fmt == 6; }
-constexpr int fmt_bytes(int fmt) { return fmt == 2 ? 8 : ((fmt == 0 || fmt == 6) ? 2 : 4); }
+constexpr int kFmtBytes = (FMT == 2 || FMT == 8 || FMT == 9) ? 8 : ((FMT == 0 || FMT == 6) ? 2 : 4);
+constexpr bool fmt_valid(int fmt) { return (fmt >= 0 && fmt <= 4) || fmt == 6 || fmt == 8 || fmt == 9; }
+constexpr int fmt_bytes(int fmt) { return (fmt == 2 || fmt == 8 || fmt == 9) ? 8 : ((fmt == 0 || fmt == 6) ? 2 : 4); }
 
 template <int FMT>
 __device__ __forceinline__ float2 load_iq(const void *__restrict__ iq, size_t i)
@@ -242,12 +255,15 @@ __device__ __forceinline__ float2 load_iq(const void *__restrict__ iq, size_t i)
     } else if (FMT == 6) {
         const unsigned v = reinterpret_cast<const unsigned short *>(iq)[i];      // I in the low byte
         return make_float2(cu8_f((int)(v & 0xff)), cu8_f((int)(v >> 8)));
+    } else if (FMT == 8 || FMT == 9) {
+        const int2 v = reinterpret_cast<const int2 *>(iq)[i];
+        return make_float2(i32_f<FMT>(v.x), i32_f<FMT>(v.y));
     } else {
         const char2 v = reinterpret_cast<const char2 *>(iq)[i];
         return make_float2((float)v.x / 128.0f, (float)v.y / 128.0f);
     }
 }
-// (irdm_create admits formats 0..4 and 6 only; anything else reads as NaN rather than as some other format)
+// (irdm_create admits formats 0..4, 6, 8 and 9 only; anything else reads as NaN rather than as some other format)
 __device__ __forceinline__ float2 load_iq(int fmt, const void *__restrict__ iq, size_t i)
 {
     switch (fmt) {
@@ -257,6 +273,8 @@ __device__ __forceinline__ float2 load_iq(int fmt, const void *__restrict__ iq, 
     case 4: return load_iq<4>(iq, i);
     case 0: return load_iq<0>(iq, i);
     case 6: return load_iq<6>(iq, i);
+    case 8: return load_iq<8>(iq, i);
+    case 9: return load_iq<9>(iq, i);
     default: return make_float2(__builtin_nanf(""), __builtin_nanf(""));
     }
 }

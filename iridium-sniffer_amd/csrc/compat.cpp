@@ -206,7 +206,7 @@ static void detector_feed(_burst_detector *d, const void *iq, size_t num_samples
     }
     d->last_cb = cb;
     d->last_user = user;
-    const size_t bps = fmt == IRDM_FMT_CF32 ? 8 : ((fmt == IRDM_FMT_CI8 || fmt == IRDM_FMT_CU8) ? 2 : 4);
+    const size_t bps = irdm_format_bytes(fmt);
     const unsigned char *src = static_cast<const unsigned char *>(iq);
     d->stage.insert(d->stage.end(), src, src + num_samples * bps);
     const size_t whole = d->stage.size() / bps / kBlock * kBlock;
@@ -270,7 +270,7 @@ extern "C" void burst_detector_destroy(_burst_detector *det)
         // (burst_detect.c:746-842), so bursts that expire there are emitted; destroy is called by the detector thread
         // right behind its feed loop (burst_detect.c:941-960), with the burst queue still open: they go through the
         // callback of the last feed.
-        const size_t bps = det->fmt == IRDM_FMT_CF32 ? 8 : ((det->fmt == IRDM_FMT_CI8 || det->fmt == IRDM_FMT_CU8) ? 2 : 4);
+        const size_t bps = irdm_format_bytes(det->fmt);
         const int emitted = irdm_feed_host(det->p, det->stage.data(), det->stage.size() / bps);
         if (emitted >= 0) detector_emit(det, emitted, det->last_cb, det->last_user);
         det->stage.clear();

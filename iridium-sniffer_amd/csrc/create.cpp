@@ -589,6 +589,7 @@ extern "C" int irdm_sincosf_probe(int device, const float *x, size_t n, float *r
 extern "C" uint64_t irdm_tagged_bursts(const irdm_pipeline_t *p) { return p ? p->st.tagged : 0; }
 extern "C" size_t irdm_max_chunk_samples(const irdm_pipeline_t *p) { return p ? p->max_chunk : 0; }
 extern "C" size_t irdm_bytes_per_sample(const irdm_pipeline_t *p) { return p ? p->bps : 0; }
+extern "C" size_t irdm_format_bytes(int format) { return fmt_valid(format) ? (size_t)fmt_bytes(format) : 0; }
 // Samples a context that takes over a stream at some position must be given from in front of it (irdm_seed_history*): the
 // reference's ring -- stale-slot reads reach one ring length back (burst_detect.c:292-296, :401-422) -- plus the longest
 // burst window.

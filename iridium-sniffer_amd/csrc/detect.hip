@@ -7,11 +7,11 @@
 namespace irdm {
 
 // ---------------------------------------------------------------------------
-// K1: load (ci8 | cu8 | ci16 | cf32, load_iq) -> Blackman/0.42 window -> N-point pinned FFT in LDS ->
+// K1: load (ci8 | cu8 | ci16 | ci32 | cf32, load_iq) -> Blackman/0.42 window -> N-point pinned FFT in LDS ->
 //     fftshift -> |.|^2  (simd_window_cf + fftwf_execute + simd_fftshift_mag,
 //     burst_detect.c:679-687; opencl/burst_fft.c:52-80 window_multiply /
 //     fftshift_magnitude).  One workgroup per frame, grid-stride.
-//     HBM: 8 B (cf32), 4 B (the int16 formats) or 2 B (ci8, cu8) read + 4 B written per sample.
+//     HBM: 8 B (cf32, the int32 formats), 4 B (the int16 formats) or 2 B (ci8, cu8) read + 4 B written per sample.
 // ---------------------------------------------------------------------------
 template <int LOGN, int NT, int FMT>
 __global__ __launch_bounds__(NT) void fft_mag_kernel(const void *__restrict__ iq,
@@ -277,6 +277,10 @@ __device__ __forceinline__ void load_pair(__amdgpu_buffer_rsrc_t r, int lane, in
         const short r0 = (short)(v.x & 0xffff), i0 = (short)(v.x >> 16), r1 = (short)(v.y & 0xffff), i1 = (short)(v.y >> 16);
         x0 = v2f{ i16_full<FMT>(r0), i16_full<FMT>(i0) };                    // load_iq<3>, load_iq<4>
         x1 = v2f{ i16_full<FMT>(r1), i16_full<FMT>(i1) };
+    } else if (FMT == 8 || FMT == 9) {
+        const int4 v = __builtin_bit_cast(int4, __builtin_amdgcn_raw_buffer_load_b128(r, lane * 16, soff, 2));
+        x0 = v2f{ i32_f<FMT>(v.x), i32_f<FMT>(v.y) };                        // load_iq<8>, load_iq<9>
+        x1 = v2f{ i32_f<FMT>(v.z), i32_f<FMT>(v.w) };
     } else if (FMT == 6) {
         const unsigned v = (unsigned)__builtin_amdgcn_raw_buffer_load_b32(r, lane * 4, soff, 2);
         x0 = v2f{ cu8_f((int)(v & 0xff)), cu8_f((int)((v >> 8) & 0xff)) };    // load_iq<6>
@@ -556,6 +560,8 @@ static int launch_p32(int fmt, const void *iq, const float *window, const float2
     else if (fmt == 4) IRDM_LAUNCH_P32(4);
     else if (fmt == 0) IRDM_LAUNCH_P32(0);
     else if (fmt == 6) IRDM_LAUNCH_P32(6);
+    else if (fmt == 8) IRDM_LAUNCH_P32(8);
+    else if (fmt == 9) IRDM_LAUNCH_P32(9);
     else return -1;
 #undef IRDM_LAUNCH_P32
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -583,6 +589,8 @@ static int launch_r16(int fmt, const void *iq, const float *window, const float2
     else if (fmt == 4) IRDM_LAUNCH_R16(4);
     else if (fmt == 0) IRDM_LAUNCH_R16(0);
     else if (fmt == 6) IRDM_LAUNCH_R16(6);
+    else if (fmt == 8) IRDM_LAUNCH_R16(8);
+    else if (fmt == 9) IRDM_LAUNCH_R16(9);
     else return -1;
 #undef IRDM_LAUNCH_R16
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -628,6 +636,8 @@ int launch_fft_mag(int log_n, int fmt, const void *iq, const float *window, cons
         else if (f == 4) IRDM_LAUNCH_FFT_F(LOGN, NT, 4);                                       \
         else if (f == 0) IRDM_LAUNCH_FFT_F(LOGN, NT, 0);                                       \
         else if (f == 6) IRDM_LAUNCH_FFT_F(LOGN, NT, 6);                                       \
+        else if (f == 8) IRDM_LAUNCH_FFT_F(LOGN, NT, 8);                                       \
+        else if (f == 9) IRDM_LAUNCH_FFT_F(LOGN, NT, 9);                                       \
         else return -1;                                                                        \
     } while (0)
     switch (log_n) {

@@ -91,6 +91,15 @@ __device__ __forceinline__ void load_piece(const void *__restrict__ base, size_t
                 x[4 * u + k] = v2f{ i16_full<FMT>(re), i16_full<FMT>(im) };
             }
         }
+    } else if (FMT == 8 || FMT == 9) {
+        // (cf32's loads: 2 samples per 16 B, ordinary loads for the reason given there)
+        const int4 *g = reinterpret_cast<const int4 *>(reinterpret_cast<const int2 *>(base) + idx);
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int4 v = g[u];
+            x[2 * u] = v2f{ i32_f<FMT>(v.x), i32_f<FMT>(v.y) };
+            x[2 * u + 1] = v2f{ i32_f<FMT>(v.z), i32_f<FMT>(v.w) };
+        }
     } else if (FMT == 6) {
         const int4 v = *reinterpret_cast<const int4 *>(reinterpret_cast<const unsigned short *>(base) + idx);   // 8 samples per 16 B
         const unsigned w[4] = { (unsigned)v.x, (unsigned)v.y, (unsigned)v.z, (unsigned)v.w };
@@ -539,6 +548,8 @@ static int launch_fir_f_fmt(const SampleSource &src, const FirGeom *geom, int n_
     else if (src.fmt == 4) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 4>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 0) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 0>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 6) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 6>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 8) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 8>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 9) hipLaunchKernelGGL((fir_decimate_kernel_f<M, 9>), dim3(grid), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -565,6 +576,8 @@ static int launch_fir_r_fmt(const SampleSource &src, const FirGeom *geom, int n_
     else if (src.fmt == 4) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 4>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 0) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 0>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else if (src.fmt == 6) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 6>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 8) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 8>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
+    else if (src.fmt == 9) hipLaunchKernelGGL((fir_decimate_kernel_r<M, 9>), dim3(n_tiles), dim3(64), 0, stream, src, geom, taps, rot_table, dec, n_tiles, kclk);
     else return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -119,6 +119,8 @@ __global__ __launch_bounds__(NT) void frontend_kernel(FrontendArgs a, const floa
         case 3: fe_stage_inside<3, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         case 4: fe_stage_inside<4, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         case 6: fe_stage_inside<6, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        case 8: fe_stage_inside<8, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
+        case 9: fe_stage_inside<9, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         default: fe_stage_inside<0, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
         }
     } else {

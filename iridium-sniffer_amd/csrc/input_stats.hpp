@@ -8,7 +8,9 @@
 //   * integer formats: x = c * 2^-K with an integer c (ci8 c = v, K = 7; cu8 c = 2u - 255, K = 8; ci16 c = v >> 8, K = 7;
 //     ci16-full c = v, K = 15; sc16q11 c = v, K = 11).  A lane sums c and c^2 of one 16-byte piece in 32 bits (int16: c^2
 //     straight into 64 -- one square already needs 31), then adds to its 64-bit accumulators; rails and the extreme codes
-//     are taken on the file's codes.  Wavefronts reduce by shuffles, the workgroup through LDS, then one 64-bit integer
+//     are taken on the file's codes.  The int32 formats (ci32 c = v, K = 31; 24-bit in int32 c = v, K = 23): c^2 reaches
+//     2^62, so 2^30 of them do not fit a 64-bit word -- a lane keeps the low and the high 32 bits of every square in two
+//     64-bit sums (each below 2^62 per launch) and the host puts them together in 128 bits.  Wavefronts reduce by shuffles, the workgroup through LDS, then one 64-bit integer
 //     atomic per quantity.  Integer sums do not depend on any order: the result is that of the stream, however it was cut.
 //   * cf32: x and x^2 are exact doubles; a workgroup's partial sums go to its row of a slab the host folds in row order
 //     (no floating-point atomics: the result is reproducible for a given cut of the stream); max |x| is an integer
@@ -41,6 +43,7 @@ struct InputStatsAcc {
     unsigned max_key[2];                // max of 2^31 + code
     unsigned abs_bits[2];               // cf32: the largest bit pattern of |x| over finite x
     unsigned pad[2];
+    unsigned long long sum_c2_hi[2];    // the int32 formats: the sum of c^2 >> 32 (sum_c2 then holds that of c^2 & 0xffffffff)
 };
 constexpr size_t kIsBlockBytes = sizeof(InputStatsAcc) + sizeof(double) * 4 * kIsMaxGrid;
 
@@ -50,6 +53,10 @@ template <> struct IsFmt<6> { static constexpr int LO = 0, HI = 255, K = 8; };
 template <> struct IsFmt<1> { static constexpr int LO = -32768, HI = 32767, K = 7; };
 template <> struct IsFmt<3> { static constexpr int LO = -32768, HI = 32767, K = 15; };
 template <> struct IsFmt<4> { static constexpr int LO = -2048, HI = 2047, K = 11; };
+template <> struct IsFmt<8> { static constexpr int LO = -0x7fffffff - 1, HI = 0x7fffffff, K = 31; };
+template <> struct IsFmt<9> { static constexpr int LO = -(1 << 23), HI = (1 << 23) - 1, K = 23; };
+constexpr bool is_fmt32(int fmt) { return fmt == 8 || fmt == 9; }
+constexpr int is_fmt_k(int fmt) { return fmt == 0 || fmt == 1 ? 7 : (fmt == 6 ? 8 : (fmt == 3 ? 15 : (fmt == 4 ? 11 : (fmt == 8 ? 31 : 23)))); }
 
 // the integer c of a file code: x = c * 2^-K is what load_iq gives
 template <int FMT>
@@ -64,6 +71,7 @@ struct IsLane {
     int cmin[2], cmax[2];
     long long s[2];
     unsigned long long s2[2];
+    unsigned long long s2h[2];          // (the int32 formats)
     int ls[2];
     unsigned ls2[2];
 };
@@ -76,6 +84,13 @@ __device__ __forceinline__ void is_take(IsLane &a, int k, int code)
     a.cmin[k] = code < a.cmin[k] ? code : a.cmin[k];
     a.cmax[k] = code > a.cmax[k] ? code : a.cmax[k];
     const int c = is_level<FMT>(code);
+    if (is_fmt32(FMT)) {                                                    // no 32-bit piece sums: one c already needs 32 bits
+        const unsigned long long c2 = (unsigned long long)((long long)c * (long long)c);   // <= 2^62
+        a.s[k] += (long long)c;
+        a.s2[k] += c2 & 0xffffffffull;
+        a.s2h[k] += c2 >> 32;
+        return;
+    }
     a.ls[k] += c;
     if (kFmtBytes<FMT> == 2) a.ls2[k] += (unsigned)(c * c);                 // at most 8 * 255^2 per piece
     else a.s2[k] += (unsigned long long)(unsigned)(c * c);                  // c^2 <= 2^30
@@ -236,7 +251,8 @@ __global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restri
             for (int j = 0; j < 4; j++) slab[(size_t)blockIdx.x * 4 + j] = d[j];
         }
     } else {
-        __shared__ unsigned long long sh_q[NW][8];
+        constexpr int NQ = is_fmt32(FMT) ? 10 : 8;
+        __shared__ unsigned long long sh_q[NW][NQ];
         __shared__ int sh_m[NW][4];
         IsLane a;
         for (int k = 0; k < 2; k++) {
@@ -245,11 +261,16 @@ __global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restri
             a.cmax[k] = -0x7fffffff - 1;
             a.s[k] = 0;
             a.s2[k] = 0ull;
+            a.s2h[k] = 0ull;
             a.ls[k] = 0;
             a.ls2[k] = 0u;
         }
         if (si >= 0) {
-            if (BPS == 2) {
+            if (BPS == 8) {
+                const int *w = reinterpret_cast<const int *>(bytes + si * BPS);
+                is_take<FMT>(a, 0, w[0]);
+                is_take<FMT>(a, 1, w[1]);
+            } else if (BPS == 2) {
                 const unsigned w = *reinterpret_cast<const unsigned short *>(bytes + si * BPS);
                 if (FMT == 0) {
                     is_take<FMT>(a, 0, (int)(signed char)(w & 0xff));
@@ -265,26 +286,33 @@ __global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restri
         }
         for (long long i = gid; i < nvec; i += stride) {
             const uint4 v = pieces[i];
-            is_word<FMT>(a, v.x);
-            is_word<FMT>(a, v.y);
-            is_word<FMT>(a, v.z);
-            is_word<FMT>(a, v.w);
-            is_piece_done(a);
+            if (BPS == 8) {
+                is_take<FMT>(a, 0, (int)v.x);
+                is_take<FMT>(a, 1, (int)v.y);
+                is_take<FMT>(a, 0, (int)v.z);
+                is_take<FMT>(a, 1, (int)v.w);
+            } else {
+                is_word<FMT>(a, v.x);
+                is_word<FMT>(a, v.y);
+                is_word<FMT>(a, v.z);
+                is_word<FMT>(a, v.w);
+                is_piece_done(a);
+            }
         }
-        unsigned long long q[8] = { a.lo[0], a.lo[1], a.hi[0], a.hi[1], (unsigned long long)a.s[0], (unsigned long long)a.s[1],
-                                    a.s2[0], a.s2[1] };
+        unsigned long long q[10] = { a.lo[0], a.lo[1], a.hi[0], a.hi[1], (unsigned long long)a.s[0], (unsigned long long)a.s[1],
+                                     a.s2[0], a.s2[1], a.s2h[0], a.s2h[1] };
         int m[4] = { a.cmin[0], a.cmin[1], a.cmax[0], a.cmax[1] };
-        for (int j = 0; j < 8; j++) q[j] = is_wave_sum(q[j]);
+        for (int j = 0; j < NQ; j++) q[j] = is_wave_sum(q[j]);
         for (int j = 0; j < 2; j++) m[j] = is_wave_min(m[j]);
         for (int j = 2; j < 4; j++) m[j] = is_wave_max(m[j]);
         if (lane == 0) {
-            for (int j = 0; j < 8; j++) sh_q[wave][j] = q[j];
+            for (int j = 0; j < NQ; j++) sh_q[wave][j] = q[j];
             for (int j = 0; j < 4; j++) sh_m[wave][j] = m[j];
         }
         __syncthreads();
         if (threadIdx.x == 0) {
             for (int w = 1; w < NW; w++) {
-                for (int j = 0; j < 8; j++) q[j] += sh_q[w][j];
+                for (int j = 0; j < NQ; j++) q[j] += sh_q[w][j];
                 for (int j = 0; j < 2; j++) m[j] = sh_m[w][j] < m[j] ? sh_m[w][j] : m[j];
                 for (int j = 2; j < 4; j++) m[j] = sh_m[w][j] > m[j] ? sh_m[w][j] : m[j];
             }
@@ -293,8 +321,11 @@ __global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restri
                 if (q[2 + k]) atomicAdd(&acc->rail_hi[k], q[2 + k]);
                 if (q[4 + k]) atomicAdd(&acc->sum_c[k], q[4 + k]);
                 if (q[6 + k]) atomicAdd(&acc->sum_c2[k], q[6 + k]);
+                if (is_fmt32(FMT) && q[8 + k]) atomicAdd(&acc->sum_c2_hi[k], q[8 + k]);
                 if (m[k] <= m[2 + k]) {                 // the workgroup saw a component
-                    atomicMax(&acc->min_key[k], 0x80000000u - (unsigned)m[k]);
+                    // (the int32 formats: 2^31 - 1 - code, so that INT32_MIN has a key; 0 is then the key of INT32_MAX, and a
+                    // launch that ran at all has seen a component)
+                    atomicMax(&acc->min_key[k], (is_fmt32(FMT) ? 0x7fffffffu : 0x80000000u) - (unsigned)m[k]);
                     atomicMax(&acc->max_key[k], 0x80000000u + (unsigned)m[2 + k]);
                 }
             }
@@ -348,6 +379,8 @@ static inline int launch_input_stats(int fmt, const void *d_in, size_t n, void *
     case 2: IRDM_LAUNCH_IS(2); break;
     case 3: IRDM_LAUNCH_IS(3); break;
     case 4: IRDM_LAUNCH_IS(4); break;
+    case 8: IRDM_LAUNCH_IS(8); break;
+    case 9: IRDM_LAUNCH_IS(9); break;
     default: IRDM_LAUNCH_IS(6); break;
     }
 #undef IRDM_LAUNCH_IS
@@ -366,7 +399,7 @@ static inline void input_stats_fold(InputStatsRun &t, int fmt, const void *h_blo
         t.hi[k] += a.rail_hi[k];
         t.nf[k] += a.nonfinite[k];
         t.sc[k] += (__int128)(long long)a.sum_c[k];
-        t.sc2[k] += (unsigned __int128)a.sum_c2[k];
+        t.sc2[k] += (unsigned __int128)a.sum_c2[k] + ((unsigned __int128)a.sum_c2_hi[k] << 32);
         t.min_key[k] = std::max(t.min_key[k], a.min_key[k]);
         t.max_key[k] = std::max(t.max_key[k], a.max_key[k]);
         t.abs_bits[k] = std::max(t.abs_bits[k], a.abs_bits[k]);
@@ -383,7 +416,8 @@ static inline void input_stats_result(const InputStatsRun &t, int fmt, irdm_inpu
 {
     memset(out, 0, sizeof(*out));
     out->n_samples = t.n;
-    const int K = fmt == 0 || fmt == 1 ? 7 : (fmt == 6 ? 8 : (fmt == 3 ? 15 : 11));
+    const int K = is_fmt_k(fmt);
+    const bool wide = is_fmt32(fmt);                     // (their keys: see the kernel)
     for (int k = 0; k < 2; k++) {
         out->n_rail_lo[k] = t.lo[k];
         out->n_rail_hi[k] = t.hi[k];
@@ -396,12 +430,13 @@ static inline void input_stats_result(const InputStatsRun &t, int fmt, irdm_inpu
         }
         out->sum[k] = ldexp((double)t.sc[k], -K);                // one rounding: the conversion; the scaling is exact
         out->sum_sq[k] = ldexp((double)t.sc2[k], -2 * K);
-        if (t.min_key[k]) {
-            out->code_min[k] = (int32_t)(0x80000000u - t.min_key[k]);
+        if (wide ? t.n != 0 : t.min_key[k] != 0) {
+            out->code_min[k] = (int32_t)((wide ? 0x7fffffffu : 0x80000000u) - t.min_key[k]);
             out->code_max[k] = (int32_t)(t.max_key[k] - 0x80000000u);
-            // the level is monotone in the code: max |x| is at one of the two extreme codes (|c| <= 2^15: exact floats)
+            // the level is monotone in the code: max |x| is at one of the two extreme codes (|c| <= 2^15: exact floats; the
+            // int32 formats: (float)|c| rounds as load_iq's (float)v does, and rounding keeps the order)
             auto level = [&](int code) {
-                const int c = fmt == 6 ? is_level<6>(code) : (fmt == 1 ? is_level<1>(code) : code);
+                const long long c = fmt == 6 ? is_level<6>(code) : (fmt == 1 ? is_level<1>(code) : code);
                 return ldexpf((float)(c < 0 ? -c : c), -K);
             };
             out->abs_max[k] = std::max(level(out->code_min[k]), level(out->code_max[k]));

@@ -233,7 +233,8 @@ struct irdm_pipeline {
     StreamState st;
     DetParams P;
     int dev_fmt;                // device sample format == cfg.format: 0 ci8, 1 ci16 (narrowed in the load stage,
-                                // main.c:245-246), 2 cf32, 3 ci16 full precision, 4 SC16Q11, 6 cu8 (common.hpp load_iq)
+                                // main.c:245-246), 2 cf32, 3 ci16 full precision, 4 SC16Q11, 6 cu8, 8 ci32,
+                                // 9 24-bit in int32 (common.hpp load_iq)
     size_t bps;                 // bytes per device sample
     int feed_block, decim, out_rate;
     bool dev_cfo;            // the fine-CFO libm step runs on the device (the port reproduces this host's cexpf)

@@ -207,6 +207,8 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
         case 3: rs_stage_inside<3>(a, g, v0, n_start, T, s, tid); break;
         case 4: rs_stage_inside<4>(a, g, v0, n_start, T, s, tid); break;
         case 6: rs_stage_inside<6>(a, g, v0, n_start, T, s, tid); break;
+        case 8: rs_stage_inside<8>(a, g, v0, n_start, T, s, tid); break;
+        case 9: rs_stage_inside<9>(a, g, v0, n_start, T, s, tid); break;
         default: rs_stage_inside<0>(a, g, v0, n_start, T, s, tid); break;
         }
     } else {

@@ -2,7 +2,8 @@
  * iridium_sniffer_hip.c -- file-mode command line over the MI355X hot path, plain C99.
  *
  * Mirrors the reference's file-mode surface (options.c:186-551, main.c:223-284, frame_output.c:160-199):
- *     iridium-sniffer-hip -f FILE -r RATE [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11] [-d DB]
+ *     iridium-sniffer-hip -f FILE [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [-d DB]
+ *                         [--container wav|sigmf|sdriq|raw] [--probe]
  *                         [--file-info STR] [--no-gardner] [--no-simd] [--chunk SAMPLES] [-v]
  *                         [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]]
  *                         [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]]
@@ -20,6 +21,20 @@
  * SoapySDR CS16 (v / 32768) and bladeRF SC16Q11 (v / 2048) paths scale it; ci16 (and a .ci16 / .cs16 file) is the
  * reference's file path, narrowed to 8 bits.  --format cu8 (and a .cu8 / .u8 file) is rtl_sdr's unsigned 8-bit I/Q,
  * (u - 127.5) / 128; the reference reads no such file.
+ * --format ci32 and --format ci32-24 read interleaved int32: v / 2^31 (SigMF ci32_le, 32-bit PCM WAV) and 24-bit samples held
+ * in int32, v / 2^23 (SDRangel's .sdriq).
+ * Self-describing recordings: a FILE ending in .wav / .wave / .rf64, .sigmf-meta / .sigmf-data or .sdriq (compared without
+ * case), or any FILE with --container wav|sigmf|sdriq, is probed (irdm_recording_probe) and its header gives the sample
+ * format, the rate, the centre frequency and the capture time: -f FILE alone runs it.  --container raw turns probing off for
+ * every -f; stdin is always raw (-f - with --container is refused), and so is --format beside a container.  An explicit -r
+ * that disagrees with the header wins, with a one-line warning; an explicit -c wins silently; --start-time (or a list entry's
+ * START_SEC) wins over the header's time; a header without a centre leaves -c or its default.  A malformed header fails
+ * that recording with the probe's message (exit 1; exit 2 when it is the only input) and nothing of it is read as samples.
+ * Several recordings must resolve to one format and one rate (exit 2 otherwise); centre and start time are each one's own
+ * (irdm_reset), except behind a front end, whose shift is fixed at creation: differing centres are refused there.  A
+ * container whose rate is no multiple of 250 kHz, without --resample-to, gets one warning that names the flag.
+ * --probe: one line per input on stdout and exit 0, before any device call (-v prints the same line on stderr before a run):
+ *     probe: FILE container=wav|sigmf|sdriq|raw format=NAME rate=HZ|- centre=HZ|- start=SEC.NNNNNNNNN|- offset=BYTES bytes=BYTES data=PATH
  * --band-center HZ --decimate D (both or neither): the file is a wideband capture -- -r and -c describe it -- and the band
  * around HZ is shifted to the centre, low-passed and decimated by D (2 .. 16) on the GPU in front of the detector
  * (irdm_frontend_*): a 50 MS/s capture with --decimate 5 runs as a 10 MS/s stream centred at HZ (at the nearest multiple
@@ -54,6 +69,8 @@
  * -v, a closing "saved band: ..." line that names the -r, -c and --format to read the file with, and, without -v, a warning
  * when components clipped.  --save-only: nothing but the file -- no context, no lines (irdm_frontend_run_device).  With several
  * recordings FILE must be `auto`, --out-dir given and --save-format named: each leaves DIR/<basename>.band.<format>.
+ * A FILE ending in .sigmf-data (format by --save-format, default cf32) also gets FILE's .sigmf-meta on close: datatype, the
+ * front end's output rate, the band's centre and the start time -- the pair reads back with -f alone.
  * --input-stats: one closing line per recording on stderr, after "tagged N bursts total" -- what the raw samples of the file
  * say about the recording, reduced on the GPU (option "input_stats"; behind a front end: of the capture, not of the band):
  *     input: N samples FMT; I dc %+.5f rms %.2f dBFS peak %.2f dBFS rails %llu (%.4f%%); Q ...; nonfinite %llu
@@ -149,7 +166,8 @@ typedef struct {
     sem_t filled, empty;
     volatile int stop;
     int n_slices;               /* 0: fread */
-    off_t pos, size;
+    off_t pos, size;            /* the slices read [pos, size) of the file */
+    long long remain;           /* fread: bytes left of a container's samples (-1: to the end of the stream) */
     slice_t sl[MAX_SLICES];
 } reader_t;
 
@@ -207,7 +225,14 @@ static void *reader_main(void *arg)
     for (int k = 0;; k ^= 1) {
         sem_wait(&r->empty);
         if (r->stop) break;
-        r->n[k] = r->n_slices ? read_slices(r, r->buf[k]) : fread(r->buf[k], r->bps, r->chunk, r->f);
+        if (r->n_slices) {
+            r->n[k] = read_slices(r, r->buf[k]);
+        } else {
+            size_t want = r->chunk;
+            if (r->remain >= 0 && (unsigned long long)r->remain / r->bps < want) want = (size_t)((unsigned long long)r->remain / r->bps);
+            r->n[k] = want ? fread(r->buf[k], r->bps, want, r->f) : 0;
+            if (r->remain >= 0) r->remain -= (long long)(r->n[k] * r->bps);
+        }
         sem_post(&r->filled);
         if (r->n[k] < r->chunk) {                   /* short read: after it an explicit end marker */
             if (r->n[k] != 0) {
@@ -244,6 +269,8 @@ static const char *format_name(int fmt)
     case IRDM_FMT_CI16_FULL: return "ci16-full";
     case IRDM_FMT_SC16Q11: return "sc16q11";
     case IRDM_FMT_CU8: return "cu8";
+    case IRDM_FMT_CI32: return "ci32";
+    case IRDM_FMT_CI32_24: return "ci32-24";
     default: return "ci8";
     }
 }
@@ -399,7 +426,14 @@ static int parse_time(const char *v, long long *sec, long long *nsec)
 /* the recordings of a run, in the order given */
 typedef struct {
     char *path;
-    uint64_t start_ns;          /* capture time (--start-time for the first, the list's second column); 0: the wall clock */
+    uint64_t start_ns;          /* capture time (--start-time for the first, the list's second column, else a container's
+                                 * header); 0: the wall clock */
+    /* what irdm_recording_probe said (resolve_input): kind 0 a raw file, > 0 a container, -1 a malformed one (err says why) */
+    int kind, fmt, hdr_rate;
+    size_t bps;
+    double centre;              /* the recording's centre frequency: -c, else the header's, else -c's default */
+    irdm_recording_info_t *info;
+    char *err;
 } input_t;
 static input_t *g_in;
 static int g_n_in;
@@ -407,7 +441,9 @@ static int g_n_in;
 static void add_input(const char *path, uint64_t start_ns)
 {
     g_in = realloc(g_in, sizeof(*g_in) * (size_t)(g_n_in + 1));
-    if (!g_in || !(g_in[g_n_in].path = strdup(path))) errx(1, "out of memory");
+    if (!g_in) errx(1, "out of memory");
+    memset(&g_in[g_n_in], 0, sizeof(*g_in));
+    if (!(g_in[g_n_in].path = strdup(path))) errx(1, "out of memory");
     g_in[g_n_in++].start_ns = start_ns;
 }
 
@@ -454,7 +490,68 @@ static int format_of(const char *format, const char *path, size_t *bps)
     /* rtl_sdr's unsigned bytes: by --format, or by an extension the reference does not know (it would read such a file as
      * ci8, which is never right) */
     if (!strcmp(format, "cu8") || (!given && !strcmp(format, "u8"))) return IRDM_FMT_CU8;
+    /* interleaved int32, by --format only */
+    if (given && !strcmp(format, "ci32")) { *bps = 8; return IRDM_FMT_CI32; }
+    if (given && !strcmp(format, "ci32-24")) { *bps = 8; return IRDM_FMT_CI32_24; }
     return IRDM_FMT_CI8;
+}
+
+static const char *container_name(int kind)
+{
+    return kind == IRDM_CONTAINER_WAV ? "wav" : (kind == IRDM_CONTAINER_SIGMF ? "sigmf" : (kind == IRDM_CONTAINER_SDRIQ ? "sdriq" : "raw"));
+}
+
+/* Probe one input (container: -1 by extension, IRDM_CONTAINER_NONE never, else the forced kind) and settle its format, centre
+ * and start time: an explicit -c and an explicit start time win over the header. */
+static void resolve_input(input_t *in, int container, const char *format, double freq, int freq_given)
+{
+    in->kind = 0;
+    in->centre = freq;
+    if (container != IRDM_CONTAINER_NONE && strcmp(in->path, "-") != 0) {
+        char msg[1024];
+        irdm_recording_info_t *info = calloc(1, sizeof(*info));
+        if (!info) errx(1, "out of memory");
+        const int rc = irdm_recording_probe(in->path, container < 0 ? 0 : container, info, msg, sizeof msg);
+        if (rc == 0) {
+            in->kind = info->kind;
+            in->info = info;
+            in->fmt = info->format;
+            in->bps = irdm_format_bytes(info->format);
+            in->hdr_rate = info->sample_rate;
+            if (info->has_center && !freq_given) in->centre = info->center_frequency;
+            if (info->has_start && in->start_ns == 0) in->start_ns = info->start_time_ns;
+            return;
+        }
+        free(info);
+        if (rc < 0) {
+            in->kind = -1;
+            if (!(in->err = strdup(msg))) errx(1, "out of memory");
+            return;
+        }
+    }
+    in->fmt = format_of(format, in->path, &in->bps);
+}
+
+/* the probe line of an input (--probe: stdout; -v: stderr) */
+static void probe_line(FILE *o, const input_t *in, double rate)
+{
+    char centre[64] = "-", start[64] = "-", r[32] = "-";
+    if (in->kind > 0) {
+        const irdm_recording_info_t *i = in->info;
+        if (i->has_center) snprintf(centre, sizeof centre, "%.0f", i->center_frequency);
+        if (i->has_start) snprintf(start, sizeof start, "%llu.%09llu", (unsigned long long)(i->start_time_ns / 1000000000ULL),
+                                   (unsigned long long)(i->start_time_ns % 1000000000ULL));
+        fprintf(o, "probe: %s container=%s format=%s rate=%d centre=%s start=%s offset=%llu bytes=%llu data=%s\n", in->path,
+                container_name(i->kind), format_name(i->format), i->sample_rate, centre, start, (unsigned long long)i->data_offset,
+                (unsigned long long)i->data_bytes, i->data_path);
+        return;
+    }
+    struct stat sb;
+    unsigned long long size = 0;
+    if (strcmp(in->path, "-") != 0 && stat(in->path, &sb) == 0) size = (unsigned long long)sb.st_size;
+    if (rate > 0) snprintf(r, sizeof r, "%.0f", rate);
+    fprintf(o, "probe: %s container=raw format=%s rate=%s centre=- start=- offset=0 bytes=%llu data=%s\n", in->path, format_name(in->fmt), r,
+            size - size % in->bps, in->path);
 }
 
 static const char *base_of(const char *p);
@@ -481,6 +578,37 @@ static int band_sink(void *user, const void *bytes, size_t n)
 }
 
 static const char *save_name(int fmt) { return fmt == IRDM_FMT_CF32 ? "cf32" : (fmt == IRDM_FMT_CI16 ? "ci16" : "ci8"); }
+
+static int has_suffix_nocase(const char *s, const char *suffix)
+{
+    const size_t n = strlen(s), m = strlen(suffix);
+    return n >= m && strcasecmp(s + n - m, suffix) == 0;
+}
+
+/* --save-band FILE.sigmf-data: FILE's .sigmf-meta beside it -- what -f FILE.sigmf-data needs to run the band alone.
+ * start_ns 0 (no capture time known): no core:datetime. */
+static int band_write_meta(const char *save_band, int fmt, int rate, double centre, uint64_t start_ns)
+{
+    char path[4608];
+    const size_t n = strlen(save_band);
+    snprintf(path, sizeof path, "%.*s%s", (int)(n - 4), save_band, save_band[n - 4] == 'D' ? "META" : "meta");
+    FILE *m = fopen(path, "w");
+    if (!m) { perror(path); return 1; }
+    fprintf(m, "{\n  \"global\": {\n    \"core:datatype\": \"%s\",\n    \"core:sample_rate\": %d,\n    \"core:version\": \"1.0.0\",\n"
+               "    \"core:recorder\": \"iridium-sniffer-hip --save-band\"\n  },\n  \"captures\": [\n    {\n      \"core:sample_start\": 0,\n"
+               "      \"core:frequency\": %.17g",
+            fmt == IRDM_FMT_CF32 ? "cf32_le" : (fmt == IRDM_FMT_CI16 ? "ci16_le" : "ci8"), rate, centre);
+    if (start_ns) {
+        const time_t sec = (time_t)(start_ns / 1000000000ULL);
+        struct tm tm;
+        char day[32];
+        gmtime_r(&sec, &tm);
+        strftime(day, sizeof day, "%Y-%m-%dT%H:%M:%S", &tm);
+        fprintf(m, ",\n      \"core:datetime\": \"%s.%09lluZ\"", day, (unsigned long long)(start_ns % 1000000000ULL));
+    }
+    fprintf(m, "\n    }\n  ],\n  \"annotations\": []\n}\n");
+    return fclose(m) != 0;
+}
 
 static int band_open(const char *save_band, const char *out_dir, const char *file, int fmt)
 {
@@ -522,20 +650,28 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
     if (!h_in || !d_in || !d_out) { fprintf(stderr, "--save-only: allocating the buffers failed\n"); return 1; }
     for (int fi = 0; fi < g_n_in; fi++) {
         const char *file = g_in[fi].path;
-        FILE *f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
+        const input_t *in = &g_in[fi];
+        if (in->kind < 0) { fprintf(stderr, "%s\n", in->err); rc_all = 1; continue; }
+        const char *data = in->kind > 0 ? in->info->data_path : file;
+        FILE *f = strcmp(file, "-") ? fopen(data, "rb") : stdin;
         int rc = 0;
-        if (!f) { perror(file); rc_all = 1; continue; }
+        unsigned long long remain = in->kind > 0 ? in->info->data_bytes / bps : ~0ULL;      /* samples left */
+        if (!f) { perror(data); rc_all = 1; continue; }
+        if (in->kind > 0 && fseeko(f, (off_t)in->info->data_offset, SEEK_SET) != 0) { perror(data); fclose(f); rc_all = 1; continue; }
         if (fi > 0 && irdm_frontend_reset(fe) != 0) { fprintf(stderr, "%s: the front end could not be reset\n", file); rc_all = 1; break; }
         if (band_open(save_band, out_dir, file, fmt) != 0) { if (f != stdin) fclose(f); rc_all = 1; continue; }
         for (;;) {
-            const size_t r = fread(h_in, bps, step, f);
+            const size_t want = remain < step ? (size_t)remain : step;
+            const size_t r = want ? fread(h_in, bps, want, f) : 0;
             if (r == 0) break;
+            remain -= r;
             if (irdm_device_upload(d_in, h_in, r * bps) != 0 || irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
             if (r < step) break;
         }
         if (rc == 0 && irdm_frontend_finish_device(fe, d_out, cap, NULL) < 0) rc = 1;
         if (rc) fprintf(stderr, "%s: GPU processing failed\n", file);
         if (band_close(fe, file, fmt, gain, verbose, centre) != 0) rc = 1;
+        if (has_suffix_nocase(save_band, ".sigmf-data") && band_write_meta(save_band, fmt, irdm_frontend_out_rate(fe), centre, in->start_ns) != 0) rc = 1;
         if (g_input_stats) {
             irdm_input_stats_t is;
             if (irdm_frontend_input_stats(fe, &is) == 0) input_line(&is, in_fmt);
@@ -559,6 +695,8 @@ int main(int argc, char **argv)
     int timing = 0;
     const char *file_info = NULL, *format = NULL, *out_dir = NULL;
     double rate = 0, freq = 1622000000.0, db = 0;
+    int freq_given = 0, probe_only = 0;
+    int container = -1;         /* --container: -1 by extension, IRDM_CONTAINER_NONE raw, else the kind every -f is read as */
     int gardner = 1, verbose = 0, no_simd = 0;
     size_t chunk = (size_t)16 << 20;
     int depth = 1;
@@ -594,7 +732,16 @@ int main(int argc, char **argv)
             start_ns = (uint64_t)sec * 1000000000ULL + (uint64_t)nsec;
         }
         else if (!strcmp(a, "-r") || !strcmp(a, "--sample-rate")) rate = atof(NEXT());
-        else if (!strcmp(a, "-c") || !strcmp(a, "--center-freq")) freq = atof(NEXT());
+        else if (!strcmp(a, "-c") || !strcmp(a, "--center-freq")) { freq = atof(NEXT()); freq_given = 1; }
+        else if (!strcmp(a, "--container")) {
+            const char *v = NEXT();
+            if (!strcmp(v, "wav")) container = IRDM_CONTAINER_WAV;
+            else if (!strcmp(v, "sigmf")) container = IRDM_CONTAINER_SIGMF;
+            else if (!strcmp(v, "sdriq")) container = IRDM_CONTAINER_SDRIQ;
+            else if (!strcmp(v, "raw")) container = IRDM_CONTAINER_NONE;
+            else { fprintf(stderr, "--container %s: wav, sigmf, sdriq or raw\n", v); return 2; }
+        }
+        else if (!strcmp(a, "--probe")) probe_only = 1;
         else if (!strcmp(a, "-d") || !strcmp(a, "--threshold")) db = atof(NEXT());
         else if (!strcmp(a, "--format")) format = NEXT();
         else if (!strcmp(a, "--file-info")) file_info = NEXT();
@@ -668,8 +815,56 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    /* the inputs: what each one is (a container's header, or a raw file described by the flags) */
+    int first = -1, n_cont = 0, n_named = 0;     /* containers read well; inputs read as containers, malformed ones too */
+    if (container > 0)
+        for (int k = 0; k < g_n_in; k++)
+            if (!strcmp(g_in[k].path, "-")) {
+                fprintf(stderr, "-f - with --container: standard input is read as a raw stream\n");
+                return 2;
+            }
+    if (g_n_in > 0 && g_in[0].start_ns == 0) g_in[0].start_ns = start_ns;
+    for (int k = 0; k < g_n_in; k++) {
+        resolve_input(&g_in[k], container, format, freq, freq_given);
+        if (g_in[k].kind > 0) n_cont++;
+        if (g_in[k].kind != 0) n_named++;
+        if (g_in[k].kind >= 0 && first < 0) first = k;
+    }
+    if (n_named && format) {
+        fprintf(stderr, "--format %s beside a container: the header names the sample format (--container raw reads the file as raw samples)\n", format);
+        return 2;
+    }
+    if (probe_only && g_n_in) {
+        int bad = 0;
+        for (int k = 0; k < g_n_in; k++) {
+            if (g_in[k].kind < 0) { fprintf(stderr, "%s\n", g_in[k].err); bad++; }
+            else probe_line(stdout, &g_in[k], rate);
+        }
+        return bad ? (g_n_in == 1 ? 2 : 1) : 0;
+    }
+    if (g_n_in && first < 0) {
+        for (int k = 0; k < g_n_in; k++) fprintf(stderr, "%s\n", g_in[k].err);
+        return g_n_in == 1 ? 2 : 1;
+    }
+    if (g_n_in && rate <= 0) {
+        /* no -r: every input carries its rate, and they agree */
+        for (int k = 0; k < g_n_in; k++) {
+            if (g_in[k].kind < 0) continue;
+            if (g_in[k].kind == 0) { rate = 0; break; }
+            if (rate > 0 && (int)rate != g_in[k].hdr_rate) {
+                fprintf(stderr, "%s (%d samples/s) and %s (%d samples/s): one context takes one sample rate (run them apart)\n", g_in[first].path,
+                        g_in[first].hdr_rate, g_in[k].path, g_in[k].hdr_rate);
+                return 2;
+            }
+            rate = g_in[k].hdr_rate;
+        }
+    } else {
+        for (int k = 0; k < g_n_in; k++)
+            if (g_in[k].kind > 0 && (double)g_in[k].hdr_rate != rate)
+                fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
+    }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] -r RATE [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -743,7 +938,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "--save-band auto: name the format with --save-format ci8|ci16|cf32\n");
             return 2;
         }
-        save_fmt = save_format_of(save_format, save_band);
+        save_fmt = save_format_of(save_format ? save_format : (has_suffix_nocase(save_band, ".sigmf-data") ? "cf32" : NULL), save_band);
         if (save_fmt < 0) {
             if (save_format) fprintf(stderr, "--save-format %s: ci8, ci16 or cf32\n", save_format);
             else fprintf(stderr, "--save-band %s: the extension names no format (.ci8, .ci16, .cs16, .cf32, .fc32, .cfile); give --save-format\n", save_band);
@@ -761,17 +956,22 @@ int main(int argc, char **argv)
         fprintf(stderr, "--save-format, --save-gain and --save-only go with --save-band FILE\n");
         return 2;
     }
-    size_t bps = 2;
-    const int fmt = format_of(format, g_in[0].path, &bps);
+    const size_t bps = g_in[first].bps;
+    const int fmt = g_in[first].fmt;
+    freq = g_in[first].centre;
     for (int k = 0; k < g_n_in; k++) {
-        size_t b;
         if (g_n_in > 1 && !strcmp(g_in[k].path, "-")) {
             fprintf(stderr, "-f -: stdin only as the sole input (%d recordings given)\n", g_n_in);
             return 2;
         }
-        if (format_of(format, g_in[k].path, &b) != fmt) {
+        if (g_in[k].kind >= 0 && g_in[k].fmt != fmt) {
             fprintf(stderr, "%s and %s resolve to different sample formats: one context takes one format (give --format, or run them apart)\n",
-                    g_in[0].path, g_in[k].path);
+                    g_in[first].path, g_in[k].path);
+            return 2;
+        }
+        if (g_in[k].kind >= 0 && (decimate || resample_to) && g_in[k].centre != freq) {
+            fprintf(stderr, "%s (%.0f Hz) and %s (%.0f Hz): behind a front end every recording has one centre frequency (its shift is fixed; give -c, or run them apart)\n",
+                    g_in[first].path, freq, g_in[k].path, g_in[k].centre);
             return 2;
         }
         for (int j = 0; out_dir && j < k; j++)
@@ -780,7 +980,15 @@ int main(int argc, char **argv)
                 return 2;
             }
     }
-    if (g_in[0].start_ns == 0) g_in[0].start_ns = start_ns;
+    if (n_cont && !resample_to && (long long)rate % 250000 != 0)
+        fprintf(stderr, "warning: %.0f samples/s is no multiple of 250 kHz: frames may decode only in part; resample with --resample-to HZ\n", rate);
+    if (verbose)
+        for (int k = 0; k < g_n_in; k++) {
+            if (g_in[k].kind <= 0) continue;
+            probe_line(stderr, &g_in[k], rate);
+            if (g_in[k].info->n_captures > 1)
+                fprintf(stderr, "%s: %d capture segments, the first one's frequency and time are used\n", g_in[k].path, g_in[k].info->n_captures);
+        }
     g_out = stdout;
 
     /* the front end first: the context behind it runs at its output rate, centred where the applied shift puts it */
@@ -818,7 +1026,7 @@ int main(int argc, char **argv)
     c.format = fe ? IRDM_FMT_CF32 : fmt;
     c.feed_block = 32768;
     c.use_gardner = gardner;
-    c.start_time_ns = g_in[0].start_ns;
+    c.start_time_ns = g_in[first].start_ns;
     /* (several GPUs: a chunk must hold the samples a member is given from in front of its chunk -- 2 s of signal, the
      * reference's ring -- so the default grows with the rate) */
     if (gpus > 1 && !chunk_given) chunk = (size_t)(2.75 * rate);
@@ -931,12 +1139,16 @@ int main(int argc, char **argv)
         double reset_ms = 0;
         int rc = 0;
         unsigned long long fed = 0;
+        const input_t *in = &g_in[fi];
+        /* (a malformed header: the probe's message, and nothing of the file is read as samples) */
+        if (in->kind < 0) { fprintf(stderr, "%s\n", in->err); rc_all = 1; f = NULL; continue; }
+        const char *data = in->kind > 0 ? in->info->data_path : file;
         g_n_demods = 0;
-        f = strcmp(file, "-") ? fopen(file, "rb") : stdin;
-        if (!f) { perror(file); rc_all = 1; continue; }
+        f = strcmp(file, "-") ? fopen(data, "rb") : stdin;
+        if (!f) { perror(data); rc_all = 1; continue; }
         if (fi > 0) {
             /* the context and the front end as they were created, for this recording's centre frequency and capture time */
-            if ((fe && irdm_frontend_reset(fe) != 0) || irdm_reset(p, c.center_frequency, g_in[fi].start_ns) != 0) {
+            if ((fe && irdm_frontend_reset(fe) != 0) || irdm_reset(p, fe ? c.center_frequency : in->centre, in->start_ns) != 0) {
                 fprintf(stderr, "%s: the context could not be reset\n", file);
                 fclose(f);
                 rc_all = 1;
@@ -1008,6 +1220,12 @@ int main(int argc, char **argv)
         rd.f = f;
         rd.bps = bps;
         rd.chunk = step;
+        rd.remain = -1;
+        if (in->kind > 0) {
+            /* a container: [data_offset, data_offset + data_bytes) of the data file, for the fread path here and the slices below */
+            rd.remain = (long long)in->info->data_bytes;
+            if (fseeko(f, (off_t)in->info->data_offset, SEEK_SET) != 0) { perror(data); return 1; }
+        }
         rd.buf[0] = pinned[0];
         rd.buf[1] = pinned[1];
         sem_init(&rd.filled, 0, 0);
@@ -1017,6 +1235,11 @@ int main(int argc, char **argv)
             if (f != stdin && read_threads > 0 && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
                 rd.n_slices = read_threads > MAX_SLICES ? MAX_SLICES : read_threads;
                 rd.size = sb.st_size - sb.st_size % (off_t)bps;
+                if (in->kind > 0) {
+                    rd.pos = (off_t)in->info->data_offset;
+                    rd.size = (off_t)(in->info->data_offset + in->info->data_bytes);
+                    if (rd.size > sb.st_size) rd.size = rd.pos + (sb.st_size > rd.pos ? (sb.st_size - rd.pos) / (off_t)bps * (off_t)bps : 0);
+                }
                 for (int i = 0; i < rd.n_slices; i++) {
                     rd.sl[i].fd = fileno(f);
                     sem_init(&rd.sl[i].go, 0, 0);
@@ -1079,6 +1302,8 @@ int main(int argc, char **argv)
             if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */
         }
         if (save_band && band_close(fe, file, save_fmt, (float)save_gain, verbose, c.center_frequency) != 0) rc = 1;
+        if (save_band && has_suffix_nocase(save_band, ".sigmf-data") &&
+            band_write_meta(save_band, save_fmt, irdm_frontend_out_rate(fe), c.center_frequency, irdm_start_time_ns(p)) != 0) rc = 1;
         if (g_input_stats) {
             irdm_input_stats_t is;
             if ((fe ? irdm_frontend_input_stats(fe, &is) : irdm_input_stats(p, &is)) == 0) input_line(&is, fmt);

@@ -20,6 +20,19 @@ FMT_CI16_FULL, FMT_SC16Q11 = 3, 4
 FMT_SCALE = {FMT_CI16_FULL: 1.0 / 32768.0, FMT_SC16Q11: 1.0 / 2048.0}
 # rtl_sdr's unsigned 8-bit I/Q (offset binary): records equal a cf32 context's on convert_cu8(u)
 FMT_CU8 = 6
+# 32-bit integer I/Q, interleaved int32 I, Q: records equal a cf32 context's on v.astype(np.float32) * np.float32(FMT_SCALE[fmt])
+# (FMT_CI32: SigMF ci32_le, 32-bit PCM WAV; FMT_CI32_24: 24-bit samples held in int32, SDRangel's .sdriq)
+FMT_CI32, FMT_CI32_24 = 8, 9
+FMT_SCALE.update({FMT_CI32: 2.0 ** -31, FMT_CI32_24: 2.0 ** -23})
+# irdm_recording_probe: container kinds
+CONTAINER_NONE, CONTAINER_WAV, CONTAINER_SIGMF, CONTAINER_SDRIQ = 0, 1, 2, 3
+
+
+def convert_ci32(v, fmt=FMT_CI32):
+    """interleaved int32 I, Q -> complex64 as the load stage converts them: (float)v, rounded to nearest even, times 2^-31
+    (FMT_CI32) or 2^-23 (FMT_CI32_24)"""
+    v = np.ascontiguousarray(v, np.int32)
+    return (v.astype(np.float32) * np.float32(FMT_SCALE[fmt])).view(np.complex64)
 
 
 def convert_cu8(u):
@@ -176,9 +189,26 @@ class InputStats(C.Structure):
                 ("sum", C.c_double * 2), ("sum_sq", C.c_double * 2), ("abs_max", C.c_float * 2)]
 
 
+class RecordingInfo(C.Structure):
+    """irdm_recording_info_t (irdm_recording_probe)"""
+    _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
+                ("center_frequency", C.c_double), ("has_start", C.c_int), ("n_captures", C.c_int),
+                ("start_time_ns", C.c_uint64), ("data_offset", C.c_uint64), ("data_bytes", C.c_uint64),
+                ("data_path", C.c_char * 4096)]
+
+
 ACARS_LINE_MAX = 8192
 RAW_LINE_MAX = 1280
 _lib = None
+
+
+def recording_probe(path, container=CONTAINER_NONE):
+    """irdm_recording_probe (host code only, no GPU needed): (rc, RecordingInfo, message) -- rc 0 a container was recognised,
+    1 not a container (a raw file), -1 malformed or unsupported, and the message says what and where"""
+    info = RecordingInfo()
+    err = C.create_string_buffer(1024)
+    rc = lib().irdm_recording_probe(os.fsencode(str(path)), int(container), C.byref(info), err, len(err))
+    return rc, info, err.value.decode(errors="replace")
 
 
 def build(force=False):
@@ -216,6 +246,11 @@ def lib():
         if hasattr(L, "irdm_input_stats"):
             L.irdm_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
             L.irdm_input_stats_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(InputStats), C.c_int, C.c_void_p]
+        if hasattr(L, "irdm_recording_probe"):
+            L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
+        if hasattr(L, "irdm_format_bytes"):
+            L.irdm_format_bytes.argtypes = [C.c_int]
+            L.irdm_format_bytes.restype = C.c_size_t
         L.irdm_host_alloc.argtypes = [C.c_size_t]
         L.irdm_host_alloc.restype = C.c_void_p
         L.irdm_host_free.argtypes = [C.c_void_p]
