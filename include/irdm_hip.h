@@ -309,6 +309,35 @@ typedef struct {
     float    abs_max[2];                  /* max |x| over finite components */
 } irdm_input_stats_t;
 
+/* option "symbol_clock": the symbol clock error of one downmixed frame, estimated on the device from the samples the
+ * demodulator is handed (irdm_poll_symbol_clock, irdm_symbol_clock_batch).  |x|^2 of a frame carries a spectral line at the
+ * symbol rate, 1 / (sps (1 + eps)) cycles per sample at the context's nominal sps = 10: the line is looked for on the grid
+ * eps = -0.08 + 0.001 k, k = 0 .. 160, and refined by a three-point parabola.  eps is the README's clock error
+ * fs / decim / 250000 - 1 as the samples show it, whatever rate was declared. */
+#define IRDM_CLOCK_INVALID       1u   /* no estimate (eps = quality = 0): the frame was dropped in front of the demodulator, is
+                                       * shorter than 64 samples, all zero, or holds a sample that is not finite */
+#define IRDM_CLOCK_OUT_OF_RANGE  2u   /* the maximum is at an edge of the grid, or one of 30 guard points of the same step beyond
+                                       * an edge (to +-11 %) exceeds it: eps is that edge */
+#define IRDM_CLOCK_NOT_OK        4u   /* (set by the context, never by the stage call) the demodulator rejected the frame's
+                                       * unique word: no demodulator record goes with this one */
+typedef struct {
+    uint64_t id;               /* the burst's id; irdm_symbol_clock_batch: the frame's index */
+    float    eps;              /* clock error, a fraction (0.0025 = +0.25 %) */
+    float    quality;          /* the maximum over the mean of the grid: 12 and more on a clean frame, 2 .. 7 without a line */
+    uint32_t flags;            /* IRDM_CLOCK_* */
+    uint32_t n;                /* samples of the frame */
+} irdm_clock_est_t;
+
+/* irdm_symbol_clock: the stream so far.  Frames count as used when their unique word passed and their record is neither
+ * invalid nor out of range; median and quartiles are centres of the 0.01 % bins of a histogram over +-8 %, so they do not
+ * depend on how the stream was cut into chunks or feeds (0 while frames_used is 0). */
+typedef struct {
+    uint64_t frames_used, frames_not_ok, frames_out_of_range;
+    double   median, q25, q75;       /* fractions */
+    double   implied_rate_hz;        /* 250000 * decim * (1 + median): the rate the samples look like */
+    uint64_t frames_invalid;         /* unique word passed, record invalid */
+} irdm_symbol_clock_t;
+
 typedef struct irdm_pipeline irdm_pipeline_t;
 
 /* burst_detector_create + burst_downmix_create (burst_detect.c:174, burst_downmix.c:223):
@@ -618,7 +647,14 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         when the option is first set to 1, never before.  -1 for a member of a group (and so through
  *                         irdm_group_set_option) and while a chunk handed over with irdm_feed_begin waits for its
  *                         irdm_feed_end
- *   "decode_frames" / "decode_ida"   0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
+ *   "symbol_clock"        0/1, default 0: 1 = one more kernel in the per-burst chain of every chunk fed from then on, behind
+ *                         the downmixer and beside the demodulator: the symbol clock error of every frame, see
+ *                         irdm_poll_symbol_clock / irdm_symbol_clock.  It reads the frames only: no other record changes.
+ *                         One pinned buffer of 16 bytes per burst and batch context is allocated when the option is first
+ *                         set to 1, never before; with 0 nothing is launched.  -1 for a member of a group (and so through
+ *                         irdm_group_set_option) and while a chunk handed over with irdm_feed_begin waits for its
+ *                         irdm_feed_end
+ *   "decode_frames" / "decode_ida"  0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
  *   "fir_order" (alias "simd_order")   default 1 = the arithmetic of the reference's AVX2 kernels, simd_avx2.c -- what
  *                         simd_init() (simd_generic.c:33-57) selects on x86: fir_ccf_dec :62-108, fir_ccf :28-55, fir_fff
@@ -965,6 +1001,22 @@ int irdm_input_stats(irdm_pipeline_t *p, irdm_input_stats_t *out);
 int irdm_frontend_input_stats_enable(irdm_frontend_t *fe, int on);
 int irdm_frontend_input_stats(irdm_frontend_t *fe, irdm_input_stats_t *out);
 int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_stats_t *out, int device, void *stream);
+
+/* ---- symbol clock check (irdm_clock_est_t / irdm_symbol_clock_t above) ----
+ * irdm_set_option(p, "symbol_clock", 1): every frame that reaches the demodulator from then on gets an estimate of its
+ * symbol clock error, by one kernel on the chain's stream that only reads the frames.
+ * irdm_poll_symbol_clock: up to `max` per-frame records, one for every frame that reached the demodulator, in the order
+ *   of the demodulator's records: those without IRDM_CLOCK_NOT_OK pair one to one with the records of irdm_poll_demods /
+ *   irdm_poll_demods_packed.  A frame's record depends on its samples alone, not on pipeline_depth or how the stream was
+ *   fed.  Returns the number written (0 with the option off), -1 on error.
+ * irdm_symbol_clock: the summary of the stream so far (of the records queued so far: irdm_flush first for the whole
+ *   stream).  irdm_reset starts it over.  Returns 0, or -1 (the option never set included).
+ * irdm_symbol_clock_batch: the kernel alone on n frames, with the calling convention of irdm_qpsk_demod_batch: samples =
+ *   n rows of IRDM_MAX_FRAME_SAMPLES interleaved float pairs, num_samples[i] <= IRDM_MAX_FRAME_SAMPLES.  Works with the
+ *   option off.  Returns 0 or -1. */
+int irdm_poll_symbol_clock(irdm_pipeline_t *p, irdm_clock_est_t *out, int max);
+int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out);
+int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out);
 
 /* ---- self-describing recordings: WAV / RF64, SigMF, SDRangel .sdriq (csrc/recording.cpp) ----
  * Host code only, no device call: works without a GPU.  irdm_recording_probe reads the header of `path` and says what the

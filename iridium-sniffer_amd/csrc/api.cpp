@@ -28,6 +28,12 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
         return input_stats_configure(p, value);
     }
+    if (!strcmp(key, "symbol_clock")) {
+        // 0 / 1; not for a member of a group (the summary is a context's, and a group merges no clock records), and not while
+        // a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
+        if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
+        return symbol_clock_configure(p, value);
+    }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
     if (!strcmp(key, "detect_only")) { p->detect_only = value; return 0; }
@@ -77,6 +83,32 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         return 0;
     }
     return -1;
+}
+
+// ---- option "symbol_clock" (symbol_clock.hpp): the pinned records of every batch context, when the option is first set ----
+int symbol_clock_configure(irdm_pipeline *p, int on)
+{
+    for (int i = 0; on && i < p->n_bc; i++) {
+        BatchCtx &b = p->bc[i];
+        if (!b.hp_clock &&
+            hipHostMalloc(reinterpret_cast<void **>(&b.hp_clock), sizeof(ClockRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
+            return -1;
+    }
+    p->symbol_clock = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_poll_symbol_clock(irdm_pipeline_t *p, irdm_clock_est_t *out, int max)
+{
+    if (!p || !out || max < 0) return -1;
+    return drain(p->st.clock.q, out, max);
+}
+
+extern "C" int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out)
+{
+    if (!p || !out || !p->bc[0].hp_clock) return -1;
+    symbol_clock_result(p->st.clock, p->decim, out);
+    return 0;
 }
 
 extern "C" int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key)

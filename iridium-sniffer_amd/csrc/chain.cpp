@@ -585,6 +585,9 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
                      b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr, b.parsed || b.framed ? 1 : 0) != 0)
         return -1;
     IRDM_HIP_CHECK(hipEventRecord(b.ev[3], st));
+    // option "symbol_clock": the clock error of every frame, from the frames post2 left (read only), into pinned memory
+    b.clocked = p->symbol_clock && b.hp_clock;
+    if (b.clocked && launch_symbol_clock(b.d_work, nb, b.d_frames, p->sps, b.hp_clock, st) != 0) return -1;
     if (b.parsed &&
         launch_ida_packed(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_ida, st) != 0)
         return -1;
@@ -672,6 +675,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             p->st.q.bursts.push_back(r);
             p->st.last_bursts.push_back(r);
             const DemodPacked &d = b.hp_packed[i];
+            if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], d.ok != 0);
             if (w.drop_reason != 0 || !d.ok) continue;
             uint64_t timestamp = p->st.start_time_ns + (uint64_t)((double)r.start / fs * 1e9);
             if (w.dec_len > 0) timestamp += (uint64_t)((p->in_ntaps / 2) * 1000000000ULL / fs);
@@ -755,6 +759,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
                           p->h_frames.begin() + (size_t)i * kMaxFrameSamples * 2 + 2 * (size_t)w.num_samples);
             p->st.q.frame_samples.push_back(std::move(sv));
         }
+        if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], b.hp_demod[i].ok != 0);
         if (w.drop_reason == 0 && b.hp_demod[i].ok) {
             const DemodOut &d = b.hp_demod[i];
             // built in place in the queue, and only the symbols the frame has are copied (a record is 4.5 KB; 667 of

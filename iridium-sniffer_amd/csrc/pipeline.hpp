@@ -37,6 +37,7 @@
 #include "types.hpp"
 #include "record_queues.hpp"
 #include "input_stats.hpp"
+#include "symbol_clock.hpp"
 
 using namespace irdm;
 
@@ -132,12 +133,14 @@ struct BatchCtx {
     DemodPacked *hp_packed;                 // packed_records: the demodulator's result without LLRs, bits 8 per byte (pinned; written by demod_par_kernel)
     IdaPacked *hp_ida;                      // parsed_records: ida_decode() of each of them (pinned; written by ida_packed_kernel)
     FramePacked *hp_frame;                  // frame_records: frame_decode() of each of them (pinned; written by frame_packed_kernel)
+    ClockRec *hp_clock;                     // symbol_clock: one record per burst (pinned; written by symbol_clock_kernel; allocated with the option)
     uint32_t *hp_flag, *hp_flag_dev;    // [0] sequence number the helper publishes, [1] time-out flag of the waiting kernel
     int4 *hp_rot_new, *hp_rot_new_dev, *d_rot_new;   // (bin, row, from, to) of the checkpoint runs this batch has to build: mapped pinned / device
     uint32_t cfo_seq;
     bool packed;                 // this batch came back as DemodPacked records
     bool parsed;                 // ... and IdaPacked records
     bool framed;                 // ... and FramePacked records
+    bool clocked;                // this batch ran the symbol clock kernel: hp_clock holds its records
     bool cfo_on_device;          // this batch's libm step ran on the device: h_cfreq is filled from the returned records
     std::vector<double> h_cfreq;
     // stream state (irdm_reset assigns a fresh one): the batch in flight
@@ -226,6 +229,8 @@ struct StreamState {
     std::deque<SpecRow> spec_q;
     // option "input_stats": the totals of the stream's raw samples and the passes in flight (input_stats.hpp)
     InputStatsStream in_stats;
+    // option "symbol_clock": the per-frame records until they are polled and the summary's histogram (symbol_clock.hpp)
+    SymbolClockStream clock;
 };
 
 struct irdm_pipeline {
@@ -417,6 +422,9 @@ struct irdm_pipeline {
     // option "input_stats" (feed.cpp, input_stats.hpp): the side stream and the blocks of the passes (cache: allocated when
     // the option is first set); in_stats.on is the switch (configuration)
     InputStatsPass in_stats;
+    // option "symbol_clock" (chain.cpp, symbol_clock.hpp): the switch (configuration); the batch contexts' hp_clock are the
+    // cache, allocated when the option is first set
+    int symbol_clock = 0;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -464,6 +472,7 @@ int process_bursts(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 // feed.cpp
 int spectrum_configure(irdm_pipeline *p, int R);
 int input_stats_configure(irdm_pipeline *p, int on);
+int symbol_clock_configure(irdm_pipeline *p, int on);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

@@ -10,7 +10,7 @@
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
- *                         [--input-stats] [--diagnostic]
+ *                         [--input-stats] [--diagnostic] [--clock-check]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -81,6 +81,15 @@
  * | Noise: ... | Peak: ..." line and its guidance clause; the elapsed time is the recording's stream time, samples / rate.
  * Both work with --save-only (statistics without a context; no Runtime line: there is no detector) and are refused with
  * --gpus N > 1.
+ * --clock-check: one closing line per recording on stderr, directly after "tagged N bursts total" -- the symbol clock error
+ * the frames themselves show, estimated on the GPU (option "symbol_clock"), whatever -r said:
+ *     clock: N frames; symbol clock %+.2f %% (quartiles %+.2f %% .. %+.2f %%); A not ok, B out of range
+ * over the frames whose unique word passed; "clock: N frames; too few to judge" below 5 of them.  From 5 frames and a median
+ * of 0.15 % on (between the 0.098 % that does no harm and the 0.25 % from which frames die half way) a clause follows:
+ *     -- the samples look like R S/s, not R0: check -r, or --resample-to R0
+ * R0 the grid rate the pipeline assumed, R rounded to 0.05 % of it (the estimator's resolution).  Behind a front end the
+ * line describes the stream the detector sees; R and R0 are scaled back to the capture's -r.  stdout and the rest of
+ * stderr are those of the run without the flag.  Refused with --gpus N > 1 and with --save-only (no context, no frames).
  */
 #include <err.h>
 #include <errno.h>
@@ -259,6 +268,8 @@ static irdm_group_t *g_group;
 
 /* --input-stats / --diagnostic */
 static int g_input_stats, g_diag;
+/* --clock-check */
+static int g_clock;
 static unsigned long long g_n_demods;       /* frames the demodulator accepted, this recording */
 
 static const char *format_name(int fmt)
@@ -290,6 +301,29 @@ static void input_line(const irdm_input_stats_t *st, int fmt)
                 rails, n > 0 ? 100.0 * (double)rails / n : 0.0);
     }
     fprintf(stderr, " nonfinite %llu\n", (unsigned long long)(st->n_nonfinite[0] + st->n_nonfinite[1]));
+}
+
+/* the closing "clock:" line of a recording.  nominal: the rate the detector's stream was taken for (its context's rate);
+ * capture: the -r of the file in front of it (the same without a front end) */
+static void clock_line(const irdm_symbol_clock_t *sc, double nominal, double capture, int front_end)
+{
+    if (sc->frames_used < 5) {
+        fprintf(stderr, "clock: %llu frames; too few to judge\n", (unsigned long long)sc->frames_used);
+        return;
+    }
+    fprintf(stderr, "clock: %llu frames; symbol clock %+.2f %% (quartiles %+.2f %% .. %+.2f %%); %llu not ok, %llu out of range",
+            (unsigned long long)sc->frames_used, 100.0 * sc->median, 100.0 * sc->q25, 100.0 * sc->q75,
+            (unsigned long long)sc->frames_not_ok, (unsigned long long)sc->frames_out_of_range);
+    if (fabs(sc->median) >= 0.0015 - 1e-12) {
+        /* the grid rate the pipeline assumed and the rate the samples look like, both as rates of the capture; the latter in
+         * steps of 0.05 % of the former */
+        const double grid = sc->implied_rate_hz / (1.0 + sc->median), scale = capture / nominal;
+        const double step = grid * scale / 2000.0;
+        const double looks = floor(sc->implied_rate_hz * scale / step + 0.5) * step;
+        fprintf(stderr, " -- the samples look like %.0f S/s, not %.0f: check -r", looks, grid * scale);
+        if (!front_end) fprintf(stderr, ", or --resample-to %.0f", grid);
+    }
+    fprintf(stderr, "\n");
 }
 
 /* --diagnostic: the reference's closing status line (main.c:444-480) over the recording's stream time */
@@ -356,6 +390,11 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
             }
             if (len > 0 && !g_diag) fwrite(line, 1, (size_t)len, g_out);
         }
+    }
+    if (g_clock) {
+        /* (the summary is the library's; the per-frame records are not printed) */
+        static irdm_clock_est_t ce[256];
+        while (irdm_poll_symbol_clock(p, ce, 256) > 0) {}
     }
     static irdm_ida_t ida[256];
     static irdm_decoded_t dec[256];
@@ -802,6 +841,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--save-only")) save_only = 1;
         else if (!strcmp(a, "--input-stats")) g_input_stats = 1;
         else if (!strcmp(a, "--diagnostic")) g_input_stats = g_diag = 1;     /* options.c:376 */
+        else if (!strcmp(a, "--clock-check")) g_clock = 1;
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -864,7 +904,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -920,6 +960,17 @@ int main(int argc, char **argv)
     if (g_input_stats) {
         if (gpus > 1) {
             fprintf(stderr, "%s: one GPU only (--gpus %d)\n", g_diag ? "--diagnostic" : "--input-stats", gpus);
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_clock) {
+        if (gpus > 1) {
+            fprintf(stderr, "--clock-check: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if (save_only) {
+            fprintf(stderr, "--clock-check with --save-only: no context runs, so there are no frames to judge\n");
             return 2;
         }
         gpus = 0;
@@ -1113,6 +1164,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "--input-stats: the library refused the statistics\n");
         return 1;
     }
+    if (g_clock && irdm_set_option(p, "symbol_clock", 1) != 0) {
+        fprintf(stderr, "--clock-check: the library refused the estimator\n");
+        return 1;
+    }
     g_save_dir = save_dir;
     /* a group is fed a super-step at a time: one chunk per member */
     /* (behind a front end the reader's chunk is D -- or M / L -- pipeline chunks of capture samples) */
@@ -1297,6 +1352,11 @@ int main(int argc, char **argv)
         }
         fprintf(stderr, "burst_detect: tagged %lu bursts total\n",
                 (unsigned long)(g_group ? (uint64_t)irdm_group_get_stat(g_group, "tagged") : irdm_tagged_bursts(p)));
+        if (g_clock) {
+            irdm_symbol_clock_t sc;
+            if (irdm_symbol_clock(p, &sc) == 0) clock_line(&sc, (double)c.sample_rate, rate, fe != NULL);
+            else { fprintf(stderr, "--clock-check: %s: no estimate\n", file); rc = 1; }
+        }
         if (g_acars) {
             char st[512];
             if (irdm_acars_format_stats(g_acars, st, sizeof st) > 0) fputs(st, stderr);      /* main.c:805-806 */

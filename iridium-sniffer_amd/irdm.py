@@ -189,6 +189,21 @@ class InputStats(C.Structure):
                 ("sum", C.c_double * 2), ("sum_sq", C.c_double * 2), ("abs_max", C.c_float * 2)]
 
 
+CLOCK_INVALID, CLOCK_OUT_OF_RANGE, CLOCK_NOT_OK = 1, 2, 4
+
+
+class ClockEst(C.Structure):
+    """irdm_clock_est_t (option symbol_clock): eps and quality of one frame, flags CLOCK_*"""
+    _fields_ = [("id", C.c_uint64), ("eps", C.c_float), ("quality", C.c_float), ("flags", C.c_uint32), ("n", C.c_uint32)]
+
+
+class SymbolClock(C.Structure):
+    """irdm_symbol_clock_t (irdm_symbol_clock): the summary of the stream so far; median and quartiles are fractions"""
+    _fields_ = [("frames_used", C.c_uint64), ("frames_not_ok", C.c_uint64), ("frames_out_of_range", C.c_uint64),
+                ("median", C.c_double), ("q25", C.c_double), ("q75", C.c_double), ("implied_rate_hz", C.c_double),
+                ("frames_invalid", C.c_uint64)]
+
+
 class RecordingInfo(C.Structure):
     """irdm_recording_info_t (irdm_recording_probe)"""
     _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
@@ -246,6 +261,10 @@ def lib():
         if hasattr(L, "irdm_input_stats"):
             L.irdm_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
             L.irdm_input_stats_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(InputStats), C.c_int, C.c_void_p]
+        if hasattr(L, "irdm_symbol_clock"):
+            L.irdm_poll_symbol_clock.argtypes = [C.c_void_p, C.POINTER(ClockEst), C.c_int]
+            L.irdm_symbol_clock.argtypes = [C.c_void_p, C.POINTER(SymbolClock)]
+            L.irdm_symbol_clock_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(ClockEst)]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -730,6 +749,35 @@ class Pipeline:
     def poll_frame_packed(self):
         """option frame_records 1: one FramePacked per polled DemodPacked, in the same order"""
         return self._poll(self.L.irdm_poll_frame_packed, FramePacked)
+
+    def poll_symbol_clock(self):
+        """option symbol_clock 1: one ClockEst per frame that reached the demodulator, in the order of the demod records"""
+        return self._poll(self.L.irdm_poll_symbol_clock, ClockEst)
+
+    def poll_symbol_clock_raw(self, chunk=4096):
+        """the same as one numpy byte matrix [n, 24]"""
+        return self._poll_raw(self.L.irdm_poll_symbol_clock, ClockEst, chunk)
+
+    def symbol_clock(self):
+        """irdm_symbol_clock (option symbol_clock): the SymbolClock summary of the stream so far"""
+        st = SymbolClock()
+        if self.L.irdm_symbol_clock(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_symbol_clock failed (option symbol_clock never set?)")
+        return st
+
+    def symbol_clock_batch(self, frames):
+        """irdm_symbol_clock_batch: frames = list of complex64 arrays (<= 4440 samples); returns a list of ClockEst"""
+        n = len(frames)
+        buf = np.zeros((max(n, 1), 2 * MAX_FRAME_SAMPLES), np.float32)
+        ns = np.zeros(max(n, 1), np.int32)
+        for i, f in enumerate(frames):
+            f = np.ascontiguousarray(f, np.complex64)
+            ns[i] = len(f)
+            buf[i, :2 * len(f)] = f.view(np.float32)
+        out = (ClockEst * max(n, 1))()
+        if self.L.irdm_symbol_clock_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
+            raise RuntimeError("irdm_symbol_clock_batch failed")
+        return [ClockEst.from_buffer_copy(out[i]) for i in range(n)]
 
     def poll_spectrum(self, chunk=64):
         """option spectrum_frames: (headers, mean, peak) of the rows finished so far -- a list of SpectrumRow and two float32
