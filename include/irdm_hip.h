@@ -338,6 +338,47 @@ typedef struct {
     uint64_t frames_invalid;         /* unique word passed, record invalid */
 } irdm_symbol_clock_t;
 
+/* option "iq_sense": which way round I and Q of one demodulated frame were (irdm_poll_iq_votes, irdm_iq_sense_batch).
+ * A recording with its two components exchanged (a Q/I WAV, the other SigMF convention, an inverting mixer) demodulates
+ * with ok = 1 and full confidence -- preamble and unique words use the DQPSK states 0 and 2 alone, which conjugation maps
+ * onto themselves -- but every frequency is mirrored about the centre and the two bits of every dibit are exchanged, so no
+ * payload decodes.  Three predicates that chance does not satisfy are evaluated on the frame's bits as they are
+ * ("recorded") and with b'[2i] = b[2i+1], b'[2i+1] = b[2i] over the whole frame, LLRs following ("exchanged"):
+ *   IRA (bit 0)  a DL or UL access code, n_bits >= 24 + 96, each of the three header blocks of the 3-way de-interleave has
+ *                a zero BCH(31,21) remainder (polynomial 1207) and its 32nd bit is their parity, nothing corrected;
+ *   IBC (bit 1)  the access code, n_bits >= 24 + 6 + 64, a zero BCH(7,3) remainder (polynomial 29) of the 6 header bits,
+ *                and the first two blocks of the 2-way de-interleave clean in the same way;
+ *   IDA (bit 2)  the device's IDA decode (Chase decoding on the LLRs, as irdm_ida_decode_batch with use_llr) succeeds
+ *                with da_len > 0 and a CRC that holds.
+ * A frame votes recorded when recorded != 0 && exchanged == 0, exchanged when the reverse holds, counts as "both" when
+ * both are non-zero and is silent otherwise. */
+#define IRDM_IQ_IRA 1u
+#define IRDM_IQ_IBC 2u
+#define IRDM_IQ_IDA 4u
+typedef struct {
+    uint64_t id;               /* the burst's id; irdm_iq_sense_batch: the frame's index */
+    uint8_t  recorded;         /* IRDM_IQ_* that hold on the bits as they are */
+    uint8_t  exchanged;        /* ... with the two bits of every dibit exchanged */
+    uint16_t pad;
+    uint32_t n_bits;           /* the bits looked at: the frame's, rounded down to whole dibits */
+} irdm_iq_vote_t;
+
+#define IRDM_IQ_TOO_FEW      0     /* fewer than 5 deciding frames (the threshold of the symbol clock check) */
+#define IRDM_IQ_AS_RECORDED  1     /* at least 9 in 10 of the deciding frames vote recorded */
+#define IRDM_IQ_EXCHANGED    2     /* at least 9 in 10 vote exchanged: the recording is I/Q-swapped */
+#define IRDM_IQ_MIXED        3
+/* irdm_iq_sense: the stream so far.  kind index 0 IRA, 1 IBC, 2 IDA: a deciding frame is counted under every kind its
+ * deciding sense holds (a frame that is IRA and IDA at once under both).  verdict over d = votes_recorded +
+ * votes_exchanged: TOO_FEW when d < 5, AS_RECORDED when 10 votes_recorded >= 9 d, EXCHANGED when 10 votes_exchanged >= 9 d,
+ * MIXED otherwise. */
+typedef struct {
+    uint64_t frames;                        /* frames seen (unique word passed) */
+    uint64_t votes_recorded, votes_exchanged, votes_both;
+    uint64_t kind_recorded[3], kind_exchanged[3], kind_both[3];
+    int32_t  verdict;                       /* IRDM_IQ_TOO_FEW .. IRDM_IQ_MIXED */
+    int32_t  pad;
+} irdm_iq_sense_t;
+
 typedef struct irdm_pipeline irdm_pipeline_t;
 
 /* burst_detector_create + burst_downmix_create (burst_detect.c:174, burst_downmix.c:223):
@@ -654,6 +695,21 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         set to 1, never before; with 0 nothing is launched.  -1 for a member of a group (and so through
  *                         irdm_group_set_option) and while a chunk handed over with irdm_feed_begin waits for its
  *                         irdm_feed_end
+ *   "iq_sense"            0/1, default 0: 1 = one more kernel in the per-burst chain of every chunk fed from then on, behind
+ *                         the demodulator: whether each frame's bits make sense as they are or with I and Q exchanged, see
+ *                         irdm_poll_iq_votes / irdm_iq_sense.  It reads the demodulator's bits and LLRs only: no other
+ *                         record changes (on the packed record path the demodulator then leaves them on the device, as
+ *                         for parsed_records).  One pinned buffer of 8 bytes per burst and batch context is allocated
+ *                         when the option is first set to 1, never before; with 0 nothing is launched.  -1 for a member
+ *                         of a group and while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
+ *   "swap_iq"             0/1, default 0: 1 = irdm_feed_host exchanges the two components of every sample of every chunk
+ *                         on the device (irdm_swap_iq_device's kernel on the feed's stream, between the host-to-device
+ *                         copy and the feed; the ring slot of irdm_ingest_ptr and the staging buffer alike), so the
+ *                         detector, the history ring, the per-burst chains, input_stats and spectrum_frames all see the
+ *                         exchanged stream.  The device feeds take const buffers the caller owns: with the option on
+ *                         irdm_feed_device / irdm_feed_begin return -1 with a line on stderr -- exchange the buffer with
+ *                         irdm_swap_iq_device first.  -1 for a member of a group, and for a change of the value between
+ *                         a stream's first feed and irdm_reset (the ring would hold both senses)
  *   "decode_frames" / "decode_ida"  0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
  *   "fir_order" (alias "simd_order")   default 1 = the arithmetic of the reference's AVX2 kernels, simd_avx2.c -- what
@@ -1017,6 +1073,33 @@ int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_s
 int irdm_poll_symbol_clock(irdm_pipeline_t *p, irdm_clock_est_t *out, int max);
 int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out);
 int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out);
+
+/* ---- exchanged I and Q (irdm_iq_vote_t / irdm_iq_sense_t above) ----
+ * irdm_swap_iq_device: the two components of each of n_samples samples of `format` (IRDM_FMT_*) at d_iq exchanged in
+ *   place -- a byte permutation, no conversion: cu8 stays cu8, a NaN stays a NaN; applied twice it is the identity.  d_iq
+ *   need only be aligned to a sample.  On `stream` (a hipStream_t) without waiting; stream == NULL: on a stream of the
+ *   call's own, complete on return.  Returns 0; -1 for an unknown format, a pointer that is not sample-aligned or a
+ *   failed launch; n_samples == 0 launches nothing.
+ * irdm_set_option(p, "swap_iq", 1) applies it to every chunk of irdm_feed_host; irdm_frontend_swap_iq (below) to every
+ *   capture chunk of irdm_frontend_feed_host.
+ * irdm_set_option(p, "iq_sense", 1): every frame whose unique word passes from then on is judged in both senses.
+ * irdm_poll_iq_votes: up to `max` per-frame records, one per record of irdm_poll_demods / irdm_poll_demods_packed, in
+ *   their order.  A frame's record depends on its bits and LLRs alone.  Returns the number written (0 with the option
+ *   off), -1 on error.
+ * irdm_iq_sense: the summary of the records queued so far (irdm_flush first for the whole stream); irdm_reset starts it
+ *   over.  Returns 0, or -1 (the option never set included).
+ * irdm_iq_sense_batch: the kernel alone on n frames (bits, llr, n_bits and direction of each irdm_demod_t are read; an odd
+ *   n_bits is rounded down), as irdm_ida_decode_batch.  Works with the option off.  Returns 0 or -1. */
+int irdm_swap_iq_device(void *d_iq, size_t n_samples, int format, int device, void *stream);
+int irdm_poll_iq_votes(irdm_pipeline_t *p, irdm_iq_vote_t *out, int max);
+int irdm_iq_sense(irdm_pipeline_t *p, irdm_iq_sense_t *out);
+int irdm_iq_sense_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_iq_vote_t *out);
+/* irdm_frontend_swap_iq: option "swap_iq" for a front end -- irdm_frontend_feed_host exchanges the components of every
+ *   capture chunk in its staging buffer, in front of K0 / K0r and of the front end's statistics pass, so the band that
+ *   irdm_frontend_save writes is the corrected one.  With it on, irdm_frontend_feed_device and irdm_frontend_run_device
+ *   return -1 with a line on stderr (they take the caller's buffer as it is).  Returns 0; -1 for a change between the
+ *   stream's first chunk and irdm_frontend_reset. */
+int irdm_frontend_swap_iq(irdm_frontend_t *fe, int on);
 
 /* ---- self-describing recordings: WAV / RF64, SigMF, SDRangel .sdriq (csrc/recording.cpp) ----
  * Host code only, no device call: works without a GPU.  irdm_recording_probe reads the header of `path` and says what the

@@ -34,6 +34,19 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
         return symbol_clock_configure(p, value);
     }
+    if (!strcmp(key, "iq_sense")) {
+        // 0 / 1; not for a member of a group (the summary is a context's, and a group merges no votes), and not while a chunk
+        // handed over with irdm_feed_begin waits for its irdm_feed_end
+        if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
+        return iq_sense_configure(p, value);
+    }
+    if (!strcmp(key, "swap_iq")) {
+        // 0 / 1; not for a member of a group (it is fed on the device), and no change between a stream's first feed and
+        // irdm_reset: the history ring would hold both senses
+        if (p->in_group || (p->st.begin_no != 0 && (value != 0) != (p->swap_iq != 0))) return -1;
+        p->swap_iq = value ? 1 : 0;
+        return 0;
+    }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
     if (!strcmp(key, "detect_only")) { p->detect_only = value; return 0; }
@@ -108,6 +121,32 @@ extern "C" int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out)
 {
     if (!p || !out || !p->bc[0].hp_clock) return -1;
     symbol_clock_result(p->st.clock, p->decim, out);
+    return 0;
+}
+
+// ---- option "iq_sense" (iq_sense.hpp): the pinned records of every batch context, when the option is first set ----
+int iq_sense_configure(irdm_pipeline *p, int on)
+{
+    for (int i = 0; on && i < p->n_bc; i++) {
+        BatchCtx &b = p->bc[i];
+        if (!b.hp_sense &&
+            hipHostMalloc(reinterpret_cast<void **>(&b.hp_sense), sizeof(SenseRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
+            return -1;
+    }
+    p->iq_sense = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_poll_iq_votes(irdm_pipeline_t *p, irdm_iq_vote_t *out, int max)
+{
+    if (!p || !out || max < 0) return -1;
+    return drain(p->st.iq.q, out, max);
+}
+
+extern "C" int irdm_iq_sense(irdm_pipeline_t *p, irdm_iq_sense_t *out)
+{
+    if (!p || !out || !p->bc[0].hp_sense) return -1;
+    iq_sense_result(p->st.iq, out);
     return 0;
 }
 

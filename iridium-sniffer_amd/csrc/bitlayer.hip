@@ -951,6 +951,194 @@ __global__ __launch_bounds__(64) void frame_packed_kernel(const DemodOut *__rest
     emit();
 }
 
+// ---------------------------------------------------------------------------
+// option "iq_sense": which way round a frame's I and Q were.  A recording with its components exchanged demodulates with
+// ok = 1 and full confidence (preamble and unique words use the DQPSK states 0 and 2 alone, and conjugation maps that
+// diagonal onto itself), but the two bits of every dibit arrive exchanged.  Three predicates that chance does not
+// satisfy, each evaluated on the bits as they are (X = 0, "recorded") and with every pair exchanged (X = 1: bit and LLR
+// index ^ 1 -- every offset below is even, so the exchange commutes with them):
+//   IRA  access code, >= 24 + 96 bits, the three header blocks of the 3-way de-interleave (frame_decode.c:178-199) have a
+//        zero BCH(31,21) remainder and the parity bit of check_parity32 (:399-407), nothing corrected;
+//   IBC  access code, >= 24 + 6 + 64 bits, zero BCH(7,3) remainder of the header, the first two blocks of the 2-way
+//        de-interleave clean in the same way;
+//   IDA  ida_decode() as ida_decode_kernel runs it, Chase decoding on the LLRs included, ends with da_len > 0 and a CRC
+//        that holds.
+// One lane per frame, its SenseRec written straight into pinned host memory (bit 0 IRA, bit 1 IBC, bit 2 IDA per sense).
+// The helpers the four decode kernels use are not touched: the exchanged reads live in helpers of their own.
+// ---------------------------------------------------------------------------
+namespace {
+
+template <int X>
+__device__ __forceinline__ bool strict_block(const uint8_t *__restrict__ in, int first_sym, int stride)
+{
+    unsigned w = 0;
+#pragma unroll
+    for (int p = 0; p < 16; p++) {
+        const int s = first_sym - stride * p;
+        w = (w << 2) | ((unsigned)(in[(2 * s) ^ X] & 1) << 1) | (unsigned)(in[(2 * s + 1) ^ X] & 1);
+    }
+    return gf2_rem(kPolyRa, 11, w >> 1) == 0 && (__popc(w) & 1) == 0;
+}
+
+// ida_decode_kernel's decode with the reads at index ^ X, down to the two facts the predicate needs
+template <int X>
+__device__ bool ida_holds(const uint8_t *__restrict__ bits, const float *__restrict__ llr_all, int n_bits, int direction,
+                          const int2 *__restrict__ syn_da, const int2 *__restrict__ syn_l1,
+                          const int2 *__restrict__ syn_l2, const int2 *__restrict__ syn_l3)
+{
+    if (n_bits < 24 + 46 + 124) return false;
+    if (direction != 1 && direction != 2) return false;
+    const uint8_t *data = bits + 24;
+    const float *llr = llr_all + 24;
+    const int data_len = n_bits - 24;
+    unsigned v1 = 0, v2 = 0, v3 = 0;
+    for (int k = 0; k < 46; k++) {
+        const unsigned b = (unsigned)(data[((c_lcw_perm[k] - 1) ^ 1) ^ X] & 1);
+        if (k < 7) v1 = (v1 << 1) | b;
+        else if (k < 20) v2 = (v2 << 1) | b;
+        else v3 = (v3 << 1) | b;
+    }
+    v2 <<= 1;
+    const unsigned s1 = gf2_rem(29u, 5, v1), s2 = gf2_rem(465u, 9, v2), s3 = gf2_rem(41u, 6, v3);
+    if (s1 != 0) { if (s1 >= 16 || syn_l1[s1].x < 0) return false; v1 ^= (unsigned)syn_l1[s1].y; }
+    if (s2 != 0 && (s2 >= 256 || syn_l2[s2].x < 0)) return false;
+    if (s3 != 0 && (s3 >= 32 || syn_l3[s3].x < 0)) return false;
+    if (((int)(v1 >> 4) & 7) != 2) return false;
+    const int payload_len = data_len - 46;
+    if (payload_len < 124) return false;
+    const uint8_t *pd = data + 46;
+    const float *pl = llr + 46;
+
+    uint8_t st[512];
+    int len = 0;
+    const int max_bch = 512;
+    const int n_full = payload_len / 124, remain = payload_len % 124;
+    bool failed = false;
+    for (int blk = 0; blk < n_full && !failed; blk++) {
+        const uint8_t *b = pd + blk * 124;
+        const float *bl = pl + blk * 124;
+        for (int c = 0; c < 4; c++) {
+            if (len + 20 > max_bch) break;
+            const int off = (c == 0 ? 3 : c == 1 ? 1 : c == 2 ? 2 : 0) * 31;
+            unsigned cw = 0;
+            float l[31];
+            for (int k = 0; k < 31; k++) {
+                const int j = off + k;
+                const int idx = (j < 62 ? deint_index(62, 0, j) : deint_index(62, 1, j - 62)) ^ X;
+                cw = (cw << 1) | (unsigned)(b[idx] & 1);
+                l[k] = bl[idx];
+            }
+            unsigned cor;
+            int fixed = 0;
+            if (chase_da(cw, l, syn_da, &cor, &fixed) < 0) { failed = true; break; }
+            put20(st, len, cor);
+        }
+    }
+    if (!failed && remain >= 4 && len + 2 * (remain / 2 - 1) <= max_bch) {
+        const int ns = remain / 2;
+        const uint8_t *b = pd + n_full * 124;
+        const float *bl = pl + n_full * 124;
+        if (ns > 1 && len + 20 <= max_bch) {
+            const int hl = ns - 1;
+            int clen = 2 * hl;
+            if (clen > 128) clen = 128;
+            int pos = 0;
+            while (pos + 31 <= clen && len + 20 <= max_bch) {
+                unsigned cw = 0;
+                float l[31];
+                for (int k = 0; k < 31; k++) {
+                    const int idx = tail_index(ns, hl, pos + k) ^ X;    // (>= -124: b is an even number of bits into the frame)
+                    cw = (cw << 1) | (unsigned)(b[idx] & 1);
+                    l[k] = bl[idx];
+                }
+                unsigned cor;
+                int fixed = 0;
+                if (chase_da(cw, l, syn_da, &cor, &fixed) < 0) break;
+                put20(st, len, cor);
+                pos += 31;
+            }
+        }
+    }
+    if (len < 196) return false;
+    const int da_len = (st[11] << 4) | (st[12] << 3) | (st[13] << 2) | (st[14] << 1) | st[15];
+    if (((st[17] << 2) | (st[18] << 1) | st[19]) != 0) return false;
+    if (da_len > 20 || da_len == 0) return false;
+    // CRC-CCITT-FALSE over the re-packed bits (:606-637), bit-serial as in ida_decode_kernel
+    const int crc_bits = 20 + 12 + (len - 20 - 4);
+    if ((crc_bits + 7) / 8 > 64) return false;
+    unsigned crc = 0xFFFFu, cur = 0;
+    int nb = 0;
+    const int total_bits = ((crc_bits + 7) / 8) * 8;
+    for (int bp = 0; bp < total_bits; bp++) {
+        unsigned bit = 0;
+        if (bp < 20) bit = st[bp];
+        else if (bp >= 32 && bp < crc_bits) bit = st[20 + (bp - 32)];
+        cur = (cur << 1) | bit;
+        if (++nb == 8) {
+            crc ^= (cur & 0xffu) << 8;
+            for (int j = 0; j < 8; j++) crc = (crc & 0x8000u) ? ((crc << 1) ^ 0x1021u) & 0xffffu : (crc << 1) & 0xffffu;
+            nb = 0;
+            cur = 0;
+        }
+    }
+    return crc == 0;
+}
+
+template <int X>
+__device__ unsigned iq_sense_of(const DemodOut &f, int n_bits, const int2 *__restrict__ syn_da,
+                                const int2 *__restrict__ syn_l1, const int2 *__restrict__ syn_l2,
+                                const int2 *__restrict__ syn_l3)
+{
+    unsigned m = 0;
+    unsigned acc = 0;
+    for (int k = 0; k < 24; k++) acc = (acc << 1) | (unsigned)(f.bits[k ^ X] & 1);
+    if (acc == 0x3030F3u || acc == 0xCC3CFCu) {
+        const uint8_t *data = f.bits + 24;
+        const int data_len = n_bits - 24;
+        if (data_len >= 96 && strict_block<X>(data, 47, 3) && strict_block<X>(data, 46, 3) && strict_block<X>(data, 45, 3))
+            m |= 1u;
+        if (data_len >= 6 + 64) {
+            unsigned hv = 0;
+            for (int k = 0; k < 6; k++) hv = (hv << 1) | (unsigned)(data[k ^ X] & 1);
+            if (gf2_rem(kPolyHdr, 5, hv) == 0 && strict_block<X>(data + 6, 31, 2) && strict_block<X>(data + 6, 30, 2)) m |= 2u;
+        }
+    }
+    if (ida_holds<X>(f.bits, f.llr, n_bits, f.direction, syn_da, syn_l1, syn_l2, syn_l3)) m |= 4u;
+    return m;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64) void iq_sense_kernel(const DemodOut *__restrict__ frames, int n_frames,
+                                                      const int2 *__restrict__ syn_da, const int2 *__restrict__ syn_l1,
+                                                      const int2 *__restrict__ syn_l2, const int2 *__restrict__ syn_l3,
+                                                      SenseRec *__restrict__ hp_sense)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_frames) return;
+    const DemodOut &f = frames[i];
+    SenseRec r;
+    r.recorded = r.exchanged = 0;
+    r.pad = 0;
+    const int n_bits = f.ok && f.n_symbols > 0 ? 2 * f.n_symbols : 0;
+    r.n_bits = (uint32_t)n_bits;
+    if (n_bits >= 24 && n_bits <= kMaxBits) {
+        r.recorded = (uint8_t)iq_sense_of<0>(f, n_bits, syn_da, syn_l1, syn_l2, syn_l3);
+        r.exchanged = (uint8_t)iq_sense_of<1>(f, n_bits, syn_da, syn_l1, syn_l2, syn_l3);
+    }
+    hp_sense[i] = r;
+    __threadfence_system();
+}
+
+int launch_iq_sense(const DemodOut *frames, int n_frames, const int2 *syn_da, const int2 *syn_l1, const int2 *syn_l2,
+                    const int2 *syn_l3, SenseRec *hp_sense, hipStream_t stream)
+{
+    if (n_frames <= 0) return 0;
+    hipLaunchKernelGGL(iq_sense_kernel, dim3((n_frames + 63) / 64), dim3(64), 0, stream, frames, n_frames, syn_da, syn_l1,
+                       syn_l2, syn_l3, hp_sense);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 int launch_frame_packed(const DemodOut *frames, int n_frames, const int2 *syn_ra, const int2 *syn_hdr, FramePacked *hp_frame,
                         hipStream_t stream)
 {

@@ -581,13 +581,19 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
                !p->keep_frame_samples;
     b.parsed = b.packed && p->parsed_records;
     b.framed = b.packed && p->frame_records;
+    b.sensed = p->iq_sense && b.hp_sense;
     if (launch_demod(b.d_work, nb, b.d_frames, p->cfg.use_gardner, p->sps, b.d_demod_ws, b.d_demod, st,
-                     b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr, b.parsed || b.framed ? 1 : 0) != 0)
+                     b.packed ? b.hp_packed : nullptr, b.packed ? b.hp_work_dev : nullptr,
+                     b.parsed || b.framed || b.sensed ? 1 : 0) != 0)
         return -1;
     IRDM_HIP_CHECK(hipEventRecord(b.ev[3], st));
     // option "symbol_clock": the clock error of every frame, from the frames post2 left (read only), into pinned memory
     b.clocked = p->symbol_clock && b.hp_clock;
     if (b.clocked && launch_symbol_clock(b.d_work, nb, b.d_frames, p->sps, b.hp_clock, st) != 0) return -1;
+    // option "iq_sense": each frame's bits judged as they are and with I and Q exchanged, from the DemodOut the demodulator
+    // left on the device (read only), into pinned memory
+    if (b.sensed && launch_iq_sense(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_sense, st) != 0)
+        return -1;
     if (b.parsed &&
         launch_ida_packed(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_ida, st) != 0)
         return -1;
@@ -677,6 +683,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             const DemodPacked &d = b.hp_packed[i];
             if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], d.ok != 0);
             if (w.drop_reason != 0 || !d.ok) continue;
+            if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
             uint64_t timestamp = p->st.start_time_ns + (uint64_t)((double)r.start / fs * 1e9);
             if (w.dec_len > 0) timestamp += (uint64_t)((p->in_ntaps / 2) * 1000000000ULL / fs);
             p->st.q.packed.emplace_back();
@@ -762,6 +769,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
         if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], b.hp_demod[i].ok != 0);
         if (w.drop_reason == 0 && b.hp_demod[i].ok) {
             const DemodOut &d = b.hp_demod[i];
+            if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
             // built in place in the queue, and only the symbols the frame has are copied (a record is 4.5 KB; 667 of
             // them filled, copied and copied again cost the feeding thread 0.5 ms per chunk)
             p->st.q.demods.emplace_back();

@@ -50,6 +50,7 @@ void pipeline_free(irdm_pipeline *p)
         if (b.hp_ida) (void)hipHostFree(b.hp_ida);
         if (b.hp_frame) (void)hipHostFree(b.hp_frame);
         if (b.hp_clock) (void)hipHostFree(b.hp_clock);
+        if (b.hp_sense) (void)hipHostFree(b.hp_sense);
         if (b.owns_buffers) {
             void *own[] = { b.d_work, b.d_tiles, b.d_dec, b.d_lpf, b.d_rrc_ws, b.d_frames, b.d_demod_ws, b.d_demod,
                             b.d_decoded, b.d_ida };

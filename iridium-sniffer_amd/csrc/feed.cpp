@@ -329,6 +329,11 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
 extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, void *stream_v)
 {
     if (!p || (!d_iq && n_samples)) return -1;
+    if (p->swap_iq && !p->feed_inner) {
+        fprintf(stderr, "irdm_hip: option swap_iq exchanges the chunks of irdm_feed_host only: a device feed takes the caller's "
+                        "buffer as it is -- exchange it with irdm_swap_iq_device first\n");
+        return -1;
+    }
     if (p->st.begin_no - p->st.end_no > (p->depth ? kLookAhead : 0u)) return -1;    // two chunks of look-ahead, pipeline_depth >= 1 only
     if (p->st.stream_closed) {
         fprintf(stderr, "irdm_hip: stream already ended by a chunk that was not a multiple of feed_block\n");
@@ -584,6 +589,17 @@ extern "C" int irdm_device_copy(void *dst, const void *src, size_t bytes)
     return 0;
 }
 
+// a chunk of irdm_feed_host where its copy lands it on fstream (the ring slot of irdm_ingest_ptr or d_stage): option
+// "swap_iq" exchanges its components there, behind the copy and in front of everything that reads the chunk
+static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples)
+{
+    if (p->swap_iq && launch_iq_swap(p->dev_fmt, d_iq, n_samples, p->fstream) != 0) return -1;
+    p->feed_inner = true;
+    const int rc = irdm_feed_device(p, d_iq, n_samples, p->fstream);
+    p->feed_inner = false;
+    return rc;
+}
+
 extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_samples)
 {
     if (!p || (!h_iq && n_samples)) return -1;
@@ -593,7 +609,7 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     // buffer, no device-to-device copy behind K1)
     if (void *slot = irdm_ingest_ptr(p, n_samples)) {
         IRDM_HIP_CHECK(hipMemcpyAsync(slot, h_iq, n_samples * p->bps, hipMemcpyHostToDevice, p->fstream));
-        return irdm_feed_device(p, slot, n_samples, p->fstream);
+        return feed_host_arrived(p, slot, n_samples);
     }
     if (!p->d_stage) {
         if (hipMalloc(&p->d_stage, p->max_chunk * p->bps) != hipSuccess) return -1;
@@ -603,7 +619,26 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     // still running and must not be waited for.  irdm_feed_device returns only after K1 and the history-ring copy of
     // its chunk are done, so one staging buffer is enough.
     IRDM_HIP_CHECK(hipMemcpyAsync(p->d_stage, h_iq, n_samples * p->bps, hipMemcpyHostToDevice, p->fstream));
-    return irdm_feed_device(p, p->d_stage, n_samples, p->fstream);
+    return feed_host_arrived(p, p->d_stage, n_samples);
+}
+
+// irdm_swap_iq_device: the exchange alone, on a buffer the caller owns (iq_swap.hpp)
+extern "C" int irdm_swap_iq_device(void *d_iq, size_t n_samples, int format, int device, void *stream_v)
+{
+    if ((!d_iq && n_samples) || !fmt_valid(format) || (reinterpret_cast<uintptr_t>(d_iq) % (size_t)fmt_bytes(format)) != 0) return -1;
+    if (n_samples == 0) return 0;
+    IRDM_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
+    if (!s) {
+        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
+        s = own;
+    }
+    int rc = launch_iq_swap(format, d_iq, n_samples, s);
+    if (own) {
+        if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
+        (void)hipStreamDestroy(own);
+    }
+    return rc;
 }
 
 

@@ -301,10 +301,27 @@ extern "C" int irdm_frontend_input_stats(irdm_frontend_t *fe, irdm_input_stats_t
     return 0;
 }
 
+// irdm_frontend_swap_iq is on and the caller hands over a device buffer of its own: refused, with the remedy
+static bool fe_swap_refuses(const irdm_frontend *fe)
+{
+    if (!fe->swap_iq || fe->feed_inner) return false;
+    fprintf(stderr, "irdm_hip: front end: irdm_frontend_swap_iq exchanges the chunks of irdm_frontend_feed_host only: a device "
+                    "feed takes the caller's buffer as it is -- exchange it with irdm_swap_iq_device first\n");
+    return true;
+}
+
+extern "C" int irdm_frontend_swap_iq(irdm_frontend_t *fe, int on)
+{
+    // no change between a stream's first chunk and irdm_frontend_reset: the carried tail would hold the other sense
+    if (!fe || (fe->st.total != 0 && (on != 0) != (fe->swap_iq != 0))) return -1;
+    fe->swap_iq = on ? 1 : 0;
+    return 0;
+}
+
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
-    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out) return -1;
+    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe)) return -1;
     const uint64_t m1 = fe_outputs(fe, fe->st.total + n_in, false);
     const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
@@ -401,7 +418,7 @@ static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
 
 extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream_v)
 {
-    if (fe_check(fe, p) != 0 || (!d_in && n_in)) return -1;
+    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe)) return -1;
     pipeline_enter(p);
     if (stream_v && static_cast<hipStream_t>(stream_v) != fe->stream) {
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
@@ -432,7 +449,11 @@ extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, 
     // (one staging buffer: the copy is ordered behind the kernels that read the previous chunk, on the same stream)
     if (bytes) IRDM_HIP_CHECK(hipMemcpyAsync(fe->d_stage, h_in, bytes, hipMemcpyHostToDevice, fe->stream));
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
+    // irdm_frontend_swap_iq: the capture's components exchanged where it landed, in front of the statistics pass and K0 / K0r
+    if (fe->swap_iq && launch_iq_swap(fe->fmt, fe->d_stage, n_in, fe->stream) != 0) return -1;
+    fe->feed_inner = true;
     const int bursts = irdm_frontend_feed_device(fe, p, fe->d_stage, n_in, nullptr);
+    fe->feed_inner = false;
     IRDM_HIP_CHECK(hipEventSynchronize(fe->ev_caller));          // the host buffer has been read
     return bursts;
 }

@@ -54,6 +54,10 @@ struct irdm_frontend {
     } sv;
     // irdm_frontend_input_stats_enable: the pass over the capture's samples in front of the kernel (cache; is.on the switch)
     irdm::InputStatsPass is;
+    // irdm_frontend_swap_iq: irdm_frontend_feed_host exchanges I and Q of every capture chunk in its staging buffer
+    // (configuration); feed_inner marks that call's own device feed, the only one the switch allows
+    int swap_iq = 0;
+    bool feed_inner = false;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

@@ -1,0 +1,97 @@
+// iq_swap.hpp -- option "swap_iq" / irdm_swap_iq_device (include/irdm_hip.h): the two components of every sample of a
+// device buffer exchanged in place, for recordings whose I and Q arrive the other way round (a WAV with Q/I channels, a
+// SigMF file of the other convention, a receiver whose mixer inverts the spectrum).
+//
+// One memory-bound pass: a pure byte permutation, no conversion (cu8 stays cu8, a NaN stays a NaN).  The component width is
+// half a sample: 1 byte (ci8, cu8), 2 bytes (ci16, ci16-full, sc16q11), 4 bytes (cf32, ci32, ci32-24).
+//   * a lane loads 16 bytes, permutes them and stores them to the address it loaded from: no lane reads what another
+//     writes, so working in place has no hazard.  Width 1: the bytes of each 16-bit half of a dword exchanged; width 2: a
+//     dword rotated by 16; width 4: the dwords of each pair renamed.
+//   * grid-stride loop, at most kSwMaxGrid workgroups of kSwNT threads;
+//   * the buffer need only be aligned to a sample: the samples in front of the first 16-byte boundary and behind the last
+//     one (at most 16 / bytes-per-sample - 1 each) are exchanged one per thread by the first threads of the grid.
+// Bounds: the vector part covers bytes [head * bps, (head + nvec * spv) * bps), head + nvec * spv <= n; the scalar part the
+// samples [0, head) and [head + nvec * spv, n).
+//
+// Included by the translation units that launch it (feed.cpp: irdm_feed_host of a context and irdm_swap_iq_device;
+// frontend.cpp: the capture in front of K0 / K0r).
+#pragma once
+#include "common.hpp"
+
+namespace irdm {
+
+constexpr int kSwNT = 256;                              // threads of a workgroup
+constexpr int kSwMaxGrid = 2048;                        // workgroups of a launch
+
+template <int W>
+__device__ __forceinline__ unsigned iq_swap_word(unsigned w)
+{
+    if (W == 1) return ((w & 0x00ff00ffu) << 8) | ((w >> 8) & 0x00ff00ffu);
+    return (w << 16) | (w >> 16);
+}
+
+// n samples of 2 W bytes at `buf` (aligned to a sample): `head` samples up to the first 16-byte boundary, nvec 16-byte
+// pieces, the rest
+template <int W>
+__global__ __launch_bounds__(kSwNT) void iq_swap_kernel(void *__restrict__ buf, long long n, long long head, long long nvec)
+{
+    constexpr int BPS = 2 * W, SPV = 16 / BPS;
+    const long long gid = (long long)blockIdx.x * kSwNT + threadIdx.x, stride = (long long)gridDim.x * kSwNT;
+    unsigned char *const bytes = static_cast<unsigned char *>(buf);
+    uint4 *const pieces = reinterpret_cast<uint4 *>(bytes + head * BPS);
+    for (long long i = gid; i < nvec; i += stride) {
+        uint4 v = pieces[i];
+        if (W == 4) {
+            v = make_uint4(v.y, v.x, v.w, v.z);
+        } else {
+            v.x = iq_swap_word<W>(v.x);
+            v.y = iq_swap_word<W>(v.y);
+            v.z = iq_swap_word<W>(v.z);
+            v.w = iq_swap_word<W>(v.w);
+        }
+        pieces[i] = v;
+    }
+    // the scalar head and tail: at most SPV - 1 samples each, one per thread
+    const long long tail0 = head + nvec * SPV;
+    long long si = -1;
+    if (gid < head) si = gid;
+    else if (gid - head < n - tail0) si = tail0 + (gid - head);
+    if (si < 0) return;
+    if (W == 1) {
+        unsigned short *q = reinterpret_cast<unsigned short *>(bytes + si * BPS);
+        const unsigned w = *q;
+        *q = (unsigned short)(((w & 0xffu) << 8) | (w >> 8));
+    } else if (W == 2) {
+        unsigned *q = reinterpret_cast<unsigned *>(bytes + si * BPS);
+        *q = iq_swap_word<2>(*q);
+    } else {
+        unsigned *q = reinterpret_cast<unsigned *>(bytes + si * BPS);
+        const unsigned a = q[0], b = q[1];
+        q[0] = b;
+        q[1] = a;
+    }
+}
+
+// n samples of format fmt at d_buf, exchanged in place on `stream`.  0, or -1 for an unknown format, a pointer that is not
+// aligned to a sample, or a launch that failed; n == 0 launches nothing.
+static inline int launch_iq_swap(int fmt, void *d_buf, size_t n, hipStream_t stream)
+{
+    if (!fmt_valid(fmt) || (reinterpret_cast<uintptr_t>(d_buf) % (size_t)fmt_bytes(fmt)) != 0) return -1;
+    if (n == 0) return 0;
+    const int bps = fmt_bytes(fmt), spv = 16 / bps;
+    const size_t mis = (size_t)(reinterpret_cast<uintptr_t>(d_buf) & 15u);
+    long long head = (long long)(((16 - mis) & 15u) / (size_t)bps);
+    if (head > (long long)n) head = (long long)n;
+    const long long nvec = ((long long)n - head) / spv;
+    const long long want = (nvec + kSwNT - 1) / kSwNT;
+    const int grid = (int)(want < 1 ? 1 : (want > kSwMaxGrid ? kSwMaxGrid : want));
+    static_assert(kSwNT >= 2 * 7, "the first workgroup holds the scalar head and tail");
+    switch (bps) {
+    case 2: hipLaunchKernelGGL((iq_swap_kernel<1>), dim3(grid), dim3(kSwNT), 0, stream, d_buf, (long long)n, head, nvec); break;
+    case 4: hipLaunchKernelGGL((iq_swap_kernel<2>), dim3(grid), dim3(kSwNT), 0, stream, d_buf, (long long)n, head, nvec); break;
+    default: hipLaunchKernelGGL((iq_swap_kernel<4>), dim3(grid), dim3(kSwNT), 0, stream, d_buf, (long long)n, head, nvec); break;
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+}  // namespace irdm

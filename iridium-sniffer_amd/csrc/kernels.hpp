@@ -207,6 +207,10 @@ int launch_ida_packed(const DemodOut *frames, int n_frames, const int2 *syn_da, 
 // with keep_bits), one wavefront per frame, each frame's FramePacked written straight into pinned host memory
 int launch_frame_packed(const DemodOut *frames, int n_frames, const int2 *syn_ra, const int2 *syn_hdr, FramePacked *hp_frame,
                         hipStream_t stream);
+// iq_sense: the IRA / IBC / IDA predicates of every frame in the recorded and in the exchanged sense (bits and LLRs
+// device-resident: launch_demod with keep_bits on the packed path), one lane per frame, SenseRec into pinned host memory
+int launch_iq_sense(const DemodOut *frames, int n_frames, const int2 *syn_da, const int2 *syn_l1, const int2 *syn_l2,
+                    const int2 *syn_l3, SenseRec *hp_sense, hipStream_t stream);
 // hp_packed / hp_work != nullptr (packed_records): demod_par_kernel writes the DemodPacked and work records straight into
 // pinned host memory -- the chain's last launch, unless keep_bits: then the DemodOut's bits and LLRs are written as well,
 // on the device, for launch_ida_packed behind it

@@ -38,6 +38,8 @@
 #include "record_queues.hpp"
 #include "input_stats.hpp"
 #include "symbol_clock.hpp"
+#include "iq_swap.hpp"
+#include "iq_sense.hpp"
 
 using namespace irdm;
 
@@ -134,6 +136,7 @@ struct BatchCtx {
     IdaPacked *hp_ida;                      // parsed_records: ida_decode() of each of them (pinned; written by ida_packed_kernel)
     FramePacked *hp_frame;                  // frame_records: frame_decode() of each of them (pinned; written by frame_packed_kernel)
     ClockRec *hp_clock;                     // symbol_clock: one record per burst (pinned; written by symbol_clock_kernel; allocated with the option)
+    SenseRec *hp_sense;                     // iq_sense: one record per burst (pinned; written by iq_sense_kernel; allocated with the option)
     uint32_t *hp_flag, *hp_flag_dev;    // [0] sequence number the helper publishes, [1] time-out flag of the waiting kernel
     int4 *hp_rot_new, *hp_rot_new_dev, *d_rot_new;   // (bin, row, from, to) of the checkpoint runs this batch has to build: mapped pinned / device
     uint32_t cfo_seq;
@@ -141,6 +144,7 @@ struct BatchCtx {
     bool parsed;                 // ... and IdaPacked records
     bool framed;                 // ... and FramePacked records
     bool clocked;                // this batch ran the symbol clock kernel: hp_clock holds its records
+    bool sensed;                 // this batch ran the I/Q sense kernel: hp_sense holds its records
     bool cfo_on_device;          // this batch's libm step ran on the device: h_cfreq is filled from the returned records
     std::vector<double> h_cfreq;
     // stream state (irdm_reset assigns a fresh one): the batch in flight
@@ -231,6 +235,8 @@ struct StreamState {
     InputStatsStream in_stats;
     // option "symbol_clock": the per-frame records until they are polled and the summary's histogram (symbol_clock.hpp)
     SymbolClockStream clock;
+    // option "iq_sense": the per-frame votes until they are polled and the counts of the summary (iq_sense.hpp)
+    IqSenseStream iq;
 };
 
 struct irdm_pipeline {
@@ -425,6 +431,13 @@ struct irdm_pipeline {
     // option "symbol_clock" (chain.cpp, symbol_clock.hpp): the switch (configuration); the batch contexts' hp_clock are the
     // cache, allocated when the option is first set
     int symbol_clock = 0;
+    // option "iq_sense" (chain.cpp, iq_sense.hpp): the switch (configuration); the batch contexts' hp_sense are the cache,
+    // allocated when the option is first set
+    int iq_sense = 0;
+    // option "swap_iq" (feed.cpp, iq_swap.hpp): irdm_feed_host exchanges I and Q of every chunk on the device (configuration);
+    // feed_inner marks irdm_feed_host's own call of irdm_feed_device, the only device feed the option allows
+    int swap_iq = 0;
+    bool feed_inner = false;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -473,6 +486,7 @@ int process_bursts(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 int spectrum_configure(irdm_pipeline *p, int R);
 int input_stats_configure(irdm_pipeline *p, int on);
 int symbol_clock_configure(irdm_pipeline *p, int on);
+int iq_sense_configure(irdm_pipeline *p, int on);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

@@ -250,9 +250,10 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     p->decode_frames = 0;
     p->decode_ida = 0;
     p->detect_only = 0;          // a stage-B call on a detect-only context still runs stage B
-    const int marks = p->chunk_marks, clock = p->symbol_clock;
+    const int marks = p->chunk_marks, clock = p->symbol_clock, sense = p->iq_sense;
     p->chunk_marks = 0;          // (the records go to private queues: no chunk mark for them)
     p->symbol_clock = 0;         // (and the probe's frame is none of the stream's)
+    p->iq_sense = 0;
     const uint64_t tagged = p->st.tagged;
     std::vector<irdm_burst_t> last; last.swap(p->st.last_bursts);
     p->keep_frame_samples = 1;
@@ -270,6 +271,7 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     p->keep_frame_samples = keep;
     p->chunk_marks = marks;
     p->symbol_clock = clock;
+    p->iq_sense = sense;
     p->detect_only = det;
     p->decode_frames = dec;
     p->decode_ida = dec_ida;
@@ -484,6 +486,40 @@ extern "C" int irdm_ida_packed_batch(irdm_pipeline_t *p, const irdm_demod_t *in,
     return packed_batch(p, in, n, reinterpret_cast<IdaPacked *>(out), [](irdm_pipeline_t *q, int nb, IdaPacked *hp) {
         return launch_ida_packed(q->d_demod, nb, q->d_syn_da, q->d_syn_l1, q->d_syn_l2, q->d_syn_l3, hp, q->stream);
     });
+}
+
+// the I/Q sense kernel alone (bitlayer.hip, iq_sense.hpp): bits, LLRs, n_bits (rounded down to whole dibits) and direction
+// of every record are read, as the chain's DemodOut carries them
+extern "C" int irdm_iq_sense_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_iq_vote_t *out)
+{
+    if (!p || !in || !out || n < 0) return -1;
+    for (int i = 0; i < n; i++)
+        if (in[i].n_bits < 0 || in[i].n_bits > kMaxBits) return -1;
+    pipeline_enter(p);
+    SenseRec *hp = nullptr;
+    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(SenseRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
+                                 hipHostMallocDefault));
+    int rc = 0;
+    for (int base = 0; base < n && rc == 0; base += p->burst_cap) {
+        const int nb = std::min(p->burst_cap, n - base);
+        p->h_demod.assign(nb, DemodOut());
+        for (int i = 0; i < nb; i++) {
+            const irdm_demod_t &f = in[base + i];
+            DemodOut &d = p->h_demod[i];
+            d.ok = 1;
+            d.direction = f.direction;
+            d.n_symbols = f.n_bits / 2;
+            memcpy(d.bits, f.bits, sizeof(d.bits));
+            memcpy(d.llr, f.llr, sizeof(d.llr));
+        }
+        rc = hipMemcpyAsync(p->d_demod, p->h_demod.data(), sizeof(DemodOut) * nb, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
+                     launch_iq_sense(p->d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, hp, p->stream) == 0 &&
+                     hipStreamSynchronize(p->stream) == hipSuccess
+                 ? 0 : -1;
+        for (int i = 0; rc == 0 && i < nb; i++) out[base + i] = iq_vote_of((uint64_t)(base + i), hp[i]);
+    }
+    (void)hipHostFree(hp);
+    return rc;
 }
 
 }  // namespace irdmh

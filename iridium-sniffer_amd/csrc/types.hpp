@@ -211,4 +211,13 @@ struct FramePacked {
 };
 static_assert(sizeof(FramePacked) == 80 && sizeof(FramePacked) % 4 == 0, "written as 20 words, one per lane");
 
+// option "iq_sense": what iq_sense_kernel writes into pinned host memory per frame -- the predicates that hold on the
+// bits as they are and with every pair exchanged (bit 0 IRA, bit 1 IBC, bit 2 IDA), and the bits it looked at (0: ok = 0)
+struct SenseRec {
+    uint8_t recorded, exchanged;
+    uint16_t pad;
+    uint32_t n_bits;
+};
+static_assert(sizeof(SenseRec) == 8, "one 8-byte store per frame");
+
 }  // namespace irdm

@@ -10,7 +10,7 @@
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
- *                         [--input-stats] [--diagnostic] [--clock-check]
+ *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -90,6 +90,19 @@
  * R0 the grid rate the pipeline assumed, R rounded to 0.05 % of it (the estimator's resolution).  Behind a front end the
  * line describes the stream the detector sees; R and R0 are scaled back to the capture's -r.  stdout and the rest of
  * stderr are those of the run without the flag.  Refused with --gpus N > 1 and with --save-only (no context, no frames).
+ * --swap-iq: the two components of every sample of every recording of the run are exchanged on the GPU where they arrive
+ * (option "swap_iq", irdm_frontend_swap_iq, irdm_swap_iq_device), raw file or container, in front of --band-center /
+ * --decimate / --resample-to: for a Q/I WAV, a SigMF file of the other convention, an inverting mixer.  Allowed with
+ * --save-only, which then writes the corrected band.  The "input:" line describes the samples as processed: its I is the
+ * file's second component (-v says so once).  Refused with --gpus N > 1.
+ * --iq-check: one closing line per recording on stderr, after "tagged N bursts total" and a "clock:" line and before the
+ * "input:" line -- whether the frames' bits make sense as they are or with I and Q exchanged (option "iq_sense"):
+ *     iq: N frames decide (A IDA, B IRA, C IBC): R as recorded, X with I and Q exchanged
+ * followed, when 9 in 10 of them say exchanged, by " -- the recording is I/Q-swapped (spectrum inverted): every payload is
+ * wrong and every frequency mirrored about -c; run with --swap-iq" (with --swap-iq given: " -- the samples are I/Q-swapped
+ * with --swap-iq in effect: remove it"), by " -- undecided" when neither sense has 9 in 10, and replaced by
+ * "iq: N frames decide; too few to judge" below 5.  stdout and the rest of stderr are those of the run without the flag.
+ * --diagnostic does not imply it.  Refused with --gpus N > 1 and with --save-only.
  */
 #include <err.h>
 #include <errno.h>
@@ -270,6 +283,8 @@ static irdm_group_t *g_group;
 static int g_input_stats, g_diag;
 /* --clock-check */
 static int g_clock;
+/* --iq-check, --swap-iq */
+static int g_iq, g_swap;
 static unsigned long long g_n_demods;       /* frames the demodulator accepted, this recording */
 
 static const char *format_name(int fmt)
@@ -323,6 +338,25 @@ static void clock_line(const irdm_symbol_clock_t *sc, double nominal, double cap
         fprintf(stderr, " -- the samples look like %.0f S/s, not %.0f: check -r", looks, grid * scale);
         if (!front_end) fprintf(stderr, ", or --resample-to %.0f", grid);
     }
+    fprintf(stderr, "\n");
+}
+
+/* the closing "iq:" line of a recording */
+static void iq_line(const irdm_iq_sense_t *q)
+{
+    const unsigned long long d = q->votes_recorded + q->votes_exchanged;
+    if (q->verdict == IRDM_IQ_TOO_FEW) {
+        fprintf(stderr, "iq: %llu frames decide; too few to judge\n", d);
+        return;
+    }
+    fprintf(stderr, "iq: %llu frames decide (%llu IDA, %llu IRA, %llu IBC): %llu as recorded, %llu with I and Q exchanged", d,
+            (unsigned long long)(q->kind_recorded[2] + q->kind_exchanged[2]), (unsigned long long)(q->kind_recorded[0] + q->kind_exchanged[0]),
+            (unsigned long long)(q->kind_recorded[1] + q->kind_exchanged[1]), (unsigned long long)q->votes_recorded,
+            (unsigned long long)q->votes_exchanged);
+    if (q->verdict == IRDM_IQ_EXCHANGED && g_swap) fprintf(stderr, " -- the samples are I/Q-swapped with --swap-iq in effect: remove it");
+    else if (q->verdict == IRDM_IQ_EXCHANGED)
+        fprintf(stderr, " -- the recording is I/Q-swapped (spectrum inverted): every payload is wrong and every frequency mirrored about -c; run with --swap-iq");
+    else if (q->verdict == IRDM_IQ_MIXED) fprintf(stderr, " -- undecided");
     fprintf(stderr, "\n");
 }
 
@@ -395,6 +429,11 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         /* (the summary is the library's; the per-frame records are not printed) */
         static irdm_clock_est_t ce[256];
         while (irdm_poll_symbol_clock(p, ce, 256) > 0) {}
+    }
+    if (g_iq) {
+        /* (likewise: the summary is the library's) */
+        static irdm_iq_vote_t iv[256];
+        while (irdm_poll_iq_votes(p, iv, 256) > 0) {}
     }
     static irdm_ida_t ida[256];
     static irdm_decoded_t dec[256];
@@ -704,7 +743,8 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
             const size_t r = want ? fread(h_in, bps, want, f) : 0;
             if (r == 0) break;
             remain -= r;
-            if (irdm_device_upload(d_in, h_in, r * bps) != 0 || irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
+            if (irdm_device_upload(d_in, h_in, r * bps) != 0 || (g_swap && irdm_swap_iq_device(d_in, r, in_fmt, 0, NULL) != 0) ||
+                irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
             if (r < step) break;
         }
         if (rc == 0 && irdm_frontend_finish_device(fe, d_out, cap, NULL) < 0) rc = 1;
@@ -842,6 +882,8 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--input-stats")) g_input_stats = 1;
         else if (!strcmp(a, "--diagnostic")) g_input_stats = g_diag = 1;     /* options.c:376 */
         else if (!strcmp(a, "--clock-check")) g_clock = 1;
+        else if (!strcmp(a, "--iq-check")) g_iq = 1;
+        else if (!strcmp(a, "--swap-iq")) g_swap = 1;
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -904,7 +946,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -971,6 +1013,24 @@ int main(int argc, char **argv)
         }
         if (save_only) {
             fprintf(stderr, "--clock-check with --save-only: no context runs, so there are no frames to judge\n");
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_iq) {
+        if (gpus > 1) {
+            fprintf(stderr, "--iq-check: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if (save_only) {
+            fprintf(stderr, "--iq-check with --save-only: no context runs, so there are no frames to judge\n");
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_swap) {
+        if (gpus > 1) {
+            fprintf(stderr, "--swap-iq: one GPU only (--gpus %d): a group is fed on the device\n", gpus);
             return 2;
         }
         gpus = 0;
@@ -1101,6 +1161,12 @@ int main(int argc, char **argv)
         fprintf(stderr, "--input-stats: the library refused the statistics\n");
         return 1;
     }
+    if (g_swap && verbose)
+        fprintf(stderr, "--swap-iq: I and Q of every sample are exchanged on the GPU; I of the \"input:\" line is the file's second component\n");
+    if (g_swap && fe && !save_only && irdm_frontend_swap_iq(fe, 1) != 0) {
+        fprintf(stderr, "--swap-iq: the library refused the exchange\n");
+        return 1;
+    }
     if (save_only) {
         const size_t so_step = resample_to ? (chunk * (size_t)rs_m + (size_t)rs_l - 1) / (size_t)rs_l : chunk * (size_t)decimate;
         if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { perror(out_dir); return 1; }
@@ -1166,6 +1232,14 @@ int main(int argc, char **argv)
     }
     if (g_clock && irdm_set_option(p, "symbol_clock", 1) != 0) {
         fprintf(stderr, "--clock-check: the library refused the estimator\n");
+        return 1;
+    }
+    if (g_iq && irdm_set_option(p, "iq_sense", 1) != 0) {
+        fprintf(stderr, "--iq-check: the library refused the check\n");
+        return 1;
+    }
+    if (g_swap && !fe && irdm_set_option(p, "swap_iq", 1) != 0) {
+        fprintf(stderr, "--swap-iq: the library refused the exchange\n");
         return 1;
     }
     g_save_dir = save_dir;
@@ -1356,6 +1430,11 @@ int main(int argc, char **argv)
             irdm_symbol_clock_t sc;
             if (irdm_symbol_clock(p, &sc) == 0) clock_line(&sc, (double)c.sample_rate, rate, fe != NULL);
             else { fprintf(stderr, "--clock-check: %s: no estimate\n", file); rc = 1; }
+        }
+        if (g_iq) {
+            irdm_iq_sense_t iq;
+            if (irdm_iq_sense(p, &iq) == 0) iq_line(&iq);
+            else { fprintf(stderr, "--iq-check: %s: no verdict\n", file); rc = 1; }
         }
         if (g_acars) {
             char st[512];

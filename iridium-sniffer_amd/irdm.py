@@ -204,6 +204,22 @@ class SymbolClock(C.Structure):
                 ("frames_invalid", C.c_uint64)]
 
 
+IQ_IRA, IQ_IBC, IQ_IDA = 1, 2, 4
+IQ_TOO_FEW, IQ_AS_RECORDED, IQ_EXCHANGED, IQ_MIXED = 0, 1, 2, 3
+
+
+class IqVote(C.Structure):
+    """irdm_iq_vote_t (option iq_sense): the predicates IQ_* that hold on a frame's bits as recorded and with I and Q exchanged"""
+    _fields_ = [("id", C.c_uint64), ("recorded", C.c_uint8), ("exchanged", C.c_uint8), ("pad", C.c_uint16), ("n_bits", C.c_uint32)]
+
+
+class IqSense(C.Structure):
+    """irdm_iq_sense_t (irdm_iq_sense): the votes of the stream so far (kind index 0 IRA, 1 IBC, 2 IDA) and the verdict IQ_*"""
+    _fields_ = [("frames", C.c_uint64), ("votes_recorded", C.c_uint64), ("votes_exchanged", C.c_uint64), ("votes_both", C.c_uint64),
+                ("kind_recorded", C.c_uint64 * 3), ("kind_exchanged", C.c_uint64 * 3), ("kind_both", C.c_uint64 * 3),
+                ("verdict", C.c_int32), ("pad", C.c_int32)]
+
+
 class RecordingInfo(C.Structure):
     """irdm_recording_info_t (irdm_recording_probe)"""
     _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
@@ -265,6 +281,11 @@ def lib():
             L.irdm_poll_symbol_clock.argtypes = [C.c_void_p, C.POINTER(ClockEst), C.c_int]
             L.irdm_symbol_clock.argtypes = [C.c_void_p, C.POINTER(SymbolClock)]
             L.irdm_symbol_clock_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(ClockEst)]
+        if hasattr(L, "irdm_iq_sense"):
+            L.irdm_swap_iq_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
+            L.irdm_poll_iq_votes.argtypes = [C.c_void_p, C.POINTER(IqVote), C.c_int]
+            L.irdm_iq_sense.argtypes = [C.c_void_p, C.POINTER(IqSense)]
+            L.irdm_iq_sense_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.POINTER(IqVote)]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -433,6 +454,8 @@ def lib():
             if hasattr(L, "irdm_frontend_input_stats"):
                 L.irdm_frontend_input_stats_enable.argtypes = [C.c_void_p, C.c_int]
                 L.irdm_frontend_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
+            if hasattr(L, "irdm_frontend_swap_iq"):
+                L.irdm_frontend_swap_iq.argtypes = [C.c_void_p, C.c_int]
             if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
                 L.irdm_frontend_create_rational.restype = C.c_void_p
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
@@ -496,6 +519,12 @@ def input_stats_device(d_in, n, fmt, device=0, stream=None):
     if lib().irdm_input_stats_device(C.c_void_p(d_in), n, fmt, C.byref(st), device, C.c_void_p(stream or 0)) != 0:
         raise RuntimeError("irdm_input_stats_device failed")
     return st
+
+
+def swap_iq_device(d_iq, n, fmt, device=0, stream=None):
+    """irdm_swap_iq_device: I and Q of the n samples of format fmt at the device address d_iq exchanged in place; returns
+    the call's result (0, or -1 for an unknown format or a pointer that is not sample-aligned)"""
+    return int(lib().irdm_swap_iq_device(C.c_void_p(d_iq), n, fmt, device, C.c_void_p(stream or 0)))
 
 
 def host_free(ptr):
@@ -779,6 +808,30 @@ class Pipeline:
             raise RuntimeError("irdm_symbol_clock_batch failed")
         return [ClockEst.from_buffer_copy(out[i]) for i in range(n)]
 
+    def poll_iq_votes(self):
+        """option iq_sense 1: one IqVote per demodulator record, in their order"""
+        return self._poll(self.L.irdm_poll_iq_votes, IqVote)
+
+    def poll_iq_votes_raw(self, chunk=4096):
+        """the same as one numpy byte matrix [n, 16]"""
+        return self._poll_raw(self.L.irdm_poll_iq_votes, IqVote, chunk)
+
+    def iq_sense(self):
+        """irdm_iq_sense (option iq_sense): the IqSense summary of the stream so far"""
+        st = IqSense()
+        if self.L.irdm_iq_sense(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_iq_sense failed (option iq_sense never set?)")
+        return st
+
+    def iq_sense_batch(self, demods):
+        """irdm_iq_sense_batch: the sense kernel for a list of Demod records (bits, llr, n_bits and direction are read)"""
+        n = len(demods)
+        arr = (Demod * max(n, 1))(*demods)
+        out = (IqVote * max(n, 1))()
+        if self.L.irdm_iq_sense_batch(self.h, arr, n, out) != 0:
+            raise RuntimeError("irdm_iq_sense_batch failed")
+        return [IqVote.from_buffer_copy(out[i]) for i in range(n)]
+
     def poll_spectrum(self, chunk=64):
         """option spectrum_frames: (headers, mean, peak) of the rows finished so far -- a list of SpectrumRow and two float32
         arrays [rows][n_bins], bin 0 at -fs/2, linear |X|^2"""
@@ -1012,6 +1065,11 @@ class Frontend:
             raise RuntimeError("irdm_frontend_save failed (mid-stream, or a bad field)")
         self.saved = saved
         self._sink = cb              # (the library calls it for as long as the front end lives)
+
+    def swap_iq(self, on=True):
+        """irdm_frontend_swap_iq: feed_host exchanges I and Q of every capture chunk in front of the kernel"""
+        if self.L.irdm_frontend_swap_iq(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("irdm_frontend_swap_iq failed")
 
     def input_stats_enable(self, on=True):
         """irdm_frontend_input_stats_enable: statistics of the capture's samples in front of the kernel"""
