@@ -571,7 +571,14 @@ int irdm_poll_ida(irdm_pipeline_t *p, irdm_ida_t *out, int max);
  * between ranks, e.g. RCCL send/recv of the same bytes).  Returns bytes written / 0, or -1.
  * irdm_seed_history: tells a fresh context that its stream position is abs_start and gives it
  * the n_samples of IQ (host buffer, configured format) that precede that position, so burst
- * windows reaching back across the chunk boundary read real samples (the chunk overlap). */
+ * windows reaching back across the chunk boundary read real samples (the chunk overlap).
+ * STREAM POSITIONS STAY BELOW IRDM_MAX_POSITION = 2^53 samples.  Every index is 64-bit, but a frame's timestamp is made of
+ * (double)start / sample_rate, as in the reference, and from 2^53 on (double)start is no longer the sample it names.
+ * The entries that SET a position -- irdm_seed_history*, irdm_import_state* -- return -1, with one line on stderr, for a
+ * position at or above it and leave the context as it was.  irdm_import_state checks the blob's sample count, the
+ * detector's frame index and every active burst; the device forms check the header's sample count only (the detector
+ * state stays on the device).  A stream that is FED across 2^53 is not checked: that is 12 years at 22.6 MHz. */
+#define IRDM_MAX_POSITION (1ull << 53)
 size_t irdm_state_bytes(const irdm_pipeline_t *p);
 long long irdm_export_state(irdm_pipeline_t *p, void *buf, size_t cap);
 int irdm_import_state(irdm_pipeline_t *p, const void *buf, size_t n);
@@ -971,6 +978,14 @@ int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p);
  * nothing held back by the feeder, not finished.  Taps, tables and the applied shift stay; nothing is allocated.  Waits for
  * the front end's stream.  0 ok, -1 error. */
 int irdm_frontend_reset(irdm_frontend_t *fe);
+/* A capture taken up at input sample total_in, not at 0: the state that feeding total_in samples of zero codes (all-zero
+ * bytes) would have left -- the stream position total_in (the rotator's phase index and the resampler's polyphase schedule
+ * with it), every output that those samples complete counted as produced, the carried tail zeros.  Valid only directly
+ * after irdm_frontend_create* or irdm_frontend_reset (nothing fed, not finished) and for total_in below IRDM_MAX_POSITION;
+ * -1 otherwise, and the object is as it was.  irdm_frontend_save and a change of irdm_frontend_swap_iq, which a stream's
+ * first sample closes, come before it.  Host state and one memset of the tail: a front end that is never sought launches
+ * exactly what it launched without this entry.  0 ok. */
+int irdm_frontend_seek(irdm_frontend_t *fe, uint64_t total_in);
 /* host wait until everything enqueued so far has read its input buffer */
 int irdm_frontend_wait_input(irdm_frontend_t *fe);
 /* irdm_kernel_clock for K0 (always on): the kernel's own spans on the device summed since the last reset.  Waits for the

@@ -486,6 +486,34 @@ extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
     return 0;
 }
 
+// A capture taken up at input sample total_in: the state that fe_emit / fe_commit would have left behind total_in samples
+// of zero codes -- the position, the count of outputs those samples complete, and as the carried tail the zeros from the
+// first sample the next output still needs (fe_commit's count).  Nothing is launched.
+extern "C" int irdm_frontend_seek(irdm_frontend_t *fe, uint64_t total_in)
+{
+    if (!fe || fe->st.total || fe->st.n_out || fe->st.n_tail || fe->st.finished || fe->st.pend) return -1;
+    if (total_in >= IRDM_MAX_POSITION) {
+        fprintf(stderr, "irdm_hip: front end: irdm_frontend_seek: stream position %llu is not below 2^53\n", (unsigned long long)total_in);
+        return -1;
+    }
+    (void)hipSetDevice(fe->cfg.device);
+    const uint64_t n_out = fe_outputs(fe, total_in, false);
+    const long long edge = (long long)(n_out * (uint64_t)fe->M) - fe->c - 1;
+    const long long need = (edge >= 0 ? edge / fe->L : -((-edge + fe->L - 1) / fe->L)) + 1;
+    const long long start = std::min<long long>(std::max<long long>(need, 0), (long long)total_in);
+    const long long n_tail = (long long)total_in - start;
+    if (n_tail > fe->ntaps / fe->L + fe->M + 16) return -1;                                // (the tail buffers' size)
+    // (waited for: the next call may run its kernel on a stream of the caller's)
+    if (n_tail) {
+        IRDM_HIP_CHECK(hipMemsetAsync(fe->d_tail[fe->st.cur], 0, (size_t)n_tail * (size_t)fe->bps, fe->stream));
+        IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+    }
+    fe->st.total = total_in;
+    fe->st.n_out = n_out;
+    fe->st.n_tail = n_tail;
+    return 0;
+}
+
 // ---- saving the band: the public calls ----
 
 static int save_scale(int format) { return format == IRDM_FMT_CI8 ? 128 : (format == IRDM_FMT_CI16 ? 32768 : 0); }

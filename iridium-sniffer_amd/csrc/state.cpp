@@ -11,6 +11,24 @@ struct StateHeader {
     int32_t host_primed, host_hist_idx;
 };
 
+// Stream positions stay below 2^53 (include/irdm_hip.h): from there (double)start, which every timestamp is made of, is no
+// longer exact.  The entries that SET a position refuse one at or above it.  (A feed that crosses it mid-stream is not checked:
+// at 22.6 MHz that is 12 years of samples.)
+static bool position_refused(const char *entry, uint64_t pos)
+{
+    if (pos < IRDM_MAX_POSITION) return false;
+    fprintf(stderr, "irdm_hip: %s: stream position %llu is not below 2^53\n", entry, (unsigned long long)pos);
+    return true;
+}
+
+// the positions a state blob's head carries: the header's sample count, the detector's next frame, the active bursts
+static bool blob_refused(const char *entry, const StateHeader &h, const DetState &d)
+{
+    uint64_t top = std::max(h.total_samples, d.index);
+    for (int i = 0; i < std::min(std::max(d.n_act, 0), kMaxActive); i++) top = std::max(top, std::max(d.act[i].start, d.act[i].last_active));
+    return position_refused(entry, top);
+}
+
 extern "C" size_t irdm_state_bytes(const irdm_pipeline_t *p)
 {
     if (!p) return 0;
@@ -49,6 +67,11 @@ extern "C" int irdm_import_state(irdm_pipeline_t *p, const void *buf, size_t n)
     memcpy(&h, i, sizeof(h));
     if (h.magic != 0x4952444d53544154ull || h.n != (uint64_t)p->P.n || h.hist != (uint64_t)kHistory) return -1;
     i += sizeof(h);
+    {
+        std::vector<DetState> d(1);
+        memcpy(d.data(), i, sizeof(DetState));
+        if (blob_refused("irdm_import_state", h, d[0])) return -1;
+    }
     IRDM_HIP_CHECK(hipMemcpy(p->d_state, i, sizeof(DetState), hipMemcpyHostToDevice));
     i += sizeof(DetState);
     IRDM_HIP_CHECK(hipMemcpy(p->d_sum, i, sizeof(float) * p->P.n, hipMemcpyHostToDevice));
@@ -95,6 +118,8 @@ extern "C" int irdm_import_state_device(irdm_pipeline_t *p, const void *d_buf, s
     IRDM_HIP_CHECK(hipMemcpyAsync(&h, i, sizeof(h), hipMemcpyDeviceToHost, p->stream));
     IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     if (h.magic != 0x4952444d53544154ull || h.n != (uint64_t)p->P.n || h.hist != (uint64_t)kHistory) return -1;
+    // (the header's position only: the detector state stays on the device)
+    if (position_refused("irdm_import_state_device", h.total_samples)) return -1;
     i += sizeof(h);
     IRDM_HIP_CHECK(hipMemcpyAsync(p->d_state, i, sizeof(DetState), hipMemcpyDeviceToDevice, p->stream));
     i += sizeof(DetState);
@@ -131,6 +156,8 @@ extern "C" int irdm_import_state_head_device(irdm_pipeline_t *p, const void *d_b
     IRDM_HIP_CHECK(hipMemcpyAsync(&h, i, sizeof(h), hipMemcpyDeviceToHost, p->stream));
     IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     if (h.magic != 0x4952444d53544154ull || h.n != (uint64_t)p->P.n || h.hist != (uint64_t)kHistory) return -1;
+    // (the header's position only: the detector state stays on the device)
+    if (position_refused("irdm_import_state_head_device", h.total_samples)) return -1;
     i += sizeof(h);
     IRDM_HIP_CHECK(hipMemcpyAsync(p->d_state, i, sizeof(DetState), hipMemcpyDeviceToDevice, p->stream));
     i += sizeof(DetState);
@@ -188,6 +215,7 @@ extern "C" int irdm_import_state_history_device(irdm_pipeline_t *p, const void *
 extern "C" int irdm_seed_history_device(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, uint64_t abs_start)
 {
     if (!p || (!d_iq && n_samples) || n_samples > abs_start || p->st.begin_no != p->st.end_no) return -1;
+    if (position_refused("irdm_seed_history_device", abs_start)) return -1;
     pipeline_enter(p);
     if (n_samples > p->ring_len) {
         d_iq = static_cast<const char *>(d_iq) + (n_samples - p->ring_len) * p->bps;
@@ -206,6 +234,7 @@ extern "C" int irdm_seed_history_device(irdm_pipeline_t *p, const void *d_iq, si
 extern "C" int irdm_seed_history(irdm_pipeline_t *p, const void *h_iq, size_t n_samples, uint64_t abs_start)
 {
     if (!p || (!h_iq && n_samples) || n_samples > abs_start || p->st.begin_no != p->st.end_no) return -1;
+    if (position_refused("irdm_seed_history", abs_start)) return -1;
     if (quiesce(p) != 0) return -1;
     if (n_samples > p->ring_len) {       // only the most recent ring_len samples can matter
         h_iq = static_cast<const char *>(h_iq) + (n_samples - p->ring_len) * p->bps;

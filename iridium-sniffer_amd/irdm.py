@@ -445,6 +445,8 @@ def lib():
             L.irdm_frontend_wait_input.argtypes = [C.c_void_p]
             if hasattr(L, "irdm_frontend_reset"):
                 L.irdm_frontend_reset.argtypes = [C.c_void_p]
+            if hasattr(L, "irdm_frontend_seek"):
+                L.irdm_frontend_seek.argtypes = [C.c_void_p, C.c_uint64]
             L.irdm_frontend_kernel_clock.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int]
             if hasattr(L, "irdm_frontend_save"):
                 L.irdm_frontend_save.argtypes = [C.c_void_p, C.POINTER(FrontendSaveConfig)]
@@ -1039,6 +1041,12 @@ class Frontend:
         """irdm_frontend_reset: back to the state after creation, for another capture (taps, tables and shift stay)"""
         if self.L.irdm_frontend_reset(self.h) != 0:
             raise RuntimeError("irdm_frontend_reset failed")
+
+    def seek(self, total_in):
+        """irdm_frontend_seek: directly after creation or reset, take the capture up at input sample total_in -- the state
+        that feeding total_in samples of zero codes would have left"""
+        if self.L.irdm_frontend_seek(self.h, int(total_in)) != 0:
+            raise RuntimeError("irdm_frontend_seek refused (samples already fed, or a position from 2^53 on)")
 
     def flush(self, pipeline):
         rc = self.L.irdm_frontend_flush(self.h, pipeline.h)

@@ -11,11 +11,72 @@ def bits_of(x):
     return np.float32(x).view(np.uint32)
 
 
+STAT_KEYS = ("scan_fast_chunks", "scan_fallbacks", "scan_dense_frames", "band_chunks",
+             "band_rounds", "band_retries", "band_aborts", "band_last_flags", "k1_lists", "band_extra",
+             "scratch_outputs", "scratch_grows", "scratch_peak", "rot_rows", "rot_runs", "rot_ckpts", "rot_blocks", "rot_blocks_cap", "rot_grows",
+             "spec_passes", "spec_scans", "scan_chained", "scan_chain_undone", "sum_restarts")
+
+
+def feed_chunks(p, iq, fmt, sizes, feed="host", off=0, past_ring_end="refuse"):
+    """Feed the samples of `iq` from sample `off` on through the context p in chunks of `sizes` samples; returns the sample
+    behind the last one fed.
+
+    feed: "host" irdm_feed_host per chunk; "ingest" every chunk written in place (irdm_ingest_ptr) and fed from there;
+    "lookahead" device buffers, irdm_feed_begin(k+1) before irdm_feed_end(k); "ingest_lookahead" both (all but "host" need
+    pipeline_depth >= 1).
+    past_ring_end: what an in-place feed does with a chunk that would run past the end of the history ring, for which
+    irdm_ingest_ptr has no slot -- "refuse": the test's chunking is not meant to get there, an assertion; "buffer": that
+    chunk goes through a device buffer, as a producer does."""
+    per = 1 if fmt == irdm.FMT_CF32 else 2
+    L = irdm.lib()
+    if feed == "host":
+        for c in sizes:
+            p.feed_host(iq[off * per:(off + c) * per])
+            off += c
+        return off
+    import ctypes as C
+    ingest = feed.startswith("ingest")
+    look = feed.endswith("lookahead")
+    held = []                # device buffers of chunks begun (not "ingest"): released after their feed_end
+
+    def begin(c, off):
+        part = np.ascontiguousarray(iq[off * per:(off + c) * per])
+        if ingest:
+            ptr = p.ingest_ptr(c)
+            assert ptr or past_ring_end == "buffer", "irdm_ingest_ptr refused a chunk of %d samples" % c
+        if ingest and ptr:
+            assert L.irdm_device_upload(C.c_void_p(ptr), part.ctypes.data_as(C.c_void_p), part.nbytes) == 0
+            held.append(None)
+        else:
+            ptr = irdm.device_buffer(part)
+            held.append(ptr)
+        p.feed_begin(ptr, c)
+
+    def end():
+        p.feed_end()
+        ptr = held.pop(0)
+        if ptr:
+            irdm.device_free(ptr)
+
+    pending = 0
+    ahead = 1 if look else 0      # chunks begun ahead of the one that is ended
+    for c in sizes:
+        begin(c, off)
+        off += c
+        pending += 1
+        if pending > ahead:
+            end()
+            pending -= 1
+    while pending:
+        end()
+        pending -= 1
+    return off
+
+
 def run_gpu(iq, fs, fmt=irdm.FMT_CF32, chunks=None, scan_mode=0, depth=0, feed="host", options=None, packed=False, **kw):
     """Feed `iq` through the HIP pipeline in the given chunk sizes (samples).
 
-    feed: "host" irdm_feed_host per chunk; "ingest" every chunk written in place (irdm_ingest_ptr) and fed from there;
-    "lookahead" device buffers, irdm_feed_begin(k+1) before irdm_feed_end(k); "ingest_lookahead" both.
+    feed: the feed forms of feed_chunks().
     packed: option packed_records -- the compact frame records only (gpu["packed"]; no frame samples, no LLRs)."""
     n = len(iq) if fmt == irdm.FMT_CF32 else len(iq) // 2
     max_chunk = max(chunks) if chunks else n
@@ -28,51 +89,9 @@ def run_gpu(iq, fs, fmt=irdm.FMT_CF32, chunks=None, scan_mode=0, depth=0, feed="
     p.set_option("scan_mode", scan_mode)
     for k, v in (options or {}).items():
         p.set_option(k, v)
-    per = 1 if fmt == irdm.FMT_CF32 else 2
-    off = 0
-    sizes = list(chunks or [n])
-    L = irdm.lib()
-    if feed == "host":
-        for c in sizes:
-            p.feed_host(iq[off * per:(off + c) * per])
-            off += c
-    else:
-        import ctypes as C
+    if feed != "host":
         assert depth >= 1
-        ingest = feed.startswith("ingest")
-        look = feed.endswith("lookahead")
-        held = []                # device buffers of chunks begun (not "ingest"): released after their feed_end
-
-        def begin(c, off):
-            part = np.ascontiguousarray(iq[off * per:(off + c) * per])
-            if ingest:
-                ptr = p.ingest_ptr(c)
-                assert ptr, "irdm_ingest_ptr refused a chunk of %d samples" % c
-                assert L.irdm_device_upload(C.c_void_p(ptr), part.ctypes.data_as(C.c_void_p), part.nbytes) == 0
-                held.append(None)
-            else:
-                ptr = irdm.device_buffer(part)
-                held.append(ptr)
-            p.feed_begin(ptr, c)
-
-        def end():
-            p.feed_end()
-            ptr = held.pop(0)
-            if ptr:
-                irdm.device_free(ptr)
-
-        pending = 0
-        ahead = 1 if look else 0      # chunks begun ahead of the one that is ended
-        for c in sizes:
-            begin(c, off)
-            off += c
-            pending += 1
-            if pending > ahead:
-                end()
-                pending -= 1
-        while pending:
-            end()
-            pending -= 1
+    off = feed_chunks(p, iq, fmt, list(chunks or [n]), feed)
     assert off == n
     if depth:
         p.flush()
@@ -81,11 +100,7 @@ def run_gpu(iq, fs, fmt=irdm.FMT_CF32, chunks=None, scan_mode=0, depth=0, feed="
     demods = p.poll_demods()
     packed_recs = p.poll_demods_packed() if packed else []
     res = dict(bursts=bursts, infos=infos, samples=samples, demods=demods, packed=packed_recs, tagged=p.tagged,
-               n_samples=p.sample_count, timings=p.timings(),
-               stats={k: p.stat(k) for k in ("scan_fast_chunks", "scan_fallbacks", "scan_dense_frames", "band_chunks",
-                                             "band_rounds", "band_retries", "band_aborts", "band_last_flags", "k1_lists", "band_extra",
-                                             "scratch_outputs", "scratch_grows", "scratch_peak", "rot_rows", "rot_runs", "rot_ckpts", "rot_blocks", "rot_blocks_cap", "rot_grows",
-                                             "spec_passes", "spec_scans", "scan_chained", "scan_chain_undone", "sum_restarts")})
+               n_samples=p.sample_count, timings=p.timings(), stats={k: p.stat(k) for k in STAT_KEYS})
     p.close()
     return res
 

@@ -21,6 +21,7 @@ def test_library_exports_every_declared_symbol():
     L = C.CDLL(irdm.LIB_PATH)
     names = declared_functions()
     assert "gpu_burst_fft_create" in names and "irdm_feed_device" in names and len(names) >= 18
+    assert "irdm_frontend_seek" in names and "irdm_frontend_reset" in names
     for n in names:
         assert hasattr(L, n), n
 
