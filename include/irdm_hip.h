@@ -379,6 +379,23 @@ typedef struct {
     int32_t  pad;
 } irdm_iq_sense_t;
 
+/* option "scrub": what the pass that zeroes non-finite and out-of-range cf32 samples has done (irdm_scrub_stats,
+ * irdm_frontend_scrub_stats, irdm_scrub_device).  With L = ldexpf(1, limit_log2) a component c is good iff fabsf(c) <= L
+ * (a NaN fails the comparison); a sample with a component that is not good becomes +0.0f, +0.0f, all 64 bits zero; every
+ * other sample keeps its bits (-0.0, subnormals and a component equal to +-L among them).  A stream position is the
+ * sample's index in the stream, counted from 0 at create / reset as irdm_sample_count counts; in front of a front end it
+ * is the index in the capture.  No figure depends on how the stream is cut into chunks. */
+#define IRDM_SCRUB_DEFAULT_LOG2 40
+typedef struct {
+    uint64_t n_samples;              /* samples the pass has covered since create / reset */
+    uint64_t n_zeroed;               /* samples zeroed */
+    uint64_t n_nonfinite;            /* components whose exponent field is all ones */
+    uint64_t n_over;                 /* finite components with |c| > L */
+    uint64_t first, last;            /* stream positions of the first and the last zeroed sample; valid when n_zeroed > 0 */
+    int32_t  limit_log2;
+    int32_t  active;                 /* 0 when the format is not cf32: nothing was launched, every figure above is 0 */
+} irdm_scrub_stats_t;
+
 typedef struct irdm_pipeline irdm_pipeline_t;
 
 /* burst_detector_create + burst_downmix_create (burst_detect.c:174, burst_downmix.c:223):
@@ -717,6 +734,24 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         irdm_feed_device / irdm_feed_begin return -1 with a line on stderr -- exchange the buffer with
  *                         irdm_swap_iq_device first.  -1 for a member of a group, and for a change of the value between
  *                         a stream's first feed and irdm_reset (the ring would hold both senses)
+ *   "scrub"               0/1, default 0: 1 = irdm_feed_host zeroes every cf32 sample of every chunk that has a non-finite
+ *                         component or one beyond +-2^scrub_limit_log2 (irdm_scrub_device's kernel on the feed's stream,
+ *                         behind the host-to-device copy and behind swap_iq's exchange, in front of the feed; the ring slot
+ *                         of irdm_ingest_ptr and the staging buffer alike), so the detector, the history ring, the
+ *                         per-burst chains, input_stats and spectrum_frames never see such a sample; irdm_scrub_stats says
+ *                         what was zeroed and where.  One such sample otherwise puts a NaN or an Inf into the detector's
+ *                         baseline sums, which never recover: no burst is found behind it.  A context of another format
+ *                         takes the option and launches nothing (its samples are always finite).  Four 8 KiB blocks on
+ *                         the device and in pinned memory are allocated when the option is first set to 1 on a cf32
+ *                         context, never before; with 0 nothing is launched.  With the option on irdm_feed_device /
+ *                         irdm_feed_begin return -1 with a line on stderr (the caller's buffer is not ours to change) --
+ *                         scrub the buffer with irdm_scrub_device first.  -1 for a member of a group, and for a change of
+ *                         the value between a stream's first feed and irdm_reset
+ *   "scrub_limit_log2"    0 .. 127, default 40: the limit's base-2 logarithm.  The limit keeps every square, and the sums
+ *                         the detector makes of them, finite (2^14 samples of 2^40 in one FFT frame square to 2^108); it
+ *                         does not judge what a glitch is -- un-normalised int16-, int24- and int32-scaled floats pass.  A
+ *                         caller who wants finite glitches gone picks a lower limit.  -1 outside 0 .. 127, for a member of
+ *                         a group, and for a change between a stream's first feed and irdm_reset
  *   "decode_frames" / "decode_ida"  0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
  *   "fir_order" (alias "simd_order")   default 1 = the arithmetic of the reference's AVX2 kernels, simd_avx2.c -- what
@@ -1115,6 +1150,33 @@ int irdm_iq_sense_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_
  *   return -1 with a line on stderr (they take the caller's buffer as it is).  Returns 0; -1 for a change between the
  *   stream's first chunk and irdm_frontend_reset. */
 int irdm_frontend_swap_iq(irdm_frontend_t *fe, int on);
+
+/* ---- non-finite and out-of-range samples (irdm_scrub_stats_t above) ----
+ * irdm_scrub_device: the pass alone, on the n_samples samples of `format` (IRDM_FMT_*) at d_iq, a buffer the caller owns;
+ *   d_iq need only be aligned to a sample.  limit_log2: 0 .. 127 (IRDM_SCRUB_DEFAULT_LOG2 = 40).  stats == NULL: on
+ *   `stream` (a hipStream_t) without waiting; stream == NULL: on a stream of the call's own, complete on return.  With
+ *   stats the call waits for the stream and fills them in; first and last are indices into the buffer.  A buffer of more
+ *   than 2^31 samples is cut into launches of at most that many.  Returns 0 -- for a format other than cf32 without
+ *   touching the buffer (stats: active 0) --; -1 for an unknown format, a pointer that is not aligned to a sample, a
+ *   limit outside 0 .. 127 or a failed launch; n_samples == 0 launches nothing.  Applied twice, the second pass changes
+ *   and counts nothing.
+ * irdm_set_option(p, "scrub", 1) applies it to every chunk of irdm_feed_host; irdm_frontend_scrub to every capture chunk of
+ *   irdm_frontend_feed_host.
+ * irdm_scrub_stats: the figures of the stream so far, positions in stream coordinates; waits for the feed stream.
+ *   irdm_reset starts them over.  They are NOT part of irdm_export_state / irdm_import_state: a context that takes a
+ *   stream over counts from zero.  Returns 0, or -1 (the option off included).
+ * irdm_frontend_scrub: option "scrub" for a front end -- irdm_frontend_feed_host scrubs every capture chunk in its staging
+ *   buffer, behind irdm_frontend_swap_iq's exchange and in front of the front end's statistics pass and K0 / K0r, so the
+ *   band that irdm_frontend_save writes is the scrubbed one.  A front end of another capture format takes the switch and
+ *   launches nothing.  With it on, irdm_frontend_feed_device and irdm_frontend_run_device return -1 with a line on
+ *   stderr.  Returns 0; -1 for a limit outside 0 .. 127 and for a change of either value between the stream's first chunk
+ *   and irdm_frontend_reset.
+ * irdm_frontend_scrub_stats: as irdm_scrub_stats, positions in capture coordinates (irdm_frontend_seek moves the origin
+ *   with the stream position); irdm_frontend_reset starts them over. */
+int irdm_scrub_device(void *d_iq, size_t n_samples, int format, int limit_log2, irdm_scrub_stats_t *stats, int device, void *stream);
+int irdm_scrub_stats(irdm_pipeline_t *p, irdm_scrub_stats_t *out);
+int irdm_frontend_scrub(irdm_frontend_t *fe, int on, int limit_log2);
+int irdm_frontend_scrub_stats(irdm_frontend_t *fe, irdm_scrub_stats_t *out);
 
 /* ---- self-describing recordings: WAV / RF64, SigMF, SDRangel .sdriq (csrc/recording.cpp) ----
  * Host code only, no device call: works without a GPU.  irdm_recording_probe reads the header of `path` and says what the

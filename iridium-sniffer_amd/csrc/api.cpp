@@ -47,6 +47,18 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         p->swap_iq = value ? 1 : 0;
         return 0;
     }
+    if (!strcmp(key, "scrub")) {
+        // 0 / 1; not for a member of a group (it is fed on the device), and no change between a stream's first feed and
+        // irdm_reset: the figures would describe half a stream
+        if (p->in_group || (p->st.begin_no != 0 && (value != 0) != (p->scrub.on != 0))) return -1;
+        return scrub_configure(p, value);
+    }
+    if (!strcmp(key, "scrub_limit_log2")) {
+        // 0 .. 127; as "scrub"
+        if (value < 0 || value > 127 || p->in_group || (p->st.begin_no != 0 && value != p->scrub.limit_log2)) return -1;
+        p->scrub.limit_log2 = value;
+        return 0;
+    }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
     if (!strcmp(key, "detect_only")) { p->detect_only = value; return 0; }

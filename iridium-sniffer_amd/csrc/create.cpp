@@ -73,6 +73,7 @@ void pipeline_free(irdm_pipeline *p)
     for (auto &e : p->ev_spec)
         if (e) (void)hipEventDestroy(e);
     input_stats_pass_free(p->in_stats);
+    scrub_pass_free(p->scrub);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);
     for (float2 *q : p->rot_retired) (void)hipFree(q);
     for (float2 *q : p->scratch_retired) (void)hipFree(q);

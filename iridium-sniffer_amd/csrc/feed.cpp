@@ -334,6 +334,11 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
                         "buffer as it is -- exchange it with irdm_swap_iq_device first\n");
         return -1;
     }
+    if (p->scrub.on && !p->feed_inner) {
+        fprintf(stderr, "irdm_hip: option scrub cleans the chunks of irdm_feed_host only: a device feed takes the caller's buffer "
+                        "as it is -- scrub it with irdm_scrub_device first\n");
+        return -1;
+    }
     if (p->st.begin_no - p->st.end_no > (p->depth ? kLookAhead : 0u)) return -1;    // two chunks of look-ahead, pipeline_depth >= 1 only
     if (p->st.stream_closed) {
         fprintf(stderr, "irdm_hip: stream already ended by a chunk that was not a multiple of feed_block\n");
@@ -590,10 +595,14 @@ extern "C" int irdm_device_copy(void *dst, const void *src, size_t bytes)
 }
 
 // a chunk of irdm_feed_host where its copy lands it on fstream (the ring slot of irdm_ingest_ptr or d_stage): option
-// "swap_iq" exchanges its components there, behind the copy and in front of everything that reads the chunk
+// "swap_iq" exchanges its components there, behind the copy and in front of everything that reads the chunk; option
+// "scrub" then zeroes its non-finite and out-of-range samples (cf32 alone: the other formats hold none)
 static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples)
 {
     if (p->swap_iq && launch_iq_swap(p->dev_fmt, d_iq, n_samples, p->fstream) != 0) return -1;
+    if (p->scrub.on && p->dev_fmt == IRDM_FMT_CF32 &&
+        scrub_enqueue(p->scrub, p->st.scrub, d_iq, n_samples, p->st.begun_samples, p->fstream) != 0)
+        return -1;
     p->feed_inner = true;
     const int rc = irdm_feed_device(p, d_iq, n_samples, p->fstream);
     p->feed_inner = false;
@@ -641,6 +650,63 @@ extern "C" int irdm_swap_iq_device(void *d_iq, size_t n_samples, int format, int
     return rc;
 }
 
+// ---- option "scrub" (scrub.hpp): the blocks of the passes, when the option is first set on a cf32 context ----
+int scrub_configure(irdm_pipeline *p, int on)
+{
+    if (on && p->dev_fmt == IRDM_FMT_CF32 && scrub_pass_alloc(p->scrub) != 0) return -1;
+    p->scrub.on = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_scrub_stats(irdm_pipeline_t *p, irdm_scrub_stats_t *out)
+{
+    if (!p || !out || !p->scrub.on) return -1;
+    pipeline_enter(p);
+    IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
+    if (scrub_settle(p->scrub, p->st.scrub) != 0) return -1;
+    scrub_result(p->st.scrub.run, p->scrub.limit_log2, p->dev_fmt == IRDM_FMT_CF32 ? 1 : 0, out);
+    return 0;
+}
+
+// irdm_scrub_device: the pass alone, on a buffer the caller owns (scrub.hpp)
+extern "C" int irdm_scrub_device(void *d_iq, size_t n_samples, int format, int limit_log2, irdm_scrub_stats_t *stats, int device,
+                                 void *stream_v)
+{
+    if ((!d_iq && n_samples) || !fmt_valid(format) || (reinterpret_cast<uintptr_t>(d_iq) % (size_t)fmt_bytes(format)) != 0 ||
+        limit_log2 < 0 || limit_log2 > 127)
+        return -1;
+    ScrubRun run;
+    if (format != IRDM_FMT_CF32 || n_samples == 0) {
+        if (stats) scrub_result(run, limit_log2, format == IRDM_FMT_CF32 ? 1 : 0, stats);
+        return 0;
+    }
+    IRDM_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
+    if (!s) {
+        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
+        s = own;
+    }
+    // (with stats: one block for the call, read back after every launch of at most 2^31 samples)
+    ScrubAcc *d_acc = nullptr;
+    int rc = !stats || hipMalloc(reinterpret_cast<void **>(&d_acc), kSbBlockBytes) == hipSuccess ? 0 : -1;
+    for (size_t off = 0; rc == 0 && off < n_samples; off += kSbMaxLaunch) {
+        const size_t piece = std::min(kSbMaxLaunch, n_samples - off);
+        if (d_acc && hipMemsetAsync(d_acc, 0, kSbBlockBytes, s) != hipSuccess) rc = -1;
+        if (rc == 0) rc = launch_scrub(static_cast<char *>(d_iq) + off * 8, piece, limit_log2, d_acc, s);
+        if (rc == 0 && d_acc) {
+            ScrubAcc h[kSbRows];
+            rc = hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h, d_acc, kSbBlockBytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+            if (rc == 0) scrub_fold(run, h, off, piece);
+        }
+    }
+    if (d_acc) (void)hipFree(d_acc);
+    if (own) {
+        if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
+        (void)hipStreamDestroy(own);
+    }
+    if (rc == 0 && stats) scrub_result(run, limit_log2, 1, stats);
+    return rc;
+}
 
 extern "C" int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max)
 {

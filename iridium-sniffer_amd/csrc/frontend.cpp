@@ -36,6 +36,7 @@ void fe_free(irdm_frontend *fe)
     if (fe->stream) (void)hipStreamSynchronize(fe->stream);
     fe_save_off(fe);
     input_stats_pass_free(fe->is);
+    scrub_pass_free(fe->scrub);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
@@ -318,10 +319,40 @@ extern "C" int irdm_frontend_swap_iq(irdm_frontend_t *fe, int on)
     return 0;
 }
 
+// irdm_frontend_scrub is on and the caller hands over a device buffer of its own: refused, with the remedy
+static bool fe_scrub_refuses(const irdm_frontend *fe)
+{
+    if (!fe->scrub.on || fe->feed_inner) return false;
+    fprintf(stderr, "irdm_hip: front end: irdm_frontend_scrub cleans the chunks of irdm_frontend_feed_host only: a device feed "
+                    "takes the caller's buffer as it is -- scrub it with irdm_scrub_device first\n");
+    return true;
+}
+
+extern "C" int irdm_frontend_scrub(irdm_frontend_t *fe, int on, int limit_log2)
+{
+    // no change between a stream's first chunk and irdm_frontend_reset: the figures would describe half a capture
+    if (!fe || limit_log2 < 0 || limit_log2 > 127) return -1;
+    if (fe->st.total != 0 && ((on != 0) != (fe->scrub.on != 0) || limit_log2 != fe->scrub.limit_log2)) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (on && fe->fmt == IRDM_FMT_CF32 && scrub_pass_alloc(fe->scrub) != 0) return -1;
+    fe->scrub.on = on ? 1 : 0;
+    fe->scrub.limit_log2 = limit_log2;
+    return 0;
+}
+
+extern "C" int irdm_frontend_scrub_stats(irdm_frontend_t *fe, irdm_scrub_stats_t *out)
+{
+    if (!fe || !out || !fe->scrub.on) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (scrub_settle(fe->scrub, fe->st.scrub) != 0) return -1;
+    scrub_result(fe->st.scrub.run, fe->scrub.limit_log2, fe->fmt == IRDM_FMT_CF32 ? 1 : 0, out);
+    return 0;
+}
+
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
-    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe)) return -1;
+    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe) || fe_scrub_refuses(fe)) return -1;
     const uint64_t m1 = fe_outputs(fe, fe->st.total + n_in, false);
     const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
@@ -418,7 +449,7 @@ static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
 
 extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream_v)
 {
-    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe)) return -1;
+    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe) || fe_scrub_refuses(fe)) return -1;
     pipeline_enter(p);
     if (stream_v && static_cast<hipStream_t>(stream_v) != fe->stream) {
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
@@ -451,6 +482,10 @@ extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, 
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
     // irdm_frontend_swap_iq: the capture's components exchanged where it landed, in front of the statistics pass and K0 / K0r
     if (fe->swap_iq && launch_iq_swap(fe->fmt, fe->d_stage, n_in, fe->stream) != 0) return -1;
+    // irdm_frontend_scrub: then its non-finite and out-of-range samples zeroed (cf32 alone), positions counted in the capture
+    if (fe->scrub.on && fe->fmt == IRDM_FMT_CF32 &&
+        scrub_enqueue(fe->scrub, fe->st.scrub, fe->d_stage, n_in, fe->st.total, fe->stream) != 0)
+        return -1;
     fe->feed_inner = true;
     const int bursts = irdm_frontend_feed_device(fe, p, fe->d_stage, n_in, nullptr);
     fe->feed_inner = false;

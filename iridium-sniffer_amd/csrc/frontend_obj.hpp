@@ -35,6 +35,8 @@ struct irdm_frontend {
         uint64_t sv_samples = 0;
         // input statistics: the totals of the capture and the passes in flight (input_stats.hpp)
         irdm::InputStatsStream is;
+        // irdm_frontend_scrub: the totals of the pass and the launches whose figures are on their way (scrub.hpp)
+        irdm::ScrubStream scrub;
     } st;
     // Saving the band (irdm_frontend_save; off: sink == nullptr and nothing below exists).  fe_emit requantises what its
     // kernel wrote in pieces of at most slot_samples, each into one of two slots: device staging d[i] copied to the pinned
@@ -58,6 +60,9 @@ struct irdm_frontend {
     // (configuration); feed_inner marks that call's own device feed, the only one the switch allows
     int swap_iq = 0;
     bool feed_inner = false;
+    // irdm_frontend_scrub: irdm_frontend_feed_host zeroes the non-finite and out-of-range samples of every cf32 capture
+    // chunk in its staging buffer (scrub.on, scrub.limit_log2: configuration; the blocks: cache)
+    irdm::ScrubPass scrub;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

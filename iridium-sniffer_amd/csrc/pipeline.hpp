@@ -39,6 +39,7 @@
 #include "input_stats.hpp"
 #include "symbol_clock.hpp"
 #include "iq_swap.hpp"
+#include "scrub.hpp"
 #include "iq_sense.hpp"
 
 using namespace irdm;
@@ -237,6 +238,8 @@ struct StreamState {
     SymbolClockStream clock;
     // option "iq_sense": the per-frame votes until they are polled and the counts of the summary (iq_sense.hpp)
     IqSenseStream iq;
+    // option "scrub": the totals of the pass and the launches whose figures are still on their way (scrub.hpp)
+    ScrubStream scrub;
 };
 
 struct irdm_pipeline {
@@ -438,6 +441,10 @@ struct irdm_pipeline {
     // feed_inner marks irdm_feed_host's own call of irdm_feed_device, the only device feed the option allows
     int swap_iq = 0;
     bool feed_inner = false;
+    // options "scrub" / "scrub_limit_log2" (feed.cpp, scrub.hpp): irdm_feed_host zeroes the non-finite and out-of-range
+    // samples of every cf32 chunk on the device; scrub.on and scrub.limit_log2 are configuration, the blocks cache
+    // (allocated when the option is first set on a cf32 context)
+    ScrubPass scrub;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -487,6 +494,7 @@ int spectrum_configure(irdm_pipeline *p, int R);
 int input_stats_configure(irdm_pipeline *p, int on);
 int symbol_clock_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
+int scrub_configure(irdm_pipeline *p, int on);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

@@ -10,7 +10,7 @@
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
- *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq]
+ *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -103,6 +103,20 @@
  * with --swap-iq in effect: remove it"), by " -- undecided" when neither sense has 9 in 10, and replaced by
  * "iq: N frames decide; too few to judge" below 5.  stdout and the rest of stderr are those of the run without the flag.
  * --diagnostic does not imply it.  Refused with --gpus N > 1 and with --save-only.
+ * --scrub[=LOG2]: every cf32 sample of every recording of the run with a component that is not finite or lies beyond
+ * +-2^LOG2 (0 .. 127, default 40) is zeroed on the GPU where it arrives (option "scrub", irdm_frontend_scrub,
+ * irdm_scrub_device), behind --swap-iq's exchange and in front of everything else: one such sample -- the ragged tail of a
+ * recorder that was killed, a division by zero upstream, corrupt bytes -- otherwise silences the detector for the rest of
+ * the run.  Raw file or container; allowed with --save-only, which then writes the scrubbed band.  One closing line per
+ * recording on stderr, after "tagged N bursts total" and the "clock:" and "iq:" lines and before the "input:" line, which
+ * describes the samples as processed:
+ *     scrub: N samples cf32, limit 2^40; none zeroed
+ *     scrub: N samples cf32, limit 2^40; Z zeroed (A non-finite, B out-of-range components), first at sample F (T s), last at L (T s)
+ * with positions in samples of the stream the pass sees (the capture in front of a front end) and times to the
+ * microsecond at its rate; followed by " -- more than 0.1 % of the recording: is this file cf32 at all? check --format"
+ * when that many were zeroed.  A recording of another format gets "scrub: ci16 samples are always finite; nothing to do".
+ * stdout and the rest of stderr of a run over a clean file are those of the run without the flag.  --diagnostic does not
+ * imply it.  Refused with --gpus N > 1.
  */
 #include <err.h>
 #include <errno.h>
@@ -285,6 +299,8 @@ static int g_input_stats, g_diag;
 static int g_clock;
 /* --iq-check, --swap-iq */
 static int g_iq, g_swap;
+/* --scrub[=LOG2] */
+static int g_scrub, g_scrub_log2 = IRDM_SCRUB_DEFAULT_LOG2;
 static unsigned long long g_n_demods;       /* frames the demodulator accepted, this recording */
 
 static const char *format_name(int fmt)
@@ -357,6 +373,26 @@ static void iq_line(const irdm_iq_sense_t *q)
     else if (q->verdict == IRDM_IQ_EXCHANGED)
         fprintf(stderr, " -- the recording is I/Q-swapped (spectrum inverted): every payload is wrong and every frequency mirrored about -c; run with --swap-iq");
     else if (q->verdict == IRDM_IQ_MIXED) fprintf(stderr, " -- undecided");
+    fprintf(stderr, "\n");
+}
+
+/* the closing "scrub:" line of a recording; rate: that of the stream the pass saw */
+static void scrub_line(const irdm_scrub_stats_t *st, int fmt, double rate)
+{
+    if (!st->active) {
+        fprintf(stderr, "scrub: %s samples are always finite; nothing to do\n", format_name(fmt));
+        return;
+    }
+    fprintf(stderr, "scrub: %llu samples %s, limit 2^%d;", (unsigned long long)st->n_samples, format_name(fmt), st->limit_log2);
+    if (!st->n_zeroed) {
+        fprintf(stderr, " none zeroed\n");
+        return;
+    }
+    fprintf(stderr, " %llu zeroed (%llu non-finite, %llu out-of-range components), first at sample %llu (%.6f s), last at %llu (%.6f s)",
+            (unsigned long long)st->n_zeroed, (unsigned long long)st->n_nonfinite, (unsigned long long)st->n_over,
+            (unsigned long long)st->first, (double)st->first / rate, (unsigned long long)st->last, (double)st->last / rate);
+    if ((double)st->n_zeroed * 1000.0 > (double)st->n_samples)
+        fprintf(stderr, " -- more than 0.1 %% of the recording: is this file cf32 at all? check --format");
     fprintf(stderr, "\n");
 }
 
@@ -721,7 +757,7 @@ static int band_close(irdm_frontend_t *fe, const char *file, int fmt, float gain
 /* --save-only: every recording through the stage-level entries -- no context, no lines.  step: capture samples per read,
  * cap: the outputs a read can complete. */
 static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char *out_dir, int fmt, float gain, int verbose,
-                         double centre, size_t step, size_t bps, size_t cap, int in_fmt)
+                         double centre, size_t step, size_t bps, size_t cap, int in_fmt, double rate)
 {
     void *h_in = irdm_host_alloc(step * bps), *d_in = irdm_device_alloc(0, step * bps), *d_out = irdm_device_alloc(0, cap * 8);
     int rc_all = 0;
@@ -738,19 +774,35 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
         if (in->kind > 0 && fseeko(f, (off_t)in->info->data_offset, SEEK_SET) != 0) { perror(data); fclose(f); rc_all = 1; continue; }
         if (fi > 0 && irdm_frontend_reset(fe) != 0) { fprintf(stderr, "%s: the front end could not be reset\n", file); rc_all = 1; break; }
         if (band_open(save_band, out_dir, file, fmt) != 0) { if (f != stdin) fclose(f); rc_all = 1; continue; }
+        irdm_scrub_stats_t sb = { 0 };                       /* --scrub: the recording's figures, summed over its reads */
+        sb.limit_log2 = g_scrub_log2;
+        sb.active = in_fmt == IRDM_FMT_CF32;
         for (;;) {
             const size_t want = remain < step ? (size_t)remain : step;
             const size_t r = want ? fread(h_in, bps, want, f) : 0;
             if (r == 0) break;
             remain -= r;
-            if (irdm_device_upload(d_in, h_in, r * bps) != 0 || (g_swap && irdm_swap_iq_device(d_in, r, in_fmt, 0, NULL) != 0) ||
-                irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
+            if (irdm_device_upload(d_in, h_in, r * bps) != 0 || (g_swap && irdm_swap_iq_device(d_in, r, in_fmt, 0, NULL) != 0)) { rc = 1; break; }
+            if (g_scrub) {
+                irdm_scrub_stats_t one;
+                if (irdm_scrub_device(d_in, r, in_fmt, g_scrub_log2, &one, 0, NULL) != 0) { rc = 1; break; }
+                if (one.n_zeroed) {
+                    if (!sb.n_zeroed) sb.first = sb.n_samples + one.first;
+                    sb.last = sb.n_samples + one.last;
+                }
+                sb.n_samples += one.n_samples;
+                sb.n_zeroed += one.n_zeroed;
+                sb.n_nonfinite += one.n_nonfinite;
+                sb.n_over += one.n_over;
+            }
+            if (irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
             if (r < step) break;
         }
         if (rc == 0 && irdm_frontend_finish_device(fe, d_out, cap, NULL) < 0) rc = 1;
         if (rc) fprintf(stderr, "%s: GPU processing failed\n", file);
         if (band_close(fe, file, fmt, gain, verbose, centre) != 0) rc = 1;
         if (has_suffix_nocase(save_band, ".sigmf-data") && band_write_meta(save_band, fmt, irdm_frontend_out_rate(fe), centre, in->start_ns) != 0) rc = 1;
+        if (g_scrub) scrub_line(&sb, in_fmt, rate);
         if (g_input_stats) {
             irdm_input_stats_t is;
             if (irdm_frontend_input_stats(fe, &is) == 0) input_line(&is, in_fmt);
@@ -884,6 +936,19 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--clock-check")) g_clock = 1;
         else if (!strcmp(a, "--iq-check")) g_iq = 1;
         else if (!strcmp(a, "--swap-iq")) g_swap = 1;
+        else if (!strcmp(a, "--scrub") || !strncmp(a, "--scrub=", 8)) {
+            /* (as --position: only the --scrub=LOG2 form takes a value) */
+            g_scrub = 1;
+            if (a[7] == '=') {
+                char *end;
+                const long v = strtol(a + 8, &end, 10);
+                if (end == a + 8 || *end || v < 0 || v > 127) {
+                    fprintf(stderr, "--scrub=%s: the limit's base-2 logarithm, an integer 0 .. 127\n", a + 8);
+                    return 2;
+                }
+                g_scrub_log2 = (int)v;
+            }
+        }
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -946,7 +1011,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1031,6 +1096,13 @@ int main(int argc, char **argv)
     if (g_swap) {
         if (gpus > 1) {
             fprintf(stderr, "--swap-iq: one GPU only (--gpus %d): a group is fed on the device\n", gpus);
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_scrub) {
+        if (gpus > 1) {
+            fprintf(stderr, "--scrub: one GPU only (--gpus %d): a group is fed on the device\n", gpus);
             return 2;
         }
         gpus = 0;
@@ -1167,11 +1239,18 @@ int main(int argc, char **argv)
         fprintf(stderr, "--swap-iq: the library refused the exchange\n");
         return 1;
     }
+    if (g_scrub && verbose)
+        fprintf(stderr, "--scrub: cf32 samples with a component that is not finite or beyond +-2^%d are zeroed on the GPU; the "
+                        "\"input:\" line describes what is left\n", g_scrub_log2);
+    if (g_scrub && fe && !save_only && irdm_frontend_scrub(fe, 1, g_scrub_log2) != 0) {
+        fprintf(stderr, "--scrub: the library refused the pass\n");
+        return 1;
+    }
     if (save_only) {
         const size_t so_step = resample_to ? (chunk * (size_t)rs_m + (size_t)rs_l - 1) / (size_t)rs_l : chunk * (size_t)decimate;
         if (out_dir && mkdir(out_dir, 0777) != 0 && errno != EEXIST) { perror(out_dir); return 1; }
         const int rc = save_only_run(fe, save_band, out_dir, save_fmt, (float)save_gain, verbose, c.center_frequency, so_step, bps,
-                                     chunk + (size_t)irdm_frontend_ntaps(fe) + 64, fmt);
+                                     chunk + (size_t)irdm_frontend_ntaps(fe) + 64, fmt, rate);
         fflush(stderr);
         _exit(rc);
     }
@@ -1240,6 +1319,10 @@ int main(int argc, char **argv)
     }
     if (g_swap && !fe && irdm_set_option(p, "swap_iq", 1) != 0) {
         fprintf(stderr, "--swap-iq: the library refused the exchange\n");
+        return 1;
+    }
+    if (g_scrub && !fe && (irdm_set_option(p, "scrub_limit_log2", g_scrub_log2) != 0 || irdm_set_option(p, "scrub", 1) != 0)) {
+        fprintf(stderr, "--scrub: the library refused the pass\n");
         return 1;
     }
     g_save_dir = save_dir;
@@ -1435,6 +1518,11 @@ int main(int argc, char **argv)
             irdm_iq_sense_t iq;
             if (irdm_iq_sense(p, &iq) == 0) iq_line(&iq);
             else { fprintf(stderr, "--iq-check: %s: no verdict\n", file); rc = 1; }
+        }
+        if (g_scrub) {
+            irdm_scrub_stats_t sb;
+            if ((fe ? irdm_frontend_scrub_stats(fe, &sb) : irdm_scrub_stats(p, &sb)) == 0) scrub_line(&sb, fmt, rate);
+            else { fprintf(stderr, "--scrub: %s: no figures\n", file); rc = 1; }
         }
         if (g_acars) {
             char st[512];

@@ -220,6 +220,15 @@ class IqSense(C.Structure):
                 ("verdict", C.c_int32), ("pad", C.c_int32)]
 
 
+SCRUB_DEFAULT_LOG2 = 40
+
+
+class ScrubStats(C.Structure):
+    """irdm_scrub_stats_t (option scrub): what the pass has zeroed; first / last are stream positions, valid when n_zeroed > 0"""
+    _fields_ = [("n_samples", C.c_uint64), ("n_zeroed", C.c_uint64), ("n_nonfinite", C.c_uint64), ("n_over", C.c_uint64),
+                ("first", C.c_uint64), ("last", C.c_uint64), ("limit_log2", C.c_int32), ("active", C.c_int32)]
+
+
 class RecordingInfo(C.Structure):
     """irdm_recording_info_t (irdm_recording_probe)"""
     _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
@@ -286,6 +295,9 @@ def lib():
             L.irdm_poll_iq_votes.argtypes = [C.c_void_p, C.POINTER(IqVote), C.c_int]
             L.irdm_iq_sense.argtypes = [C.c_void_p, C.POINTER(IqSense)]
             L.irdm_iq_sense_batch.argtypes = [C.c_void_p, C.POINTER(Demod), C.c_int, C.POINTER(IqVote)]
+        if hasattr(L, "irdm_scrub_device"):
+            L.irdm_scrub_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(ScrubStats), C.c_int, C.c_void_p]
+            L.irdm_scrub_stats.argtypes = [C.c_void_p, C.POINTER(ScrubStats)]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -458,6 +470,9 @@ def lib():
                 L.irdm_frontend_input_stats.argtypes = [C.c_void_p, C.POINTER(InputStats)]
             if hasattr(L, "irdm_frontend_swap_iq"):
                 L.irdm_frontend_swap_iq.argtypes = [C.c_void_p, C.c_int]
+            if hasattr(L, "irdm_frontend_scrub"):
+                L.irdm_frontend_scrub.argtypes = [C.c_void_p, C.c_int, C.c_int]
+                L.irdm_frontend_scrub_stats.argtypes = [C.c_void_p, C.POINTER(ScrubStats)]
             if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
                 L.irdm_frontend_create_rational.restype = C.c_void_p
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
@@ -527,6 +542,16 @@ def swap_iq_device(d_iq, n, fmt, device=0, stream=None):
     """irdm_swap_iq_device: I and Q of the n samples of format fmt at the device address d_iq exchanged in place; returns
     the call's result (0, or -1 for an unknown format or a pointer that is not sample-aligned)"""
     return int(lib().irdm_swap_iq_device(C.c_void_p(d_iq), n, fmt, device, C.c_void_p(stream or 0)))
+
+
+def scrub_device(d_iq, n, fmt, limit_log2=SCRUB_DEFAULT_LOG2, stats=True, device=0, stream=None):
+    """irdm_scrub_device: every cf32 sample of the n at the device address d_iq with a component that is not finite or beyond
+    +-2^limit_log2 zeroed in place.  Returns (rc, ScrubStats with positions relative to the buffer, or None without stats):
+    rc 0, or -1 for an unknown format, a pointer that is not sample-aligned or a limit outside 0 .. 127"""
+    st = ScrubStats() if stats else None
+    rc = int(lib().irdm_scrub_device(C.c_void_p(d_iq), n, fmt, limit_log2, C.byref(st) if stats else None, device,
+                                     C.c_void_p(stream or 0)))
+    return rc, st
 
 
 def host_free(ptr):
@@ -825,6 +850,13 @@ class Pipeline:
             raise RuntimeError("irdm_iq_sense failed (option iq_sense never set?)")
         return st
 
+    def scrub_stats(self):
+        """irdm_scrub_stats (option scrub): the ScrubStats of the stream so far, positions in stream coordinates"""
+        st = ScrubStats()
+        if self.L.irdm_scrub_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_scrub_stats failed (option scrub off?)")
+        return st
+
     def iq_sense_batch(self, demods):
         """irdm_iq_sense_batch: the sense kernel for a list of Demod records (bits, llr, n_bits and direction are read)"""
         n = len(demods)
@@ -1078,6 +1110,19 @@ class Frontend:
         """irdm_frontend_swap_iq: feed_host exchanges I and Q of every capture chunk in front of the kernel"""
         if self.L.irdm_frontend_swap_iq(self.h, 1 if on else 0) != 0:
             raise RuntimeError("irdm_frontend_swap_iq failed")
+
+    def scrub(self, on=True, limit_log2=SCRUB_DEFAULT_LOG2):
+        """irdm_frontend_scrub: feed_host zeroes the non-finite and out-of-range samples of every cf32 capture chunk in
+        front of the kernel"""
+        if self.L.irdm_frontend_scrub(self.h, 1 if on else 0, limit_log2) != 0:
+            raise RuntimeError("irdm_frontend_scrub failed")
+
+    def scrub_stats(self):
+        """irdm_frontend_scrub_stats: the ScrubStats of the capture so far, positions in capture coordinates"""
+        st = ScrubStats()
+        if self.L.irdm_frontend_scrub_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_frontend_scrub_stats failed (never switched on?)")
+        return st
 
     def input_stats_enable(self, on=True):
         """irdm_frontend_input_stats_enable: statistics of the capture's samples in front of the kernel"""
