@@ -396,6 +396,24 @@ typedef struct {
     int32_t  active;                 /* 0 when the format is not cf32: nothing was launched, every figure above is 0 */
 } irdm_scrub_stats_t;
 
+/* option "iq_moments": the second moments of the stream's I and Q and the receiver's I/Q imbalance derived from them
+ * (irdm_iq_moments, irdm_frontend_iq_moments_stats, irdm_iq_moments_device).  The samples are taken as the pipeline's load
+ * stage converts them; every term is formed in binary64, where i, q and their products are exact, so the sums depend on
+ * the order of addition alone.  A cf32 sample with a component that is not finite is left out (n_samples - n_used of them).
+ * Derived on the host in binary64 with N = n_used and the central moments C_ab = sum_ab / N - (sum_a / N)(sum_b / N):
+ *   valid      1 iff N >= 2, C_II > 0, C_QQ > 0 and |C_IQ| < sqrt(C_II C_QQ); otherwise the three figures below are 0
+ *   gain_db    10 log10(C_QQ / C_II): the Q arm's gain over the I arm's (g = sqrt(C_QQ / C_II))
+ *   phase_deg  asin(C_IQ / sqrt(C_II C_QQ)) in degrees: by how much the two arms miss quadrature
+ *   image_db   20 log10(|1 - g e^{j phi}| / |1 + g e^{-j phi}|), not below -120: the level of the image at -f of a signal
+ *              at +f.  The estimator's own floor on 2 M samples of a clean scene is -70 to -82 dB.
+ * A DC offset in either arm does not disturb the figures (the moments are central). */
+typedef struct {
+    uint64_t n_samples, n_used;              /* seen; with both components finite */
+    double   sum_i, sum_q, sum_ii, sum_qq, sum_iq;
+    double   gain_db, phase_deg, image_db;
+    int      valid, reserved;
+} irdm_iq_moments_t;
+
 typedef struct irdm_pipeline irdm_pipeline_t;
 
 /* burst_detector_create + burst_downmix_create (burst_detect.c:174, burst_downmix.c:223):
@@ -752,6 +770,13 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         does not judge what a glitch is -- un-normalised int16-, int24- and int32-scaled floats pass.  A
  *                         caller who wants finite glitches gone picks a lower limit.  -1 outside 0 .. 127, for a member of
  *                         a group, and for a change between a stream's first feed and irdm_reset
+ *   "iq_moments"          0/1, default 0: 1 = every chunk's samples are reduced on the GPU to the sums of irdm_iq_moments_t
+ *                         (one pass on a side stream behind the chunk's arrival, beside K1, where "input_stats" runs its
+ *                         own; device feeds included); irdm_iq_moments returns them with the imbalance derived from them.
+ *                         It measures the stream as processed: behind swap_iq, irdm_iq_balance and scrub.  A side stream,
+ *                         four 128 KiB blocks on the device and in pinned memory are allocated when the option is first
+ *                         set, never before; with 0 nothing is launched.  irdm_reset starts the sums over.  -1 for a
+ *                         member of a group and while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
  *   "decode_frames" / "decode_ida"  0/1, default 0: the post-demod bit layer, see irdm_poll_decoded / irdm_poll_ida
  *   "detect_only"         0/1, default 0: 1 = stage A alone (burst_detector_feed's role): burst records only
  *   "fir_order" (alias "simd_order")   default 1 = the arithmetic of the reference's AVX2 kernels, simd_avx2.c -- what
@@ -1177,6 +1202,47 @@ int irdm_scrub_device(void *d_iq, size_t n_samples, int format, int limit_log2, 
 int irdm_scrub_stats(irdm_pipeline_t *p, irdm_scrub_stats_t *out);
 int irdm_frontend_scrub(irdm_frontend_t *fe, int on, int limit_log2);
 int irdm_frontend_scrub_stats(irdm_frontend_t *fe, irdm_scrub_stats_t *out);
+
+/* ---- receiver I/Q imbalance: the measurement (irdm_iq_moments_t above) and the correction ----
+ * A zero-IF receiver whose arms differ in gain (g) and are not exactly 90 degrees apart (phi) delivers
+ *   y_I = x_I,  y_Q = g (x_Q cos phi + x_I sin phi):  every signal at +f leaves an image at -f, image_db down.  The image
+ * of a burst is its conjugate, which the demodulator accepts (see "Exchanged I and Q" in the README).
+ * irdm_iq_moments: option "iq_moments" -- the sums of the stream so far and the figures derived from them; waits for the
+ *   passes in flight.  NOT part of irdm_export_state / irdm_import_state.  Returns 0, or -1 (the option never set included).
+ * irdm_iq_moments_device: the pass alone over the n samples of `format` at d_iq (aligned to a sample), complete on
+ *   return; on `stream` (a hipStream_t) or, with NULL, on a stream of the call's own.  Launches of at most 2^31 samples.
+ *   n == 0 launches nothing and returns 0 with valid 0.  -1 for an unknown format, a misaligned pointer, a failed launch.
+ *   out == NULL (with a stream): the launches alone on `stream`, without waiting and without figures -- for timing.
+ * irdm_frontend_iq_moments / irdm_frontend_iq_moments_stats: the same for a front end, over the capture in front of
+ *   K0 / K0r (behind irdm_frontend_swap_iq, irdm_frontend_iq_balance and irdm_frontend_scrub); the image mirrors about the
+ *   capture's centre.  irdm_frontend_reset starts the sums over.
+ *
+ * irdm_iq_balance_coeffs (host only): alpha = -tan(phi), beta = 1 / (g cos(phi)) with g = 10^(gain_db / 20), computed in
+ *   binary64 and rounded once to float.  -1 outside |gain_db| <= 6, |phase_deg| <= 30.  Either pointer may be NULL.
+ * irdm_iq_balance_device: the n samples of `format` at d_in (aligned to a sample) become cf32 at d_out_cf32 (aligned to 8
+ *   bytes): i' = i, q' = alpha i + beta q -- two rounded binary32 products and one rounded sum, never fused; i, q as the
+ *   load stage converts them.  d_out_cf32 == d_in is allowed for the 8-byte formats (in place); any other overlap, an
+ *   unknown format, a misaligned pointer and coefficients outside what irdm_iq_balance_coeffs can return give -1.  On
+ *   `stream` without waiting, or with NULL on a stream of the call's own, complete on return.
+ * irdm_iq_balance: for a context created as IRDM_FMT_CF32, before its first feed.  From then on irdm_feed_host takes
+ *   n_samples of wire_format (any IRDM_FMT_*): the host-to-device copy lands in a wire staging buffer (max_chunk samples
+ *   of the wire format, allocated by this call; none for a cf32 wire format, which lands where it lands today and is
+ *   corrected in place), option "swap_iq" exchanges the components there, the kernel above writes the ring slot or the
+ *   staging buffer, and "scrub" and everything else follow on cf32.  A context so set, fed F's bytes, yields bit for bit
+ *   every record of a plain cf32 context fed the corrected samples.  The setting survives irdm_reset.  With it on
+ *   irdm_feed_device / irdm_feed_begin return -1 with a line on stderr -- correct the buffer with irdm_iq_balance_device
+ *   first.  -1 after the stream's first feed, for a context of another format, for a member of a group, for an unknown
+ *   wire format and for figures outside the limits.
+ * irdm_frontend_iq_balance: the same for a front end created with in_format cf32; irdm_frontend_feed_host then takes
+ *   wire_format's bytes and the kernel writes the capture staging buffer. */
+int irdm_iq_moments(irdm_pipeline_t *p, irdm_iq_moments_t *out);
+int irdm_iq_moments_device(const void *d_iq, size_t n, int format, irdm_iq_moments_t *out, int device, void *stream);
+int irdm_frontend_iq_moments(irdm_frontend_t *fe, int on);
+int irdm_frontend_iq_moments_stats(irdm_frontend_t *fe, irdm_iq_moments_t *out);
+int irdm_iq_balance_coeffs(double gain_db, double phase_deg, float *alpha, float *beta);
+int irdm_iq_balance_device(void *d_out_cf32, const void *d_in, size_t n, int format, float alpha, float beta, int device, void *stream);
+int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_db, double phase_deg);
+int irdm_frontend_iq_balance(irdm_frontend_t *fe, int wire_format, double gain_db, double phase_deg);
 
 /* ---- self-describing recordings: WAV / RF64, SigMF, SDRangel .sdriq (csrc/recording.cpp) ----
  * Host code only, no device call: works without a GPU.  irdm_recording_probe reads the header of `path` and says what the

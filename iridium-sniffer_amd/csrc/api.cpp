@@ -59,6 +59,11 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         p->scrub.limit_log2 = value;
         return 0;
     }
+    if (!strcmp(key, "iq_moments")) {
+        // 0 / 1; as "input_stats"
+        if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
+        return iq_moments_configure(p, value);
+    }
     if (!strcmp(key, "decode_frames")) { p->decode_frames = value; return 0; }
     if (!strcmp(key, "decode_ida")) { p->decode_ida = value; return 0; }
     if (!strcmp(key, "detect_only")) { p->detect_only = value; return 0; }

@@ -1,5 +1,6 @@
 // feed.cpp -- the feeding calls (irdm_feed_begin / _end / _device / _host, irdm_flush, irdm_advance), irdm_reset, the polls, and the
 // buffer helpers for hosts without HIP headers.
+#include <mutex>
 #include "pipeline.hpp"
 
 namespace irdmh {
@@ -284,6 +285,7 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
     if (p->stream != p->fstream) IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
     if (p->stream_spec) IRDM_HIP_CHECK(hipStreamSynchronize(p->stream_spec));
     if (p->in_stats.stream) IRDM_HIP_CHECK(hipStreamSynchronize(p->in_stats.stream));   // (its totals go with the stream state)
+    if (p->iqm.stream) IRDM_HIP_CHECK(hipStreamSynchronize(p->iqm.stream));             // (likewise)
     for (int i = 0; i < p->n_bc; i++) {
         BatchCtx &b = p->bc[i];
         IRDM_HIP_CHECK(hipStreamSynchronize(b.stream));
@@ -339,6 +341,11 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
                         "as it is -- scrub it with irdm_scrub_device first\n");
         return -1;
     }
+    if (p->bal.on && !p->feed_inner) {
+        fprintf(stderr, "irdm_hip: irdm_iq_balance corrects the chunks of irdm_feed_host only: a device feed takes the caller's "
+                        "buffer as it is -- correct it with irdm_iq_balance_device first\n");
+        return -1;
+    }
     if (p->st.begin_no - p->st.end_no > (p->depth ? kLookAhead : 0u)) return -1;    // two chunks of look-ahead, pipeline_depth >= 1 only
     if (p->st.stream_closed) {
         fprintf(stderr, "irdm_hip: stream already ended by a chunk that was not a multiple of feed_block\n");
@@ -368,6 +375,8 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     if (p->in_stats.on &&
         input_stats_enqueue(p->in_stats, p->st.in_stats, p->dev_fmt, d_iq, n_samples, caller, p->st.begin_no) != 0)
         return -1;
+    // option "iq_moments": likewise, on a side stream of its own
+    if (p->iqm.on && iq_moments_enqueue(p->iqm, p->st.iqm, p->dev_fmt, d_iq, n_samples, caller, p->st.begin_no) != 0) return -1;
 
     // K1 of this chunk.  pipeline_depth 1: on its own stream and into the other magnitude buffer, while the detector
     // scan of the previous chunk may still be running
@@ -511,6 +520,7 @@ extern "C" int irdm_feed_end(irdm_pipeline_t *p)
     if (!p->st.in_stats.pending.empty() &&
         input_stats_settle(p->in_stats, p->st.in_stats, p->dev_fmt, p->st.end_no) != 0)
         return -1;
+    if (!p->st.iqm.pending.empty() && iq_moments_settle(p->iqm, p->st.iqm, p->st.end_no) != 0) return -1;
     p->st.chunk_no++;
     p->st.end_no++;
     p->st.total_samples = c1;
@@ -596,10 +606,16 @@ extern "C" int irdm_device_copy(void *dst, const void *src, size_t bytes)
 
 // a chunk of irdm_feed_host where its copy lands it on fstream (the ring slot of irdm_ingest_ptr or d_stage): option
 // "swap_iq" exchanges its components there, behind the copy and in front of everything that reads the chunk; option
-// "scrub" then zeroes its non-finite and out-of-range samples (cf32 alone: the other formats hold none)
-static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples)
+// "scrub" then zeroes its non-finite and out-of-range samples (cf32 alone: the other formats hold none).  With
+// irdm_iq_balance the chunk has arrived at d_wire in the wire format (nullptr: cf32, at d_iq itself): the exchange happens
+// there, and the correction writes d_iq between the two.
+static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples, void *d_wire = nullptr)
 {
-    if (p->swap_iq && launch_iq_swap(p->dev_fmt, d_iq, n_samples, p->fstream) != 0) return -1;
+    if (p->bal.on) {
+        void *src = d_wire ? d_wire : d_iq;
+        if (p->swap_iq && launch_iq_swap(p->bal.wire_fmt, src, n_samples, p->fstream) != 0) return -1;
+        if (launch_iq_balance(p->bal.wire_fmt, d_iq, src, n_samples, p->bal.alpha, p->bal.beta, p->fstream) != 0) return -1;
+    } else if (p->swap_iq && launch_iq_swap(p->dev_fmt, d_iq, n_samples, p->fstream) != 0) return -1;
     if (p->scrub.on && p->dev_fmt == IRDM_FMT_CF32 &&
         scrub_enqueue(p->scrub, p->st.scrub, d_iq, n_samples, p->st.begun_samples, p->fstream) != 0)
         return -1;
@@ -616,9 +632,13 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     pipeline_enter(p);
     // throughput mode: the H2D copy lands in the chunk's slot of the history ring and the chunk is fed in place (no staging
     // buffer, no device-to-device copy behind K1)
+    // irdm_iq_balance with a wire format other than cf32: the bytes land in the wire staging buffer (the previous chunk's
+    // correction, which read it, lies in front of the copy on the same stream)
+    void *wire = p->bal.on && p->bal.wire_fmt != IRDM_FMT_CF32 ? p->bal.d_wire : nullptr;
+    const size_t wire_bytes = n_samples * (size_t)(p->bal.on ? fmt_bytes(p->bal.wire_fmt) : p->bps);
     if (void *slot = irdm_ingest_ptr(p, n_samples)) {
-        IRDM_HIP_CHECK(hipMemcpyAsync(slot, h_iq, n_samples * p->bps, hipMemcpyHostToDevice, p->fstream));
-        return feed_host_arrived(p, slot, n_samples);
+        IRDM_HIP_CHECK(hipMemcpyAsync(wire ? wire : slot, h_iq, wire_bytes, hipMemcpyHostToDevice, p->fstream));
+        return feed_host_arrived(p, slot, n_samples, wire);
     }
     if (!p->d_stage) {
         if (hipMalloc(&p->d_stage, p->max_chunk * p->bps) != hipSuccess) return -1;
@@ -627,8 +647,8 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     // The copy goes on K1's stream, never the null stream: with pipeline_depth 1 the previous chunk's detector scan is
     // still running and must not be waited for.  irdm_feed_device returns only after K1 and the history-ring copy of
     // its chunk are done, so one staging buffer is enough.
-    IRDM_HIP_CHECK(hipMemcpyAsync(p->d_stage, h_iq, n_samples * p->bps, hipMemcpyHostToDevice, p->fstream));
-    return feed_host_arrived(p, p->d_stage, n_samples);
+    IRDM_HIP_CHECK(hipMemcpyAsync(wire ? wire : p->d_stage, h_iq, wire_bytes, hipMemcpyHostToDevice, p->fstream));
+    return feed_host_arrived(p, p->d_stage, n_samples, wire);
 }
 
 // irdm_swap_iq_device: the exchange alone, on a buffer the caller owns (iq_swap.hpp)
@@ -648,6 +668,123 @@ extern "C" int irdm_swap_iq_device(void *d_iq, size_t n_samples, int format, int
         (void)hipStreamDestroy(own);
     }
     return rc;
+}
+
+// ---- option "iq_moments" (iq_moments.hpp) and irdm_iq_balance (iq_balance.hpp) ----
+int iq_moments_configure(irdm_pipeline *p, int on)
+{
+    if (on && iq_moments_pass_alloc(p->iqm) != 0) return -1;
+    p->iqm.on = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_iq_moments(irdm_pipeline_t *p, irdm_iq_moments_t *out)
+{
+    if (!p || !out || !p->iqm.stream) return -1;
+    pipeline_enter(p);
+    if (iq_moments_settle(p->iqm, p->st.iqm, ~0ull) != 0) return -1;
+    iq_moments_result(p->st.iqm.run, out);
+    return 0;
+}
+
+extern "C" int irdm_iq_moments_device(const void *d_in, size_t n, int format, irdm_iq_moments_t *out, int device, void *stream_v)
+{
+    if ((!d_in && n) || !fmt_valid(format) || (reinterpret_cast<uintptr_t>(d_in) % (size_t)fmt_bytes(format)) != 0) return -1;
+    if (!out && !stream_v) return -1;
+    IqmRun run;
+    if (n == 0) {
+        if (out) iq_moments_result(run, out);
+        return 0;
+    }
+    IRDM_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
+    if (!out) {
+        // the launches alone, on the caller's stream without waiting (for timing the kernel): the rows go to a block that
+        // is never read, one per device for the life of the process
+        static std::mutex mu;
+        static void *d_unread[64] = {};
+        if (device < 0 || device >= 64) return -1;
+        {
+            std::lock_guard<std::mutex> lock(mu);
+            if (!d_unread[device] && hipMalloc(&d_unread[device], kImBlockBytes) != hipSuccess) return -1;
+        }
+        const size_t bps0 = (size_t)fmt_bytes(format);
+        for (size_t off = 0; off < n; off += kImMaxLaunch)
+            if (launch_iq_moments(format, static_cast<const char *>(d_in) + off * bps0, std::min(kImMaxLaunch, n - off), d_unread[device], s) < 0)
+                return -1;
+        return 0;
+    }
+    void *d_block = nullptr;
+    std::vector<unsigned char> h(kImBlockBytes);
+    int rc = 0;
+    if (!s) {
+        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
+        s = own;
+    }
+    if (hipMalloc(&d_block, kImBlockBytes) != hipSuccess) rc = -1;
+    const size_t bps = (size_t)fmt_bytes(format);
+    for (size_t off = 0; rc == 0 && off < n; off += kImMaxLaunch) {
+        const size_t piece = std::min(kImMaxLaunch, n - off);
+        const int grid = launch_iq_moments(format, static_cast<const char *>(d_in) + off * bps, piece, d_block, s);
+        if (grid < 0 || hipMemcpyAsync(h.data(), d_block, sizeof(IqmRow) * (size_t)grid, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess) {
+            rc = -1;
+            break;
+        }
+        iq_moments_fold(run, h.data(), grid, piece);
+    }
+    if (d_block) (void)hipFree(d_block);
+    if (own) (void)hipStreamDestroy(own);
+    if (rc == 0) iq_moments_result(run, out);
+    return rc;
+}
+
+extern "C" int irdm_iq_balance_coeffs(double gain_db, double phase_deg, float *alpha, float *beta)
+{
+    return iq_balance_coeffs(gain_db, phase_deg, alpha, beta);
+}
+
+extern "C" int irdm_iq_balance_device(void *d_out, const void *d_in, size_t n, int format, float alpha, float beta, int device,
+                                      void *stream_v)
+{
+    if (((!d_in || !d_out) && n) || !fmt_valid(format)) return -1;
+    if (n == 0) return launch_iq_balance(format, d_out, d_in, 0, alpha, beta, nullptr);     // (the checks alone)
+    IRDM_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
+    if (!s) {
+        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
+        s = own;
+    }
+    int rc = launch_iq_balance(format, d_out, d_in, n, alpha, beta, s);
+    if (own) {
+        if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
+        (void)hipStreamDestroy(own);
+    }
+    return rc;
+}
+
+extern "C" int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_db, double phase_deg)
+{
+    // a cf32 context, not a member of a group (it is fed on the device), and only before the stream's first feed: the ring
+    // would hold corrected and uncorrected samples
+    if (!p || p->dev_fmt != IRDM_FMT_CF32 || p->in_group || p->st.begin_no != 0 || !fmt_valid(wire_format)) return -1;
+    float alpha, beta;
+    if (iq_balance_coeffs(gain_db, phase_deg, &alpha, &beta) != 0) return -1;
+    pipeline_enter(p);
+    const size_t need = wire_format == IRDM_FMT_CF32 ? 0 : p->max_chunk * (size_t)fmt_bytes(wire_format);
+    if (need > p->bal.wire_bytes) {
+        IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
+        if (p->bal.d_wire) (void)hipFree(p->bal.d_wire);
+        p->bal.d_wire = nullptr;
+        p->bal.wire_bytes = 0;
+        if (hipMalloc(&p->bal.d_wire, need) != hipSuccess) return -1;
+        p->bal.wire_bytes = need;
+    }
+    p->bal.on = 1;
+    p->bal.wire_fmt = wire_format;
+    p->bal.alpha = alpha;
+    p->bal.beta = beta;
+    return 0;
 }
 
 // ---- option "scrub" (scrub.hpp): the blocks of the passes, when the option is first set on a cf32 context ----

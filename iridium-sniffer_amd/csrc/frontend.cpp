@@ -37,6 +37,8 @@ void fe_free(irdm_frontend *fe)
     fe_save_off(fe);
     input_stats_pass_free(fe->is);
     scrub_pass_free(fe->scrub);
+    iq_moments_pass_free(fe->iqm);
+    if (fe->bal.d_wire) (void)hipFree(fe->bal.d_wire);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
@@ -272,6 +274,7 @@ static int fe_commit(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream
 // the pass over the chunk that has arrived on s, on the side stream
 static int fe_stats_enqueue(irdm_frontend *fe, const void *d_in, size_t n_in, hipStream_t s)
 {
+    if (fe->iqm.on && n_in && iq_moments_enqueue(fe->iqm, fe->st.iqm, fe->fmt, d_in, n_in, s, fe->st.iqm.launches) != 0) return -1;
     if (!fe->is.on || !n_in) return 0;
     return input_stats_enqueue(fe->is, fe->st.is, fe->fmt, d_in, n_in, s, fe->st.is.launches);
 }
@@ -279,6 +282,7 @@ static int fe_stats_enqueue(irdm_frontend *fe, const void *d_in, size_t n_in, hi
 // s goes on behind that pass: what s records or runs next may hand the chunk's memory back
 static int fe_stats_join(irdm_frontend *fe, size_t n_in, hipStream_t s)
 {
+    if (fe->iqm.on && n_in && fe->st.iqm.last_slot >= 0) IRDM_HIP_CHECK(hipStreamWaitEvent(s, fe->iqm.ev[fe->st.iqm.last_slot], 0));
     if (!fe->is.on || !n_in || fe->st.is.last_slot < 0) return 0;
     IRDM_HIP_CHECK(hipStreamWaitEvent(s, fe->is.ev[fe->st.is.last_slot], 0));
     return 0;
@@ -299,6 +303,46 @@ extern "C" int irdm_frontend_input_stats(irdm_frontend_t *fe, irdm_input_stats_t
     (void)hipSetDevice(fe->cfg.device);
     if (input_stats_settle(fe->is, fe->st.is, fe->fmt, ~0ull) != 0) return -1;
     input_stats_result(fe->st.is.run, fe->fmt, out);
+    return 0;
+}
+
+extern "C" int irdm_frontend_iq_moments(irdm_frontend_t *fe, int on)
+{
+    if (!fe) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (on && iq_moments_pass_alloc(fe->iqm) != 0) return -1;
+    fe->iqm.on = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_frontend_iq_moments_stats(irdm_frontend_t *fe, irdm_iq_moments_t *out)
+{
+    if (!fe || !out || !fe->iqm.stream) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (iq_moments_settle(fe->iqm, fe->st.iqm, ~0ull) != 0) return -1;
+    iq_moments_result(fe->st.iqm.run, out);
+    return 0;
+}
+
+// irdm_frontend_iq_balance is on and the caller hands over a device buffer of its own: refused, with the remedy
+static bool fe_balance_refuses(const irdm_frontend *fe)
+{
+    if (!fe->bal.on || fe->feed_inner) return false;
+    fprintf(stderr, "irdm_hip: front end: irdm_frontend_iq_balance corrects the chunks of irdm_frontend_feed_host only: a device "
+                    "feed takes the caller's buffer as it is -- correct it with irdm_iq_balance_device first\n");
+    return true;
+}
+
+extern "C" int irdm_frontend_iq_balance(irdm_frontend_t *fe, int wire_format, double gain_db, double phase_deg)
+{
+    // a cf32 front end, and only before the capture's first chunk: the carried tail would hold uncorrected samples
+    if (!fe || fe->fmt != IRDM_FMT_CF32 || fe->st.total != 0 || !fmt_valid(wire_format)) return -1;
+    float alpha, beta;
+    if (iq_balance_coeffs(gain_db, phase_deg, &alpha, &beta) != 0) return -1;
+    fe->bal.on = 1;
+    fe->bal.wire_fmt = wire_format;
+    fe->bal.alpha = alpha;
+    fe->bal.beta = beta;
     return 0;
 }
 
@@ -352,7 +396,7 @@ extern "C" int irdm_frontend_scrub_stats(irdm_frontend_t *fe, irdm_scrub_stats_t
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
-    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe) || fe_scrub_refuses(fe)) return -1;
+    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe)) return -1;
     const uint64_t m1 = fe_outputs(fe, fe->st.total + n_in, false);
     const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
@@ -449,7 +493,7 @@ static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
 
 extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream_v)
 {
-    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe) || fe_scrub_refuses(fe)) return -1;
+    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe)) return -1;
     pipeline_enter(p);
     if (stream_v && static_cast<hipStream_t>(stream_v) != fe->stream) {
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
@@ -478,10 +522,24 @@ extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, 
         fe->stage_bytes = bytes;
     }
     // (one staging buffer: the copy is ordered behind the kernels that read the previous chunk, on the same stream)
-    if (bytes) IRDM_HIP_CHECK(hipMemcpyAsync(fe->d_stage, h_in, bytes, hipMemcpyHostToDevice, fe->stream));
+    // irdm_frontend_iq_balance: the caller's bytes are the wire format's; other than cf32 they land in the wire staging buffer
+    const bool wired = fe->bal.on && fe->bal.wire_fmt != IRDM_FMT_CF32;
+    const size_t wire_bytes = wired ? n_in * (size_t)fmt_bytes(fe->bal.wire_fmt) : bytes;
+    if (wired && wire_bytes > fe->bal.wire_bytes) {
+        IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+        if (fe->bal.d_wire) (void)hipFree(fe->bal.d_wire);
+        fe->bal.d_wire = nullptr;
+        fe->bal.wire_bytes = 0;
+        IRDM_HIP_CHECK(hipMalloc(&fe->bal.d_wire, wire_bytes));
+        fe->bal.wire_bytes = wire_bytes;
+    }
+    void *const land = wired ? fe->bal.d_wire : fe->d_stage;
+    if (bytes) IRDM_HIP_CHECK(hipMemcpyAsync(land, h_in, wire_bytes, hipMemcpyHostToDevice, fe->stream));
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
     // irdm_frontend_swap_iq: the capture's components exchanged where it landed, in front of the statistics pass and K0 / K0r
-    if (fe->swap_iq && launch_iq_swap(fe->fmt, fe->d_stage, n_in, fe->stream) != 0) return -1;
+    if (fe->swap_iq && launch_iq_swap(fe->bal.on ? fe->bal.wire_fmt : fe->fmt, land, n_in, fe->stream) != 0) return -1;
+    // irdm_frontend_iq_balance: then corrected into the cf32 staging buffer (a cf32 wire format: in place)
+    if (fe->bal.on && launch_iq_balance(fe->bal.wire_fmt, fe->d_stage, land, n_in, fe->bal.alpha, fe->bal.beta, fe->stream) != 0) return -1;
     // irdm_frontend_scrub: then its non-finite and out-of-range samples zeroed (cf32 alone), positions counted in the capture
     if (fe->scrub.on && fe->fmt == IRDM_FMT_CF32 &&
         scrub_enqueue(fe->scrub, fe->st.scrub, fe->d_stage, n_in, fe->st.total, fe->stream) != 0)
@@ -517,6 +575,7 @@ extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
     if (fe->sv.copy) IRDM_HIP_CHECK(hipStreamSynchronize(fe->sv.copy));
     if (fe->sv.d_stats) IRDM_HIP_CHECK(hipMemset(fe->sv.d_stats, 0, 3 * sizeof(unsigned long long)));
     if (fe->is.stream) IRDM_HIP_CHECK(hipStreamSynchronize(fe->is.stream));       // (the passes in flight are dropped with the state)
+    if (fe->iqm.stream) IRDM_HIP_CHECK(hipStreamSynchronize(fe->iqm.stream));
     fe->st = irdm_frontend::State{};
     return 0;
 }

@@ -37,6 +37,8 @@ struct irdm_frontend {
         irdm::InputStatsStream is;
         // irdm_frontend_scrub: the totals of the pass and the launches whose figures are on their way (scrub.hpp)
         irdm::ScrubStream scrub;
+        // irdm_frontend_iq_moments: the sums of the capture and the passes in flight (iq_moments.hpp)
+        irdm::IqMomentsStream iqm;
     } st;
     // Saving the band (irdm_frontend_save; off: sink == nullptr and nothing below exists).  fe_emit requantises what its
     // kernel wrote in pieces of at most slot_samples, each into one of two slots: device staging d[i] copied to the pinned
@@ -63,6 +65,11 @@ struct irdm_frontend {
     // irdm_frontend_scrub: irdm_frontend_feed_host zeroes the non-finite and out-of-range samples of every cf32 capture
     // chunk in its staging buffer (scrub.on, scrub.limit_log2: configuration; the blocks: cache)
     irdm::ScrubPass scrub;
+    // irdm_frontend_iq_moments: the pass over the capture's samples in front of the kernel (cache; iqm.on the switch)
+    irdm::IqMomentsPass iqm;
+    // irdm_frontend_iq_balance: irdm_frontend_feed_host takes the wire format's bytes and corrects them into the cf32
+    // staging buffer (configuration; the wire staging buffer: cache, grown as d_stage is)
+    irdm::IqBalance bal;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

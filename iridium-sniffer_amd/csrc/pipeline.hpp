@@ -40,6 +40,8 @@
 #include "symbol_clock.hpp"
 #include "iq_swap.hpp"
 #include "scrub.hpp"
+#include "iq_moments.hpp"
+#include "iq_balance.hpp"
 #include "iq_sense.hpp"
 
 using namespace irdm;
@@ -240,6 +242,8 @@ struct StreamState {
     IqSenseStream iq;
     // option "scrub": the totals of the pass and the launches whose figures are still on their way (scrub.hpp)
     ScrubStream scrub;
+    // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)
+    IqMomentsStream iqm;
 };
 
 struct irdm_pipeline {
@@ -445,6 +449,12 @@ struct irdm_pipeline {
     // samples of every cf32 chunk on the device; scrub.on and scrub.limit_log2 are configuration, the blocks cache
     // (allocated when the option is first set on a cf32 context)
     ScrubPass scrub;
+    // option "iq_moments" (feed.cpp, iq_moments.hpp): the pass over every chunk on its side stream (iqm.on: configuration;
+    // the stream and the blocks: cache, allocated when the option is first set)
+    IqMomentsPass iqm;
+    // irdm_iq_balance (feed.cpp, iq_balance.hpp): irdm_feed_host takes the wire format's bytes and corrects them into cf32
+    // (configuration; the wire staging buffer: cache)
+    IqBalance bal;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -495,6 +505,7 @@ int input_stats_configure(irdm_pipeline *p, int on);
 int symbol_clock_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
 int scrub_configure(irdm_pipeline *p, int on);
+int iq_moments_configure(irdm_pipeline *p, int on);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

@@ -11,6 +11,7 @@
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
  *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]]
+ *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -117,6 +118,26 @@
  * when that many were zeroed.  A recording of another format gets "scrub: ci16 samples are always finite; nothing to do".
  * stdout and the rest of stderr of a run over a clean file are those of the run without the flag.  --diagnostic does not
  * imply it.  Refused with --gpus N > 1.
+ * --image-check: the receiver's I/Q imbalance (option "iq_moments", irdm_frontend_iq_moments: the second moments of every
+ * sample of the stream as processed, reduced on the GPU).  A zero-IF receiver whose arms differ in gain and miss quadrature
+ * leaves an image at -f of every signal at +f; the image of a strong burst is its conjugate, which the demodulator accepts
+ * and prints as a RAW line with a mirrored frequency and a garbage payload.  One closing line per recording on stderr,
+ * behind "iq:" and in front of "scrub:" and "input:":
+ *     image: N samples; Q/I gain +0.999 dB, phase +4.99 deg: image at -22.8 dB; 10 of 24 frames are images of a stronger frame -- receiver I/Q imbalance: run with --iq-balance=0.999,4.99
+ *     image: N samples; Q/I gain +0.000 dB, phase +0.00 deg: image below -60 dB; 0 of 12 frames are images
+ *     image: 0 samples; nothing to judge
+ * The clause behind "are images" appears when the image lies at -40 dB or above or any frame is an image; with
+ * --iq-balance in effect it ends "with --iq-balance in effect: adjust it".  A frame j is an image when some frame i
+ * lies within 1 ms of it, mirrors it about the capture's centre (-c) within 500 Hz (|f_i + f_j - 2 c| <= 500) and is at
+ * least 10 dB stronger; the count is made on the host over all frames of the recording, whatever --chunk and --depth.
+ * stdout and the rest of stderr are those of the run without the flag.  --diagnostic does not imply it.  Refused with
+ * --gpus N > 1 and with --save-only.
+ * --iq-balance=GAIN_DB,PHASE_DEG (this form only; |GAIN_DB| <= 6, |PHASE_DEG| <= 30): every sample of every recording of
+ * the run is corrected on the GPU where it arrives, q' = alpha i + beta q with alpha = -tan(phase), beta = 1 / (gain
+ * cos(phase)) (irdm_iq_balance, irdm_frontend_iq_balance, irdm_iq_balance_device): the context or the front end is
+ * created as cf32 and takes the file's format as its wire format.  Raw file or container; allowed with --save-only /
+ * --save-band, which then write the corrected band.  -v names the option and alpha, beta once.  Every closing line then
+ * describes the stream as processed, which is cf32.  Refused with --gpus N > 1.
  */
 #include <err.h>
 #include <errno.h>
@@ -301,6 +322,13 @@ static int g_clock;
 static int g_iq, g_swap;
 /* --scrub[=LOG2] */
 static int g_scrub, g_scrub_log2 = IRDM_SCRUB_DEFAULT_LOG2;
+/* --image-check, --iq-balance=G,P */
+static int g_image, g_bal;
+static double g_bal_gain, g_bal_phase;
+/* --image-check: time, frequency and magnitude of every frame of the recording whose unique word was accepted */
+typedef struct { uint64_t t; double f; float mag; } img_frame_t;
+static img_frame_t *g_img;
+static size_t g_n_img, g_cap_img;
 static unsigned long long g_n_demods;       /* frames the demodulator accepted, this recording */
 
 static const char *format_name(int fmt)
@@ -396,6 +424,65 @@ static void scrub_line(const irdm_scrub_stats_t *st, int fmt, double rate)
     fprintf(stderr, "\n");
 }
 
+static void image_note(uint64_t t, double f, float mag, int ok)
+{
+    if (!ok) return;
+    if (g_n_img == g_cap_img) {
+        g_cap_img = g_cap_img ? 2 * g_cap_img : 4096;
+        g_img = realloc(g_img, g_cap_img * sizeof(*g_img));
+        if (!g_img) { fprintf(stderr, "--image-check: out of memory\n"); exit(1); }
+    }
+    g_img[g_n_img].t = t;
+    g_img[g_n_img].f = f;
+    g_img[g_n_img].mag = mag;
+    g_n_img++;
+}
+
+static int image_by_time(const void *a, const void *b)
+{
+    const img_frame_t *x = a, *y = b;
+    if (x->t != y->t) return x->t < y->t ? -1 : 1;
+    return x->f < y->f ? -1 : (x->f > y->f ? 1 : 0);
+}
+
+/* frames that are images of a stronger frame: |t_i - t_j| <= 1 ms, |f_i + f_j - 2 c| <= 500 Hz, mag_j <= mag_i - 10 dB.  Over
+ * all frames of the recording, sorted by time: the count does not depend on how the stream was cut or queued. */
+static size_t image_count(double centre)
+{
+    size_t images = 0;
+    qsort(g_img, g_n_img, sizeof(*g_img), image_by_time);
+    for (size_t j = 0, lo = 0; j < g_n_img; j++) {
+        while (g_img[j].t - g_img[lo].t > 1000000u) lo++;
+        for (size_t i = lo; i < g_n_img && g_img[i].t <= g_img[j].t + 1000000u; i++)
+            if (fabs(g_img[i].f + g_img[j].f - 2.0 * centre) <= 500.0 && g_img[j].mag <= g_img[i].mag - 10.0f) { images++; break; }
+    }
+    return images;
+}
+
+/* the closing "image:" line of a recording */
+static void image_line(const irdm_iq_moments_t *m, double centre)
+{
+    const size_t images = image_count(centre);
+    if (!m->n_samples) {
+        fprintf(stderr, "image: 0 samples; nothing to judge\n");
+        return;
+    }
+    if (!m->valid) {
+        fprintf(stderr, "image: %llu samples; no variance in I or Q; nothing to judge\n", (unsigned long long)m->n_samples);
+        return;
+    }
+    fprintf(stderr, "image: %llu samples; Q/I gain %+.3f dB, phase %+.2f deg: ", (unsigned long long)m->n_samples, m->gain_db, m->phase_deg);
+    if (m->image_db >= -60.0) fprintf(stderr, "image at %.1f dB", m->image_db);
+    else fprintf(stderr, "image below -60 dB");
+    fprintf(stderr, "; %zu of %zu frames are images", images, g_n_img);
+    if (m->image_db >= -40.0 || images) {
+        fprintf(stderr, " of a stronger frame -- receiver I/Q imbalance: ");
+        if (g_bal) fprintf(stderr, "with --iq-balance in effect: adjust it");
+        else fprintf(stderr, "run with --iq-balance=%.3f,%.2f", m->gain_db, m->phase_deg);
+    }
+    fprintf(stderr, "\n");
+}
+
 /* --diagnostic: the reference's closing status line (main.c:444-480) over the recording's stream time */
 static void diagnostic_line(double elapsed, unsigned long det, unsigned long sub, float noise_floor, float peak_signal)
 {
@@ -440,6 +527,8 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         while ((n = irdm_poll_demods_packed(p, dp, 256)) > 0) {
             long long len;
             g_n_demods += (unsigned long long)n;
+            if (g_image)
+                for (int i = 0; i < n; i++) image_note(dp[i].timestamp, dp[i].center_frequency, dp[i].magnitude, dp[i].ok);
             if (g_dop) {
                 /* one compact frame_decode() record per compact frame record, decoded on the GPU (option frame_records) */
                 if (irdm_poll_frame_packed(p, fp, n) != n) { fprintf(stderr, "--position: frame records out of step\n"); exit(1); }
@@ -476,6 +565,8 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
     while ((n = irdm_poll_demods(p, d, 256)) > 0) {
         long long len = 0;
         g_n_demods += (unsigned long long)n;
+        if (g_image)
+            for (int i = 0; i < n; i++) image_note(d[i].timestamp, d[i].center_frequency, d[i].magnitude, d[i].ok);
         if (g_dop) {
             /* the full-record path (--save-bursts): option decode_frames, one irdm_decoded_t per frame record */
             if (irdm_poll_decoded(p, dec, n) != n) { fprintf(stderr, "--position: frame records out of step\n"); exit(1); }
@@ -760,8 +851,13 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
                          double centre, size_t step, size_t bps, size_t cap, int in_fmt, double rate)
 {
     void *h_in = irdm_host_alloc(step * bps), *d_in = irdm_device_alloc(0, step * bps), *d_out = irdm_device_alloc(0, cap * 8);
+    /* --iq-balance: the front end is a cf32 one; every read is corrected into d_bal (a cf32 file: in place) */
+    const int fe_fmt = g_bal ? IRDM_FMT_CF32 : in_fmt;
+    void *d_bal = g_bal && in_fmt != IRDM_FMT_CF32 ? irdm_device_alloc(0, step * 8) : d_in;
+    float bal_a = 0.0f, bal_b = 1.0f;
+    if (g_bal) irdm_iq_balance_coeffs(g_bal_gain, g_bal_phase, &bal_a, &bal_b);
     int rc_all = 0;
-    if (!h_in || !d_in || !d_out) { fprintf(stderr, "--save-only: allocating the buffers failed\n"); return 1; }
+    if (!h_in || !d_in || !d_out || !d_bal) { fprintf(stderr, "--save-only: allocating the buffers failed\n"); return 1; }
     for (int fi = 0; fi < g_n_in; fi++) {
         const char *file = g_in[fi].path;
         const input_t *in = &g_in[fi];
@@ -776,16 +872,17 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
         if (band_open(save_band, out_dir, file, fmt) != 0) { if (f != stdin) fclose(f); rc_all = 1; continue; }
         irdm_scrub_stats_t sb = { 0 };                       /* --scrub: the recording's figures, summed over its reads */
         sb.limit_log2 = g_scrub_log2;
-        sb.active = in_fmt == IRDM_FMT_CF32;
+        sb.active = fe_fmt == IRDM_FMT_CF32;
         for (;;) {
             const size_t want = remain < step ? (size_t)remain : step;
             const size_t r = want ? fread(h_in, bps, want, f) : 0;
             if (r == 0) break;
             remain -= r;
             if (irdm_device_upload(d_in, h_in, r * bps) != 0 || (g_swap && irdm_swap_iq_device(d_in, r, in_fmt, 0, NULL) != 0)) { rc = 1; break; }
+            if (g_bal && irdm_iq_balance_device(d_bal, d_in, r, in_fmt, bal_a, bal_b, 0, NULL) != 0) { rc = 1; break; }
             if (g_scrub) {
                 irdm_scrub_stats_t one;
-                if (irdm_scrub_device(d_in, r, in_fmt, g_scrub_log2, &one, 0, NULL) != 0) { rc = 1; break; }
+                if (irdm_scrub_device(d_bal, r, fe_fmt, g_scrub_log2, &one, 0, NULL) != 0) { rc = 1; break; }
                 if (one.n_zeroed) {
                     if (!sb.n_zeroed) sb.first = sb.n_samples + one.first;
                     sb.last = sb.n_samples + one.last;
@@ -795,17 +892,17 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
                 sb.n_nonfinite += one.n_nonfinite;
                 sb.n_over += one.n_over;
             }
-            if (irdm_frontend_run_device(fe, d_in, r, d_out, cap, NULL) < 0) { rc = 1; break; }
+            if (irdm_frontend_run_device(fe, d_bal, r, d_out, cap, NULL) < 0) { rc = 1; break; }
             if (r < step) break;
         }
         if (rc == 0 && irdm_frontend_finish_device(fe, d_out, cap, NULL) < 0) rc = 1;
         if (rc) fprintf(stderr, "%s: GPU processing failed\n", file);
         if (band_close(fe, file, fmt, gain, verbose, centre) != 0) rc = 1;
         if (has_suffix_nocase(save_band, ".sigmf-data") && band_write_meta(save_band, fmt, irdm_frontend_out_rate(fe), centre, in->start_ns) != 0) rc = 1;
-        if (g_scrub) scrub_line(&sb, in_fmt, rate);
+        if (g_scrub) scrub_line(&sb, fe_fmt, rate);
         if (g_input_stats) {
             irdm_input_stats_t is;
-            if (irdm_frontend_input_stats(fe, &is) == 0) input_line(&is, in_fmt);
+            if (irdm_frontend_input_stats(fe, &is) == 0) input_line(&is, fe_fmt);
             else { fprintf(stderr, "--input-stats: %s: no statistics\n", file); rc = 1; }
         }
         if (f != stdin) fclose(f);
@@ -949,6 +1046,19 @@ int main(int argc, char **argv)
                 g_scrub_log2 = (int)v;
             }
         }
+        else if (!strcmp(a, "--image-check")) g_image = 1;
+        else if (!strcmp(a, "--iq-balance") || !strncmp(a, "--iq-balance=", 13)) {
+            /* (the --iq-balance=GAIN_DB,PHASE_DEG form only) */
+            char *end = NULL, *end2 = NULL;
+            const char *v = a[12] == '=' ? a + 13 : "";
+            g_bal_gain = strtod(v, &end);
+            if (end != v && *end == ',') g_bal_phase = strtod(end + 1, &end2);
+            if (!end2 || end2 == end + 1 || *end2 || irdm_iq_balance_coeffs(g_bal_gain, g_bal_phase, NULL, NULL) != 0) {
+                fprintf(stderr, "%s: give --iq-balance=GAIN_DB,PHASE_DEG, two numbers within +-6 dB and +-30 degrees\n", a);
+                return 2;
+            }
+            g_bal = 1;
+        }
         else if (!strcmp(a, "--read-threads")) read_threads = atoi(NEXT());
         else if (!strcmp(a, "--depth")) depth = atoi(NEXT());       /* 0: per-chunk latency, 1: throughput (default) */
         else if (!strcmp(a, "-v") || !strcmp(a, "--verbose")) verbose = 1;
@@ -1011,7 +1121,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1107,6 +1217,24 @@ int main(int argc, char **argv)
         }
         gpus = 0;
     }
+    if (g_image) {
+        if (gpus > 1) {
+            fprintf(stderr, "--image-check: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if (save_only) {
+            fprintf(stderr, "--image-check with --save-only: no context runs, so there are no frames to judge\n");
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_bal) {
+        if (gpus > 1) {
+            fprintf(stderr, "--iq-balance: one GPU only (--gpus %d): a group is fed on the device\n", gpus);
+            return 2;
+        }
+        gpus = 0;
+    }
     if (save_band) {
         if (!decimate && !resample_to) {
             fprintf(stderr, "--save-band saves the band a front end selects: give --band-center / --decimate or --resample-to\n");
@@ -1141,6 +1269,8 @@ int main(int argc, char **argv)
     }
     const size_t bps = g_in[first].bps;
     const int fmt = g_in[first].fmt;
+    /* --iq-balance: the context or the front end is a cf32 one and takes the file's format as its wire format */
+    const int proc_fmt = g_bal ? IRDM_FMT_CF32 : fmt;
     freq = g_in[first].centre;
     for (int k = 0; k < g_n_in; k++) {
         if (g_n_in > 1 && !strcmp(g_in[k].path, "-")) {
@@ -1180,7 +1310,7 @@ int main(int argc, char **argv)
         irdm_frontend_config_t fc;
         memset(&fc, 0, sizeof(fc));
         fc.in_rate = (int)rate;
-        fc.in_format = fmt;
+        fc.in_format = proc_fmt;
         fc.decim = decimate;
         fc.shift_hz = band_center - freq;
         fe = irdm_frontend_create(&fc);
@@ -1192,7 +1322,7 @@ int main(int argc, char **argv)
         irdm_frontend_rational_config_t fc;
         memset(&fc, 0, sizeof(fc));
         fc.in_rate = (int)rate;
-        fc.in_format = fmt;
+        fc.in_format = proc_fmt;
         fc.out_rate = resample_to;
         fc.shift_hz = band_given ? band_center - freq : 0.0;
         fe = irdm_frontend_create_rational(&fc);
@@ -1206,7 +1336,7 @@ int main(int argc, char **argv)
     c.center_frequency = fe ? freq + irdm_frontend_applied_shift_hz(fe) : freq;
     c.sample_rate = fe ? irdm_frontend_out_rate(fe) : (int)rate;
     c.threshold_db = (float)db;
-    c.format = fe ? IRDM_FMT_CF32 : fmt;
+    c.format = fe ? IRDM_FMT_CF32 : proc_fmt;
     c.feed_block = 32768;
     c.use_gardner = gardner;
     c.start_time_ns = g_in[first].start_ns;
@@ -1237,6 +1367,20 @@ int main(int argc, char **argv)
         fprintf(stderr, "--swap-iq: I and Q of every sample are exchanged on the GPU; I of the \"input:\" line is the file's second component\n");
     if (g_swap && fe && !save_only && irdm_frontend_swap_iq(fe, 1) != 0) {
         fprintf(stderr, "--swap-iq: the library refused the exchange\n");
+        return 1;
+    }
+    if (g_bal && verbose) {
+        float a = 0.0f, b = 1.0f;
+        irdm_iq_balance_coeffs(g_bal_gain, g_bal_phase, &a, &b);
+        fprintf(stderr, "--iq-balance: Q/I gain %+.3f dB, phase %+.2f deg: q' = %.9g i + %.9g q on the GPU, %s in, cf32 from there on; "
+                        "the closing lines describe the corrected stream\n", g_bal_gain, g_bal_phase, (double)a, (double)b, format_name(fmt));
+    }
+    if (g_bal && fe && !save_only && irdm_frontend_iq_balance(fe, fmt, g_bal_gain, g_bal_phase) != 0) {
+        fprintf(stderr, "--iq-balance: the library refused the correction\n");
+        return 1;
+    }
+    if (g_image && fe && irdm_frontend_iq_moments(fe, 1) != 0) {
+        fprintf(stderr, "--image-check: the library refused the measurement\n");
         return 1;
     }
     if (g_scrub && verbose)
@@ -1325,6 +1469,14 @@ int main(int argc, char **argv)
         fprintf(stderr, "--scrub: the library refused the pass\n");
         return 1;
     }
+    if (g_bal && !fe && irdm_iq_balance(p, fmt, g_bal_gain, g_bal_phase) != 0) {
+        fprintf(stderr, "--iq-balance: the library refused the correction\n");
+        return 1;
+    }
+    if (g_image && !fe && irdm_set_option(p, "iq_moments", 1) != 0) {
+        fprintf(stderr, "--image-check: the library refused the measurement\n");
+        return 1;
+    }
     g_save_dir = save_dir;
     /* a group is fed a super-step at a time: one chunk per member */
     /* (behind a front end the reader's chunk is D -- or M / L -- pipeline chunks of capture samples) */
@@ -1356,6 +1508,7 @@ int main(int argc, char **argv)
         if (in->kind < 0) { fprintf(stderr, "%s\n", in->err); rc_all = 1; f = NULL; continue; }
         const char *data = in->kind > 0 ? in->info->data_path : file;
         g_n_demods = 0;
+        g_n_img = 0;
         f = strcmp(file, "-") ? fopen(data, "rb") : stdin;
         if (!f) { perror(data); rc_all = 1; continue; }
         if (fi > 0) {
@@ -1519,9 +1672,14 @@ int main(int argc, char **argv)
             if (irdm_iq_sense(p, &iq) == 0) iq_line(&iq);
             else { fprintf(stderr, "--iq-check: %s: no verdict\n", file); rc = 1; }
         }
+        if (g_image) {
+            irdm_iq_moments_t im;
+            if ((fe ? irdm_frontend_iq_moments_stats(fe, &im) : irdm_iq_moments(p, &im)) == 0) image_line(&im, fe ? freq : in->centre);
+            else { fprintf(stderr, "--image-check: %s: no figures\n", file); rc = 1; }
+        }
         if (g_scrub) {
             irdm_scrub_stats_t sb;
-            if ((fe ? irdm_frontend_scrub_stats(fe, &sb) : irdm_scrub_stats(p, &sb)) == 0) scrub_line(&sb, fmt, rate);
+            if ((fe ? irdm_frontend_scrub_stats(fe, &sb) : irdm_scrub_stats(p, &sb)) == 0) scrub_line(&sb, proc_fmt, rate);
             else { fprintf(stderr, "--scrub: %s: no figures\n", file); rc = 1; }
         }
         if (g_acars) {
@@ -1533,7 +1691,7 @@ int main(int argc, char **argv)
             band_write_meta(save_band, save_fmt, irdm_frontend_out_rate(fe), c.center_frequency, irdm_start_time_ns(p)) != 0) rc = 1;
         if (g_input_stats) {
             irdm_input_stats_t is;
-            if ((fe ? irdm_frontend_input_stats(fe, &is) : irdm_input_stats(p, &is)) == 0) input_line(&is, fmt);
+            if ((fe ? irdm_frontend_input_stats(fe, &is) : irdm_input_stats(p, &is)) == 0) input_line(&is, proc_fmt);
             else { fprintf(stderr, "--input-stats: %s: no statistics\n", file); rc = 1; }
         }
         if (g_diag) {

@@ -229,6 +229,13 @@ class ScrubStats(C.Structure):
                 ("first", C.c_uint64), ("last", C.c_uint64), ("limit_log2", C.c_int32), ("active", C.c_int32)]
 
 
+class IqMoments(C.Structure):
+    """irdm_iq_moments_t (option iq_moments): the second moments of I and Q and the imbalance derived from them"""
+    _fields_ = [("n_samples", C.c_uint64), ("n_used", C.c_uint64), ("sum_i", C.c_double), ("sum_q", C.c_double),
+                ("sum_ii", C.c_double), ("sum_qq", C.c_double), ("sum_iq", C.c_double), ("gain_db", C.c_double),
+                ("phase_deg", C.c_double), ("image_db", C.c_double), ("valid", C.c_int), ("reserved", C.c_int)]
+
+
 class RecordingInfo(C.Structure):
     """irdm_recording_info_t (irdm_recording_probe)"""
     _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
@@ -298,6 +305,12 @@ def lib():
         if hasattr(L, "irdm_scrub_device"):
             L.irdm_scrub_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(ScrubStats), C.c_int, C.c_void_p]
             L.irdm_scrub_stats.argtypes = [C.c_void_p, C.POINTER(ScrubStats)]
+        if hasattr(L, "irdm_iq_moments_device"):
+            L.irdm_iq_moments.argtypes = [C.c_void_p, C.POINTER(IqMoments)]
+            L.irdm_iq_moments_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(IqMoments), C.c_int, C.c_void_p]
+            L.irdm_iq_balance_coeffs.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+            L.irdm_iq_balance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]
+            L.irdm_iq_balance.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -473,6 +486,10 @@ def lib():
             if hasattr(L, "irdm_frontend_scrub"):
                 L.irdm_frontend_scrub.argtypes = [C.c_void_p, C.c_int, C.c_int]
                 L.irdm_frontend_scrub_stats.argtypes = [C.c_void_p, C.POINTER(ScrubStats)]
+            if hasattr(L, "irdm_frontend_iq_moments"):
+                L.irdm_frontend_iq_moments.argtypes = [C.c_void_p, C.c_int]
+                L.irdm_frontend_iq_moments_stats.argtypes = [C.c_void_p, C.POINTER(IqMoments)]
+                L.irdm_frontend_iq_balance.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
             if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
                 L.irdm_frontend_create_rational.restype = C.c_void_p
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
@@ -554,6 +571,30 @@ def scrub_device(d_iq, n, fmt, limit_log2=SCRUB_DEFAULT_LOG2, stats=True, device
     return rc, st
 
 
+def iq_moments_device(d_iq, n, fmt, device=0, stream=None, stats=True):
+    """irdm_iq_moments_device: (rc, IqMoments) of the n samples of format fmt at the device address d_iq alone; stats False
+    (with a stream): the launches alone, without waiting -- (rc, None)"""
+    st = IqMoments() if stats else None
+    rc = int(lib().irdm_iq_moments_device(C.c_void_p(d_iq), n, fmt, C.byref(st) if stats else None, device, C.c_void_p(stream or 0)))
+    return rc, st
+
+
+def iq_balance_coeffs(gain_db, phase_deg):
+    """irdm_iq_balance_coeffs: (alpha, beta) as np.float32 for a Q arm gain_db above the I arm and phase_deg off quadrature;
+    None outside |gain_db| <= 6, |phase_deg| <= 30"""
+    a, b = C.c_float(), C.c_float()
+    if lib().irdm_iq_balance_coeffs(float(gain_db), float(phase_deg), C.byref(a), C.byref(b)) != 0:
+        return None
+    return np.float32(a.value), np.float32(b.value)
+
+
+def iq_balance_device(d_out, d_in, n, fmt, alpha, beta, device=0, stream=None):
+    """irdm_iq_balance_device: the n samples of format fmt at d_in become cf32 at d_out, i' = i, q' = alpha i + beta q;
+    returns the call's result (0 or -1)"""
+    return int(lib().irdm_iq_balance_device(C.c_void_p(d_out), C.c_void_p(d_in), n, fmt, float(alpha), float(beta), device,
+                                            C.c_void_p(stream or 0)))
+
+
 def host_free(ptr):
     lib().irdm_host_free(C.c_void_p(ptr))
 
@@ -623,9 +664,22 @@ class Pipeline:
             raise RuntimeError("irdm_input_stats failed (option input_stats never set?)")
         return st
 
+    def iq_moments(self):
+        """irdm_iq_moments (option iq_moments): the IqMoments of the stream so far"""
+        st = IqMoments()
+        if self.L.irdm_iq_moments(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_iq_moments failed (option iq_moments never set?)")
+        return st
+
+    def iq_balance(self, wire_fmt, gain_db, phase_deg):
+        """irdm_iq_balance: from now on feed_host takes wire_fmt's samples and corrects them into the cf32 context"""
+        if self.L.irdm_iq_balance(self.h, wire_fmt, float(gain_db), float(phase_deg)) != 0:
+            raise RuntimeError("irdm_iq_balance refused (not a cf32 context, the stream has begun, or figures outside the limits)")
+        self.wire_fmt = wire_fmt
+
     def feed_host(self, iq):
         iq = np.ascontiguousarray(iq)
-        n = len(iq) if self.fmt == FMT_CF32 else len(iq) // 2
+        n = len(iq) if getattr(self, "wire_fmt", self.fmt) == FMT_CF32 else len(iq) // 2
         rc = self.L.irdm_feed_host(self.h, iq.ctypes.data_as(C.c_void_p), n)
         if rc < 0:
             raise RuntimeError("irdm_feed_host failed")
@@ -1051,9 +1105,27 @@ class Frontend:
             raise RuntimeError("irdm_frontend_taps failed")
         return out
 
+    def iq_moments_enable(self, on=True):
+        """irdm_frontend_iq_moments: the second moments of the capture's samples in front of the kernel"""
+        if self.L.irdm_frontend_iq_moments(self.h, 1 if on else 0) != 0:
+            raise RuntimeError("irdm_frontend_iq_moments failed")
+
+    def iq_moments(self):
+        """irdm_frontend_iq_moments_stats: the IqMoments of the capture so far"""
+        st = IqMoments()
+        if self.L.irdm_frontend_iq_moments_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_frontend_iq_moments_stats failed (never switched on?)")
+        return st
+
+    def iq_balance(self, wire_fmt, gain_db, phase_deg):
+        """irdm_frontend_iq_balance: from now on feed_host takes wire_fmt's samples and corrects them into the cf32 capture"""
+        if self.L.irdm_frontend_iq_balance(self.h, wire_fmt, float(gain_db), float(phase_deg)) != 0:
+            raise RuntimeError("irdm_frontend_iq_balance refused (not a cf32 front end, the capture has begun, or figures outside the limits)")
+        self.wire_fmt = wire_fmt
+
     def feed_host(self, pipeline, x):
         x = np.ascontiguousarray(x)
-        n = len(x) if self.fmt == FMT_CF32 else len(x) // 2
+        n = len(x) if getattr(self, "wire_fmt", self.fmt) == FMT_CF32 else len(x) // 2
         rc = self.L.irdm_frontend_feed_host(self.h, pipeline.h, x.ctypes.data_as(C.c_void_p), n)
         if rc < 0:
             raise RuntimeError("irdm_frontend_feed_host failed")
