@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 // The detector's kernels (prefilter, band scan) are chains of small, latency-bound launches that decide when the next
 // chunk may be scanned; their wavefronts share SIMDs with the per-burst chains' long-running ones (decimator, demod),
@@ -239,6 +240,24 @@ template <int FMT>
 constexpr int kFmtBytes = (FMT == 2 || FMT == 8 || FMT == 9) ? 8 : ((FMT == 0 || FMT == 6) ? 2 : 4);
 constexpr bool fmt_valid(int fmt) { return (fmt >= 0 && fmt <= 4) || fmt == 6 || fmt == 8 || fmt == 9; }
 constexpr int fmt_bytes(int fmt) { return (fmt == 2 || fmt == 8 || fmt == 9) ? 8 : ((fmt == 0 || fmt == 6) ? 2 : 4); }
+
+// The host's step from a format number to a template parameter: f(std::integral_constant<int, FMT>{}) for a device format,
+// false (and no call) for a number that is none.
+template <typename F>
+static inline bool fmt_dispatch(int fmt, F &&f)
+{
+    switch (fmt) {
+    case 0: f(std::integral_constant<int, 0>{}); return true;
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 3: f(std::integral_constant<int, 3>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 6: f(std::integral_constant<int, 6>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    case 9: f(std::integral_constant<int, 9>{}); return true;
+    default: return false;
+    }
+}
 
 template <int FMT>
 __device__ __forceinline__ float2 load_iq(const void *__restrict__ iq, size_t i)

@@ -72,9 +72,9 @@ void pipeline_free(irdm_pipeline *p)
         if (h) (void)hipHostFree(h);
     for (auto &e : p->ev_spec)
         if (e) (void)hipEventDestroy(e);
-    input_stats_pass_free(p->in_stats);
-    scrub_pass_free(p->scrub);
-    iq_moments_pass_free(p->iqm);
+    p->in_stats.free();
+    p->scrub.free();
+    p->iqm.free();
     if (p->bal.d_wire) (void)hipFree(p->bal.d_wire);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);
     for (float2 *q : p->rot_retired) (void)hipFree(q);

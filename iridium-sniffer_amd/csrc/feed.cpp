@@ -129,9 +129,62 @@ static int spectrum_flush(irdm_pipeline *p)
 
 int input_stats_configure(irdm_pipeline *p, int on)
 {
-    if (on && input_stats_pass_alloc(p->in_stats) != 0) return -1;
+    if (on && p->in_stats.alloc(kIsBlockBytes, true) != 0) return -1;
     p->in_stats.on = on ? 1 : 0;
     return 0;
+}
+
+// ---- the chunk passes alone, on a buffer the caller owns (irdm_*_device) ----
+
+// The stream such a call works on: the caller's, or one of its own, which finish() waits for and destroys.
+struct CallerStream {
+    hipStream_t s = nullptr, own = nullptr;
+    CallerStream(int device, void *stream_v)
+    {
+        if (hipSetDevice(device) != hipSuccess) {
+            fprintf(stderr, "irdm_hip: hipSetDevice(%d) failed\n", device);
+            return;
+        }
+        s = static_cast<hipStream_t>(stream_v);
+        if (!s && hipStreamCreateWithFlags(&own, hipStreamNonBlocking) == hipSuccess) s = own;
+    }
+    bool ok() const { return s != nullptr; }
+    int finish(int rc)
+    {
+        if (own) {
+            if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
+            (void)hipStreamDestroy(own);
+            own = nullptr;
+        }
+        return rc;
+    }
+    ~CallerStream() { (void)finish(0); }
+    CallerStream(const CallerStream &) = delete;
+    CallerStream &operator=(const CallerStream &) = delete;
+};
+
+// A pass whose figures the call returns: n samples of bps bytes at d_in in launches of at most max_launch samples on s,
+// all into one device block of block_bytes.  launch(in, piece, d_block) enqueues one and returns how many bytes of the
+// block to read back (< 0: failed); they are waited for and handed to fold(host copy, off, piece).
+template <typename Launch, typename Fold>
+static int one_block_pass(const void *d_in, size_t n, size_t bps, size_t max_launch, size_t block_bytes, hipStream_t s,
+                          Launch &&launch, Fold &&fold)
+{
+    void *d_block = nullptr;
+    if (hipMalloc(&d_block, block_bytes) != hipSuccess) return -1;
+    std::vector<unsigned char> h(block_bytes);
+    int rc = 0;
+    for (size_t off = 0; rc == 0 && off < n; off += max_launch) {
+        const size_t piece = std::min(max_launch, n - off);
+        const long long bytes = launch(static_cast<const char *>(d_in) + off * bps, piece, d_block);
+        if (bytes < 0 || hipMemcpyAsync(h.data(), d_block, (size_t)bytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+            hipStreamSynchronize(s) != hipSuccess)
+            rc = -1;
+        else
+            fold(static_cast<const void *>(h.data()), off, piece);
+    }
+    (void)hipFree(d_block);
+    return rc;
 }
 
 extern "C" int irdm_input_stats(irdm_pipeline_t *p, irdm_input_stats_t *out)
@@ -146,30 +199,17 @@ extern "C" int irdm_input_stats(irdm_pipeline_t *p, irdm_input_stats_t *out)
 extern "C" int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_stats_t *out, int device, void *stream_v)
 {
     if (!out || (!d_in && n) || !fmt_valid(format) || (reinterpret_cast<uintptr_t>(d_in) % (size_t)fmt_bytes(format)) != 0) return -1;
-    IRDM_HIP_CHECK(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
-    void *d_block = nullptr;
-    std::vector<unsigned char> h(kIsBlockBytes);
+    CallerStream cs(device, stream_v);
+    if (!cs.ok()) return -1;
     InputStatsRun run;
-    int rc = 0;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
-        s = own;
-    }
-    if (hipMalloc(&d_block, kIsBlockBytes) != hipSuccess) rc = -1;
-    const size_t bps = (size_t)fmt_bytes(format);
-    for (size_t off = 0; rc == 0 && off < n; off += kIsMaxLaunch) {
-        const size_t piece = std::min(kIsMaxLaunch, n - off);
-        const int grid = launch_input_stats(format, static_cast<const char *>(d_in) + off * bps, piece, d_block, s);
-        if (grid < 0 || hipMemcpyAsync(h.data(), d_block, kIsBlockBytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            rc = -1;
-            break;
-        }
-        input_stats_fold(run, format, h.data(), grid, piece);
-    }
-    if (d_block) (void)hipFree(d_block);
-    if (own) (void)hipStreamDestroy(own);
+    int grid = 0;
+    const int rc = cs.finish(one_block_pass(
+        d_in, n, (size_t)fmt_bytes(format), kIsMaxLaunch, kIsBlockBytes, cs.s,
+        [&](const void *in, size_t piece, void *d_block) {
+            grid = launch_input_stats(format, in, piece, d_block, cs.s);
+            return grid < 0 ? -1ll : (long long)kIsBlockBytes;
+        },
+        [&](const void *h_block, size_t, size_t piece) { input_stats_fold(run, format, h_block, grid, piece); }));
     if (rc == 0) input_stats_result(run, format, out);
     return rc;
 }
@@ -656,24 +696,14 @@ extern "C" int irdm_swap_iq_device(void *d_iq, size_t n_samples, int format, int
 {
     if ((!d_iq && n_samples) || !fmt_valid(format) || (reinterpret_cast<uintptr_t>(d_iq) % (size_t)fmt_bytes(format)) != 0) return -1;
     if (n_samples == 0) return 0;
-    IRDM_HIP_CHECK(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
-        s = own;
-    }
-    int rc = launch_iq_swap(format, d_iq, n_samples, s);
-    if (own) {
-        if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
-        (void)hipStreamDestroy(own);
-    }
-    return rc;
+    CallerStream cs(device, stream_v);
+    return cs.ok() ? cs.finish(launch_iq_swap(format, d_iq, n_samples, cs.s)) : -1;
 }
 
 // ---- option "iq_moments" (iq_moments.hpp) and irdm_iq_balance (iq_balance.hpp) ----
 int iq_moments_configure(irdm_pipeline *p, int on)
 {
-    if (on && iq_moments_pass_alloc(p->iqm) != 0) return -1;
+    if (on && p->iqm.alloc(kImBlockBytes, true) != 0) return -1;
     p->iqm.on = on ? 1 : 0;
     return 0;
 }
@@ -696,8 +726,8 @@ extern "C" int irdm_iq_moments_device(const void *d_in, size_t n, int format, ir
         if (out) iq_moments_result(run, out);
         return 0;
     }
-    IRDM_HIP_CHECK(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
+    CallerStream cs(device, stream_v);
+    if (!cs.ok()) return -1;
     if (!out) {
         // the launches alone, on the caller's stream without waiting (for timing the kernel): the rows go to a block that
         // is never read, one per device for the life of the process
@@ -709,32 +739,20 @@ extern "C" int irdm_iq_moments_device(const void *d_in, size_t n, int format, ir
             if (!d_unread[device] && hipMalloc(&d_unread[device], kImBlockBytes) != hipSuccess) return -1;
         }
         const size_t bps0 = (size_t)fmt_bytes(format);
-        for (size_t off = 0; off < n; off += kImMaxLaunch)
-            if (launch_iq_moments(format, static_cast<const char *>(d_in) + off * bps0, std::min(kImMaxLaunch, n - off), d_unread[device], s) < 0)
+        for (size_t off = 0; off < n; off += kChunkMaxLaunch)
+            if (launch_iq_moments(format, static_cast<const char *>(d_in) + off * bps0, std::min(kChunkMaxLaunch, n - off), d_unread[device],
+                                  cs.s) < 0)
                 return -1;
         return 0;
     }
-    void *d_block = nullptr;
-    std::vector<unsigned char> h(kImBlockBytes);
-    int rc = 0;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
-        s = own;
-    }
-    if (hipMalloc(&d_block, kImBlockBytes) != hipSuccess) rc = -1;
-    const size_t bps = (size_t)fmt_bytes(format);
-    for (size_t off = 0; rc == 0 && off < n; off += kImMaxLaunch) {
-        const size_t piece = std::min(kImMaxLaunch, n - off);
-        const int grid = launch_iq_moments(format, static_cast<const char *>(d_in) + off * bps, piece, d_block, s);
-        if (grid < 0 || hipMemcpyAsync(h.data(), d_block, sizeof(IqmRow) * (size_t)grid, hipMemcpyDeviceToHost, s) != hipSuccess ||
-            hipStreamSynchronize(s) != hipSuccess) {
-            rc = -1;
-            break;
-        }
-        iq_moments_fold(run, h.data(), grid, piece);
-    }
-    if (d_block) (void)hipFree(d_block);
-    if (own) (void)hipStreamDestroy(own);
+    int grid = 0;
+    const int rc = cs.finish(one_block_pass(
+        d_in, n, (size_t)fmt_bytes(format), kChunkMaxLaunch, kImBlockBytes, cs.s,
+        [&](const void *in, size_t piece, void *d_block) {
+            grid = launch_iq_moments(format, in, piece, d_block, cs.s);
+            return grid < 0 ? -1ll : (long long)(sizeof(IqmRow) * (size_t)grid);
+        },
+        [&](const void *h_rows, size_t, size_t piece) { iq_moments_fold(run, h_rows, grid, piece); }));
     if (rc == 0) iq_moments_result(run, out);
     return rc;
 }
@@ -749,18 +767,8 @@ extern "C" int irdm_iq_balance_device(void *d_out, const void *d_in, size_t n, i
 {
     if (((!d_in || !d_out) && n) || !fmt_valid(format)) return -1;
     if (n == 0) return launch_iq_balance(format, d_out, d_in, 0, alpha, beta, nullptr);     // (the checks alone)
-    IRDM_HIP_CHECK(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
-        s = own;
-    }
-    int rc = launch_iq_balance(format, d_out, d_in, n, alpha, beta, s);
-    if (own) {
-        if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
-        (void)hipStreamDestroy(own);
-    }
-    return rc;
+    CallerStream cs(device, stream_v);
+    return cs.ok() ? cs.finish(launch_iq_balance(format, d_out, d_in, n, alpha, beta, cs.s)) : -1;
 }
 
 extern "C" int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_db, double phase_deg)
@@ -790,7 +798,7 @@ extern "C" int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_
 // ---- option "scrub" (scrub.hpp): the blocks of the passes, when the option is first set on a cf32 context ----
 int scrub_configure(irdm_pipeline *p, int on)
 {
-    if (on && p->dev_fmt == IRDM_FMT_CF32 && scrub_pass_alloc(p->scrub) != 0) return -1;
+    if (on && p->dev_fmt == IRDM_FMT_CF32 && p->scrub.alloc(kSbBlockBytes, false) != 0) return -1;
     p->scrub.on = on ? 1 : 0;
     return 0;
 }
@@ -817,31 +825,23 @@ extern "C" int irdm_scrub_device(void *d_iq, size_t n_samples, int format, int l
         if (stats) scrub_result(run, limit_log2, format == IRDM_FMT_CF32 ? 1 : 0, stats);
         return 0;
     }
-    IRDM_HIP_CHECK(hipSetDevice(device));
-    hipStream_t s = static_cast<hipStream_t>(stream_v), own = nullptr;
-    if (!s) {
-        if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) return -1;
-        s = own;
+    CallerStream cs(device, stream_v);
+    if (!cs.ok()) return -1;
+    int rc = 0;
+    if (!stats) {
+        for (size_t off = 0; rc == 0 && off < n_samples; off += kChunkMaxLaunch)
+            rc = launch_scrub(static_cast<char *>(d_iq) + off * 8, std::min(kChunkMaxLaunch, n_samples - off), limit_log2, nullptr, cs.s);
+        return cs.finish(rc);
     }
     // (with stats: one block for the call, read back after every launch of at most 2^31 samples)
-    ScrubAcc *d_acc = nullptr;
-    int rc = !stats || hipMalloc(reinterpret_cast<void **>(&d_acc), kSbBlockBytes) == hipSuccess ? 0 : -1;
-    for (size_t off = 0; rc == 0 && off < n_samples; off += kSbMaxLaunch) {
-        const size_t piece = std::min(kSbMaxLaunch, n_samples - off);
-        if (d_acc && hipMemsetAsync(d_acc, 0, kSbBlockBytes, s) != hipSuccess) rc = -1;
-        if (rc == 0) rc = launch_scrub(static_cast<char *>(d_iq) + off * 8, piece, limit_log2, d_acc, s);
-        if (rc == 0 && d_acc) {
-            ScrubAcc h[kSbRows];
-            rc = hipStreamSynchronize(s) == hipSuccess && hipMemcpy(h, d_acc, kSbBlockBytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-            if (rc == 0) scrub_fold(run, h, off, piece);
-        }
-    }
-    if (d_acc) (void)hipFree(d_acc);
-    if (own) {
-        if (hipStreamSynchronize(own) != hipSuccess) rc = -1;
-        (void)hipStreamDestroy(own);
-    }
-    if (rc == 0 && stats) scrub_result(run, limit_log2, 1, stats);
+    rc = cs.finish(one_block_pass(
+        d_iq, n_samples, 8, kChunkMaxLaunch, kSbBlockBytes, cs.s,
+        [&](const void *in, size_t piece, void *d_block) {
+            if (hipMemsetAsync(d_block, 0, kSbBlockBytes, cs.s) != hipSuccess) return -1ll;
+            return launch_scrub(const_cast<void *>(in), piece, limit_log2, static_cast<ScrubAcc *>(d_block), cs.s) != 0 ? -1ll : (long long)kSbBlockBytes;
+        },
+        [&](const void *h_acc, size_t off, size_t piece) { scrub_fold(run, static_cast<const ScrubAcc *>(h_acc), off, piece); }));
+    if (rc == 0) scrub_result(run, limit_log2, 1, stats);
     return rc;
 }
 

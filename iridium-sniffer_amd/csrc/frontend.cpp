@@ -35,9 +35,9 @@ void fe_free(irdm_frontend *fe)
     (void)hipSetDevice(fe->cfg.device);
     if (fe->stream) (void)hipStreamSynchronize(fe->stream);
     fe_save_off(fe);
-    input_stats_pass_free(fe->is);
-    scrub_pass_free(fe->scrub);
-    iq_moments_pass_free(fe->iqm);
+    fe->is.free();
+    fe->scrub.free();
+    fe->iqm.free();
     if (fe->bal.d_wire) (void)hipFree(fe->bal.d_wire);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
@@ -282,17 +282,15 @@ static int fe_stats_enqueue(irdm_frontend *fe, const void *d_in, size_t n_in, hi
 // s goes on behind that pass: what s records or runs next may hand the chunk's memory back
 static int fe_stats_join(irdm_frontend *fe, size_t n_in, hipStream_t s)
 {
-    if (fe->iqm.on && n_in && fe->st.iqm.last_slot >= 0) IRDM_HIP_CHECK(hipStreamWaitEvent(s, fe->iqm.ev[fe->st.iqm.last_slot], 0));
-    if (!fe->is.on || !n_in || fe->st.is.last_slot < 0) return 0;
-    IRDM_HIP_CHECK(hipStreamWaitEvent(s, fe->is.ev[fe->st.is.last_slot], 0));
-    return 0;
+    if (fe->iqm.on && n_in && fe->iqm.lead(fe->st.iqm, s) != 0) return -1;
+    return fe->is.on && n_in ? fe->is.lead(fe->st.is, s) : 0;
 }
 
 extern "C" int irdm_frontend_input_stats_enable(irdm_frontend_t *fe, int on)
 {
     if (!fe) return -1;
     (void)hipSetDevice(fe->cfg.device);
-    if (on && input_stats_pass_alloc(fe->is) != 0) return -1;
+    if (on && fe->is.alloc(kIsBlockBytes, true) != 0) return -1;
     fe->is.on = on ? 1 : 0;
     return 0;
 }
@@ -310,7 +308,7 @@ extern "C" int irdm_frontend_iq_moments(irdm_frontend_t *fe, int on)
 {
     if (!fe) return -1;
     (void)hipSetDevice(fe->cfg.device);
-    if (on && iq_moments_pass_alloc(fe->iqm) != 0) return -1;
+    if (on && fe->iqm.alloc(kImBlockBytes, true) != 0) return -1;
     fe->iqm.on = on ? 1 : 0;
     return 0;
 }
@@ -378,7 +376,7 @@ extern "C" int irdm_frontend_scrub(irdm_frontend_t *fe, int on, int limit_log2)
     if (!fe || limit_log2 < 0 || limit_log2 > 127) return -1;
     if (fe->st.total != 0 && ((on != 0) != (fe->scrub.on != 0) || limit_log2 != fe->scrub.limit_log2)) return -1;
     (void)hipSetDevice(fe->cfg.device);
-    if (on && fe->fmt == IRDM_FMT_CF32 && scrub_pass_alloc(fe->scrub) != 0) return -1;
+    if (on && fe->fmt == IRDM_FMT_CF32 && fe->scrub.alloc(kSbBlockBytes, false) != 0) return -1;
     fe->scrub.on = on ? 1 : 0;
     fe->scrub.limit_log2 = limit_log2;
     return 0;

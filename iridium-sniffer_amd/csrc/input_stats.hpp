@@ -3,8 +3,7 @@
 //
 // One memory-bound pass per chunk on a side stream, behind the chunk's arrival and beside K1; nothing of it is fused into
 // K1 or the decimator.  The kernel reads b_in bytes per sample and writes nothing but its sums:
-//   * 16-byte loads per lane (8 / 4 / 2 samples at 2 / 4 / 8 bytes per sample), a scalar head and tail for a base that is
-//     aligned to a sample only;
+//   * the span geometry of chunk_span.hpp, the codes taken from a piece by iq_piece.hpp;
 //   * integer formats: x = c * 2^-K with an integer c (ci8 c = v, K = 7; cu8 c = 2u - 255, K = 8; ci16 c = v >> 8, K = 7;
 //     ci16-full c = v, K = 15; sc16q11 c = v, K = 11).  A lane sums c and c^2 of one 16-byte piece in 32 bits (int16: c^2
 //     straight into 64 -- one square already needs 31), then adds to its 64-bit accumulators; rails and the extreme codes
@@ -23,18 +22,19 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <deque>
 #include "common.hpp"
+#include "chunk_span.hpp"
+#include "iq_piece.hpp"
+#include "pass_ring.hpp"
+#include "wave_reduce.hpp"
 #include "../../include/irdm_hip.h"
 
 namespace irdm {
 
-constexpr int kIsNT = 256;                              // threads of a workgroup
-constexpr int kIsMaxGrid = 2048;                        // workgroups of a launch (rows of the cf32 slab)
-constexpr size_t kIsMaxLaunch = (size_t)1 << 30;        // samples of a launch: a lane's 32-bit counts cannot overflow
-constexpr int kIsSlots = 4;                             // launches in flight per context
+// samples of a launch, below kChunkMaxLaunch: a lane's 32-bit counts cannot overflow (two components per sample)
+constexpr size_t kIsMaxLaunch = (size_t)1 << 30;
 
-// one launch's sums on the device, all zero before the launch; cf32: [kIsMaxGrid][4] doubles behind it
+// one launch's sums on the device, all zero before the launch; cf32: [kChunkMaxGrid][4] doubles behind it
 struct InputStatsAcc {
     unsigned long long rail_lo[2], rail_hi[2], nonfinite[2];
     unsigned long long sum_c[2];        // two's complement
@@ -45,7 +45,7 @@ struct InputStatsAcc {
     unsigned pad[2];
     unsigned long long sum_c2_hi[2];    // the int32 formats: the sum of c^2 >> 32 (sum_c2 then holds that of c^2 & 0xffffffff)
 };
-constexpr size_t kIsBlockBytes = sizeof(InputStatsAcc) + sizeof(double) * 4 * kIsMaxGrid;
+constexpr size_t kIsBlockBytes = sizeof(InputStatsAcc) + sizeof(double) * 4 * kChunkMaxGrid;
 
 template <int FMT> struct IsFmt;
 template <> struct IsFmt<0> { static constexpr int LO = -128, HI = 127, K = 7; };
@@ -106,26 +106,6 @@ __device__ __forceinline__ void is_piece_done(IsLane &a)
     }
 }
 
-// one 32-bit word of the input: two samples (8-bit formats) or one (int16 formats)
-template <int FMT>
-__device__ __forceinline__ void is_word(IsLane &a, unsigned w)
-{
-    if (FMT == 0) {
-        is_take<FMT>(a, 0, (int)(signed char)(w & 0xff));
-        is_take<FMT>(a, 1, (int)(signed char)((w >> 8) & 0xff));
-        is_take<FMT>(a, 0, (int)(signed char)((w >> 16) & 0xff));
-        is_take<FMT>(a, 1, (int)(signed char)(w >> 24));
-    } else if (FMT == 6) {
-        is_take<FMT>(a, 0, (int)(w & 0xff));
-        is_take<FMT>(a, 1, (int)((w >> 8) & 0xff));
-        is_take<FMT>(a, 0, (int)((w >> 16) & 0xff));
-        is_take<FMT>(a, 1, (int)(w >> 24));
-    } else {
-        is_take<FMT>(a, 0, (int)(short)(w & 0xffff));
-        is_take<FMT>(a, 1, (int)(short)(w >> 16));
-    }
-}
-
 // a lane's accumulators, cf32
 struct IsLaneF {
     unsigned lo[2], hi[2], nf[2], absb[2];
@@ -148,62 +128,17 @@ __device__ __forceinline__ void is_take_f(IsLaneF &a, int k, unsigned bits)
     a.s2[k] += q;
 }
 
-// a wavefront's reductions into lane 0: shuffles of 32-bit words (a 64-bit value travels as its two halves)
-__device__ __forceinline__ unsigned long long is_down64(unsigned long long v, int d)
-{
-    const unsigned lo = __shfl_down((unsigned)v, d), hi = __shfl_down((unsigned)(v >> 32), d);
-    return ((unsigned long long)hi << 32) | lo;
-}
-__device__ __forceinline__ unsigned is_wave_sum(unsigned v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-__device__ __forceinline__ unsigned long long is_wave_sum(unsigned long long v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += is_down64(v, d);
-    return v;
-}
-__device__ __forceinline__ double is_wave_sum(double v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __builtin_bit_cast(double, is_down64(__builtin_bit_cast(unsigned long long, v), d));
-    return v;
-}
-__device__ __forceinline__ int is_wave_min(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const int o = __shfl_down(v, d);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T is_wave_max(T v)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const T o = __shfl_down(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// n samples at `in` (aligned to a sample): `head` samples up to the first 16-byte boundary, nvec 16-byte pieces, the rest.
-// Every thread reaches every shuffle and barrier.
+// The samples of span sp at `in` (aligned to a sample).  Every thread reaches every shuffle and barrier.
 template <int FMT>
-__global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restrict__ in, long long n, long long head,
-                                                            long long nvec, InputStatsAcc *__restrict__ acc,
-                                                            double *__restrict__ slab)
+__global__ __launch_bounds__(kChunkNT) void input_stats_kernel(const void *__restrict__ in, const ChunkSpan sp,
+                                                               InputStatsAcc *__restrict__ acc, double *__restrict__ slab)
 {
-    constexpr int BPS = kFmtBytes<FMT>, SPV = 16 / BPS, NW = kIsNT / 64;
-    const long long gid = (long long)blockIdx.x * kIsNT + threadIdx.x, stride = (long long)gridDim.x * kIsNT;
+    constexpr int BPS = kFmtBytes<FMT>, SPV = 16 / BPS, NW = kChunkNT / 64;
+    const ChunkLane cl = chunk_lane();
+    const long long si = cl.scalar<SPV>(sp);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned char *const bytes = static_cast<const unsigned char *>(in);
-    const uint4 *const pieces = reinterpret_cast<const uint4 *>(bytes + head * BPS);
-    // the scalar head and tail: at most SPV - 1 samples each, one per thread of the first workgroup
-    const long long tail0 = head + nvec * SPV;
-    long long si = -1;
-    if (gid < head) si = gid;
-    else if (gid - head < n - tail0) si = tail0 + (gid - head);
+    const uint4 *const pieces = reinterpret_cast<const uint4 *>(bytes + sp.head * BPS);
 
     if constexpr (FMT == 2) {
         __shared__ double sh_d[NW][4];
@@ -213,24 +148,15 @@ __global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restri
             a.lo[k] = a.hi[k] = a.nf[k] = a.absb[k] = 0u;
             a.s[k] = a.s2[k] = 0.0;
         }
-        if (si >= 0) {
-            const unsigned *w = reinterpret_cast<const unsigned *>(bytes + si * BPS);
-            is_take_f(a, 0, w[0]);
-            is_take_f(a, 1, w[1]);
-        }
-        for (long long i = gid; i < nvec; i += stride) {
-            const uint4 v = pieces[i];
-            is_take_f(a, 0, v.x);
-            is_take_f(a, 1, v.y);
-            is_take_f(a, 0, v.z);
-            is_take_f(a, 1, v.w);
-        }
+        const auto take = [&](int k, int code) { is_take_f(a, k, (unsigned)code); };
+        if (si >= 0) iq_sample_codes<FMT>(bytes + si * BPS, take);
+        for (long long i = cl.gid; i < sp.nvec; i += cl.stride) iq_piece_codes<FMT>(pieces[i], take);
         // the order of every sum is fixed by the launch geometry: a lane's pieces, the shuffle tree, the waves in turn
         unsigned u[8] = { a.lo[0], a.lo[1], a.hi[0], a.hi[1], a.nf[0], a.nf[1], a.absb[0], a.absb[1] };
         double d[4] = { a.s[0], a.s[1], a.s2[0], a.s2[1] };
-        for (int j = 0; j < 6; j++) u[j] = is_wave_sum(u[j]);
-        for (int j = 6; j < 8; j++) u[j] = is_wave_max(u[j]);
-        for (int j = 0; j < 4; j++) d[j] = is_wave_sum(d[j]);
+        for (int j = 0; j < 6; j++) u[j] = wave_sum(u[j]);
+        for (int j = 6; j < 8; j++) u[j] = wave_max(u[j]);
+        for (int j = 0; j < 4; j++) d[j] = wave_sum(d[j]);
         if (lane == 0) {
             for (int j = 0; j < 8; j++) sh_u[wave][j] = u[j];
             for (int j = 0; j < 4; j++) sh_d[wave][j] = d[j];
@@ -265,46 +191,21 @@ __global__ __launch_bounds__(kIsNT) void input_stats_kernel(const void *__restri
             a.ls[k] = 0;
             a.ls2[k] = 0u;
         }
+        const auto take = [&](int k, int code) { is_take<FMT>(a, k, code); };
         if (si >= 0) {
-            if (BPS == 8) {
-                const int *w = reinterpret_cast<const int *>(bytes + si * BPS);
-                is_take<FMT>(a, 0, w[0]);
-                is_take<FMT>(a, 1, w[1]);
-            } else if (BPS == 2) {
-                const unsigned w = *reinterpret_cast<const unsigned short *>(bytes + si * BPS);
-                if (FMT == 0) {
-                    is_take<FMT>(a, 0, (int)(signed char)(w & 0xff));
-                    is_take<FMT>(a, 1, (int)(signed char)(w >> 8));
-                } else {
-                    is_take<FMT>(a, 0, (int)(w & 0xff));
-                    is_take<FMT>(a, 1, (int)(w >> 8));
-                }
-            } else {
-                is_word<FMT>(a, *reinterpret_cast<const unsigned *>(bytes + si * BPS));
-            }
+            iq_sample_codes<FMT>(bytes + si * BPS, take);
             is_piece_done(a);
         }
-        for (long long i = gid; i < nvec; i += stride) {
-            const uint4 v = pieces[i];
-            if (BPS == 8) {
-                is_take<FMT>(a, 0, (int)v.x);
-                is_take<FMT>(a, 1, (int)v.y);
-                is_take<FMT>(a, 0, (int)v.z);
-                is_take<FMT>(a, 1, (int)v.w);
-            } else {
-                is_word<FMT>(a, v.x);
-                is_word<FMT>(a, v.y);
-                is_word<FMT>(a, v.z);
-                is_word<FMT>(a, v.w);
-                is_piece_done(a);
-            }
+        for (long long i = cl.gid; i < sp.nvec; i += cl.stride) {
+            iq_piece_codes<FMT>(pieces[i], take);
+            is_piece_done(a);               // (the int32 formats keep no piece sums: nothing to add)
         }
         unsigned long long q[10] = { a.lo[0], a.lo[1], a.hi[0], a.hi[1], (unsigned long long)a.s[0], (unsigned long long)a.s[1],
                                      a.s2[0], a.s2[1], a.s2h[0], a.s2h[1] };
         int m[4] = { a.cmin[0], a.cmin[1], a.cmax[0], a.cmax[1] };
-        for (int j = 0; j < NQ; j++) q[j] = is_wave_sum(q[j]);
-        for (int j = 0; j < 2; j++) m[j] = is_wave_min(m[j]);
-        for (int j = 2; j < 4; j++) m[j] = is_wave_max(m[j]);
+        for (int j = 0; j < NQ; j++) q[j] = wave_sum(q[j]);
+        for (int j = 0; j < 2; j++) m[j] = wave_min(m[j]);
+        for (int j = 2; j < 4; j++) m[j] = wave_max(m[j]);
         if (lane == 0) {
             for (int j = 0; j < NQ; j++) sh_q[wave][j] = q[j];
             for (int j = 0; j < 4; j++) sh_m[wave][j] = m[j];
@@ -345,45 +246,20 @@ struct InputStatsRun {
     double fs[2] = { 0.0, 0.0 }, fs2[2] = { 0.0, 0.0 };
 };
 
-// workgroups of the launch over n samples at d_in (0: nothing to launch)
-static inline int input_stats_grid(int fmt, const void *d_in, size_t n, long long *head_out, long long *nvec_out)
-{
-    const int bps = fmt_bytes(fmt), spv = 16 / bps;
-    const size_t mis = (size_t)(reinterpret_cast<uintptr_t>(d_in) & 15u);
-    long long head = (long long)(((16 - mis) & 15u) / (size_t)bps);
-    if (head > (long long)n) head = (long long)n;
-    const long long nvec = ((long long)n - head) / spv;
-    *head_out = head;
-    *nvec_out = nvec;
-    if (n == 0) return 0;
-    const long long want = (nvec + kIsNT - 1) / kIsNT;
-    return (int)(want < 1 ? 1 : (want > kIsMaxGrid ? kIsMaxGrid : want));
-}
-
 // One launch over n <= kIsMaxLaunch samples (aligned to a sample of fmt) into d_block (kIsBlockBytes, zeroed here) on
-// `stream`; returns the grid (the rows of the slab a cf32 launch wrote), -1 on error.
+// `stream`; returns the grid (the rows of the slab a cf32 launch wrote; 0: n == 0, nothing launched), -1 on error.
 static inline int launch_input_stats(int fmt, const void *d_in, size_t n, void *d_block, hipStream_t stream)
 {
     if (!fmt_valid(fmt) || n > kIsMaxLaunch || (reinterpret_cast<uintptr_t>(d_in) % (size_t)fmt_bytes(fmt)) != 0) return -1;
-    long long head = 0, nvec = 0;
-    const int grid = input_stats_grid(fmt, d_in, n, &head, &nvec);
-    if (grid == 0) return 0;
+    if (n == 0) return 0;
+    int grid = 0;
+    const ChunkSpan sp = chunk_span(fmt_bytes(fmt), d_in, n, kChunkNT, kChunkMaxGrid, &grid);
     InputStatsAcc *acc = static_cast<InputStatsAcc *>(d_block);
     double *slab = reinterpret_cast<double *>(acc + 1);
     if (hipMemsetAsync(acc, 0, sizeof(InputStatsAcc), stream) != hipSuccess) return -1;
-#define IRDM_LAUNCH_IS(F)                                                                                               \
-    hipLaunchKernelGGL((input_stats_kernel<F>), dim3(grid), dim3(kIsNT), 0, stream, d_in, (long long)n, head, nvec, acc, slab)
-    switch (fmt) {
-    case 0: IRDM_LAUNCH_IS(0); break;
-    case 1: IRDM_LAUNCH_IS(1); break;
-    case 2: IRDM_LAUNCH_IS(2); break;
-    case 3: IRDM_LAUNCH_IS(3); break;
-    case 4: IRDM_LAUNCH_IS(4); break;
-    case 8: IRDM_LAUNCH_IS(8); break;
-    case 9: IRDM_LAUNCH_IS(9); break;
-    default: IRDM_LAUNCH_IS(6); break;
-    }
-#undef IRDM_LAUNCH_IS
+    fmt_dispatch(fmt, [&](auto f) {
+        hipLaunchKernelGGL((input_stats_kernel<decltype(f)::value>), dim3(grid), dim3(kChunkNT), 0, stream, d_in, sp, acc, slab);
+    });
     return hipGetLastError() == hipSuccess ? grid : -1;
 }
 
@@ -444,64 +320,24 @@ static inline void input_stats_result(const InputStatsRun &t, int fmt, irdm_inpu
     }
 }
 
-// The pass of a context or a front end.  Cache: the side stream, kIsSlots blocks on the device with their pinned copies.
-struct InputStatsPass {
+// The pass of a context or a front end: its switch (configuration) and its ring on a side stream (cache; pass_ring.hpp).
+struct InputStatsPass : PassRing {
     int on = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr;
-    void *d_block[kIsSlots] = {}, *h_block[kIsSlots] = {};
-    hipEvent_t ev[kIsSlots] = {};
 };
-// Stream state: the totals, and the launches whose blocks have not been folded yet, oldest first.
-struct InputStatsStream {
+// Stream state: the totals, and the launches in flight (an entry's meta: the launch's grid).
+struct InputStatsStream : PassRingStream {
     InputStatsRun run;
-    struct Pending { int slot, grid; size_t n; uint64_t tag; };
-    std::deque<Pending> pending;
-    uint64_t launches = 0;
-    int last_slot = -1;                 // the slot of the launch enqueued last (-1: none since the stream began)
 };
 
-static inline void input_stats_pass_free(InputStatsPass &ps)
+static inline auto input_stats_folder(InputStatsStream &st, int fmt)
 {
-    if (ps.stream) (void)hipStreamSynchronize(ps.stream);
-    for (int i = 0; i < kIsSlots; i++) {
-        if (ps.d_block[i]) (void)hipFree(ps.d_block[i]);
-        if (ps.h_block[i]) (void)hipHostFree(ps.h_block[i]);
-        if (ps.ev[i]) (void)hipEventDestroy(ps.ev[i]);
-    }
-    if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
-    if (ps.stream) (void)hipStreamDestroy(ps.stream);
-    ps = InputStatsPass{};
-}
-
-// the buffers, when the option is first set (the device is current)
-static inline int input_stats_pass_alloc(InputStatsPass &ps)
-{
-    if (ps.stream) return 0;
-    bool ok = hipStreamCreateWithFlags(&ps.stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&ps.ev_in, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < kIsSlots; i++) {
-        ok = ok && hipMalloc(&ps.d_block[i], kIsBlockBytes) == hipSuccess;
-        ok = ok && hipHostMalloc(&ps.h_block[i], kIsBlockBytes, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&ps.ev[i], hipEventDisableTiming) == hipSuccess;
-    }
-    if (!ok) {
-        input_stats_pass_free(ps);
-        return -1;
-    }
-    return 0;
+    return [&st, fmt](const void *h_block, const PassRingStream::Entry &e) { input_stats_fold(st.run, fmt, h_block, (int)e.meta, e.n); };
 }
 
 // launches up to and including tag `upto` are waited for and folded, oldest first
 static inline int input_stats_settle(InputStatsPass &ps, InputStatsStream &st, int fmt, uint64_t upto)
 {
-    while (!st.pending.empty() && st.pending.front().tag <= upto) {
-        const InputStatsStream::Pending e = st.pending.front();
-        if (hipEventSynchronize(ps.ev[e.slot]) != hipSuccess) return -1;
-        input_stats_fold(st.run, fmt, ps.h_block[e.slot], e.grid, e.n);
-        st.pending.pop_front();
-    }
-    return 0;
+    return ps.settle(st, upto, input_stats_folder(st, fmt));
 }
 
 // n samples at d_in, produced on `arrival` (nullptr: complete in memory): their pass on the side stream.  The launches
@@ -510,27 +346,16 @@ static inline int input_stats_enqueue(InputStatsPass &ps, InputStatsStream &st, 
                                       hipStream_t arrival, uint64_t tag)
 {
     if (n == 0) return 0;
-    if (arrival) {
-        if (hipEventRecord(ps.ev_in, arrival) != hipSuccess || hipStreamWaitEvent(ps.stream, ps.ev_in, 0) != hipSuccess) return -1;
-    }
+    if (ps.follow(arrival) != 0) return -1;
     const size_t bps = (size_t)fmt_bytes(fmt);
     for (size_t off = 0; off < n; off += kIsMaxLaunch) {
         const size_t piece = std::min(kIsMaxLaunch, n - off);
-        const int slot = (int)(st.launches % kIsSlots);
-        // the slot's previous launch (kIsSlots launches ago) leaves its pinned block first
-        for (bool busy = true; busy;) {
-            busy = false;
-            for (const auto &e : st.pending) busy = busy || e.slot == slot;
-            if (busy && input_stats_settle(ps, st, fmt, st.pending.front().tag) != 0) return -1;
-        }
+        const int slot = ps.acquire(st, input_stats_folder(st, fmt));
+        if (slot < 0) return -1;
         const int grid = launch_input_stats(fmt, static_cast<const char *>(d_in) + off * bps, piece, ps.d_block[slot], ps.stream);
         if (grid < 0) return -1;
         const size_t bytes = sizeof(InputStatsAcc) + (fmt == IRDM_FMT_CF32 ? sizeof(double) * 4 * (size_t)grid : 0);
-        if (hipMemcpyAsync(ps.h_block[slot], ps.d_block[slot], bytes, hipMemcpyDeviceToHost, ps.stream) != hipSuccess) return -1;
-        if (hipEventRecord(ps.ev[slot], ps.stream) != hipSuccess) return -1;
-        st.pending.push_back(InputStatsStream::Pending{ slot, grid, piece, tag });
-        st.launches++;
-        st.last_slot = slot;
+        if (ps.commit(st, slot, bytes, ps.stream, (uint64_t)grid, piece, tag) != 0) return -1;
     }
     return 0;
 }

@@ -13,18 +13,17 @@
 //     4-byte formats the wavefront turns its 64 pieces through LDS first, so that each of its store instructions writes
 //     1 KiB of consecutive bytes (straight from the lanes the ci8 pass took 226 us per 64 Mi samples where a copy of the
 //     same bytes takes 124);
-//   * the samples in front of src's first 16-byte boundary and behind its last one (at most 16 / bps - 1 each) are
-//     handled one per thread by the first threads of the grid;
-//   * grid-stride loop, at most kIbMaxGrid workgroups of kIbNT threads, at most 2^31 samples per launch.
+//   * the span geometry of chunk_span.hpp on src, at most kChunkMaxLaunch samples per launch.
 // In place (dst == src) for the 8-byte formats: a lane has read its piece before it writes it and reads no other lane's.
-// Bounds: the vector part reads src bytes [head * bps, (head + nvec * spv) * bps) and writes dst samples
-// [head, head + nvec * spv), head + nvec * spv <= n; the scalar part the samples [0, head) and [head + nvec * spv, n).
+// Bounds: it reads the samples of src's span (chunk_span.hpp) and writes the same sample indices of dst: the vector part
+// dst samples [head, head + nvec * spv), the scalar part [0, head) and [head + nvec * spv, n).
 //
 // Included by the translation units that launch it (feed.cpp: irdm_feed_host of a context and irdm_iq_balance_device;
 // frontend.cpp: the capture in front of K0 / K0r).
 #pragma once
 #include <math.h>
 #include "common.hpp"
+#include "chunk_span.hpp"
 #include "iq_piece.hpp"
 
 #if !defined(__HIP__)
@@ -35,9 +34,6 @@ static inline float __fadd_rn(float a, float b) { volatile float s = a + b; retu
 
 namespace irdm {
 
-constexpr int kIbNT = 256;                              // threads of a workgroup
-constexpr int kIbMaxGrid = 2048;                        // workgroups of a launch
-constexpr size_t kIbMaxLaunch = (size_t)1 << 31;        // samples of a launch
 constexpr double kIbMaxGainDb = 6.0, kIbMaxPhaseDeg = 30.0;
 // what those limits allow: |alpha| <= tan 30, 10^-0.3 <= beta <= 10^0.3 / cos 30 (the floats just outside)
 constexpr float kIbMaxAlpha = 0.5773504f, kIbMinBeta = 0.5011872f, kIbMaxBeta = 2.303931f;
@@ -62,15 +58,15 @@ __device__ __forceinline__ unsigned ib_q(unsigned i_bits, unsigned q_bits, float
     return __float_as_uint(__fadd_rn(__fmul_rn(alpha, __uint_as_float(i_bits)), __fmul_rn(beta, __uint_as_float(q_bits))));
 }
 
-// n samples of FMT at `src` (aligned to a sample) to cf32 at `dst` (aligned to 8 bytes): `head` samples up to src's first
-// 16-byte boundary, nvec 16-byte pieces, the rest.  dst16: dst + head samples lies on a 16-byte boundary.  (No __restrict__:
-// dst may be src.)
+// The samples of FMT of span sp at `src` (aligned to a sample) to cf32 at `dst` (aligned to 8 bytes).  dst16: dst + head
+// samples lies on a 16-byte boundary.  (No __restrict__: dst may be src.)
 template <int FMT>
-__global__ __launch_bounds__(kIbNT) void iq_balance_kernel(void *dst, const void *src, long long n, long long head, long long nvec,
-                                                           float alpha, float beta, int dst16)
+__global__ __launch_bounds__(kChunkNT) void iq_balance_kernel(void *dst, const void *src, const ChunkSpan sp, float alpha, float beta,
+                                                              int dst16)
 {
     constexpr int BPS = kFmtBytes<FMT>, SPV = 16 / BPS;
-    const long long gid = (long long)blockIdx.x * kIbNT + threadIdx.x, stride = (long long)gridDim.x * kIbNT;
+    const ChunkLane cl = chunk_lane();
+    const long long gid = cl.gid, stride = cl.stride, head = sp.head, nvec = sp.nvec;
     const unsigned char *const bytes = static_cast<const unsigned char *>(src);
     const uint4 *const pieces = reinterpret_cast<const uint4 *>(bytes + head * BPS);
     unsigned *const out = static_cast<unsigned *>(dst);
@@ -82,7 +78,7 @@ __global__ __launch_bounds__(kIbNT) void iq_balance_kernel(void *dst, const void
         // lane reaches both wavefront barriers.  (Slot s of lane k sits at k QPL + (s ^ k % QPL): the 8 lanes a b128 write
         // serves at once then cover all banks.)
         constexpr int QPL = SPV / 2;
-        __shared__ uint4 sh[kIbNT * QPL];
+        __shared__ uint4 sh[kChunkNT * QPL];
         const int lane = threadIdx.x & 63;
         uint4 *const mine = sh + (threadIdx.x >> 6) * 64 * QPL;
         for (long long b = gid - lane; dst16 && b < nvec; b += stride) {
@@ -125,18 +121,14 @@ __global__ __launch_bounds__(kIbNT) void iq_balance_kernel(void *dst, const void
             for (int k = 0; k < SPV; k++) reinterpret_cast<uint2 *>(q)[k] = uint2{ o[2 * k], o[2 * k + 1] };
         }
     }
-    // the scalar head and tail: at most SPV - 1 samples each, one per thread
-    const long long tail0 = head + nvec * SPV;
-    long long si = -1;
-    if (gid < head) si = gid;
-    else if (gid - head < n - tail0) si = tail0 + (gid - head);
+    const long long si = cl.scalar<SPV>(sp);
     if (si < 0) return;
     unsigned o[2];
     iq_sample_bits<FMT>(bytes + si * BPS, o);
     reinterpret_cast<uint2 *>(out)[si] = uint2{ o[0], ib_q(o[0], o[1], alpha, beta) };
 }
 
-// n samples of format fmt at d_in to cf32 at d_out on `stream`, in launches of at most kIbMaxLaunch samples.  0, or -1 for
+// n samples of format fmt at d_in to cf32 at d_out on `stream`, in launches of at most kChunkMaxLaunch samples.  0, or -1 for
 // an unknown format, d_in not aligned to a sample or d_out not to 8 bytes, coefficients outside the limits, buffers that
 // overlap (other than d_out == d_in with an 8-byte format) or a launch that failed; n == 0 launches nothing.
 static inline int launch_iq_balance(int fmt, void *d_out, const void *d_in, size_t n, float alpha, float beta, hipStream_t stream)
@@ -147,27 +139,16 @@ static inline int launch_iq_balance(int fmt, void *d_out, const void *d_in, size
     if (a_in % bps != 0 || a_out % 8u != 0) return -1;
     if (n == 0) return 0;
     if (!(a_out == a_in && bps == 8) && a_in < a_out + n * 8 && a_out < a_in + n * bps) return -1;
-    static_assert(kIbNT >= 2 * 7, "the first workgroup holds the scalar head and tail");
-    for (size_t off = 0; off < n; off += kIbMaxLaunch) {
-        const size_t piece = n - off < kIbMaxLaunch ? n - off : kIbMaxLaunch;
+    for (size_t off = 0; off < n; off += kChunkMaxLaunch) {
+        const size_t piece = n - off < kChunkMaxLaunch ? n - off : kChunkMaxLaunch;
         const void *in = static_cast<const char *>(d_in) + off * bps;
         void *out = static_cast<char *>(d_out) + off * 8;
-        long long head = 0, nvec = 0;
-        const int grid = iq_piece_grid(fmt, in, piece, kIbNT, kIbMaxGrid, &head, &nvec);
-        const int dst16 = ((reinterpret_cast<uintptr_t>(out) + (uintptr_t)head * 8u) & 15u) == 0 ? 1 : 0;
-#define IRDM_LAUNCH_IB(F) \
-    hipLaunchKernelGGL((iq_balance_kernel<F>), dim3(grid), dim3(kIbNT), 0, stream, out, in, (long long)piece, head, nvec, alpha, beta, dst16)
-        switch (fmt) {
-        case 0: IRDM_LAUNCH_IB(0); break;
-        case 1: IRDM_LAUNCH_IB(1); break;
-        case 2: IRDM_LAUNCH_IB(2); break;
-        case 3: IRDM_LAUNCH_IB(3); break;
-        case 4: IRDM_LAUNCH_IB(4); break;
-        case 8: IRDM_LAUNCH_IB(8); break;
-        case 9: IRDM_LAUNCH_IB(9); break;
-        default: IRDM_LAUNCH_IB(6); break;
-        }
-#undef IRDM_LAUNCH_IB
+        int grid = 0;
+        const ChunkSpan sp = chunk_span((int)bps, in, piece, kChunkNT, kChunkMaxGrid, &grid);
+        const int dst16 = ((reinterpret_cast<uintptr_t>(out) + (uintptr_t)sp.head * 8u) & 15u) == 0 ? 1 : 0;
+        fmt_dispatch(fmt, [&](auto f) {
+            hipLaunchKernelGGL((iq_balance_kernel<decltype(f)::value>), dim3(grid), dim3(kChunkNT), 0, stream, out, in, sp, alpha, beta, dst16);
+        });
         if (hipGetLastError() != hipSuccess) return -1;
     }
     return 0;

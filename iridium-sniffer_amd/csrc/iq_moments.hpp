@@ -3,18 +3,16 @@
 // I arm, the phase by which the two miss 90 degrees, and the level of the image at -f that every signal at +f leaves.
 //
 // One pass per chunk that reads b_in bytes per sample and writes nothing but its sums:
-//   * 16-byte loads per lane (8 / 4 / 2 samples at 2 / 4 / 8 bytes per sample), a scalar head and tail for a base that is
-//     aligned to a sample only (one sample per thread of the first workgroup), a grid-stride loop under kImMaxGrid
-//     workgroups, at most kImMaxLaunch = 2^31 samples per launch;
+//   * the span geometry of chunk_span.hpp, at most kChunkMaxLaunch = 2^31 samples per launch (a lane's 32-bit count cannot
+//     overflow);
 //   * every sample converted as load_iq<FMT> converts it (iq_piece.hpp), then widened to binary64: i, q and the products
 //     i i, q q, i q of two floats are exact doubles, so only the order of the additions is free (the products enter as
 //     fma(i, q, sum): one rounding, that of the addition).  A cf32 sample with a component whose exponent field is all ones
 //     is left out and not counted in n_used;
-//   * a lane's five sums and its count are reduced over the wavefront by shuffles (input_stats.hpp's), over the workgroup
+//   * a lane's five sums and its count are reduced over the wavefront by shuffles (wave_reduce.hpp), over the workgroup
 //     through LDS, and the workgroup writes its row of a block that the host adds up in row order.  No atomics: the figures
 //     of a launch depend on its geometry alone, two launches over one buffer give the same bytes.
-// Bounds: the vector part covers bytes [head * bps, (head + nvec * spv) * bps), head + nvec * spv <= n; the scalar part the
-// samples [0, head) and [head + nvec * spv, n); a workgroup writes rows[blockIdx.x], blockIdx.x < grid <= kImMaxGrid.
+// Bounds: it reads the span's samples (chunk_span.hpp); a workgroup writes rows[blockIdx.x], blockIdx.x < grid <= kChunkMaxGrid.
 //
 // Included by the translation units that launch it (feed.cpp: a context's stream and irdm_iq_moments_device;
 // frontend.cpp: the capture in front of K0 / K0r).
@@ -22,25 +20,21 @@
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <deque>
 #include "common.hpp"
+#include "chunk_span.hpp"
 #include "iq_piece.hpp"
-#include "input_stats.hpp"
+#include "pass_ring.hpp"
+#include "wave_reduce.hpp"
 #include "../../include/irdm_hip.h"
 
 namespace irdm {
-
-constexpr int kImNT = 256;                              // threads of a workgroup
-constexpr int kImMaxGrid = 2048;                        // workgroups of a launch (rows of its block)
-constexpr size_t kImMaxLaunch = (size_t)1 << 31;        // samples of a launch: a lane's 32-bit count cannot overflow
-constexpr int kImSlots = 4;                             // launches in flight per context
 
 // a workgroup's row: sum i, sum q, sum i i, sum q q, sum i q, and the samples that entered them
 struct alignas(64) IqmRow {
     double s[5];
     unsigned long long used;
 };
-constexpr size_t kImBlockBytes = sizeof(IqmRow) * kImMaxGrid;
+constexpr size_t kImBlockBytes = sizeof(IqmRow) * kChunkMaxGrid;
 
 struct IqmLane {
     double s[5];
@@ -60,33 +54,27 @@ __device__ __forceinline__ void iqm_take(IqmLane &a, unsigned i_bits, unsigned q
     a.used += 1u;
 }
 
-// n samples at `in` (aligned to a sample): `head` samples up to the first 16-byte boundary, nvec 16-byte pieces, the rest.
-// Every thread reaches every shuffle and the barrier.
+// The samples of span sp at `in` (aligned to a sample).  Every thread reaches every shuffle and the barrier.
 template <int FMT>
-__global__ __launch_bounds__(kImNT) void iq_moments_kernel(const void *__restrict__ in, long long n, long long head, long long nvec,
-                                                           IqmRow *__restrict__ rows)
+__global__ __launch_bounds__(kChunkNT) void iq_moments_kernel(const void *__restrict__ in, const ChunkSpan sp, IqmRow *__restrict__ rows)
 {
-    constexpr int BPS = kFmtBytes<FMT>, SPV = 16 / BPS, NW = kImNT / 64;
+    constexpr int BPS = kFmtBytes<FMT>, SPV = 16 / BPS, NW = kChunkNT / 64;
     __shared__ double sh_d[NW][5];
     __shared__ unsigned sh_u[NW];
-    const long long gid = (long long)blockIdx.x * kImNT + threadIdx.x, stride = (long long)gridDim.x * kImNT;
+    const ChunkLane cl = chunk_lane();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const unsigned char *const bytes = static_cast<const unsigned char *>(in);
-    const uint4 *const pieces = reinterpret_cast<const uint4 *>(bytes + head * BPS);
+    const uint4 *const pieces = reinterpret_cast<const uint4 *>(bytes + sp.head * BPS);
     IqmLane a;
     for (int j = 0; j < 5; j++) a.s[j] = 0.0;
     a.used = 0u;
-    // the scalar head and tail: at most SPV - 1 samples each, one per thread of the first workgroup
-    const long long tail0 = head + nvec * SPV;
-    long long si = -1;
-    if (gid < head) si = gid;
-    else if (gid - head < n - tail0) si = tail0 + (gid - head);
+    const long long si = cl.scalar<SPV>(sp);
     if (si >= 0) {
         unsigned o[2];
         iq_sample_bits<FMT>(bytes + si * BPS, o);
         iqm_take<FMT>(a, o[0], o[1]);
     }
-    for (long long i = gid; i < nvec; i += stride) {
+    for (long long i = cl.gid; i < sp.nvec; i += cl.stride) {
         unsigned o[2 * SPV];
         iq_piece_bits<FMT>(pieces[i], o);
 #pragma unroll
@@ -94,8 +82,8 @@ __global__ __launch_bounds__(kImNT) void iq_moments_kernel(const void *__restric
     }
     // the order of every sum is fixed by the launch geometry: a lane's pieces, the shuffle tree, the waves in turn
     double d[5];
-    for (int j = 0; j < 5; j++) d[j] = is_wave_sum(a.s[j]);
-    unsigned long long u = is_wave_sum(a.used);
+    for (int j = 0; j < 5; j++) d[j] = wave_sum(a.s[j]);
+    unsigned long long u = wave_sum(a.used);
     if (lane == 0) {
         for (int j = 0; j < 5; j++) sh_d[wave][j] = d[j];
         sh_u[wave] = (unsigned)u;
@@ -121,29 +109,18 @@ struct IqmRun {
     double s[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };
 };
 
-// One launch over n <= kImMaxLaunch samples (aligned to a sample of fmt) into d_rows (kImBlockBytes) on `stream`; returns
+// One launch over n <= kChunkMaxLaunch samples (aligned to a sample of fmt) into d_rows (kImBlockBytes) on `stream`; returns
 // the grid (the rows the launch wrote; 0: n == 0, nothing launched), -1 on error.
 static inline int launch_iq_moments(int fmt, const void *d_in, size_t n, void *d_rows, hipStream_t stream)
 {
-    if (!fmt_valid(fmt) || n > kImMaxLaunch || (reinterpret_cast<uintptr_t>(d_in) % (size_t)fmt_bytes(fmt)) != 0) return -1;
+    if (!fmt_valid(fmt) || n > kChunkMaxLaunch || (reinterpret_cast<uintptr_t>(d_in) % (size_t)fmt_bytes(fmt)) != 0) return -1;
     if (n == 0) return 0;
-    long long head = 0, nvec = 0;
-    const int grid = iq_piece_grid(fmt, d_in, n, kImNT, kImMaxGrid, &head, &nvec);
-    static_assert(kImNT >= 2 * 7, "the first workgroup holds the scalar head and tail");
+    int grid = 0;
+    const ChunkSpan sp = chunk_span(fmt_bytes(fmt), d_in, n, kChunkNT, kChunkMaxGrid, &grid);
     IqmRow *rows = static_cast<IqmRow *>(d_rows);
-#define IRDM_LAUNCH_IM(F) \
-    hipLaunchKernelGGL((iq_moments_kernel<F>), dim3(grid), dim3(kImNT), 0, stream, d_in, (long long)n, head, nvec, rows)
-    switch (fmt) {
-    case 0: IRDM_LAUNCH_IM(0); break;
-    case 1: IRDM_LAUNCH_IM(1); break;
-    case 2: IRDM_LAUNCH_IM(2); break;
-    case 3: IRDM_LAUNCH_IM(3); break;
-    case 4: IRDM_LAUNCH_IM(4); break;
-    case 8: IRDM_LAUNCH_IM(8); break;
-    case 9: IRDM_LAUNCH_IM(9); break;
-    default: IRDM_LAUNCH_IM(6); break;
-    }
-#undef IRDM_LAUNCH_IM
+    fmt_dispatch(fmt, [&](auto f) {
+        hipLaunchKernelGGL((iq_moments_kernel<decltype(f)::value>), dim3(grid), dim3(kChunkNT), 0, stream, d_in, sp, rows);
+    });
     return hipGetLastError() == hipSuccess ? grid : -1;
 }
 
@@ -185,64 +162,24 @@ static inline void iq_moments_result(const IqmRun &t, irdm_iq_moments_t *out)
     out->valid = 1;
 }
 
-// The pass of a context or a front end.  Cache: the side stream, kImSlots blocks on the device with their pinned copies.
-struct IqMomentsPass {
+// The pass of a context or a front end: its switch (configuration) and its ring on a side stream (cache; pass_ring.hpp).
+struct IqMomentsPass : PassRing {
     int on = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_in = nullptr;
-    void *d_block[kImSlots] = {}, *h_block[kImSlots] = {};
-    hipEvent_t ev[kImSlots] = {};
 };
-// Stream state: the totals, and the launches whose rows have not been folded yet, oldest first.
-struct IqMomentsStream {
+// Stream state: the totals, and the launches in flight (an entry's meta: the launch's grid, the rows it wrote).
+struct IqMomentsStream : PassRingStream {
     IqmRun run;
-    struct Pending { int slot, grid; size_t n; uint64_t tag; };
-    std::deque<Pending> pending;
-    uint64_t launches = 0;
-    int last_slot = -1;                 // the slot of the launch enqueued last (-1: none since the stream began)
 };
 
-static inline void iq_moments_pass_free(IqMomentsPass &ps)
+static inline auto iq_moments_folder(IqMomentsStream &st)
 {
-    if (ps.stream) (void)hipStreamSynchronize(ps.stream);
-    for (int i = 0; i < kImSlots; i++) {
-        if (ps.d_block[i]) (void)hipFree(ps.d_block[i]);
-        if (ps.h_block[i]) (void)hipHostFree(ps.h_block[i]);
-        if (ps.ev[i]) (void)hipEventDestroy(ps.ev[i]);
-    }
-    if (ps.ev_in) (void)hipEventDestroy(ps.ev_in);
-    if (ps.stream) (void)hipStreamDestroy(ps.stream);
-    ps = IqMomentsPass{};
-}
-
-// the buffers, when the option is first set (the device is current)
-static inline int iq_moments_pass_alloc(IqMomentsPass &ps)
-{
-    if (ps.stream) return 0;
-    bool ok = hipStreamCreateWithFlags(&ps.stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&ps.ev_in, hipEventDisableTiming) == hipSuccess;
-    for (int i = 0; i < kImSlots; i++) {
-        ok = ok && hipMalloc(&ps.d_block[i], kImBlockBytes) == hipSuccess;
-        ok = ok && hipHostMalloc(&ps.h_block[i], kImBlockBytes, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&ps.ev[i], hipEventDisableTiming) == hipSuccess;
-    }
-    if (!ok) {
-        iq_moments_pass_free(ps);
-        return -1;
-    }
-    return 0;
+    return [&st](const void *h_rows, const PassRingStream::Entry &e) { iq_moments_fold(st.run, h_rows, (int)e.meta, e.n); };
 }
 
 // launches up to and including tag `upto` are waited for and folded, oldest first
 static inline int iq_moments_settle(IqMomentsPass &ps, IqMomentsStream &st, uint64_t upto)
 {
-    while (!st.pending.empty() && st.pending.front().tag <= upto) {
-        const IqMomentsStream::Pending e = st.pending.front();
-        if (hipEventSynchronize(ps.ev[e.slot]) != hipSuccess) return -1;
-        iq_moments_fold(st.run, ps.h_block[e.slot], e.grid, e.n);
-        st.pending.pop_front();
-    }
-    return 0;
+    return ps.settle(st, upto, iq_moments_folder(st));
 }
 
 // n samples at d_in, produced on `arrival` (nullptr: complete in memory): their pass on the side stream.  The launches
@@ -251,27 +188,15 @@ static inline int iq_moments_enqueue(IqMomentsPass &ps, IqMomentsStream &st, int
                                      hipStream_t arrival, uint64_t tag)
 {
     if (n == 0) return 0;
-    if (arrival) {
-        if (hipEventRecord(ps.ev_in, arrival) != hipSuccess || hipStreamWaitEvent(ps.stream, ps.ev_in, 0) != hipSuccess) return -1;
-    }
+    if (ps.follow(arrival) != 0) return -1;
     const size_t bps = (size_t)fmt_bytes(fmt);
-    for (size_t off = 0; off < n; off += kImMaxLaunch) {
-        const size_t piece = std::min(kImMaxLaunch, n - off);
-        const int slot = (int)(st.launches % kImSlots);
-        // the slot's previous launch (kImSlots launches ago) leaves its pinned block first
-        for (bool busy = true; busy;) {
-            busy = false;
-            for (const auto &e : st.pending) busy = busy || e.slot == slot;
-            if (busy && iq_moments_settle(ps, st, st.pending.front().tag) != 0) return -1;
-        }
+    for (size_t off = 0; off < n; off += kChunkMaxLaunch) {
+        const size_t piece = std::min(kChunkMaxLaunch, n - off);
+        const int slot = ps.acquire(st, iq_moments_folder(st));
+        if (slot < 0) return -1;
         const int grid = launch_iq_moments(fmt, static_cast<const char *>(d_in) + off * bps, piece, ps.d_block[slot], ps.stream);
         if (grid < 0) return -1;
-        if (hipMemcpyAsync(ps.h_block[slot], ps.d_block[slot], sizeof(IqmRow) * (size_t)grid, hipMemcpyDeviceToHost, ps.stream) != hipSuccess)
-            return -1;
-        if (hipEventRecord(ps.ev[slot], ps.stream) != hipSuccess) return -1;
-        st.pending.push_back(IqMomentsStream::Pending{ slot, grid, piece, tag });
-        st.launches++;
-        st.last_slot = slot;
+        if (ps.commit(st, slot, sizeof(IqmRow) * (size_t)grid, ps.stream, (uint64_t)grid, piece, tag) != 0) return -1;
     }
     return 0;
 }

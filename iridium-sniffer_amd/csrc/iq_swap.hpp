@@ -7,21 +7,16 @@
 //   * a lane loads 16 bytes, permutes them and stores them to the address it loaded from: no lane reads what another
 //     writes, so working in place has no hazard.  Width 1: the bytes of each 16-bit half of a dword exchanged; width 2: a
 //     dword rotated by 16; width 4: the dwords of each pair renamed.
-//   * grid-stride loop, at most kSwMaxGrid workgroups of kSwNT threads;
-//   * the buffer need only be aligned to a sample: the samples in front of the first 16-byte boundary and behind the last
-//     one (at most 16 / bytes-per-sample - 1 each) are exchanged one per thread by the first threads of the grid.
-// Bounds: the vector part covers bytes [head * bps, (head + nvec * spv) * bps), head + nvec * spv <= n; the scalar part the
-// samples [0, head) and [head + nvec * spv, n).
+//   * the buffer need only be aligned to a sample: the span geometry of chunk_span.hpp.
+// Bounds: it reads and writes the span's samples (chunk_span.hpp) and nothing else.
 //
 // Included by the translation units that launch it (feed.cpp: irdm_feed_host of a context and irdm_swap_iq_device;
 // frontend.cpp: the capture in front of K0 / K0r).
 #pragma once
 #include "common.hpp"
+#include "chunk_span.hpp"
 
 namespace irdm {
-
-constexpr int kSwNT = 256;                              // threads of a workgroup
-constexpr int kSwMaxGrid = 2048;                        // workgroups of a launch
 
 template <int W>
 __device__ __forceinline__ unsigned iq_swap_word(unsigned w)
@@ -30,16 +25,15 @@ __device__ __forceinline__ unsigned iq_swap_word(unsigned w)
     return (w << 16) | (w >> 16);
 }
 
-// n samples of 2 W bytes at `buf` (aligned to a sample): `head` samples up to the first 16-byte boundary, nvec 16-byte
-// pieces, the rest
+// the samples of 2 W bytes of span sp at `buf` (aligned to a sample)
 template <int W>
-__global__ __launch_bounds__(kSwNT) void iq_swap_kernel(void *__restrict__ buf, long long n, long long head, long long nvec)
+__global__ __launch_bounds__(kChunkNT) void iq_swap_kernel(void *__restrict__ buf, const ChunkSpan sp)
 {
     constexpr int BPS = 2 * W, SPV = 16 / BPS;
-    const long long gid = (long long)blockIdx.x * kSwNT + threadIdx.x, stride = (long long)gridDim.x * kSwNT;
+    const ChunkLane cl = chunk_lane();
     unsigned char *const bytes = static_cast<unsigned char *>(buf);
-    uint4 *const pieces = reinterpret_cast<uint4 *>(bytes + head * BPS);
-    for (long long i = gid; i < nvec; i += stride) {
+    uint4 *const pieces = reinterpret_cast<uint4 *>(bytes + sp.head * BPS);
+    for (long long i = cl.gid; i < sp.nvec; i += cl.stride) {
         uint4 v = pieces[i];
         if (W == 4) {
             v = make_uint4(v.y, v.x, v.w, v.z);
@@ -51,11 +45,7 @@ __global__ __launch_bounds__(kSwNT) void iq_swap_kernel(void *__restrict__ buf, 
         }
         pieces[i] = v;
     }
-    // the scalar head and tail: at most SPV - 1 samples each, one per thread
-    const long long tail0 = head + nvec * SPV;
-    long long si = -1;
-    if (gid < head) si = gid;
-    else if (gid - head < n - tail0) si = tail0 + (gid - head);
+    const long long si = cl.scalar<SPV>(sp);
     if (si < 0) return;
     if (W == 1) {
         unsigned short *q = reinterpret_cast<unsigned short *>(bytes + si * BPS);
@@ -78,18 +68,13 @@ static inline int launch_iq_swap(int fmt, void *d_buf, size_t n, hipStream_t str
 {
     if (!fmt_valid(fmt) || (reinterpret_cast<uintptr_t>(d_buf) % (size_t)fmt_bytes(fmt)) != 0) return -1;
     if (n == 0) return 0;
-    const int bps = fmt_bytes(fmt), spv = 16 / bps;
-    const size_t mis = (size_t)(reinterpret_cast<uintptr_t>(d_buf) & 15u);
-    long long head = (long long)(((16 - mis) & 15u) / (size_t)bps);
-    if (head > (long long)n) head = (long long)n;
-    const long long nvec = ((long long)n - head) / spv;
-    const long long want = (nvec + kSwNT - 1) / kSwNT;
-    const int grid = (int)(want < 1 ? 1 : (want > kSwMaxGrid ? kSwMaxGrid : want));
-    static_assert(kSwNT >= 2 * 7, "the first workgroup holds the scalar head and tail");
+    const int bps = fmt_bytes(fmt);
+    int grid = 0;
+    const ChunkSpan sp = chunk_span(bps, d_buf, n, kChunkNT, kChunkMaxGrid, &grid);
     switch (bps) {
-    case 2: hipLaunchKernelGGL((iq_swap_kernel<1>), dim3(grid), dim3(kSwNT), 0, stream, d_buf, (long long)n, head, nvec); break;
-    case 4: hipLaunchKernelGGL((iq_swap_kernel<2>), dim3(grid), dim3(kSwNT), 0, stream, d_buf, (long long)n, head, nvec); break;
-    default: hipLaunchKernelGGL((iq_swap_kernel<4>), dim3(grid), dim3(kSwNT), 0, stream, d_buf, (long long)n, head, nvec); break;
+    case 2: hipLaunchKernelGGL((iq_swap_kernel<1>), dim3(grid), dim3(kChunkNT), 0, stream, d_buf, sp); break;
+    case 4: hipLaunchKernelGGL((iq_swap_kernel<2>), dim3(grid), dim3(kChunkNT), 0, stream, d_buf, sp); break;
+    default: hipLaunchKernelGGL((iq_swap_kernel<4>), dim3(grid), dim3(kChunkNT), 0, stream, d_buf, sp); break;
     }
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

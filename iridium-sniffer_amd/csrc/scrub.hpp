@@ -10,35 +10,31 @@
 // One memory-bound pass, cf32 only (the integer formats hold no such value: nothing is launched for them):
 //   * a lane loads 16 bytes (two samples) and stores them to the address it loaded from ONLY if it changed them: on a clean
 //     recording the pass reads and writes nothing;
-//   * grid-stride loop, at most kSbMaxGrid workgroups of kSbNT threads;
-//   * the buffer need only be aligned to a sample: the sample in front of the first 16-byte boundary and the one behind the
-//     last are handled one per thread by the first threads of the grid (iq_swap.hpp's head and tail).
-// Counting: a lane counts in registers; the counts are reduced over the wavefront by shuffles and lane 0 issues one atomic
+//   * the buffer need only be aligned to a sample: the span geometry of chunk_span.hpp (at 8 bytes per sample a head and a
+//     tail of at most one sample each).
+// Counting: a lane counts in registers; the counts are reduced over the wavefront by shuffles (wave_reduce.hpp) and lane 0 issues one atomic
 // per non-zero count -- a file that is all NaN costs a few atomics per wavefront, not one per sample.  The wavefronts of a
 // launch spread their atomics over kSbRows copies of the figures, 128 bytes apart, which the host adds up: with one copy
 // the 8192 wavefronts of a full grid queue at one address, and a chunk with 1 % bad samples took 487 us where the pass
 // without counting takes 129 (measured on the MI355X, 64 Mi samples).  The positions of the
 // first and the last zeroed sample of a launch are two 32-bit maxima, 0xffffffff - index and index + 1 (0: none); the host
-// adds the launch's base and cuts a buffer into launches of at most kSbMaxLaunch = 2^31 samples, so an index fits.
+// adds the launch's base and cuts a buffer into launches of at most kChunkMaxLaunch = 2^31 samples, so an index fits.
 // Every thread reaches every shuffle.
-// Bounds: the vector part covers bytes [head * 8, (head + 2 nvec) * 8), head + 2 nvec <= n; the scalar part the samples
-// [0, head) and [head + 2 nvec, n).
+// Bounds: it reads and writes the span's samples (chunk_span.hpp) and, counting, its block of kSbRows figures.
 //
 // Included by the translation units that launch it (feed.cpp: irdm_feed_host of a context and irdm_scrub_device;
 // frontend.cpp: the capture in front of K0 / K0r).
 #pragma once
 #include <string.h>
 #include <algorithm>
-#include <deque>
 #include "common.hpp"
+#include "chunk_span.hpp"
+#include "pass_ring.hpp"
+#include "wave_reduce.hpp"
 #include "../../include/irdm_hip.h"
 
 namespace irdm {
 
-constexpr int kSbNT = 256;                              // threads of a workgroup
-constexpr int kSbMaxGrid = 2048;                        // workgroups of a launch
-constexpr size_t kSbMaxLaunch = (size_t)1 << 31;        // samples of a launch: an index and a lane's counts fit 32 bits
-constexpr int kSbSlots = 4;                             // launches in flight per context
 constexpr int kSbRows = 64;                             // copies of a launch's figures (a power of two)
 constexpr int kSbDefaultLog2 = 40;
 
@@ -49,9 +45,9 @@ struct alignas(128) ScrubAcc {
     unsigned last_key;                  // max of index + 1
 };
 
-// the bit pattern of 2^e
 constexpr size_t kSbBlockBytes = sizeof(ScrubAcc) * kSbRows;
 
+// the bit pattern of 2^e
 static inline unsigned scrub_limit_bits(int limit_log2) { return (unsigned)(limit_log2 + 127) << 23; }
 
 // a lane's counts
@@ -73,34 +69,20 @@ __device__ __forceinline__ bool sb_take(SbLane &a, unsigned i_bits, unsigned q_b
     return true;
 }
 
-__device__ __forceinline__ unsigned sb_wave_sum(unsigned v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_down(v, d);
-    return v;
-}
-__device__ __forceinline__ unsigned sb_wave_max(unsigned v)
-{
-    for (int d = 32; d > 0; d >>= 1) {
-        const unsigned o = __shfl_down(v, d);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-// n <= 2^31 cf32 samples at `buf` (aligned to a sample): `head` samples up to the first 16-byte boundary, nvec 16-byte
-// pieces, the rest.  COUNT false: nothing is counted, acc is not touched.
+// The cf32 samples of span sp (at most 2^31) at `buf` (aligned to a sample).  COUNT false: nothing is counted, acc is not
+// touched.
 template <bool COUNT>
-__global__ __launch_bounds__(kSbNT) void scrub_kernel(void *__restrict__ buf, long long n, long long head, long long nvec,
-                                                      unsigned limit_bits, ScrubAcc *__restrict__ acc)
+__global__ __launch_bounds__(kChunkNT) void scrub_kernel(void *__restrict__ buf, const ChunkSpan sp, unsigned limit_bits,
+                                                         ScrubAcc *__restrict__ acc)
 {
-    const long long gid = (long long)blockIdx.x * kSbNT + threadIdx.x, stride = (long long)gridDim.x * kSbNT;
+    const ChunkLane cl = chunk_lane();
     unsigned char *const bytes = static_cast<unsigned char *>(buf);
-    uint4 *const pieces = reinterpret_cast<uint4 *>(bytes + head * 8);
+    uint4 *const pieces = reinterpret_cast<uint4 *>(bytes + sp.head * 8);
     SbLane a;
     a.zeroed = a.nonfinite = a.over = a.first_key = a.last_key = 0u;
-    for (long long i = gid; i < nvec; i += stride) {
+    for (long long i = cl.gid; i < sp.nvec; i += cl.stride) {
         uint4 v = pieces[i];
-        const unsigned idx = (unsigned)(head + 2 * i);
+        const unsigned idx = (unsigned)(sp.head + 2 * i);
         const bool b0 = sb_take(a, v.x, v.y, limit_bits, idx);
         const bool b1 = sb_take(a, v.z, v.w, limit_bits, idx + 1u);
         if (b0 || b1) {
@@ -109,11 +91,7 @@ __global__ __launch_bounds__(kSbNT) void scrub_kernel(void *__restrict__ buf, lo
             pieces[i] = v;
         }
     }
-    // the scalar head and tail: at most one sample each, one per thread
-    const long long tail0 = head + nvec * 2;
-    long long si = -1;
-    if (gid < head) si = gid;
-    else if (gid - head < n - tail0) si = tail0 + (gid - head);
+    const long long si = cl.scalar<2>(sp);
     if (si >= 0) {
         unsigned *q = reinterpret_cast<unsigned *>(bytes + si * 8);
         if (sb_take(a, q[0], q[1], limit_bits, (unsigned)si)) {
@@ -122,9 +100,9 @@ __global__ __launch_bounds__(kSbNT) void scrub_kernel(void *__restrict__ buf, lo
         }
     }
     if (!COUNT) return;
-    const unsigned z = sb_wave_sum(a.zeroed), nf = sb_wave_sum(a.nonfinite), ov = sb_wave_sum(a.over);
-    const unsigned fk = sb_wave_max(a.first_key), lk = sb_wave_max(a.last_key);
-    acc += (blockIdx.x * (kSbNT / 64) + (threadIdx.x >> 6)) & (kSbRows - 1);
+    const unsigned z = wave_sum(a.zeroed), nf = wave_sum(a.nonfinite), ov = wave_sum(a.over);
+    const unsigned fk = wave_max(a.first_key), lk = wave_max(a.last_key);
+    acc += (blockIdx.x * (kChunkNT / 64) + (threadIdx.x >> 6)) & (kSbRows - 1);
     if ((threadIdx.x & 63) == 0 && z) {
         atomicAdd(&acc->n_zeroed, (unsigned long long)z);
         if (nf) atomicAdd(&acc->n_nonfinite, (unsigned long long)nf);
@@ -136,26 +114,19 @@ __global__ __launch_bounds__(kSbNT) void scrub_kernel(void *__restrict__ buf, lo
 
 // ---- host side ----
 
-// One launch over n <= kSbMaxLaunch cf32 samples at d_buf (aligned to a sample) on `stream`; the block d_acc (kSbBlockBytes,
+// One launch over n <= kChunkMaxLaunch cf32 samples at d_buf (aligned to a sample) on `stream`; the block d_acc (kSbBlockBytes,
 // zero; or nullptr: no counting) takes the figures.  0, or -1 for a pointer that is not aligned to a sample, a limit outside 0 .. 127, too many
 // samples or a launch that failed; n == 0 launches nothing.
 static inline int launch_scrub(void *d_buf, size_t n, int limit_log2, ScrubAcc *d_acc, hipStream_t stream)
 {
-    if (limit_log2 < 0 || limit_log2 > 127 || n > kSbMaxLaunch || (reinterpret_cast<uintptr_t>(d_buf) % 8u) != 0) return -1;
+    if (limit_log2 < 0 || limit_log2 > 127 || n > kChunkMaxLaunch || (reinterpret_cast<uintptr_t>(d_buf) % 8u) != 0) return -1;
     if (n == 0) return 0;
-    const size_t mis = (size_t)(reinterpret_cast<uintptr_t>(d_buf) & 15u);
-    long long head = mis ? 1 : 0;
-    if (head > (long long)n) head = (long long)n;
-    const long long nvec = ((long long)n - head) / 2;
-    const long long want = (nvec + kSbNT - 1) / kSbNT;
-    const int grid = (int)(want < 1 ? 1 : (want > kSbMaxGrid ? kSbMaxGrid : want));
-    static_assert(kSbNT >= 2, "the first workgroup holds the scalar head and tail");
+    int grid = 0;
+    const ChunkSpan sp = chunk_span(8, d_buf, n, kChunkNT, kChunkMaxGrid, &grid);
     if (d_acc)
-        hipLaunchKernelGGL((scrub_kernel<true>), dim3(grid), dim3(kSbNT), 0, stream, d_buf, (long long)n, head, nvec,
-                           scrub_limit_bits(limit_log2), d_acc);
+        hipLaunchKernelGGL((scrub_kernel<true>), dim3(grid), dim3(kChunkNT), 0, stream, d_buf, sp, scrub_limit_bits(limit_log2), d_acc);
     else
-        hipLaunchKernelGGL((scrub_kernel<false>), dim3(grid), dim3(kSbNT), 0, stream, d_buf, (long long)n, head, nvec,
-                           scrub_limit_bits(limit_log2), d_acc);
+        hipLaunchKernelGGL((scrub_kernel<false>), dim3(grid), dim3(kChunkNT), 0, stream, d_buf, sp, scrub_limit_bits(limit_log2), d_acc);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -198,77 +169,36 @@ static inline void scrub_result(const ScrubRun &t, int limit_log2, int active, i
     out->active = active;
 }
 
-// The pass of a context or a front end.  Configuration: the switch and the limit.  Cache: kSbSlots blocks on the device
-// with their pinned copies, allocated when the switch is first set.
-struct ScrubPass {
+// The pass of a context or a front end: the switch and the limit (configuration) and its ring (cache; pass_ring.hpp),
+// without a side stream -- the pass runs on the stream its chunk arrives on, in front of everything that reads the chunk.
+struct ScrubPass : PassRing {
     int on = 0, limit_log2 = kSbDefaultLog2;
-    ScrubAcc *d_acc[kSbSlots] = {}, *h_acc[kSbSlots] = {};
-    hipEvent_t ev[kSbSlots] = {};
 };
-// Stream state: the totals, and the launches whose figures have not been folded yet, oldest first.
-struct ScrubStream {
+// Stream state: the totals, and the launches in flight (an entry's meta: the stream position of the launch's first sample).
+struct ScrubStream : PassRingStream {
     ScrubRun run;
-    struct Pending { int slot; uint64_t base; size_t n; };
-    std::deque<Pending> pending;
-    uint64_t launches = 0;
 };
 
-static inline void scrub_pass_free(ScrubPass &ps)
+static inline auto scrub_folder(ScrubStream &st)
 {
-    for (int i = 0; i < kSbSlots; i++) {
-        if (ps.d_acc[i]) (void)hipFree(ps.d_acc[i]);
-        if (ps.h_acc[i]) (void)hipHostFree(ps.h_acc[i]);
-        if (ps.ev[i]) (void)hipEventDestroy(ps.ev[i]);
-    }
-    ps = ScrubPass{};
-}
-
-// the blocks, when the switch is first set (the device is current)
-static inline int scrub_pass_alloc(ScrubPass &ps)
-{
-    if (ps.ev[0]) return 0;
-    bool ok = true;
-    for (int i = 0; i < kSbSlots; i++) {
-        ok = ok && hipMalloc(reinterpret_cast<void **>(&ps.d_acc[i]), kSbBlockBytes) == hipSuccess;
-        ok = ok && hipHostMalloc(reinterpret_cast<void **>(&ps.h_acc[i]), kSbBlockBytes, hipHostMallocDefault) == hipSuccess;
-        ok = ok && hipEventCreateWithFlags(&ps.ev[i], hipEventDisableTiming) == hipSuccess;
-    }
-    if (!ok) {
-        const int on = ps.on, lim = ps.limit_log2;
-        scrub_pass_free(ps);
-        ps.on = on;
-        ps.limit_log2 = lim;
-        return -1;
-    }
-    return 0;
+    return [&st](const void *h_acc, const PassRingStream::Entry &e) { scrub_fold(st.run, static_cast<const ScrubAcc *>(h_acc), e.meta, e.n); };
 }
 
 // every launch in flight is waited for and folded, oldest first
-static inline int scrub_settle(ScrubPass &ps, ScrubStream &st, size_t keep = 0)
-{
-    while (st.pending.size() > keep) {
-        const ScrubStream::Pending e = st.pending.front();
-        if (hipEventSynchronize(ps.ev[e.slot]) != hipSuccess) return -1;
-        scrub_fold(st.run, ps.h_acc[e.slot], e.base, e.n);
-        st.pending.pop_front();
-    }
-    return 0;
-}
+static inline int scrub_settle(ScrubPass &ps, ScrubStream &st) { return ps.settle(st, ~0ull, scrub_folder(st)); }
 
 // The n cf32 samples at d_buf, which `stream` has produced, from stream position `base`: scrubbed on `stream`, the figures
-// on their way to a pinned block.  (At most kSbSlots - 1 launches stay in flight: a slot is free when it is taken again.)
+// on their way to a pinned block.  (A launch's tag is its number: taking a slot again settles its previous launch alone.)
 static inline int scrub_enqueue(ScrubPass &ps, ScrubStream &st, void *d_buf, size_t n, uint64_t base, hipStream_t stream)
 {
-    for (size_t off = 0; off < n; off += kSbMaxLaunch) {
-        const size_t piece = std::min(kSbMaxLaunch, n - off);
-        if (scrub_settle(ps, st, kSbSlots - 1) != 0) return -1;
-        const int slot = (int)(st.launches % kSbSlots);
-        if (hipMemsetAsync(ps.d_acc[slot], 0, kSbBlockBytes, stream) != hipSuccess) return -1;
-        if (launch_scrub(static_cast<char *>(d_buf) + off * 8, piece, ps.limit_log2, ps.d_acc[slot], stream) != 0) return -1;
-        if (hipMemcpyAsync(ps.h_acc[slot], ps.d_acc[slot], kSbBlockBytes, hipMemcpyDeviceToHost, stream) != hipSuccess) return -1;
-        if (hipEventRecord(ps.ev[slot], stream) != hipSuccess) return -1;
-        st.pending.push_back(ScrubStream::Pending{ slot, base + off, piece });
-        st.launches++;
+    for (size_t off = 0; off < n; off += kChunkMaxLaunch) {
+        const size_t piece = std::min(kChunkMaxLaunch, n - off);
+        const int slot = ps.acquire(st, scrub_folder(st));
+        if (slot < 0) return -1;
+        ScrubAcc *d_acc = static_cast<ScrubAcc *>(ps.d_block[slot]);
+        if (hipMemsetAsync(d_acc, 0, kSbBlockBytes, stream) != hipSuccess) return -1;
+        if (launch_scrub(static_cast<char *>(d_buf) + off * 8, piece, ps.limit_log2, d_acc, stream) != 0) return -1;
+        if (ps.commit(st, slot, kSbBlockBytes, stream, base + off, piece, st.launches) != 0) return -1;
     }
     return 0;
 }

@@ -1,6 +1,7 @@
 """The input statistics on the GPU (csrc/input_stats.hpp): irdm_input_stats_device against the integer / fsum model of
 tests/inputstats_model.py; the context option at pipeline_depth 0 and 3 with in-place look-ahead, records untouched by it,
-irdm_reset; the front end's getter; --input-stats and --diagnostic."""
+irdm_reset; the front end's getter; the result rings of input_stats, iq_moments and scrub (csrc/pass_ring.hpp) taken round
+more than twice without a read; --input-stats and --diagnostic."""
 import os
 import re
 import subprocess
@@ -8,11 +9,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import balance_checks as bc
+import balance_model as bm
 import cu8
 import formats16 as f16
 import input_stats_checks as ic
 import inputstats_model as im
 import irdm
+import scrub_checks as sc
+import scrub_model as sm
 import siggen
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +60,102 @@ def test_context_cuts_and_cf32(scene):
 
 def test_frontend_getter():
     ic.frontend_cuts((1 << 20) + 4321)
+
+
+# ---------------------------------------------------------------- the result ring, more than two turns ----
+RING_CHUNKS, RING_CHUNK = 11, 4099          # four slots: the eleventh launch takes slot 2 for the third time
+
+
+def ring_cf32(sizes):
+    """noise in the given cuts with a handful of bad samples in chunks 0, 5 and 10 -- in the vector part and, where the cut
+    has one, on its tail sample --, as interleaved floats; with it what option scrub leaves of it and the figures"""
+    n = sum(sizes)
+    x = (0.3 * np.random.default_rng(411).standard_normal(2 * n)).astype(np.float32)
+    starts = np.concatenate(([0], np.cumsum(sizes)))
+    for c in (0, 5, 10):
+        s, last = int(starts[c]), int(starts[c + 1]) - 1
+        x[2 * s] = np.float32("nan")                                   # I of the chunk's first sample
+        x[2 * (s + 7) + 1] = np.float32("inf")                         # Q inside a piece
+        x[2 * (s + 1026)], x[2 * (s + 1026) + 1] = np.float32("-inf"), np.float32("nan")
+        x[2 * last] = np.float32(1e30)                                 # finite, over the limit: the chunk's last sample
+    y, fig = sm.scrub(x, 40)
+    assert (fig["n_zeroed"], fig["n_nonfinite"], fig["n_over"], fig["first"], fig["last"]) == (12, 12, 3, 0, n - 1)
+    return x, y, fig
+
+
+def check_ring_records(scrub_st, stats_st, moments_st, y, fig, where):
+    """the three records, read once, against the models over what the passes behind the scrub saw"""
+    n = len(y) // 2
+    assert (int(scrub_st.n_samples), scrub_st.limit_log2, scrub_st.active) == (n, 40, 1), where
+    assert sc.stat_tuple(scrub_st) == tuple(fig[f] for f in sc.FIGURES), (where, sc.stat_tuple(scrub_st), fig)
+    im.check(stats_st, im.model(y.view(np.complex64), irdm.FMT_CF32), irdm.FMT_CF32, where)
+    assert list(stats_st.n_nonfinite) == [0, 0], where
+    bc.check_moments(moments_st, bm.moments(y), where)
+    assert int(moments_st.n_used) == n, where
+
+
+def test_ring_reuse_context():
+    """one cf32 context with scrub, input_stats and iq_moments on, eleven chunks through irdm_feed_host, no figure read in
+    between: every slot of the three rings is taken again while its previous launch may still be in flight, and the
+    records read at the end are the models'.  (A context's stream takes whole feed blocks until its last chunk: ten chunks
+    of two 2048-sample blocks, then one of 4099 samples with a tail behind its last 16-byte piece.)"""
+    sizes = [4096] * (RING_CHUNKS - 1) + [RING_CHUNK]
+    x, y, fig = ring_cf32(sizes)
+    p = irdm.Pipeline(2_000_000, fmt=irdm.FMT_CF32, feed_block=2048, max_chunk_samples=3 * 2048, max_bursts_per_chunk=256)
+    try:
+        for opt in ("scrub", "input_stats", "iq_moments"):
+            p.set_option(opt, 1)
+        c, off = x.view(np.complex64), 0
+        for s in sizes:
+            p.feed_host(np.ascontiguousarray(c[off:off + s]))
+            off += s
+        check_ring_records(p.scrub_stats(), p.input_stats(), p.iq_moments(), y, fig, "context")
+    finally:
+        p.close()
+
+
+def ring_front_end(fmt, scrub):
+    fe = irdm.Frontend(10_000_000, fmt, 5, 1_000_000.0)
+    p = irdm.Pipeline(fe.out_rate, fmt=irdm.FMT_CF32, max_chunk_samples=1 << 18, max_bursts_per_chunk=256)
+    fe.input_stats_enable(True)
+    fe.iq_moments_enable(True)
+    if scrub:
+        fe.scrub(True)
+    return fe, p
+
+
+def test_ring_reuse_front_end_cf32():
+    """the same through a cf32 front end, which takes any cut: eleven chunks of 4099 samples through
+    irdm_frontend_feed_host, every launch of the three passes with a vector part and a tail"""
+    sizes = [RING_CHUNK] * RING_CHUNKS
+    x, y, fig = ring_cf32(sizes)
+    fe, p = ring_front_end(irdm.FMT_CF32, True)
+    try:
+        c = x.view(np.complex64)
+        for k in range(RING_CHUNKS):
+            fe.feed_host(p, c[k * RING_CHUNK:(k + 1) * RING_CHUNK])
+        check_ring_records(fe.scrub_stats(), fe.input_stats(), fe.iq_moments(), y, fig, "cf32 front end")
+    finally:
+        p.close()
+        fe.close()
+
+
+def test_ring_reuse_front_end_ci16():
+    """the two statistics over a ci16 capture in eleven chunks of 4099 samples (1024 pieces and three samples behind them):
+    the integer record exactly the model's, the moments within the bound of any order of addition"""
+    n = RING_CHUNKS * RING_CHUNK
+    v = im.with_rails_at_the_ends(im.random_input(irdm.FMT_CI16, n, seed=412), irdm.FMT_CI16)
+    fe, p = ring_front_end(irdm.FMT_CI16, False)
+    try:
+        for k in range(RING_CHUNKS):
+            fe.feed_host(p, v[2 * k * RING_CHUNK:2 * (k + 1) * RING_CHUNK])
+        stats_st, moments_st = fe.input_stats(), fe.iq_moments()
+    finally:
+        p.close()
+        fe.close()
+    im.check(stats_st, im.model(v, irdm.FMT_CI16), irdm.FMT_CI16, "ci16 front end")
+    bc.check_moments(moments_st, bm.moments(bm.convert(v, irdm.FMT_CI16)), "ci16 front end")
+    assert int(moments_st.n_used) == n
 
 
 def clipped_scene():
