@@ -1081,6 +1081,29 @@ irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_rational_conf
  * irdm_frontend_create_rational would take the pair of rates as far as the ratio goes (an integer ratio 2 .. 16 included),
  * -1 with the create call's message on stderr otherwise.  L, M (either may be NULL) are set whenever both rates are positive. */
 int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L, int *M);
+
+/* The rational mode beyond L <= 125 and M <= 768 (K0w): the same function y[m], the same arithmetic, the same prototype from
+ * the same design, for 2 <= L <= 4096, M <= 65536, 24/25 <= M / L <= 16 (L != M) and a prototype of at most 2^20 taps -- a
+ * clock that is off by a fraction of a per cent (10.025 MS/s declared 10 MS/s: 400/401) and capture rates such as 2.88 MS/s
+ * (275/288 to 2.75 MS/s) or 8.01 MS/s (100/801 to 1 MS/s).  Its tile is a run of consecutive outputs and a lane owns whole
+ * outputs, so neither a period nor a phase block has to fit anything; the price is one vector load per tap where K0r has
+ * scalar loads.  A ratio both kernels take gives the same output bit for bit.
+ *
+ * irdm_frontend_resampler_ratio: the ratio out_rate / in_rate in lowest terms and the kernel that
+ * irdm_frontend_create_resampler would use -- *kernel 0: K0 (an integer ratio 2 .. 16), 1: K0r, 2: K0w -- without a device.
+ * 0, or -1 with a message on stderr beyond K0w's limits.  L, M (any of the three may be NULL) are set whenever both rates
+ * are positive. */
+int irdm_frontend_resampler_ratio(int in_rate, int out_rate, int *L, int *M, int *kernel);
+/* The front end for any pair of rates one of the three kernels takes: wherever irdm_frontend_create (an integer ratio) or
+ * irdm_frontend_create_rational would make the object it is theirs, bit for bit; K0w otherwise.  NULL (message on stderr)
+ * as irdm_frontend_create_rational. */
+irdm_frontend_t *irdm_frontend_create_resampler(const irdm_frontend_rational_config_t *cfg);
+/* Always K0w, for any ratio in K0w's limits (L >= 2: K0r's ratios included, for tests and measurements). */
+irdm_frontend_t *irdm_frontend_create_wide(const irdm_frontend_rational_config_t *cfg);
+/* K0w's launch geometry for a pair of rates, without a device: the prototype's length, the outputs per tile (one workgroup),
+ * the workgroup's dynamic LDS in bytes and how many workgroups per CU that size is chosen for.  Any pointer may be NULL.
+ * 0, or -1 (message) where irdm_frontend_create_wide would refuse the ratio or the prototype. */
+int irdm_frontend_wide_geometry(int in_rate, int out_rate, int *ntaps, int *tile_outputs, int *lds_bytes, int *workgroups_per_cu);
 /* the ratio in lowest terms: output rate = capture rate * L / M (1 / D for irdm_frontend_create's object).  0 ok, -1 error. */
 int irdm_frontend_ratio(const irdm_frontend_t *fe, int *L, int *M);
 

@@ -1,7 +1,8 @@
-// frontend_obj.hpp -- the front end's object, shared by its two makers: irdm_frontend_create (frontend.cpp: K0, integer
-// decimation) and irdm_frontend_create_rational (resample.cpp: K0r, L / M).  Everything behind creation -- the stream
-// bookkeeping, the feeder, reset -- is frontend.cpp's and works on the ratio L / M (1 / D for K0); the object carries its
-// kernel's launch function, so frontend.cpp refers to neither kernel file by name beyond K0's.
+// frontend_obj.hpp -- the front end's object, shared by its makers: irdm_frontend_create (frontend.cpp: K0, integer
+// decimation), irdm_frontend_create_rational (resample.cpp: K0r, L / M) and irdm_frontend_create_wide (resample_wide.cpp:
+// K0w, L / M at large L or M).  Everything behind creation -- the stream bookkeeping, the feeder, reset -- is frontend.cpp's
+// and works on the ratio L / M (1 / D for K0); the object carries its kernel's launch function, so frontend.cpp refers to
+// no kernel file by name beyond K0's.
 #pragma once
 #include "pipeline.hpp"
 
@@ -14,11 +15,13 @@ struct irdm_frontend {
     float *d_hr = nullptr, *d_G = nullptr;
     float2 *d_T = nullptr;
     void *d_tail[2] = { nullptr, nullptr };
-    // outputs [a.m0, a.m1) of [tail | chunk] on stream s: K0 (frontend.cpp) or K0r (resample.cpp)
+    // outputs [a.m0, a.m1) of [tail | chunk] on stream s: K0 (frontend.cpp), K0r (resample.cpp) or K0w (resample_wide.cpp)
     int (*launch)(irdm_frontend *fe, const irdm::FrontendArgs &a, hipStream_t s) = nullptr;
     // K0r: the launch geometry and the phase blocks' descriptors (d_G holds their tap rows)
     irdm::ResampleGeom geom{};
     int *d_desc = nullptr;
+    // K0w: the launch geometry (d_desc holds the phases' first inputs, d_G the prototype laid out [step][phase])
+    irdm::WideGeom wide{};
     // stream state (irdm_frontend_reset assigns a fresh one)
     struct State {
         int cur = 0;                // which of d_tail holds the carried tail
@@ -83,4 +86,11 @@ void fe_free(irdm_frontend *fe);
 // what both modes allocate: the rotation table, the kernel clock record, the two tail buffers (tail_samples each, 8 bytes
 // per sample), the stream in K1's priority class and the events.  fe->cfg.device is current.  false: allocation failed.
 bool fe_alloc_common(irdm_frontend *fe, size_t tail_samples);
+// resample.cpp.  out_rate / in_rate in lowest terms, L / M (false, with a message: a rate that is not positive).  K0r's limits: 0 inside them, 1 L or M too large, 2 M / L outside its
+// range.  The prototype of out_rate / in_rate = L / M.  What K0r and K0w share of creation: the checks behind the ratio, the object and its prototype -- launch function,
+// kernel tables and device memory are the caller's; nullptr with a message on stderr.
+bool fe_ratio(int in_rate, int out_rate, long long *L, long long *M);
+int fe_rational_domain(long long L, long long M);
+std::vector<float> fe_resample_taps(int in_rate, int out_rate, long long L);
+irdm_frontend *fe_new_resampled(const irdm_frontend_rational_config_t *cfg, long long L, long long M);
 }  // namespace irdmh

@@ -263,4 +263,28 @@ size_t resample_lds_bytes(const ResampleGeom &g);
 int launch_resample(const ResampleGeom &g, const FrontendArgs &a, const int *desc, const float *G, const float2 *T,
                     hipStream_t stream, unsigned long long *kclk);
 
+// resample_wide.hip (K0w): the same function as K0r for ratios K0r's shape does not fit (2 <= L <= 4096, M <= 65536, a
+// prototype of at most kRwMaxTaps taps).  A tile is a run of B consecutive outputs; the host-laid tables
+// (resample_wide_plan) are the first input of every phase, relative to its period's p M, and the prototype laid out as
+// [step][phase].
+constexpr int kRwU = 8;                   // steps per block of the tap loop
+constexpr int kRwMaxTaps = 1 << 20;
+struct WideGeom {
+    int L, M;                    // the ratio in lowest terms
+    int C;                       // (ntaps - 1) / 2
+    int S;                       // steps: the most terms an output has, ceil(ntaps / L); every output has S - 1 at least
+    int B;                       // outputs per tile
+    int cnt_max;                 // staged samples per tile, at most
+    int pad_s;                   // a pad sample follows every pad_s staged samples (0: none)
+    unsigned magic;              // floor(2^32 / pad_s) + 1: g / pad_s = (g * magic) >> 32 for every staged index g
+    int wg_per_cu;               // workgroups the tile's LDS lets a CU hold: 4, 2 or 1
+};
+// taps: the prototype P (ntaps, odd).  Fills the geometry, nlo[r] (L ints) and W ((S + 2 kRwU) rows of L floats; no term:
+// zero, and not used); false when the ratio or the prototype does not fit the kernel.
+bool resample_wide_plan(int L, int M, const float *taps, int ntaps, WideGeom *g, std::vector<int> *nlo, std::vector<float> *W);
+size_t resample_wide_lds_bytes(const WideGeom &g);
+// outputs [a.m0, a.m1) of the rational front end into a.out
+int launch_resample_wide(const WideGeom &g, const FrontendArgs &a, const int *nlo, const float *W, const float2 *T,
+                         hipStream_t stream, unsigned long long *kclk);
+
 }  // namespace irdm

@@ -16,34 +16,46 @@ static int fe_launch_k0r(irdm_frontend *fe, const FrontendArgs &a, hipStream_t s
     return launch_resample(fe->geom, a, fe->d_desc, fe->d_G, fe->d_T, s, fe->d_kclk);
 }
 
-static long long gcd_ll(long long a, long long b)
+// out_rate / in_rate in lowest terms, L / M; false (message) for a rate that is not positive
+bool fe_ratio(int in_rate, int out_rate, long long *L, long long *M)
 {
+    if (in_rate <= 0 || out_rate <= 0) {
+        fprintf(stderr, "irdm_hip: front end: sample rates %d -> %d\n", in_rate, out_rate);
+        return false;
+    }
+    long long a = in_rate, b = out_rate;
     while (b) {
         const long long t = a % b;
         a = b;
         b = t;
     }
-    return a;
+    *L = out_rate / a;
+    *M = in_rate / a;
+    return true;
+}
+
+// K0r's limits on a ratio in lowest terms: 0 inside them, 1 L or M too large, 2 M / L outside 24/25 .. 16 or equal to 1
+int fe_rational_domain(long long L, long long M)
+{
+    if (L > 125 || M > 768) return 1;
+    return L == M || 25 * M < 24 * L || M > 16 * L ? 2 : 0;
 }
 
 // the ratio in lowest terms and the limits on it, for the create call and for callers that must refuse before they start
 // (the binary): 0 within the limits (an integer ratio 2 .. 16 included), -1 with a message otherwise.  Needs no device.
 extern "C" int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L_out, int *M_out)
 {
-    if (in_rate <= 0 || out_rate <= 0) {
-        fprintf(stderr, "irdm_hip: front end: sample rates %d -> %d\n", in_rate, out_rate);
-        return -1;
-    }
-    const long long gd = gcd_ll(in_rate, out_rate);
-    const long long L = out_rate / gd, M = in_rate / gd;
+    long long L = 0, M = 0;
+    if (!fe_ratio(in_rate, out_rate, &L, &M)) return -1;
     if (L_out) *L_out = (int)L;
     if (M_out) *M_out = (int)M;
-    if (L > 125 || M > 768) {
+    const int where = fe_rational_domain(L, M);
+    if (where == 1) {
         fprintf(stderr, "irdm_hip: front end: %d -> %d samples/s is the ratio %lld/%lld; L <= 125 and M <= 768 are built\n",
                 in_rate, out_rate, L, M);
         return -1;
     }
-    if (L == M || 25 * M < 24 * L || M > 16 * L) {
+    if (where == 2) {
         fprintf(stderr, "irdm_hip: front end: %d -> %d samples/s (ratio %lld/%lld): M / L must lie in 24/25 .. 16 and differ from 1\n",
                 in_rate, out_rate, L, M);
         return -1;
@@ -51,22 +63,18 @@ extern "C" int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L_ou
     return 0;
 }
 
-extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_rational_config_t *cfg)
+// the prototype P of the ratio L / M = out_rate / in_rate (the header comment)
+std::vector<float> fe_resample_taps(int in_rate, int out_rate, long long L)
 {
-    if (!cfg) return nullptr;
-    int Li = 0, Mi = 0;
-    if (irdm_frontend_rational_ratio(cfg->in_rate, cfg->out_rate, &Li, &Mi) != 0) return nullptr;
-    const long long L = Li, M = Mi;
-    if (L == 1 && M >= 2 && M <= 16) {
-        irdm_frontend_config_t ic;
-        memset(&ic, 0, sizeof(ic));
-        ic.device = cfg->device;
-        ic.in_rate = cfg->in_rate;
-        ic.in_format = cfg->in_format;
-        ic.decim = (int)M;
-        ic.shift_hz = cfg->shift_hz;
-        return irdm_frontend_create(&ic);
-    }
+    const float f_min = (float)std::min(in_rate, out_rate);
+    return design_lpf((float)L, (float)(L * (long long)in_rate), 0.5f * f_min, 0.09f * f_min);
+}
+
+// What K0r and K0w (resample_wide.cpp) share of creation, for the ratio L / M in lowest terms: the checks of format, output
+// rate, shift and device, the object and its prototype.  The kernel's tables, the launch function and the device memory
+// are the caller's.  nullptr with a message on stderr.
+irdm_frontend *fe_new_resampled(const irdm_frontend_rational_config_t *cfg, long long L, long long M)
+{
     if (!fmt_valid(cfg->in_format)) {
         fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
         return nullptr;
@@ -98,15 +106,35 @@ extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_ra
     fe->D = 0;
     fe->L = (int)L;
     fe->M = (int)M;
-    fe->launch = fe_launch_k0r;
     fe->fmt = cfg->in_format;
     fe->bps = fmt_bytes(fe->fmt);
     fe->out_rate = cfg->out_rate;
     fe->q = q;
-    const float f_min = (float)std::min(cfg->in_rate, cfg->out_rate);
-    fe->taps = design_lpf((float)L, (float)(L * (long long)cfg->in_rate), 0.5f * f_min, 0.09f * f_min);
+    fe->taps = fe_resample_taps(cfg->in_rate, cfg->out_rate, L);
     fe->ntaps = (int)fe->taps.size();
     fe->c = (fe->ntaps - 1) / 2;
+    return fe;
+}
+
+extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_rational_config_t *cfg)
+{
+    if (!cfg) return nullptr;
+    int Li = 0, Mi = 0;
+    if (irdm_frontend_rational_ratio(cfg->in_rate, cfg->out_rate, &Li, &Mi) != 0) return nullptr;
+    const long long L = Li, M = Mi;
+    if (L == 1 && M >= 2 && M <= 16) {
+        irdm_frontend_config_t ic;
+        memset(&ic, 0, sizeof(ic));
+        ic.device = cfg->device;
+        ic.in_rate = cfg->in_rate;
+        ic.in_format = cfg->in_format;
+        ic.decim = (int)M;
+        ic.shift_hz = cfg->shift_hz;
+        return irdm_frontend_create(&ic);
+    }
+    irdm_frontend *fe = fe_new_resampled(cfg, L, M);
+    if (!fe) return nullptr;
+    fe->launch = fe_launch_k0r;
     std::vector<int> desc;
     std::vector<float> G;
     if (!resample_plan(fe->L, fe->M, fe->taps.data(), fe->ntaps, &fe->geom, &desc, &G)) {

@@ -40,10 +40,11 @@
  * around HZ is shifted to the centre, low-passed and decimated by D (2 .. 16) on the GPU in front of the detector
  * (irdm_frontend_*): a 50 MS/s capture with --decimate 5 runs as a 10 MS/s stream centred at HZ (at the nearest multiple
  * of RATE / 65536 from -c, printed with -v).  --chunk stays in samples of the decimated stream.
- * --resample-to HZ: the same front end in its rational mode (irdm_frontend_create_rational) -- the capture, described by -r
- * and -c, is resampled on the GPU to HZ = RATE * L / M (L <= 125, M <= 768, 24/25 <= M / L <= 16) in front of the detector:
+ * --resample-to HZ: the same front end in its rational mode (irdm_frontend_create_resampler) -- the capture, described by -r
+ * and -c, is resampled on the GPU to HZ = RATE * L / M (L <= 4096, M <= 65536, 24/25 <= M / L <= 16) in front of the detector:
  * for captures whose rate is no multiple of 250 kHz (2.4 MS/s, 11.2 MS/s, 61.44 MS/s ...), which the demodulator cannot
- * follow to the end of a frame.  --band-center is optional with it (without: no shift); --decimate, --gpus N > 1 and HZ =
+ * follow to the end of a frame, and for a clock that is off (10.025 MS/s declared 10 MS/s: 400/401, what --clock-check
+ * suggests).  --band-center is optional with it (without: no shift); --decimate, --gpus N > 1 and HZ =
  * RATE are refused.  --chunk counts samples of the resampled stream.
  * Several recordings in one run: -f more than once and / or --files-from LIST (one "PATH" or "PATH START_SEC[.NNNNNNNNN]"
  * per line).  They go, in the order given, through ONE context, one front end and one pair of pinned buffers, with
@@ -1146,7 +1147,7 @@ int main(int argc, char **argv)
             return 2;
         }
         /* the library's own check of the ratio (its message), before anything is started */
-        if (irdm_frontend_rational_ratio((int)rate, resample_to, &rs_l, &rs_m) != 0) return 2;
+        if (irdm_frontend_resampler_ratio((int)rate, resample_to, &rs_l, &rs_m, NULL) != 0) return 2;
         gpus = 0;
     }
     if (decimate && gpus > 1) {
@@ -1325,9 +1326,9 @@ int main(int argc, char **argv)
         fc.in_format = proc_fmt;
         fc.out_rate = resample_to;
         fc.shift_hz = band_given ? band_center - freq : 0.0;
-        fe = irdm_frontend_create_rational(&fc);
+        fe = irdm_frontend_create_resampler(&fc);
         if (!fe) {
-            fprintf(stderr, "irdm_frontend_create_rational failed (no MI355X / bad parameters)\n");
+            fprintf(stderr, "irdm_frontend_create_resampler failed (no MI355X / bad parameters)\n");
             return 1;
         }
     }

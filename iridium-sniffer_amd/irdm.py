@@ -495,6 +495,12 @@ def lib():
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
                 L.irdm_frontend_ratio.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
                 L.irdm_frontend_rational_ratio.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            if hasattr(L, "irdm_frontend_create_wide"):        # (csrc/resample_wide.cpp)
+                for name in ("irdm_frontend_create_wide", "irdm_frontend_create_resampler"):
+                    getattr(L, name).restype = C.c_void_p
+                    getattr(L, name).argtypes = [C.POINTER(FrontendRationalConfig)]
+                L.irdm_frontend_resampler_ratio.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
+                L.irdm_frontend_wide_geometry.argtypes = [C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 4
         _lib = L
     return _lib
 
@@ -1070,16 +1076,16 @@ class Frontend:
     """irdm_frontend_*: band select in front of a Pipeline -- shift by shift_hz, low-pass, decimate by decim.  The pipeline
     behind it is a cf32 context at out_rate, centred at the capture centre + applied_shift_hz."""
 
-    def __init__(self, in_rate, fmt, decim, shift_hz=0.0, device=0, out_rate=None):
+    def __init__(self, in_rate, fmt, decim, shift_hz=0.0, device=0, out_rate=None, maker="rational"):
         self.L = lib()
         if out_rate is None:
             self.cfg = FrontendConfig(device, int(in_rate), fmt, int(decim), float(shift_hz))
             self.h = self.L.irdm_frontend_create(C.byref(self.cfg))
         else:
             self.cfg = FrontendRationalConfig(device, int(in_rate), fmt, int(out_rate), float(shift_hz))
-            self.h = self.L.irdm_frontend_create_rational(C.byref(self.cfg))
+            self.h = getattr(self.L, "irdm_frontend_create_" + maker)(C.byref(self.cfg))
         if not self.h:
-            raise RuntimeError("irdm_frontend_create%s failed (no GPU, or bad config)" % ("" if out_rate is None else "_rational"))
+            raise RuntimeError("irdm_frontend_create%s failed (no GPU, or bad config)" % ("" if out_rate is None else "_" + maker))
         self.fmt = fmt
         self.out_rate = self.L.irdm_frontend_out_rate(self.h)
         self.applied_shift_hz = self.L.irdm_frontend_applied_shift_hz(self.h)
@@ -1090,6 +1096,32 @@ class Frontend:
         """irdm_frontend_create_rational: resample to out_rate = in_rate * L / M (an integer ratio 2 .. 16 gives the
         integer front end)"""
         return cls(in_rate, fmt, None, shift_hz, device, out_rate=out_rate)
+
+    @classmethod
+    def resampler(cls, in_rate, fmt, out_rate, shift_hz=0.0, device=0):
+        """irdm_frontend_create_resampler: the integer front end, K0r or K0w, whichever takes out_rate / in_rate"""
+        return cls(in_rate, fmt, None, shift_hz, device, out_rate=out_rate, maker="resampler")
+
+    @classmethod
+    def wide(cls, in_rate, fmt, out_rate, shift_hz=0.0, device=0):
+        """irdm_frontend_create_wide: K0w, for any ratio with 2 <= L <= 4096, M <= 65536, 24/25 <= M / L <= 16"""
+        return cls(in_rate, fmt, None, shift_hz, device, out_rate=out_rate, maker="wide")
+
+    @staticmethod
+    def resampler_ratio(in_rate, out_rate):
+        """irdm_frontend_resampler_ratio: (L, M, kernel) -- kernel 0 K0, 1 K0r, 2 K0w -- or None beyond K0w's limits"""
+        l, m, k = C.c_int(0), C.c_int(0), C.c_int(-1)
+        if lib().irdm_frontend_resampler_ratio(int(in_rate), int(out_rate), C.byref(l), C.byref(m), C.byref(k)) != 0:
+            return None
+        return l.value, m.value, k.value
+
+    @staticmethod
+    def wide_geometry(in_rate, out_rate):
+        """irdm_frontend_wide_geometry: dict(ntaps, tile, lds_bytes, wg_per_cu) of K0w at out_rate / in_rate (no device)"""
+        v = [C.c_int(0) for _ in range(4)]
+        if lib().irdm_frontend_wide_geometry(int(in_rate), int(out_rate), *[C.byref(x) for x in v]) != 0:
+            raise RuntimeError("irdm_frontend_wide_geometry refused %d -> %d" % (in_rate, out_rate))
+        return dict(zip(("ntaps", "tile", "lds_bytes", "wg_per_cu"), (x.value for x in v)))
 
     @property
     def ratio(self):
