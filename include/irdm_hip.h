@@ -563,7 +563,8 @@ int irdm_burst_samples(irdm_pipeline_t *p, int burst_in_chunk, float *out, size_
 
 /* Stage B alone for one burst: burst_downmix_process() (burst_downmix.h:70).  `info` carries the
  * burst_info_t fields (id, start, center_bin, magnitude, noise are used), `samples` the burst_data_t IQ
- * (host, num_samples complex floats).  Fills *frame (drop_reason 0 = frame produced, 1..5 = the reference's
+ * (host, num_samples complex floats), used verbatim whatever info->start: the window need not lie where the detector's
+ * feed blocks would have delivered it.  Fills *frame (drop_reason 0 = frame produced, 1..5 = the reference's
  * early returns) and, when a frame was produced, frame_samples (2 * IRDM_MAX_FRAME_SAMPLES floats).
  * cf32 contexts only.  Returns 1 (frame), 0 (dropped) or -1 (error). */
 int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, const float *samples, size_t num_samples,

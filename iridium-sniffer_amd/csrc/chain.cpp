@@ -433,6 +433,9 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
         // the frame [stop, stop+N) was processed by the feed call that delivered its last sample
         uint64_t e = (g.stop + (uint64_t)P.n + p->feed_block - 1) / p->feed_block * p->feed_block;
         r.avail_end = std::min<uint64_t>(e, src.chunk_end);
+        // (a stage-level call hands over the samples the reference's detector had extracted already: burst_downmix.c reads
+        // burst->samples verbatim, wherever the window lies in the feed blocks)
+        if (p->whole_window) r.avail_end = src.chunk_end;
 
         BurstWork &w = b.hp_work[i];
         memset(&w, 0, sizeof(w));

@@ -385,6 +385,7 @@ struct irdm_pipeline {
     int frame_records;          // option: packed_records, and one irdm_frame_packed_t per irdm_demod_packed_t
     int chunk_marks;            // option: StreamState::q_marks
     int keep_frame_samples;
+    int whole_window = 0;       // irdm_downmix_burst is running: the source IS the burst window, every sample of it delivered
     // rotator checkpoint rows on demand (rot_rows_prepare)
     int *d_rot_slot = nullptr;              // [n][rot_runs] centre bin, run -> block of d_rot_table, -1: none yet (written by the kernel that builds the run)
     int rot_runs = 0;                       // runs of kRotRun checkpoints per bin

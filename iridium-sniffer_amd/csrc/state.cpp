@@ -286,7 +286,9 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     const uint64_t tagged = p->st.tagged;
     std::vector<irdm_burst_t> last; last.swap(p->st.last_bursts);
     p->keep_frame_samples = 1;
+    p->whole_window = 1;         // avail_end = info->start + num_samples, not what a feed block would have delivered
     const int rc = process_bursts(p, p->bc[0], src, &g, 1);
+    p->whole_window = 0;
     int ret = -1;
     if (rc == 0 && !p->st.q.frames.empty()) {
         *frame = p->st.q.frames.front();

@@ -365,6 +365,7 @@ def lib():
         L.irdm_sample_count.argtypes = [C.c_void_p]
         L.irdm_sample_count.restype = C.c_uint64
         L.irdm_fft_size.argtypes = [C.c_void_p]
+        L.irdm_set_stream_origin.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
         L.irdm_last_magnitudes.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         L.irdm_baseline_sum.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.irdm_burst_samples.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float), C.c_size_t]

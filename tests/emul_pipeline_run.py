@@ -92,6 +92,14 @@ def main():
             fs, iq = scenes.ALL[name]()
             ref = orc.run_stream(iq, fs)
             res[name] = parity.compare(parity.run_gpu(iq, fs), ref)
+        # a batch that mixes the frame classes: the simplex scene centred at 1625.55 MHz, frames below 1626 MHz (1910 samples)
+        # and above (4440) in one chunk -- one post2 / rot_phase_rows launch over both
+        fs, iq = scenes.frame_lengths(simplex=True)
+        ref = orc.run_stream(iq, fs, center_frequency=1625.55e6)
+        lens = [f.num_samples for f in ref.frames if f.drop_reason == 0]
+        assert 1910 in lens and 4440 in lens, lens
+        res["frame_lengths_simplex_mixed"] = parity.compare(parity.run_gpu(iq, fs, center_frequency=1625.55e6), ref)
+        res["frame_lengths_simplex_mixed"].update(normal=lens.count(1910), simplex=lens.count(4440))
     elif case == "10mhz":
         # 8192-point frames, decimation by 40: K1's radix-16 kernel (writing the band scan's candidate lists once the
         # detector is primed) and the register-resident decimator (fir_reg.hip: columns in registers, DPP shifts,

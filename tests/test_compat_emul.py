@@ -4,6 +4,7 @@ program that drives them the way main.c does -- linked against the emulated buil
 checked by the very functions of tests/test_gpu_compat.py against the oracle."""
 import os
 import subprocess
+import sys
 
 import pytest
 
@@ -31,3 +32,13 @@ def test_reference_stage_api_on_the_emulation(compat_exe_emul, tmp_path, fmt):
 
 def test_stream_tail_and_getters_on_the_emulation(compat_exe_emul, tmp_path):
     G.test_stream_tail_and_stats_getters(compat_exe_emul, tmp_path)
+
+
+def test_downmix_process_uses_the_whole_window_on_the_emulation():
+    """(the emulated library in a process of its own, like every emulated run: the check is the -m gpu test's)"""
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import ctypes, sys; sys.path[:0] = [%r, %r]; import test_gpu_compat as G; "
+            "G.downmix_process_whole_window(ctypes.CDLL(sys.argv[1])); print('RESULT ok')"
+            % (here, os.path.join(ROOT, "iridium-sniffer_amd")))
+    p = subprocess.run([sys.executable, "-c", code, emul_build.build()], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "RESULT ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]

@@ -152,3 +152,83 @@ def test_non_default_geometry_is_refused(compat_exe):
     assert h
     L.burst_downmix_destroy.argtypes = [C.c_void_p]
     L.burst_downmix_destroy(h)
+
+
+def downmix_process_whole_window(L):
+    """burst_downmix_process of the library L (ctypes) on a hand-built burst_data_t whose window ends exactly on a feed-block
+    boundary minus N, past the reference's ring -- where the detector's feed block would not have delivered its last N
+    samples: the reference reads burst->samples verbatim (burst_downmix.c:650-651), so the frame equals the oracle's on
+    the same samples, every sample bit for bit."""
+    import ctypes as C
+    import rates
+    import stage_b_cases as sb
+
+    class Info(C.Structure):                # include/irdm_compat.h: burst_info_t
+        _fields_ = [("id", C.c_uint64), ("start", C.c_uint64), ("stop", C.c_uint64), ("last_active", C.c_uint64),
+                    ("center_bin", C.c_int), ("magnitude", C.c_float), ("noise", C.c_float)]
+
+    class Data(C.Structure):                # burst_data_t
+        _fields_ = [("info", Info), ("center_frequency", C.c_double), ("sample_rate", C.c_int), ("fft_size", C.c_int),
+                    ("start_time_ns", C.c_uint64), ("num_samples", C.c_size_t), ("samples", C.POINTER(C.c_float))]
+
+    class Out(C.Structure):                 # downmix_frame_t
+        _fields_ = [("id", C.c_uint64), ("timestamp", C.c_uint64), ("center_frequency", C.c_double),
+                    ("sample_rate", C.c_float), ("samples_per_symbol", C.c_float), ("direction", C.c_int),
+                    ("magnitude", C.c_float), ("noise", C.c_float), ("uw_start", C.c_float), ("num_samples", C.c_size_t),
+                    ("samples", C.POINTER(C.c_float))]
+
+    class Dm(C.Structure):
+        _fields_ = [("output_sample_rate", C.c_int), ("search_depth", C.c_int), ("handle_multiple_frames", C.c_int)]
+
+    fs = 10_000_000
+    n_fft = rates.fft_size(fs)
+    # the downlink window at 2300 outputs: the frame reaches into the window's last N samples
+    name, iq, center_bin, fc = [w for w in sb.windows(fs) if w[0] == "downlink_2300"][0]
+    start = dict(sb.starts(fs, len(iq)))["ends_on_block"]
+    assert start >= sb.ref_ring(fs) and (start + len(iq) - n_fft) % sb.BLOCK == 0
+    O = orc.lib()
+    rec = orc.BurstRec(id=7, start=start, stop=start + len(iq) - 2 * n_fft, last_active=start, center_bin=center_bin,
+                       magnitude=-21.5, noise=-109.25, num_samples=len(iq))
+    want = orc.Frame()
+    odm = O.orc_downmix_create()
+    ok = O.orc_downmix_process(odm, C.byref(rec), orc.fptr(iq.view(np.float32)), fc, fs, n_fft, sb.T0, C.byref(want))
+    O.orc_downmix_destroy(odm)
+    assert ok and want.num_samples == 1910
+
+    L.burst_downmix_create.restype = C.c_void_p
+    L.burst_downmix_create.argtypes = [C.POINTER(Dm)]
+    L.burst_downmix_process.argtypes = [C.c_void_p, C.POINTER(Data), C.POINTER(C.POINTER(Out))]
+    L.burst_downmix_destroy.argtypes = [C.c_void_p]
+    L.irdm_compat_shutdown.restype = None
+    libc = C.CDLL(None)
+    libc.free.argtypes = [C.c_void_p]
+    libc.free.restype = None
+    x = np.array(iq, np.complex64)          # (the reference's burst->samples is not const: a copy of the shared window)
+    burst = Data(Info(rec.id, rec.start, rec.stop, rec.last_active, center_bin, rec.magnitude, rec.noise), fc, fs, n_fft,
+                 sb.T0, len(x), orc.fptr(x.view(np.float32)))
+    dm = L.burst_downmix_create(C.byref(Dm(0, 0, 0)))
+    assert dm
+    try:
+        out = C.POINTER(Out)()
+        assert L.burst_downmix_process(dm, C.byref(burst), C.byref(out)) == 1 and out
+        f = out.contents
+        try:
+            assert f.num_samples == want.num_samples and f.direction == want.direction == 1
+            assert np.float32(f.uw_start).view(np.uint32) == np.float32(want.uw_start).view(np.uint32)
+            assert (f.id, f.timestamp, f.center_frequency) == (want.id, want.timestamp, want.center_frequency)
+            got = np.ctypeslib.as_array(f.samples, (2 * f.num_samples,)).view(np.uint32)
+            ws = np.ctypeslib.as_array(want.samples)[:2 * want.num_samples].view(np.uint32)
+            bad = np.flatnonzero(got != ws)
+            assert len(bad) == 0, "%d of %d frame floats differ from the oracle, from index %d" % (len(bad), len(ws), bad[0])
+            assert np.array_equal(x, iq), "burst_downmix_process wrote to the burst's samples"
+        finally:
+            # burst_downmix.c:812-823: the caller frees the frame and its samples; the burst stays the caller's
+            libc.free(f.samples)
+            libc.free(out)
+    finally:
+        L.burst_downmix_destroy(dm)
+        L.irdm_compat_shutdown()
+
+
+def test_downmix_process_uses_the_whole_window():
+    downmix_process_whole_window(irdm.lib())

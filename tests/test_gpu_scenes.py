@@ -29,14 +29,24 @@ def _chunks(n, parts):
 CASES = {name: ({}, {}) for name in scenes.ALL}
 # capture centred above 1626 MHz: the simplex frame-length rules (burst_downmix.c:764-767)
 CASES["frame_lengths_simplex"] = (dict(simplex=True), dict(center_frequency=1626.4e6))
+# the same scene centred at 1625.55 MHz: four frames below 1626 MHz (1910 samples) and five above (4440) in ONE chunk, hence
+# one post2 / rot_phase_rows launch over both classes of frame length
+CASES["frame_lengths_simplex_mixed"] = (dict(simplex=True), dict(center_frequency=1625.55e6))
+
+
+def _frame_classes(case, ref):
+    if case == "frame_lengths_simplex_mixed":
+        lens = [f.num_samples for f in ref.frames if f.drop_reason == 0]
+        assert 1910 in lens and 4440 in lens, lens
 
 
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_scene_parity_sparse_dense_and_chunked(case):
-    name = case.replace("_simplex", "")
+    name = case.split("_simplex")[0]
     skw, ckw = CASES[case]
     fs, iq = scenes.ALL[name](**skw)
     ref = orc.run_stream(iq, fs, **ckw)
+    _frame_classes(case, ref)
     got = parity.run_gpu(iq, fs, **ckw)                            # band scan (sequential kernels if it declines)
     s = parity.compare(got, ref)
     dense = parity.run_gpu(iq, fs, scan_mode=1, **ckw)
@@ -57,10 +67,11 @@ def test_scene_parity_single_cu_scan(case):
     """scan_mode 2: the sparse scan confined to one workgroup (the default, scan_mode 0, spreads the baseline updates over
     updater workgroups on MI355X -- scan_fast.hip, MC form) -- same scenes, one chunk and chunked in throughput mode;
     every record must equal the oracle's"""
-    name = case.replace("_simplex", "")
+    name = case.split("_simplex")[0]
     skw, ckw = CASES[case]
     fs, iq = scenes.ALL[name](**skw)
     ref = orc.run_stream(iq, fs, **ckw)
+    _frame_classes(case, ref)
     got = parity.run_gpu(iq, fs, scan_mode=2, **ckw)
     parity.compare(got, ref)
     chunked = parity.run_gpu(iq, fs, chunks=_chunks(len(iq), 5), depth=1, scan_mode=2, **ckw)

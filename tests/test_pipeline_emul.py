@@ -57,6 +57,8 @@ def test_workgroup_order_does_not_matter(emul_lib, order):
 def test_whole_path_scene_zoo(emul_lib):
     res = run_case(emul_lib, "scene_zoo")
     assert res["too_long"]["bursts"] >= 2 and res["squelch"]["bursts"] >= 1 and res["dc_and_edges"]["bursts"] >= 1, res
+    mixed = res["frame_lengths_simplex_mixed"]
+    assert mixed["normal"] >= 1 and mixed["simplex"] >= 1 and mixed["frames"] == mixed["normal"] + mixed["simplex"], res
 
 
 def test_whole_path_10mhz_register_resident_decimator(emul_lib):
