@@ -478,6 +478,38 @@ int irdm_advance(irdm_pipeline_t *p);
  * irdm_feed_begin still waits for its irdm_feed_end, when a scan waits for a history import (irdm_expect_history), or for
  * a member of a group (a group is not reset: destroy and create it). */
 int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t start_time_ns);
+/* Priming from the recording's own head (no reference counterpart: burst_detect.c can start no burst before its 512-frame
+ * history is full, so a recording's first 512 FFT frames -- 0.37 to 0.70 s -- are searched by nobody; a program that has
+ * the whole file can do better).  Given the n_samples leading samples of a recording -- in the format irdm_feed_host
+ * takes: the configured one, or irdm_iq_balance's wire format --, with N = irdm_fft_size and H = 512 N:
+ *   F = min(512, n_samples / N) whole frames are used (F == 0: -1);
+ *   the prefix P is H samples long, frame k of it is frame k mod F of the given samples (a recording shorter than H is
+ *   primed from itself, tiled: the tiling is device copies, F frames are uploaded once);
+ *   P is fed as the head of the stream through the ordinary path, in pieces of at most max_chunk_samples: K1, the detector
+ *   scan and the history ring as usual, options swap_iq and scrub and irdm_iq_balance applied as on any chunk of
+ *   irdm_feed_host -- and every side pass off: nothing of P enters irdm_input_stats, irdm_iq_moments, irdm_scrub_stats or
+ *   the rows of option spectrum_frames;
+ *   the time origin moves to T0' = T0 - floor(H 10^9 / sample_rate) ns, which irdm_start_time_ns returns from then on.
+ * The caller then feeds the recording from its sample 0 as usual: file sample i is stream position H + i.
+ * Records (bursts, frames, demods, packed, parsed and frame records, symbol_clock and iq_sense votes): exactly those of a
+ * plain context with the same options, created with start time T0' and fed P followed by the recording; sample indices
+ * in them count from the start of P.  Bursts of P itself are found and queued like any others (they repeat the
+ * recording's).  Not promised: equality with the unprimed run on later bursts -- the baseline is a running float sum with a
+ * different past.
+ * Side passes: the results of a plain context fed the recording alone with start time T0 -- counts and sums without P,
+ * positions relative to the recording (irdm_scrub_stats first / last; a spectrum row's first_frame and timestamp_ns).
+ * irdm_sample_count, chunk marks and irdm_chunks_complete count the priming feeds like any other feed.
+ * Valid only on a fresh stream -- after irdm_create or irdm_reset, before the first feed, import or seed -- and not for a
+ * member of a group; feed_block must divide H (the default does).  Otherwise -1 and nothing changed.  -1 from a failed feed
+ * leaves the stream where it stopped: irdm_reset starts over.  irdm_reset ends the priming with the stream;
+ * irdm_export_state / irdm_import_state work as on any stream at a position >= H.
+ * _device: the same from a device buffer (stream: its producer, as in irdm_feed_device); the buffer may be reused when the
+ * call returns.  Unlike irdm_feed_device it goes the way of irdm_feed_host's chunks, swap_iq / scrub / irdm_iq_balance
+ * included: the prefix is assembled in the context's own buffers, the caller's is only read. */
+int irdm_prime_host(irdm_pipeline_t *p, const void *h_iq, size_t n_samples);
+int irdm_prime_device(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, void *stream);
+uint64_t irdm_primed_samples(const irdm_pipeline_t *p);  /* H, or 0 when the stream is not primed */
+int irdm_primed_frames(const irdm_pipeline_t *p);        /* F, or 0 */
 /* Pinned (page-locked) host memory for feed buffers, for hosts without HIP headers.  NULL on failure. */
 void *irdm_host_alloc(size_t bytes);
 void irdm_host_free(void *ptr);
@@ -1039,6 +1071,15 @@ int irdm_frontend_flush(irdm_frontend_t *fe, irdm_pipeline_t *p);
  * nothing held back by the feeder, not finished.  Taps, tables and the applied shift stay; nothing is allocated.  Waits for
  * the front end's stream.  0 ok, -1 error. */
 int irdm_frontend_reset(irdm_frontend_t *fe);
+/* irdm_prime_host behind a front end: the capture's first n_in samples (the format irdm_frontend_feed_host takes) run
+ * through K0 / K0r / K0w without a flush -- irdm_frontend_swap_iq, _iq_balance and _scrub applied; saving, input statistics,
+ * moments and the scrub's figures off -- until 512 frames of the band are there, and p is primed from the whole frames the
+ * front end handed on (F: irdm_primed_frames(p); fewer than one: -1).  Then the front end is as irdm_frontend_reset leaves
+ * it: the real run starts at input 0.  The band irdm_frontend_save writes and every figure of the front end are exactly
+ * those of the run without priming; the context's records are those of a plain context fed P(y) followed by y, the band
+ * of the plain run.  For 512 frames hand over at least ceil((512 N M + ntaps) / L) samples at the ratio L / M.  fe and
+ * p must both be fresh (irdm_prime_host's conditions); -1 otherwise. */
+int irdm_frontend_prime_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in);
 /* A capture taken up at input sample total_in, not at 0: the state that feeding total_in samples of zero codes (all-zero
  * bytes) would have left -- the stream position total_in (the rotator's phase index and the resampler's polyphase schedule
  * with it), every output that those samples complete counted as produced, the carried tail zeros.  Valid only directly

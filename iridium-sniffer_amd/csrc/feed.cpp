@@ -65,7 +65,7 @@ static int spectrum_harvest(irdm_pipeline *p, int wait_slot)
             SpecRow r;
             r.hdr.row = b.row0 + (uint64_t)i;
             r.hdr.first_frame = b.frame0 + (uint64_t)i * (uint64_t)p->spectrum_R;
-            r.hdr.timestamp_ns = s.start_time_ns + (uint64_t)((double)(r.hdr.first_frame * n) / (double)p->cfg.sample_rate * 1e9);
+            r.hdr.timestamp_ns = s.start_time_ns + s.prime_shift_ns + (uint64_t)((double)(r.hdr.first_frame * n) / (double)p->cfg.sample_rate * 1e9);
             r.hdr.n_frames = (uint32_t)b.n_frames;
             r.hdr.n_bins = (uint32_t)n;
             const float *src = p->hp_spec[b.slot] + (size_t)i * 2 * n;
@@ -99,7 +99,7 @@ static int spectrum_enqueue(irdm_pipeline *p, const float *mag, int n_frames, ui
     const int R = p->spectrum_R;
     if (!s.spec_started) {
         s.spec_started = true;
-        s.spec_row_frame = c0 / (uint64_t)p->P.n;
+        s.spec_row_frame = (c0 - s.primed_samples) / (uint64_t)p->P.n;    // (a primed stream: frames of the recording)
     }
     if (spectrum_harvest(p, (int)(s.spec_batches % kSpecSlots)) != 0) return -1;
     if (launch_spectrum(mag, p->P.n, n_frames, R, s.spec_fill, p->spec_carry(s.spec_sel), p->spec_carry(s.spec_sel ^ 1), p->d_spec_ws,
@@ -412,11 +412,11 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     const int n_frames = (int)(n_samples / (size_t)P.n);
     // option "input_stats": the chunk's pass, on its side stream behind the chunk's arrival (settled by this chunk's
     // irdm_feed_end, before the caller may overwrite d_iq)
-    if (p->in_stats.on &&
+    if (p->in_stats.on && !p->priming &&
         input_stats_enqueue(p->in_stats, p->st.in_stats, p->dev_fmt, d_iq, n_samples, caller, p->st.begin_no) != 0)
         return -1;
     // option "iq_moments": likewise, on a side stream of its own
-    if (p->iqm.on && iq_moments_enqueue(p->iqm, p->st.iqm, p->dev_fmt, d_iq, n_samples, caller, p->st.begin_no) != 0) return -1;
+    if (p->iqm.on && !p->priming && iq_moments_enqueue(p->iqm, p->st.iqm, p->dev_fmt, d_iq, n_samples, caller, p->st.begin_no) != 0) return -1;
 
     // K1 of this chunk.  pipeline_depth 1: on its own stream and into the other magnitude buffer, while the detector
     // scan of the previous chunk may still be running
@@ -452,7 +452,7 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
     if (p->depth && !in_ring && (ring_guard(p, c0, c1, p->fstream) != 0 || ring_update(p, d_iq, c0, c1, p->fstream) != 0)) return -1;
     IRDM_HIP_CHECK(hipEventRecord(f.ev_copy, p->fstream));
     // option "spectrum_frames": the plane's reduction, behind everything a feed waits for
-    if (p->spectrum_R && n_frames > 0 && spectrum_enqueue(p, mag, n_frames, c0) != 0) return -1;
+    if (p->spectrum_R && !p->priming && n_frames > 0 && spectrum_enqueue(p, mag, n_frames, c0) != 0) return -1;
     f.st.iq = d_iq;
     f.st.c0 = c0;
     f.st.c1 = c1;
@@ -656,9 +656,16 @@ static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples, voi
         if (p->swap_iq && launch_iq_swap(p->bal.wire_fmt, src, n_samples, p->fstream) != 0) return -1;
         if (launch_iq_balance(p->bal.wire_fmt, d_iq, src, n_samples, p->bal.alpha, p->bal.beta, p->fstream) != 0) return -1;
     } else if (p->swap_iq && launch_iq_swap(p->dev_fmt, d_iq, n_samples, p->fstream) != 0) return -1;
-    if (p->scrub.on && p->dev_fmt == IRDM_FMT_CF32 &&
-        scrub_enqueue(p->scrub, p->st.scrub, d_iq, n_samples, p->st.begun_samples, p->fstream) != 0)
-        return -1;
+    if (p->scrub.on && p->dev_fmt == IRDM_FMT_CF32) {
+        if (p->priming) {
+            // (the prefix of irdm_prime_*: cleaned like any chunk, no figures)
+            for (size_t off = 0; off < n_samples; off += kChunkMaxLaunch)
+                if (launch_scrub(static_cast<char *>(d_iq) + off * 8, std::min(kChunkMaxLaunch, n_samples - off), p->scrub.limit_log2,
+                                 nullptr, p->fstream) != 0)
+                    return -1;
+        } else if (scrub_enqueue(p->scrub, p->st.scrub, d_iq, n_samples, p->st.begun_samples - p->st.primed_samples, p->fstream) != 0)
+            return -1;
+    }
     p->feed_inner = true;
     const int rc = irdm_feed_device(p, d_iq, n_samples, p->fstream);
     p->feed_inner = false;
@@ -690,6 +697,97 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     IRDM_HIP_CHECK(hipMemcpyAsync(wire ? wire : p->d_stage, h_iq, wire_bytes, hipMemcpyHostToDevice, p->fstream));
     return feed_host_arrived(p, p->d_stage, n_samples, wire);
 }
+
+// ---- irdm_prime_host / irdm_prime_device: the detector's 512-frame history filled from the recording's own head ----
+
+// May the context be primed from n_samples leading samples?  The whole frames that would be used (1 .. 512), or -1: not a
+// fresh stream (something has been fed, imported or primed since irdm_create / irdm_reset), a member of a group, fewer
+// samples than one frame, or a feed_block that 512 frames are not a whole number of.
+int prime_check(const irdm_pipeline *p, size_t n_samples)
+{
+    if (!p || p->in_group) return -1;
+    const StreamState &s = p->st;
+    if (s.begin_no || s.begun_samples || s.total_samples || s.chunk_no || s.host_primed || s.primed_samples || s.stream_closed ||
+        s.gate_armed || s.gate_open_pending)
+        return -1;
+    const size_t N = (size_t)p->P.n, H = (size_t)kHistory * N;
+    if (H % (size_t)p->feed_block != 0 || n_samples < N) return -1;
+    return (int)std::min<size_t>((size_t)kHistory, n_samples / N);
+}
+
+// The prefix P -- frame k of it is frame k mod F of the F whole frames at d_head (device memory, the format irdm_feed_host
+// takes; whatever produced them lies in front on fstream) -- fed as the head of the stream: every piece of at most
+// max_chunk is put together by device copies where a chunk of irdm_feed_host lands, and goes the way such a chunk goes
+// (swap_iq, irdm_iq_balance, scrub, K1, the ring, the scan) with the side passes off; the time origin moves back by the
+// prefix.  -1: a feed failed and the stream stands where it stopped (irdm_reset starts over).
+int prime_from_device(irdm_pipeline *p, const void *d_head, int F)
+{
+    const size_t N = (size_t)p->P.n, H = (size_t)kHistory * N, period = (size_t)F * N;
+    void *wire = p->bal.on && p->bal.wire_fmt != IRDM_FMT_CF32 ? p->bal.d_wire : nullptr;
+    const size_t wb = (size_t)(p->bal.on ? fmt_bytes(p->bal.wire_fmt) : p->bps);
+    const size_t step = p->max_chunk / (size_t)p->feed_block * (size_t)p->feed_block;
+    // (the origin first: the records of bursts that end inside the prefix are built during these feeds)
+    const uint64_t shift = (uint64_t)H * 1000000000ull / (uint64_t)p->cfg.sample_rate;
+    p->st.start_time_ns -= shift;
+    p->st.prime_shift_ns = shift;
+    p->st.primed_samples = H;
+    p->st.primed_frames = F;
+    int rc = 0;
+    p->priming = true;
+    for (size_t s0 = 0; rc >= 0 && s0 < H; s0 += step) {
+        const size_t len = std::min(step, H - s0);
+        void *slot = irdm_ingest_ptr(p, len);
+        if (!slot) {
+            if (!p->d_stage && hipMalloc(&p->d_stage, p->max_chunk * p->bps) != hipSuccess) rc = -1;
+            slot = p->d_stage;
+        }
+        char *land = static_cast<char *>(wire ? wire : slot);
+        for (size_t pos = s0; rc >= 0 && pos < s0 + len;) {
+            const size_t o = pos % period, run = std::min(period - o, s0 + len - pos);
+            if (hipMemcpyAsync(land + (pos - s0) * wb, static_cast<const char *>(d_head) + o * wb, run * wb, hipMemcpyDeviceToDevice,
+                               p->fstream) != hipSuccess)
+                rc = -1;
+            pos += run;
+        }
+        if (rc >= 0) rc = feed_host_arrived(p, slot, len, wire);
+    }
+    p->priming = false;
+    if (rc < 0) return -1;
+    // (the copies read d_head on fstream: behind them the caller's buffer is its own again)
+    IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
+    return 0;
+}
+
+extern "C" int irdm_prime_host(irdm_pipeline_t *p, const void *h_iq, size_t n_samples)
+{
+    const int F = prime_check(p, n_samples);
+    if (F < 0 || !h_iq) return -1;
+    pipeline_enter(p);
+    const size_t bytes = (size_t)F * (size_t)p->P.n * (size_t)(p->bal.on ? fmt_bytes(p->bal.wire_fmt) : p->bps);
+    void *d_head = nullptr;
+    if (hipMalloc(&d_head, bytes) != hipSuccess) return -1;
+    int rc = hipMemcpyAsync(d_head, h_iq, bytes, hipMemcpyHostToDevice, p->fstream) == hipSuccess ? 0 : -1;
+    if (rc == 0) rc = prime_from_device(p, d_head, F);
+    if (rc != 0) (void)hipStreamSynchronize(p->fstream);
+    (void)hipFree(d_head);
+    return rc;
+}
+
+extern "C" int irdm_prime_device(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, void *stream_v)
+{
+    const int F = prime_check(p, n_samples);
+    if (F < 0 || !d_iq) return -1;
+    pipeline_enter(p);
+    hipStream_t caller = static_cast<hipStream_t>(stream_v);
+    if (caller && caller != p->fstream) {
+        IRDM_HIP_CHECK(hipEventRecord(p->ev[8], caller));
+        IRDM_HIP_CHECK(hipStreamWaitEvent(p->fstream, p->ev[8], 0));
+    }
+    return prime_from_device(p, d_iq, F);
+}
+
+extern "C" uint64_t irdm_primed_samples(const irdm_pipeline_t *p) { return p ? p->st.primed_samples : 0; }
+extern "C" int irdm_primed_frames(const irdm_pipeline_t *p) { return p ? p->st.primed_frames : 0; }
 
 // irdm_swap_iq_device: the exchange alone, on a buffer the caller owns (iq_swap.hpp)
 extern "C" int irdm_swap_iq_device(void *d_iq, size_t n_samples, int format, int device, void *stream_v)

@@ -245,7 +245,7 @@ static int fe_emit(irdm_frontend *fe, const void *d_in, size_t n_in, uint64_t m1
     a.fmt = fe->fmt;
     if (fe->launch(fe, a, s) != 0) return -1;
     if (launch_kclk_fold(fe->d_kclk, s) != 0) return -1;
-    if (fe->sv.sink && fe_save_tap(fe, out, (size_t)(m1 - fe->st.n_out), s) != 0) return -1;
+    if (fe->sv.sink && !fe->priming && fe_save_tap(fe, out, (size_t)(m1 - fe->st.n_out), s) != 0) return -1;
     fe->st.n_out = m1;
     return 0;
 }
@@ -506,10 +506,11 @@ extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p
     return bursts;
 }
 
-extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in)
+// n_in capture samples at h_in into the staging buffer on the front end's stream, the way irdm_frontend_feed_host takes a
+// chunk: irdm_frontend_swap_iq, irdm_frontend_iq_balance and irdm_frontend_scrub applied (count: with the scrub's figures,
+// positions from fe->st.total).  ev_caller is recorded behind the copy from h_in.
+static int fe_land_host(irdm_frontend *fe, const void *h_in, size_t n_in, bool count)
 {
-    if (fe_check(fe, p) != 0 || (!h_in && n_in)) return -1;
-    pipeline_enter(p);
     const size_t bytes = n_in * (size_t)fe->bps;
     if (bytes > fe->stage_bytes) {
         IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
@@ -539,9 +540,24 @@ extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, 
     // irdm_frontend_iq_balance: then corrected into the cf32 staging buffer (a cf32 wire format: in place)
     if (fe->bal.on && launch_iq_balance(fe->bal.wire_fmt, fe->d_stage, land, n_in, fe->bal.alpha, fe->bal.beta, fe->stream) != 0) return -1;
     // irdm_frontend_scrub: then its non-finite and out-of-range samples zeroed (cf32 alone), positions counted in the capture
-    if (fe->scrub.on && fe->fmt == IRDM_FMT_CF32 &&
-        scrub_enqueue(fe->scrub, fe->st.scrub, fe->d_stage, n_in, fe->st.total, fe->stream) != 0)
-        return -1;
+    if (fe->scrub.on && fe->fmt == IRDM_FMT_CF32) {
+        if (count) {
+            if (scrub_enqueue(fe->scrub, fe->st.scrub, fe->d_stage, n_in, fe->st.total, fe->stream) != 0) return -1;
+        } else {
+            for (size_t off = 0; off < n_in; off += kChunkMaxLaunch)
+                if (launch_scrub(static_cast<char *>(fe->d_stage) + off * 8, std::min(kChunkMaxLaunch, n_in - off), fe->scrub.limit_log2,
+                                 nullptr, fe->stream) != 0)
+                    return -1;
+        }
+    }
+    return 0;
+}
+
+extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in)
+{
+    if (fe_check(fe, p) != 0 || (!h_in && n_in)) return -1;
+    pipeline_enter(p);
+    if (fe_land_host(fe, h_in, n_in, true) != 0) return -1;
     fe->feed_inner = true;
     const int bursts = irdm_frontend_feed_device(fe, p, fe->d_stage, n_in, nullptr);
     fe->feed_inner = false;
@@ -576,6 +592,41 @@ extern "C" int irdm_frontend_reset(irdm_frontend_t *fe)
     if (fe->iqm.stream) IRDM_HIP_CHECK(hipStreamSynchronize(fe->iqm.stream));
     fe->st = irdm_frontend::State{};
     return 0;
+}
+
+// The capture's first n_in samples through the kernel without a flush, in pieces of at most 4 Mi samples, until 512
+// frames of the band are there (or the samples are used up); saving, the statistics passes and the scrub's figures off.
+// The context is primed from the whole frames of that band (irdm_prime_device), and the front end is reset: the real run
+// starts at input 0, and what it saves and reports is what the run without priming saves and reports.
+extern "C" int irdm_frontend_prime_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in)
+{
+    if (fe_check(fe, p) != 0 || !h_in || fe->st.total || fe->st.n_out || fe->st.n_tail || fe->st.pend) return -1;
+    const size_t N = (size_t)p->P.n, H = (size_t)kHistory * N;
+    // (no more of the capture than completes H outputs: fe_commit keeps a tail of a few taps, not a backlog)
+    const uint64_t n_full = (((uint64_t)H - 1) * (uint64_t)fe->M + (uint64_t)fe->c + (uint64_t)fe->L) / (uint64_t)fe->L;
+    n_in = (size_t)std::min<uint64_t>(n_in, n_full);
+    const uint64_t m_all = fe_outputs(fe, n_in, false);
+    if (prime_check(p, (size_t)m_all) < 0) return -1;
+    pipeline_enter(p);
+    float2 *d_band = dev_alloc<float2>((size_t)m_all);
+    if (!d_band) return -1;
+    const size_t piece_max = (size_t)4 << 20;
+    int rc = 0;
+    fe->priming = true;
+    for (size_t off = 0; rc == 0 && off < n_in; off += piece_max) {
+        const size_t piece = std::min(piece_max, n_in - off);
+        const uint64_t m1 = fe_outputs(fe, fe->st.total + piece, false);
+        rc = fe_land_host(fe, static_cast<const char *>(h_in) + off * (size_t)(fe->bal.on ? fmt_bytes(fe->bal.wire_fmt) : fe->bps), piece, false);
+        if (rc == 0) rc = fe_emit(fe, fe->d_stage, piece, m1, d_band + fe->st.n_out, fe->stream);
+        if (rc == 0) rc = fe_commit(fe, fe->d_stage, piece, fe->stream);
+        if (rc == 0 && hipEventSynchronize(fe->ev_caller) != hipSuccess) rc = -1;
+    }
+    fe->priming = false;
+    if (rc == 0) rc = irdm_prime_device(p, d_band, (size_t)fe->st.n_out, fe->stream);
+    (void)hipStreamSynchronize(fe->stream);
+    (void)hipFree(d_band);
+    if (irdm_frontend_reset(fe) != 0) return -1;
+    return rc;
 }
 
 // A capture taken up at input sample total_in: the state that fe_emit / fe_commit would have left behind total_in samples

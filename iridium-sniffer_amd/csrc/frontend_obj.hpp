@@ -65,6 +65,8 @@ struct irdm_frontend {
     // (configuration); feed_inner marks that call's own device feed, the only one the switch allows
     int swap_iq = 0;
     bool feed_inner = false;
+    // irdm_frontend_prime_host is running the capture's head through the kernel: fe_emit saves nothing of it
+    bool priming = false;
     // irdm_frontend_scrub: irdm_frontend_feed_host zeroes the non-finite and out-of-range samples of every cf32 capture
     // chunk in its staging buffer (scrub.on, scrub.limit_log2: configuration; the blocks: cache)
     irdm::ScrubPass scrub;

@@ -244,6 +244,12 @@ struct StreamState {
     ScrubStream scrub;
     // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)
     IqMomentsStream iqm;
+    // irdm_prime_host / _device (feed.cpp): the samples of the prefix fed in front of the recording (0: not primed), the
+    // whole frames of the recording's head it was tiled from, and what the prefix moved start_time_ns back by -- the side
+    // passes count positions and times from the recording's first sample, that is from primed_samples and
+    // start_time_ns + prime_shift_ns
+    uint64_t primed_samples = 0, prime_shift_ns = 0;
+    int primed_frames = 0;
 };
 
 struct irdm_pipeline {
@@ -446,6 +452,8 @@ struct irdm_pipeline {
     // feed_inner marks irdm_feed_host's own call of irdm_feed_device, the only device feed the option allows
     int swap_iq = 0;
     bool feed_inner = false;
+    // irdm_prime_*'s own feeds of the prefix are under way: every side pass is off for them (feed.cpp)
+    bool priming = false;
     // options "scrub" / "scrub_limit_log2" (feed.cpp, scrub.hpp): irdm_feed_host zeroes the non-finite and out-of-range
     // samples of every cf32 chunk on the device; scrub.on and scrub.limit_log2 are configuration, the blocks cache
     // (allocated when the option is first set on a cf32 context)
@@ -507,6 +515,8 @@ int symbol_clock_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
 int scrub_configure(irdm_pipeline *p, int on);
 int iq_moments_configure(irdm_pipeline *p, int on);
+int prime_check(const irdm_pipeline *p, size_t n_samples);
+int prime_from_device(irdm_pipeline *p, const void *d_head, int F);
 
 // scan_host.cpp
 int scan_hop_in(irdm_pipeline *p);

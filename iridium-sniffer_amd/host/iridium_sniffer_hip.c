@@ -11,7 +11,7 @@
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
  *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]]
- *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG]
+ *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -139,6 +139,23 @@
  * created as cf32 and takes the file's format as its wire format.  Raw file or container; allowed with --save-only /
  * --save-band, which then write the corrected band.  -v names the option and alpha, beta once.  Every closing line then
  * describes the stream as processed, which is cf32.  Refused with --gpus N > 1.
+ * --prime: the detector finds nothing in a stream's first 512 FFT frames (0.37 to 0.70 s), which fill its noise history; a
+ * file is all there, so every recording of the run is primed from its own head first (irdm_prime_host,
+ * irdm_frontend_prime_host): the first 512 frames -- of a shorter recording the frames it has, repeated -- go through the
+ * detector in front of the recording, and the recording then runs from its sample 0 with a full history.  Raw file,
+ * container or standard input (the head, at most 64 MiB, is kept in memory and not read twice), behind --band-center /
+ * --decimate / --resample-to (the head goes through the front end), in a batch after each reset.  --start-time and header
+ * times still name the recording's first sample.  stdout gains the early frames; every closing line but "tagged" and every
+ * side file (--spectrum, --save-band) is what the run without the flag writes.  -v: "primed: 512 frames from the first F".
+ * A recording shorter than one frame runs unprimed with a warning.  Refused with --gpus N > 1 and with --save-only.
+ * --join: every -f and every --files-from entry is a part of ONE recording, cut by the recorder (SDR#, HDSDR and SDR Console
+ * start a new WAV every 2 or 4 GB): the parts' sample regions -- a container's data, a raw file whole -- run one behind the
+ * other as one stream: one reset, one output (--out-dir names it after the first part; --spectrum and --save-band take plain
+ * names), one set of closing lines, one ACARS / position state, chunks filled across the parts' edges wherever they fall.
+ * Format and rate must agree, and the centres wherever headers give them (exit 2).  The start time is the first part's or
+ * --start-time; a later part whose own time is more than 1 ms off the stream's gets one warning, no gap is inserted.  The
+ * parts are read with one fread() thread.  -f - beside other inputs, --gpus N > 1 and --save-only are refused.  --prime with
+ * --join primes from the joined stream's head.
  */
 #include <err.h>
 #include <errno.h>
@@ -216,6 +233,13 @@ typedef struct {
     pthread_t th;
 } slice_t;
 
+/* --join: the sample region of one input, [off, off + bytes) of f (bytes -1: to the end of the stream) */
+typedef struct {
+    FILE *f;
+    off_t off;
+    long long bytes;
+} seg_t;
+
 typedef struct {
     FILE *f;
     size_t bps, chunk;
@@ -226,6 +250,12 @@ typedef struct {
     int n_slices;               /* 0: fread */
     off_t pos, size;            /* the slices read [pos, size) of the file */
     long long remain;           /* fread: bytes left of a container's samples (-1: to the end of the stream) */
+    /* fread, --prime on standard input: the head that was read for priming, handed out again in front of the stream */
+    const char *pre;
+    size_t pre_n;
+    /* fread, --join: the regions behind the one at hand (f, remain), taken up one after the other in mid-chunk */
+    const seg_t *segs;
+    int n_seg, seg;
     slice_t sl[MAX_SLICES];
 } reader_t;
 
@@ -286,10 +316,27 @@ static void *reader_main(void *arg)
         if (r->n_slices) {
             r->n[k] = read_slices(r, r->buf[k]);
         } else {
-            size_t want = r->chunk;
-            if (r->remain >= 0 && (unsigned long long)r->remain / r->bps < want) want = (size_t)((unsigned long long)r->remain / r->bps);
-            r->n[k] = want ? fread(r->buf[k], r->bps, want, r->f) : 0;
-            if (r->remain >= 0) r->remain -= (long long)(r->n[k] * r->bps);
+            size_t got = 0;
+            if (r->pre_n) {
+                got = r->pre_n < r->chunk ? r->pre_n : r->chunk;
+                memcpy(r->buf[k], r->pre, got * r->bps);
+                r->pre += got * r->bps;
+                r->pre_n -= got;
+            }
+            while (got < r->chunk) {
+                size_t want = r->chunk - got;
+                if (r->remain >= 0 && (unsigned long long)r->remain / r->bps < want) want = (size_t)((unsigned long long)r->remain / r->bps);
+                const size_t g = want ? fread((char *)r->buf[k] + got * r->bps, r->bps, want, r->f) : 0;
+                if (r->remain >= 0) r->remain -= (long long)(g * r->bps);
+                got += g;
+                if (got == r->chunk) break;
+                /* this region is used up: the next one goes on in the same chunk (--join), or the stream ends here */
+                if (r->seg + 1 >= r->n_seg) break;
+                r->seg++;
+                r->f = r->segs[r->seg].f;
+                r->remain = r->segs[r->seg].bytes;
+            }
+            r->n[k] = got;
         }
         sem_post(&r->filled);
         if (r->n[k] < r->chunk) {                   /* short read: after it an explicit end marker */
@@ -918,6 +965,43 @@ static const char *base_of(const char *p)
     return s ? s + 1 : p;
 }
 
+/* The sample region of an opened input: a container's [data_offset, data_offset + data_bytes), cut to what the file
+ * holds; a raw file whole; whole samples either way.  bytes -1: a pipe, read to its end. */
+static seg_t region_of(FILE *f, const input_t *in, size_t bps)
+{
+    seg_t s = { f, 0, -1 };
+    struct stat sb;
+    const int regular = f != stdin && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode);
+    if (in->kind > 0) {
+        s.off = (off_t)in->info->data_offset;
+        s.bytes = (long long)in->info->data_bytes;
+        if (regular && (off_t)s.off + (off_t)s.bytes > sb.st_size) s.bytes = sb.st_size > s.off ? (long long)(sb.st_size - s.off) : 0;
+    } else if (regular)
+        s.bytes = (long long)sb.st_size;
+    if (s.bytes > 0) s.bytes -= s.bytes % (long long)bps;
+    return s;
+}
+
+/* --prime: up to `want` leading samples of the regions into head -- pread() on files, which leaves their read positions
+ * alone; standard input is read, and the reader hands those samples out again (reader_t.pre).  Returns the samples read. */
+static size_t read_head(const seg_t *segs, int n_seg, size_t bps, size_t want, char *head)
+{
+    size_t got = 0;
+    for (int k = 0; k < n_seg && got < want; k++) {
+        if (segs[k].bytes < 0) return k == 0 ? fread(head, bps, want, segs[k].f) : got;     /* (a pipe: only in front) */
+        size_t left = want - got, have = (size_t)((unsigned long long)segs[k].bytes / bps), done = 0;
+        if (left > have) left = have;
+        while (done < left * bps) {
+            const ssize_t r = pread(fileno(segs[k].f), head + got * bps + done, left * bps - done, segs[k].off + (off_t)done);
+            if (r <= 0) break;
+            done += (size_t)r;
+        }
+        got += done / bps;
+        if (done < left * bps) break;
+    }
+    return got;
+}
+
 int main(int argc, char **argv)
 {
     const double t_main = now_s();
@@ -948,6 +1032,7 @@ int main(int argc, char **argv)
     const char *save_band = NULL, *save_format = NULL;     /* --save-band FILE | auto, --save-format */
     double save_gain = 1.0;
     int save_gain_given = 0, save_only = 0, save_fmt = -1;
+    int prime = 0, join = 0;               /* --prime, --join */
     for (int i = 1; i < argc; i++) {
         const char *a = argv[i];
 #define NEXT() (i + 1 < argc ? argv[++i] : (fprintf(stderr, "missing value for %s\n", a), exit(2), ""))
@@ -1048,6 +1133,8 @@ int main(int argc, char **argv)
             }
         }
         else if (!strcmp(a, "--image-check")) g_image = 1;
+        else if (!strcmp(a, "--prime")) prime = 1;
+        else if (!strcmp(a, "--join")) join = 1;
         else if (!strcmp(a, "--iq-balance") || !strncmp(a, "--iq-balance=", 13)) {
             /* (the --iq-balance=GAIN_DB,PHASE_DEG form only) */
             char *end = NULL, *end2 = NULL;
@@ -1104,6 +1191,33 @@ int main(int argc, char **argv)
         for (int k = 0; k < g_n_in; k++) fprintf(stderr, "%s\n", g_in[k].err);
         return g_n_in == 1 ? 2 : 1;
     }
+    if (join) {
+        /* one recording in parts: every part must be there, and the headers must describe one capture */
+        int bad = 0;
+        for (int k = 0; k < g_n_in; k++)
+            if (g_in[k].kind < 0) { fprintf(stderr, "%s\n", g_in[k].err); bad = 1; }
+        if (bad) { fprintf(stderr, "--join: every part must be readable\n"); return 2; }
+        for (int k = 0, c0 = -1, r0 = -1; k < g_n_in; k++) {
+            if (g_in[k].kind <= 0) continue;
+            if (r0 >= 0 && g_in[k].hdr_rate != g_in[r0].hdr_rate) {
+                fprintf(stderr, "--join: %s (%d samples/s) and %s (%d samples/s) are not parts of one capture\n", g_in[r0].path,
+                        g_in[r0].hdr_rate, g_in[k].path, g_in[k].hdr_rate);
+                return 2;
+            }
+            r0 = k;
+            if (!g_in[k].info->has_center) continue;
+            if (c0 >= 0 && g_in[k].info->center_frequency != g_in[c0].info->center_frequency) {
+                fprintf(stderr, "--join: %s (%.0f Hz) and %s (%.0f Hz) are not parts of one capture\n", g_in[c0].path,
+                        g_in[c0].info->center_frequency, g_in[k].path, g_in[k].info->center_frequency);
+                return 2;
+            }
+            c0 = k;
+        }
+        if (gpus > 1) { fprintf(stderr, "--join: one GPU only (--gpus %d)\n", gpus); return 2; }
+        if (save_only) { fprintf(stderr, "--join with --save-only: not supported; run the band's recording through --save-band\n"); return 2; }
+    }
+    /* the recordings of the run: with --join all inputs are one */
+    const int n_rec = join ? (g_n_in > 0) : g_n_in;
     if (g_n_in && rate <= 0) {
         /* no -r: every input carries its rate, and they agree */
         for (int k = 0; k < g_n_in; k++) {
@@ -1122,7 +1236,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1161,12 +1275,23 @@ int main(int argc, char **argv)
         return 2;
     }
     if (g_n_in > 1) gpus = 0;
+    if (prime) {
+        if (gpus > 1) {
+            fprintf(stderr, "--prime: one GPU only (--gpus %d): a member of a group is not primed\n", gpus);
+            return 2;
+        }
+        if (save_only) {
+            fprintf(stderr, "--prime with --save-only: no context runs, so there is no detector to prime\n");
+            return 2;
+        }
+        gpus = 0;
+    }
     if (spectrum) {
         if (gpus > 1) {
             fprintf(stderr, "--spectrum: one GPU only (--gpus %d)\n", gpus);
             return 2;
         }
-        if ((g_n_in > 1 || !strcmp(spectrum, "auto")) && (strcmp(spectrum, "auto") != 0 || !out_dir)) {
+        if ((n_rec > 1 || !strcmp(spectrum, "auto")) && (strcmp(spectrum, "auto") != 0 || !out_dir)) {
             fprintf(stderr, "--spectrum with several recordings: give --spectrum auto and --out-dir DIR (DIR/<basename>.spec each)\n");
             return 2;
         }
@@ -1241,7 +1366,7 @@ int main(int argc, char **argv)
             fprintf(stderr, "--save-band saves the band a front end selects: give --band-center / --decimate or --resample-to\n");
             return 2;
         }
-        const int many = g_n_in > 1 || !strcmp(save_band, "auto");
+        const int many = n_rec > 1 || !strcmp(save_band, "auto");
         if (many && (strcmp(save_band, "auto") != 0 || !out_dir)) {
             fprintf(stderr, "--save-band with several recordings: give --save-band auto and --out-dir DIR (DIR/<basename>.band.<format> each)\n");
             return 2;
@@ -1288,7 +1413,7 @@ int main(int argc, char **argv)
                     g_in[first].path, freq, g_in[k].path, g_in[k].centre);
             return 2;
         }
-        for (int j = 0; out_dir && j < k; j++)
+        for (int j = 0; out_dir && !join && j < k; j++)
             if (!strcmp(base_of(g_in[j].path), base_of(g_in[k].path))) {
                 fprintf(stderr, "--out-dir: %s and %s would share %s/%s.out\n", g_in[j].path, g_in[k].path, out_dir, base_of(g_in[k].path));
                 return 2;
@@ -1498,7 +1623,19 @@ int main(int argc, char **argv)
     int rc_all = 0;
     FILE *f = NULL;
     double t_down = 0;
-    for (int fi = 0; fi < g_n_in; fi++) {
+    seg_t *segs = calloc((size_t)g_n_in, sizeof(*segs));
+    if (!d || !segs) { fprintf(stderr, "out of memory\n"); return 1; }
+    /* --prime: the capture samples that complete 512 frames in front of the detector (behind a front end: at its ratio, with
+     * its taps; the library takes no more of them than it needs) */
+    size_t head_cap = 0;
+    char *head = NULL;
+    if (prime) {
+        const size_t H = (size_t)512 * (size_t)irdm_fft_size(p);
+        head_cap = !fe ? H : (resample_to ? (H * (size_t)rs_m + (size_t)irdm_frontend_ntaps(fe)) / (size_t)rs_l + 2
+                                          : H * (size_t)decimate + (size_t)irdm_frontend_ntaps(fe) + 2);
+        if (!(head = malloc(head_cap * bps))) { fprintf(stderr, "--prime: out of memory\n"); return 1; }
+    }
+    for (int fi = 0; fi < n_rec; fi++) {
         const char *file = g_in[fi].path;
         const double t_file = now_s();
         double reset_ms = 0;
@@ -1571,6 +1708,30 @@ int main(int argc, char **argv)
             irdm_doppler_set_origin(g_dop, irdm_start_time_ns(p));
             fprintf(stderr, "Doppler positioning: enabled (height aiding: %.0f m)\n", position_height);     /* main.c:597-605 */
         }
+        /* the recording's time origin: a primed context's own lies 512 frames earlier */
+        const uint64_t rec_t0 = irdm_start_time_ns(p);
+        /* the recording's sample regions: its own, or with --join every input's, one behind the other */
+        int n_seg = 1;
+        segs[0] = region_of(f, in, bps);
+        if (join) {
+            unsigned long long before = segs[0].bytes > 0 ? (unsigned long long)segs[0].bytes / bps : 0;
+            for (int k = 1; k < g_n_in; k++) {
+                const input_t *part = &g_in[k];
+                const char *pd = part->kind > 0 ? part->info->data_path : part->path;
+                FILE *pf = fopen(pd, "rb");
+                if (!pf) { perror(pd); return 1; }
+                segs[k] = region_of(pf, part, bps);
+                if (part->start_ns) {
+                    /* the part's own time against the stream's: said once, no gap is inserted */
+                    const double late = ((double)part->start_ns - (double)rec_t0) * 1e-9 - (double)before / rate;
+                    if (fabs(late) > 1e-3)
+                        fprintf(stderr, "warning: --join: %s starts %.6f s %s than the stream has got to; the parts are joined without a gap\n",
+                                part->path, fabs(late), late > 0 ? "later" : "earlier");
+                }
+                before += segs[k].bytes > 0 ? (unsigned long long)segs[k].bytes / bps : 0;
+            }
+            n_seg = g_n_in;
+        }
         if (verbose && fi == 0) fprintf(stderr, "%s: fft_size=%d chunk=%zu samples, %d GPU%s\n", irdm_version(), irdm_fft_size(p), chunk,
                              gpus > 0 ? gpus : 1, gpus > 1 ? "s" : "");
         if (verbose && fi == 0 && fe && resample_to)
@@ -1592,13 +1753,34 @@ int main(int argc, char **argv)
             rd.remain = (long long)in->info->data_bytes;
             if (fseeko(f, (off_t)in->info->data_offset, SEEK_SET) != 0) { perror(data); return 1; }
         }
+        if (join) {
+            /* the regions one behind the other, read with fread(): a chunk is filled across their edges */
+            rd.segs = segs;
+            rd.n_seg = n_seg;
+            rd.remain = segs[0].bytes;
+            for (int k = 1; k < n_seg; k++)
+                if (segs[k].off && fseeko(segs[k].f, segs[k].off, SEEK_SET) != 0) { perror(g_in[k].path); return 1; }
+        }
+        if (prime) {
+            /* the detector's history from the recording's own head, before the recording itself is fed from its sample 0 */
+            const size_t got = read_head(segs, n_seg, bps, head_cap, head);
+            if (segs[0].bytes < 0) { rd.pre = head; rd.pre_n = got; }
+            if ((fe ? irdm_frontend_prime_host(fe, p, head, got) : irdm_prime_host(p, head, got)) != 0) {
+                if (irdm_sample_count(p) != 0 || irdm_primed_samples(p) != 0) {
+                    fprintf(stderr, "burst_detect: GPU processing failed\n");
+                    rc = 1;
+                } else
+                    fprintf(stderr, "warning: --prime: %s is shorter than one FFT frame; it runs unprimed\n", file);
+            } else if (verbose)
+                fprintf(stderr, "primed: 512 frames from the first %d\n", irdm_primed_frames(p));
+        }
         rd.buf[0] = pinned[0];
         rd.buf[1] = pinned[1];
         sem_init(&rd.filled, 0, 0);
         sem_init(&rd.empty, 0, 2);
         {
             struct stat sb;
-            if (f != stdin && read_threads > 0 && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
+            if (!join && f != stdin && read_threads > 0 && fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) {
                 rd.n_slices = read_threads > MAX_SLICES ? MAX_SLICES : read_threads;
                 rd.size = sb.st_size - sb.st_size % (off_t)bps;
                 if (in->kind > 0) {
@@ -1650,7 +1832,7 @@ int main(int argc, char **argv)
             g_spec = NULL;
         }
         if (g_dop && rc == 0)          /* the ticks up to the stream's end (samples / rate), then the final solve */
-            position_out(irdm_doppler_finish(g_dop, irdm_start_time_ns(p) + (uint64_t)((double)fed / rate * 1e9), g_dop_text,
+            position_out(irdm_doppler_finish(g_dop, rec_t0 + (uint64_t)((double)fed / rate * 1e9), g_dop_text,
                                              sizeof g_dop_text));
         if (timing) {
             const double t_done = now_s();
@@ -1689,7 +1871,7 @@ int main(int argc, char **argv)
         }
         if (save_band && band_close(fe, file, save_fmt, (float)save_gain, verbose, c.center_frequency) != 0) rc = 1;
         if (save_band && has_suffix_nocase(save_band, ".sigmf-data") &&
-            band_write_meta(save_band, save_fmt, irdm_frontend_out_rate(fe), c.center_frequency, irdm_start_time_ns(p)) != 0) rc = 1;
+            band_write_meta(save_band, save_fmt, irdm_frontend_out_rate(fe), c.center_frequency, rec_t0) != 0) rc = 1;
         if (g_input_stats) {
             irdm_input_stats_t is;
             if ((fe ? irdm_frontend_input_stats(fe, &is) : irdm_input_stats(p, &is)) == 0) input_line(&is, proc_fmt);
@@ -1703,7 +1885,7 @@ int main(int argc, char **argv)
             else { fprintf(stderr, "--diagnostic: %s: no detector statistics\n", file); rc = 1; }
         }
         if (rc) rc_all = 1;
-        if (fi + 1 == g_n_in) break;        /* (the last recording's objects go with the process, below) */
+        if (fi + 1 == n_rec) break;         /* (the last recording's objects go with the process, below) */
         if (out_dir) { fclose(g_out); g_out = stdout; }
         irdm_acars_destroy(g_acars);
         irdm_ida_reasm_destroy(g_reasm);

@@ -287,6 +287,16 @@ def lib():
             L.irdm_reset.argtypes = [C.c_void_p, C.c_double, C.c_uint64]
         if hasattr(L, "irdm_advance"):
             L.irdm_advance.argtypes = [C.c_void_p]
+        if hasattr(L, "irdm_prime_host"):
+            L.irdm_prime_host.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+            L.irdm_prime_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            L.irdm_primed_samples.argtypes = [C.c_void_p]
+            L.irdm_primed_samples.restype = C.c_uint64
+            L.irdm_primed_frames.argtypes = [C.c_void_p]
+            L.irdm_start_time_ns.argtypes = [C.c_void_p]
+            L.irdm_start_time_ns.restype = C.c_uint64
+            if hasattr(L, "irdm_frontend_prime_host"):
+                L.irdm_frontend_prime_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         if hasattr(L, "irdm_poll_spectrum"):
             L.irdm_spectrum_bins.argtypes = [C.c_void_p]
             L.irdm_poll_spectrum.argtypes = [C.c_void_p, C.POINTER(SpectrumRow), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int]
@@ -691,6 +701,37 @@ class Pipeline:
         if rc < 0:
             raise RuntimeError("irdm_feed_host failed")
         return rc
+
+    def prime_host(self, iq):
+        """irdm_prime_host: the detector's 512-frame history filled from the recording's leading samples iq (the array
+        feed_host takes), tiled when they are fewer than 512 frames, before the recording itself is fed; returns the whole
+        frames used.  Only on a fresh stream: after creation or reset(), before the first feed."""
+        iq = np.ascontiguousarray(iq)
+        n = len(iq) if getattr(self, "wire_fmt", self.fmt) == FMT_CF32 else len(iq) // 2
+        if self.L.irdm_prime_host(self.h, iq.ctypes.data_as(C.c_void_p), n) != 0:
+            raise RuntimeError("irdm_prime_host refused (not a fresh stream, a member of a group, or less than one frame)")
+        return self.primed_frames
+
+    def prime_device(self, ptr, n_samples, stream=None):
+        """irdm_prime_device: prime_host from a device buffer"""
+        if self.L.irdm_prime_device(self.h, C.c_void_p(ptr), n_samples, C.c_void_p(stream or 0)) != 0:
+            raise RuntimeError("irdm_prime_device refused (not a fresh stream, a member of a group, or less than one frame)")
+        return self.primed_frames
+
+    @property
+    def primed_samples(self):
+        """samples of the priming prefix in front of the recording (512 frames), 0: not primed"""
+        return int(self.L.irdm_primed_samples(self.h))
+
+    @property
+    def primed_frames(self):
+        """whole frames of the recording's head the prefix was tiled from, 0: not primed"""
+        return int(self.L.irdm_primed_frames(self.h))
+
+    @property
+    def start_time_ns(self):
+        """irdm_start_time_ns: the stream's time origin (a primed stream: that of the prefix's first sample)"""
+        return int(self.L.irdm_start_time_ns(self.h))
 
     def poll_decoded(self):
         """irdm_poll_decoded: one Decoded per polled Demod (option "decode_frames" = 1)."""
@@ -1173,6 +1214,15 @@ class Frontend:
     def wait_input(self):
         if self.L.irdm_frontend_wait_input(self.h) != 0:
             raise RuntimeError("irdm_frontend_wait_input failed")
+
+    def prime_host(self, pipeline, x):
+        """irdm_frontend_prime_host: the capture's leading samples x through the kernel, the pipeline primed from the band's
+        whole frames, the front end reset; returns the frames used"""
+        x = np.ascontiguousarray(x)
+        n = len(x) if getattr(self, "wire_fmt", self.fmt) == FMT_CF32 else len(x) // 2
+        if self.L.irdm_frontend_prime_host(self.h, pipeline.h, x.ctypes.data_as(C.c_void_p), n) != 0:
+            raise RuntimeError("irdm_frontend_prime_host refused (front end or pipeline not fresh, or less than one frame of band)")
+        return pipeline.primed_frames
 
     def reset(self):
         """irdm_frontend_reset: back to the state after creation, for another capture (taps, tables and shift stay)"""
