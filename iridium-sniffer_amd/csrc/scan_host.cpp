@@ -493,7 +493,7 @@ int quiesce(irdm_pipeline *p)
 
 // pipeline_depth >= 1: the finished bursts of the previously scanned chunk (pend_gone) go through the per-burst
 // stages on the next batch context, reading the history ring only; nothing waits here.  A chunk with more bursts than
-// burst_cap is worked off synchronously, batch by batch, except for its last batch.
+// burst_cap is worked off synchronously, batch by batch, except for its last batch, behind the records of every older chunk.
 int deferred_enqueue(irdm_pipeline *p)
 {
     if (!p->st.has_pending) return 0;
@@ -511,6 +511,17 @@ int deferred_enqueue(irdm_pipeline *p)
         const FeedSlot &newest = p->fs[(p->st.begin_no - 1) % kFeedSlots];
         if (p->k1_first >= 2) IRDM_HIP_CHECK(hipStreamWaitEvent(b.stream, newest.ev_copy, 0));
         else if (p->k1_first == 1) IRDM_HIP_CHECK(hipStreamWaitEvent(b.stream, newest.ev_k1, 0));
+    }
+    if (n > p->burst_cap) {
+        // the batches below leave their records in the queues at once, and records leave in chunk order: the chains of
+        // older chunks still in flight on the other contexts are finished first, oldest first
+        for (;;) {
+            BatchCtx *oldest = nullptr;
+            for (int i = 0; i < p->n_bc; i++)
+                if (p->bc[i].st.n > 0 && (!oldest || p->bc[i].st.chunk_no < oldest->st.chunk_no)) oldest = &p->bc[i];
+            if (!oldest) break;
+            if (deferred_finish(p, *oldest) < 0) return -1;
+        }
     }
     while (n - base > p->burst_cap) {
         if (process_bursts(p, b, src, p->st.pend_gone.data() + base, p->burst_cap) != 0) return -1;

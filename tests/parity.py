@@ -73,14 +73,16 @@ def feed_chunks(p, iq, fmt, sizes, feed="host", off=0, past_ring_end="refuse"):
     return off
 
 
-def run_gpu(iq, fs, fmt=irdm.FMT_CF32, chunks=None, scan_mode=0, depth=0, feed="host", options=None, packed=False, **kw):
+def run_gpu(iq, fs, fmt=irdm.FMT_CF32, chunks=None, scan_mode=0, depth=0, feed="host", options=None, packed=False,
+            max_bursts_per_chunk=1024, **kw):
     """Feed `iq` through the HIP pipeline in the given chunk sizes (samples).
 
     feed: the feed forms of feed_chunks().
-    packed: option packed_records -- the compact frame records only (gpu["packed"]; no frame samples, no LLRs)."""
+    packed: option packed_records -- the compact frame records only (gpu["packed"]; no frame samples, no LLRs).
+    max_bursts_per_chunk: the context's sizing hint (a chunk with more finished bursts must come out all the same)."""
     n = len(iq) if fmt == irdm.FMT_CF32 else len(iq) // 2
     max_chunk = max(chunks) if chunks else n
-    p = irdm.Pipeline(fs, fmt=fmt, max_chunk_samples=max_chunk, max_bursts_per_chunk=1024,
+    p = irdm.Pipeline(fs, fmt=fmt, max_chunk_samples=max_chunk, max_bursts_per_chunk=max_bursts_per_chunk,
                       pipeline_depth=depth, **kw)
     if packed:
         p.set_option("packed_records", 1)

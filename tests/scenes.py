@@ -196,6 +196,72 @@ def random_scene(seed, fs=2_000_000, secs=1.6):
     return fs, siggen.make_stream(fs, n, bursts, seed=seed)[0]
 
 
+# ---- scenes of tests/decline_checks.py: what makes the band scan decline a chunk, in mid-stream (NOT in ALL) ----
+def click_index(fs=10_000_000):
+    """the sample click() raises: the centre of the frame that holds sample first + 1_700_000"""
+    nfft = nfft_of(fs)
+    return (530 * nfft + 1_700_000) // nfft * nfft + nfft // 2
+
+
+def click(fs=10_000_000, amp=0.5, seed=31):
+    """Ten ordinary bursts 400_000 samples apart and, between the fifth and the sixth, ONE sample raised by `amp`: a
+    click is white, so in that one frame every bin of the spectrum rises by the same amount.  amp 0.5: a burst is born in
+    most of the bins that may hold one, fewer than max_bursts (200 at 10 MHz: no squelch) -- more than K1's candidate list
+    of the frame holds and more than the 64 lanes of the sparse scan.  amp 2.0: more than max_bursts, the squelch dumps
+    them.  amp 0: the ten bursts alone."""
+    nfft = nfft_of(fs)
+    first = 530 * nfft
+    n = int(first + 0.45 * fs) // 32768 * 32768
+    rng = np.random.default_rng(seed)
+    bursts = [dict(start=first + 20_000 + 400_000 * i, freq_hz=siggen.channel_freq(7 * i - 40), payload=_payload(rng, 160))
+              for i in range(10)]
+    iq = siggen.make_stream(fs, n, bursts, seed=seed)[0]
+    if amp:
+        iq[click_index(fs)] += np.float32(amp)
+    return fs, iq
+
+
+def squelch_late(fs=2_000_000, seed=33):
+    """squelch()'s wave of max_bursts + 4 carriers 1.2 M samples into the stream: seven ordinary bursts have been committed
+    in front of it, one more is still active when it starts, six follow the re-priming."""
+    lay = _Layout(fs, 2.7)
+    n = int(lay.n + 1_200_000 * lay.k) // 32768 * 32768
+    rng = np.random.default_rng(seed)
+    half = (int((fs / 40000.0) * 0.8) + 4) // 2
+    chans = [c for c in range(-half, half + 1) if c != 0]
+    bursts = [dict(start=lay.at(20_000 + 150_000 * i), freq_hz=siggen.channel_freq(5 * i - 16), payload=_payload(rng))
+              for i in range(7)]
+    bursts.append(dict(start=lay.at(1_200_000 - 9000), freq_hz=siggen.channel_freq(9), payload=_payload(rng, 170)))
+    bursts += [dict(start=lay.at(1_200_000 + 37 * i), freq_hz=siggen.channel_freq(ch), payload=_payload(rng), amp=0.03)
+               for i, ch in enumerate(chans)]
+    for i, ch in enumerate(chans[:6]):
+        bursts.append(dict(start=lay.at(3_600_000 + 70_000 * i), freq_hz=siggen.channel_freq(ch), payload=_payload(rng)))
+    return fs, siggen.make_stream(fs, n, bursts, seed=seed)[0]
+
+
+def noise_drop_cut(fs):
+    """the first sample noise_drop() scales"""
+    return 32768 * 100 + 7000 if fs == 2_000_000 else click_index(fs)
+
+
+def noise_drop(fs=2_000_000):
+    """An ordinary scene whose every sample, noise and bursts, is multiplied by 0.25 from a mid-stream sample on: the
+    noise floor falls by 12 dB inside a chunk, further than the candidate lists of that chunk allow for.  2 MHz: ten
+    bursts of siggen.standard_scene; 10 MHz: click()'s ten bursts, the cut where the click was."""
+    assert fs in (2_000_000, 10_000_000)
+    if fs == 2_000_000:
+        iq = siggen.standard_scene(fs, 32768 * 170, 10, seed=16, first_start=600 * 2048)[0].copy()
+    else:
+        iq = click(fs, amp=0)[1]
+    iq[noise_drop_cut(fs):] *= np.float32(0.25)
+    return fs, iq
+
+
+def crowded(fs=2_000_000):
+    """24 bursts in 170 feed blocks at 2 MHz: three and more of them end within ten blocks"""
+    return fs, siggen.standard_scene(fs, 32768 * 170, 24, seed=16, first_start=600 * 2048)[0]
+
+
 UW_QUADS = {1: [0, 2, 2, 2, 2, 0, 0, 0, 2, 0, 0, 2], 2: [2, 2, 0, 0, 0, 2, 0, 0, 2, 0, 2, 2]}        # qpsk_demod.c:40-44
 
 
