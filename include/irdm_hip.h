@@ -803,6 +803,11 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         does not judge what a glitch is -- un-normalised int16-, int24- and int32-scaled floats pass.  A
  *                         caller who wants finite glitches gone picks a lower limit.  -1 outside 0 .. 127, for a member of
  *                         a group, and for a change between a stream's first feed and irdm_reset
+ *   "dc_block"            0/1, default 0: 1 = irdm_dc_block(p, IRDM_FMT_CF32, dc_block_log2, 0, 0) -- irdm_feed_host tracks the DC
+ *                         offset of every chunk over aligned blocks and subtracts the mean of the block in front; 0 =
+ *                         off.  See irdm_dc_block for the rule, the order among the passes and the refusals
+ *   "dc_block_log2"       12 .. 24, default 20: the block length's base-2 logarithm "dc_block" switches on with.  -1 outside
+ *                         12 .. 24, for a member of a group, while the pass is on and after a stream's first feed
  *   "iq_moments"          0/1, default 0: 1 = every chunk's samples are reduced on the GPU to the sums of irdm_iq_moments_t
  *                         (one pass on a side stream behind the chunk's arrival, beside K1, where "input_stats" runs its
  *                         own; device feeds included); irdm_iq_moments returns them with the imbalance derived from them.
@@ -1308,6 +1313,75 @@ int irdm_iq_balance_coeffs(double gain_db, double phase_deg, float *alpha, float
 int irdm_iq_balance_device(void *d_out_cf32, const void *d_in, size_t n, int format, float alpha, float beta, int device, void *stream);
 int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_db, double phase_deg);
 int irdm_frontend_iq_balance(irdm_frontend_t *fe, int wire_format, double gain_db, double phase_deg);
+
+/* ---- a receiver's DC offset: tracked block by block and subtracted (csrc/dc_block.hpp) ----
+ * A constant added to every sample is a tone at the capture's centre; the downmix and the demodulator lose the frames of
+ * the channel it falls into (the README has the figures).  The rule, for all eight formats alike:
+ *   a component c is the float the load stage makes of the sample; q(c) = llrint(c' 2^32) as int64, c' = c clamped to +-64,
+ *   a NaN counting 0; the stream is cut into blocks of B = 2^block_log2 samples (12 .. 24, IRDM_DC_DEFAULT_LOG2 = 20) aligned
+ *   to the stream position; S_k = the int64 sum of q over block k per arm; m_k = (float)((double)S_k / (B 2^32)); a sample of
+ *   block k >= 1 becomes (i - m_{k-1}.i, q - m_{k-1}.q), one rounded binary32 subtraction each, block 0 uses the seed; a NaN
+ *   component leaves with its quiet bit set.  Integer sums: the output does not depend on how feeds cut the stream.
+ * irdm_dc_mean_host (host only, no device call): out = the mean by that rule of the n <= 2^24 leading samples of `format` at
+ *   h_iq, (float)((double)sum q / (n 2^32)) per arm -- what the binary seeds a recording with.  0, or -1.
+ * irdm_dc_block_device: n samples of `format` at d_in (aligned to a sample) become cf32 at d_out_cf32 (aligned to 8 bytes;
+ *   d_in itself for an 8-byte format, any other overlap is refused), the sample at d_in lying at stream position
+ *   first_sample.  state_io carries a stream from call to call: on entry the sums of the block first_sample lies in as far
+ *   as earlier calls have seen it (ignored when first_sample is a multiple of B) and the mean that block is corrected by
+ *   (the seed, for a stream's first call); on return those of the block first_sample + n lies in.  One stream cut into
+ *   calls anywhere gives the bytes and the final state of a single call.  The call works on `stream` (a hipStream_t) or,
+ *   with NULL, on a stream of its own, on the current device, and is complete on return.  0, or -1 for an unknown
+ *   format, a block length outside 12 .. 24, a misaligned pointer, overlapping buffers, a mean in state_io that is not finite
+ *   or lies beyond +-64, or a failed launch; n == 0 launches nothing.
+ * irdm_dc_block: for a context created as IRDM_FMT_CF32, before its first feed; it works as irdm_iq_balance does.  From
+ *   then on irdm_feed_host takes n_samples of wire_format: they land in a wire staging buffer (none for cf32, which is
+ *   corrected where it lands, in the ring slot or the staging buffer), and three launches on the feed's stream write the
+ *   corrected cf32 chunk.  Order where a chunk lands: option "swap_iq", then this, then irdm_iq_balance (then on cf32, in
+ *   place, whatever its own wire format), then "scrub".  A prefix of irdm_prime_* goes through like any chunk: blocks count
+ *   from the start of the prefix.  block_log2 < 0 switches it off.  seed_i, seed_q: what block 0 is corrected by.  Switch,
+ *   block length, wire format and seed are configuration and survive irdm_reset; the position, the open block's sums, the
+ *   means and the figures are stream state, which irdm_reset starts over; they are NOT part of irdm_export_state /
+ *   irdm_import_state.  With it on irdm_feed_device / irdm_feed_begin return -1 with a line on stderr -- correct the
+ *   buffer with irdm_dc_block_device first.  -1 after the stream's first feed, for a context of another format, for a
+ *   member of a group, for a block length outside 12 .. 24, an unknown wire format and a seed that is not finite or lies
+ *   beyond +-64.  Off, nothing is allocated and nothing launched.  Options "dc_block_log2" (12 .. 24) and "dc_block" (1:
+ *   irdm_dc_block with a cf32 wire format, that block length and a zero seed; 0: off) reach the same switch.
+ * irdm_dc_stats: the figures of the stream so far; waits for the feed stream.  0, or -1 (the option off included).
+ * irdm_frontend_dc_block: the same for a front end created with in_format cf32, on the capture in front of K0 / K0r / K0w:
+ *   irdm_frontend_feed_host takes wire_format's bytes and the three launches write the capture staging buffer, behind
+ *   irdm_frontend_swap_iq's exchange and in front of irdm_frontend_iq_balance, irdm_frontend_scrub, the statistics passes
+ *   and the kernel.  The tone is removed before the shift, and irdm_frontend_save writes the corrected band.  Blocks count
+ *   from the first sample fed since creation, irdm_frontend_reset or irdm_frontend_seek; irdm_frontend_reset starts the
+ *   stream state over and keeps the setting.  With it on irdm_frontend_feed_device and irdm_frontend_run_device return -1
+ *   with a line on stderr.  -1 after the capture's first chunk and for the values irdm_dc_block refuses.
+ * irdm_frontend_dc_stats: as irdm_dc_stats.
+ * irdm_dc_block_time_device (measurement surface: tools/dc_block_rate.py): the three kernels over the n <= 2^26 samples of
+ *   `format` at d_in (out of place, or an 8-byte format in place), each launched `reps` times between two events of its
+ *   own on a stream of the call's: us[0] the sums pass, us[1] the close pass, us[2] the subtraction, microseconds per
+ *   launch.  The output at d_out_cf32 is corrected by means that mean nothing.  0, or -1. */
+#define IRDM_DC_DEFAULT_LOG2 20
+typedef struct {
+    int64_t sum_i, sum_q;          /* the open block's sums of q */
+    float   mean_i, mean_q;        /* what the open block is corrected by */
+} irdm_dc_state_t;
+typedef struct {
+    uint64_t n_samples;            /* samples the pass has taken */
+    uint64_t n_blocks;             /* whole blocks among them */
+    int      block_log2;
+    int      wire_format;
+    float    seed_i, seed_q;
+    float    first_i, first_q;     /* m_0; these and the following: 0 while n_blocks == 0 */
+    float    last_i, last_q;       /* the mean of the last whole block */
+    float    min_i, max_i, min_q, max_q;
+} irdm_dc_stats_t;
+int irdm_dc_mean_host(int format, const void *h_iq, size_t n, float out[2]);
+int irdm_dc_block_device(int format, void *d_out_cf32, const void *d_in, size_t n, int block_log2, uint64_t first_sample,
+                         irdm_dc_state_t *state_io, void *stream);
+int irdm_dc_block(irdm_pipeline_t *p, int wire_format, int block_log2, float seed_i, float seed_q);
+int irdm_dc_stats(irdm_pipeline_t *p, irdm_dc_stats_t *out);
+int irdm_frontend_dc_block(irdm_frontend_t *fe, int wire_format, int block_log2, float seed_i, float seed_q);
+int irdm_frontend_dc_stats(irdm_frontend_t *fe, irdm_dc_stats_t *out);
+int irdm_dc_block_time_device(int format, void *d_out_cf32, const void *d_in, size_t n, int block_log2, int reps, float us[3]);
 
 /* ---- self-describing recordings: WAV / RF64, SigMF, SDRangel .sdriq (csrc/recording.cpp) ----
  * Host code only, no device call: works without a GPU.  irdm_recording_probe reads the header of `path` and says what the

@@ -74,6 +74,7 @@ void pipeline_free(irdm_pipeline *p)
         if (e) (void)hipEventDestroy(e);
     p->in_stats.free();
     p->scrub.free();
+    dc_free(p->dc);
     p->iqm.free();
     if (p->bal.d_wire) (void)hipFree(p->bal.d_wire);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);

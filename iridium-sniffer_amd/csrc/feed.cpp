@@ -386,6 +386,11 @@ extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_sa
                         "buffer as it is -- correct it with irdm_iq_balance_device first\n");
         return -1;
     }
+    if (p->dc.on && !p->feed_inner) {
+        fprintf(stderr, "irdm_hip: irdm_dc_block corrects the chunks of irdm_feed_host only: a device feed takes the caller's "
+                        "buffer as it is -- correct it with irdm_dc_block_device first\n");
+        return -1;
+    }
     if (p->st.begin_no - p->st.end_no > (p->depth ? kLookAhead : 0u)) return -1;    // two chunks of look-ahead, pipeline_depth >= 1 only
     if (p->st.stream_closed) {
         fprintf(stderr, "irdm_hip: stream already ended by a chunk that was not a multiple of feed_block\n");
@@ -648,10 +653,24 @@ extern "C" int irdm_device_copy(void *dst, const void *src, size_t bytes)
 // "swap_iq" exchanges its components there, behind the copy and in front of everything that reads the chunk; option
 // "scrub" then zeroes its non-finite and out-of-range samples (cf32 alone: the other formats hold none).  With
 // irdm_iq_balance the chunk has arrived at d_wire in the wire format (nullptr: cf32, at d_iq itself): the exchange happens
-// there, and the correction writes d_iq between the two.
+// there, and the correction writes d_iq between the two.  With irdm_dc_block the wire format and d_wire are its own: the
+// exchange there, its three launches write d_iq, and irdm_iq_balance follows on cf32 in place.
+// The format irdm_feed_host's bytes have, and where they land when that is not the chunk's own place (nullptr: it is).
+static int feed_wire_fmt(const irdm_pipeline *p) { return p->dc.on ? p->dc.wire_fmt : (p->bal.on ? p->bal.wire_fmt : p->dev_fmt); }
+static void *feed_wire_buf(const irdm_pipeline *p)
+{
+    if (p->dc.on) return p->dc.wire_fmt != IRDM_FMT_CF32 ? p->dc.d_wire : nullptr;
+    return p->bal.on && p->bal.wire_fmt != IRDM_FMT_CF32 ? p->bal.d_wire : nullptr;
+}
+
 static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples, void *d_wire = nullptr)
 {
-    if (p->bal.on) {
+    if (p->dc.on) {
+        void *src = d_wire ? d_wire : d_iq;
+        if (p->swap_iq && launch_iq_swap(p->dc.wire_fmt, src, n_samples, p->fstream) != 0) return -1;
+        if (dc_feed(p->dc, p->st.dc, d_iq, src, n_samples, p->fstream) != 0) return -1;
+        if (p->bal.on && launch_iq_balance(IRDM_FMT_CF32, d_iq, d_iq, n_samples, p->bal.alpha, p->bal.beta, p->fstream) != 0) return -1;
+    } else if (p->bal.on) {
         void *src = d_wire ? d_wire : d_iq;
         if (p->swap_iq && launch_iq_swap(p->bal.wire_fmt, src, n_samples, p->fstream) != 0) return -1;
         if (launch_iq_balance(p->bal.wire_fmt, d_iq, src, n_samples, p->bal.alpha, p->bal.beta, p->fstream) != 0) return -1;
@@ -681,8 +700,9 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     // buffer, no device-to-device copy behind K1)
     // irdm_iq_balance with a wire format other than cf32: the bytes land in the wire staging buffer (the previous chunk's
     // correction, which read it, lies in front of the copy on the same stream)
-    void *wire = p->bal.on && p->bal.wire_fmt != IRDM_FMT_CF32 ? p->bal.d_wire : nullptr;
-    const size_t wire_bytes = n_samples * (size_t)(p->bal.on ? fmt_bytes(p->bal.wire_fmt) : p->bps);
+    // irdm_dc_block: likewise, its own wire staging buffer
+    void *wire = feed_wire_buf(p);
+    const size_t wire_bytes = n_samples * (size_t)fmt_bytes(feed_wire_fmt(p));
     if (void *slot = irdm_ingest_ptr(p, n_samples)) {
         IRDM_HIP_CHECK(hipMemcpyAsync(wire ? wire : slot, h_iq, wire_bytes, hipMemcpyHostToDevice, p->fstream));
         return feed_host_arrived(p, slot, n_samples, wire);
@@ -723,8 +743,8 @@ int prime_check(const irdm_pipeline *p, size_t n_samples)
 int prime_from_device(irdm_pipeline *p, const void *d_head, int F)
 {
     const size_t N = (size_t)p->P.n, H = (size_t)kHistory * N, period = (size_t)F * N;
-    void *wire = p->bal.on && p->bal.wire_fmt != IRDM_FMT_CF32 ? p->bal.d_wire : nullptr;
-    const size_t wb = (size_t)(p->bal.on ? fmt_bytes(p->bal.wire_fmt) : p->bps);
+    void *wire = feed_wire_buf(p);
+    const size_t wb = (size_t)fmt_bytes(feed_wire_fmt(p));
     const size_t step = p->max_chunk / (size_t)p->feed_block * (size_t)p->feed_block;
     // (the origin first: the records of bursts that end inside the prefix are built during these feeds)
     const uint64_t shift = (uint64_t)H * 1000000000ull / (uint64_t)p->cfg.sample_rate;
@@ -763,7 +783,7 @@ extern "C" int irdm_prime_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sa
     const int F = prime_check(p, n_samples);
     if (F < 0 || !h_iq) return -1;
     pipeline_enter(p);
-    const size_t bytes = (size_t)F * (size_t)p->P.n * (size_t)(p->bal.on ? fmt_bytes(p->bal.wire_fmt) : p->bps);
+    const size_t bytes = (size_t)F * (size_t)p->P.n * (size_t)fmt_bytes(feed_wire_fmt(p));
     void *d_head = nullptr;
     if (hipMalloc(&d_head, bytes) != hipSuccess) return -1;
     int rc = hipMemcpyAsync(d_head, h_iq, bytes, hipMemcpyHostToDevice, p->fstream) == hipSuccess ? 0 : -1;
@@ -891,6 +911,150 @@ extern "C" int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_
     p->bal.alpha = alpha;
     p->bal.beta = beta;
     return 0;
+}
+
+// ---- irdm_dc_block (dc_block.hpp) ----
+int dc_block_configure(irdm_pipeline *p, int wire_format, int block_log2, float seed_i, float seed_q)
+{
+    // as irdm_iq_balance: a cf32 context, not a member of a group, and only before the stream's first feed
+    if (!p || p->dev_fmt != IRDM_FMT_CF32 || p->in_group || p->st.begin_no != 0) return -1;
+    pipeline_enter(p);
+    if (block_log2 >= 0) IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
+    return dc_configure(p->dc, wire_format, block_log2, seed_i, seed_q, p->max_chunk);
+}
+
+extern "C" int irdm_dc_block(irdm_pipeline_t *p, int wire_format, int block_log2, float seed_i, float seed_q)
+{
+    return dc_block_configure(p, wire_format, block_log2, seed_i, seed_q);
+}
+
+extern "C" int irdm_dc_stats(irdm_pipeline_t *p, irdm_dc_stats_t *out)
+{
+    if (!p || !out || !p->dc.on) return -1;
+    pipeline_enter(p);
+    IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
+    return dc_result(p->dc, p->st.dc, out);
+}
+
+extern "C" int irdm_dc_mean_host(int format, const void *h_iq, size_t n, float out[2]) { return dc_mean_host(format, h_iq, n, out); }
+
+// irdm_dc_block_device: the pass alone, on buffers the caller owns, in rounds of at most kDcDevicePiece samples with rings of
+// the call's own; the open block's sums enter copy 0 of its slot and leave through the record
+extern "C" int irdm_dc_block_device(int format, void *d_out, const void *d_in, size_t n, int block_log2, uint64_t first_sample,
+                                    irdm_dc_state_t *state_io, void *stream_v)
+{
+    if (!fmt_valid(format) || block_log2 < kDcMinLog2 || block_log2 > kDcMaxLog2 || !state_io || ((!d_in || !d_out) && n)) return -1;
+    if (!(fabsf(state_io->mean_i) <= 64.0f) || !(fabsf(state_io->mean_q) <= 64.0f)) return -1;
+    const uintptr_t a_in = reinterpret_cast<uintptr_t>(d_in), a_out = reinterpret_cast<uintptr_t>(d_out);
+    const size_t bps = (size_t)fmt_bytes(format);
+    if (a_in % bps != 0 || a_out % 8u != 0) return -1;
+    if (n == 0) return 0;
+    if (!(a_out == a_in && bps == 8) && a_in < a_out + n * 8 && a_out < a_in + n * bps) return -1;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return -1;
+    CallerStream cs(device, stream_v);
+    if (!cs.ok()) return -1;
+    const uint64_t B = 1ull << block_log2;
+    DcRings r;
+    int rc = r.alloc(std::min(n, kDcDevicePiece), block_log2);
+    uint64_t pos = first_sample, opened = pos >> block_log2;
+    if (rc == 0 && pos % B != 0) {
+        // the block under way: its slot cleared, the sums so far into copy 0
+        const long long sums[2] = { (long long)state_io->sum_i, (long long)state_io->sum_q };
+        rc = dc_clear_slots(r, opened, opened + 1, cs.s);
+        if (rc == 0 && hipMemcpyAsync(r.d_acc + (opened & (r.slots - 1)) * kDcSlotWords, sums, sizeof(sums), hipMemcpyHostToDevice, cs.s) != hipSuccess)
+            rc = -1;
+        if (rc == 0 && hipStreamSynchronize(cs.s) != hipSuccess) rc = -1;     // (sums: this frame's)
+        opened++;
+    }
+    uint64_t k0 = pos >> block_log2;
+    float m0[2] = { state_io->mean_i, state_io->mean_q };
+    DcRec rec{};
+    for (size_t off = 0; rc == 0 && off < n; off += kDcDevicePiece) {
+        const size_t piece = std::min(kDcDevicePiece, n - off);
+        rc = dc_enqueue(r, block_log2, format, static_cast<char *>(d_out) + off * 8, static_cast<const char *>(d_in) + off * bps, piece, pos,
+                        opened, k0, m0[0], m0[1], true, true, cs.s);
+        if (rc == 0 && (hipMemcpyAsync(&rec, r.d_rec, sizeof(rec), hipMemcpyDeviceToHost, cs.s) != hipSuccess ||
+                        hipStreamSynchronize(cs.s) != hipSuccess))
+            rc = -1;
+        if (rc != 0) break;
+        pos += piece;
+        if (rec.blocks) {
+            // the next round's first block is corrected by the mean of the last block this one closed
+            k0 = pos >> block_log2;
+            m0[0] = rec.last[0];
+            m0[1] = rec.last[1];
+        }
+    }
+    rc = cs.finish(rc);
+    r.free();
+    if (rc != 0) return -1;
+    state_io->mean_i = m0[0];
+    state_io->mean_q = m0[1];
+    state_io->sum_i = pos % B ? rec.open[0] : 0;
+    state_io->sum_q = pos % B ? rec.open[1] : 0;
+    return 0;
+}
+
+// irdm_dc_block_time_device (measurement surface, tools/dc_block_rate.py): the three launches over one resident buffer, each
+// kind `reps` times between two events of its own.  The sums are added `reps` times into the same slots and the means are
+// those of that sum: the figures mean nothing, the spans are those of the kernels.
+extern "C" int irdm_dc_block_time_device(int format, void *d_out, const void *d_in, size_t n, int block_log2, int reps, float us[3])
+{
+    if (!fmt_valid(format) || block_log2 < kDcMinLog2 || block_log2 > kDcMaxLog2 || !d_in || !d_out || !us || reps < 1 || n == 0 ||
+        n > kDcSpan)
+        return -1;
+    const size_t bps = (size_t)fmt_bytes(format);
+    if (reinterpret_cast<uintptr_t>(d_in) % bps != 0 || reinterpret_cast<uintptr_t>(d_out) % 8u != 0) return -1;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return -1;
+    CallerStream cs(device, nullptr);
+    if (!cs.ok()) return -1;
+    DcRings r;
+    hipEvent_t ev[6] = {};
+    int rc = r.alloc(n, block_log2);
+    for (auto &e : ev) rc = rc == 0 && hipEventCreate(&e) == hipSuccess ? 0 : -1;
+    if (rc == 0) {
+        int grid = 0;
+        const ChunkSpan sp = chunk_span((int)bps, d_in, n, kChunkNT, kChunkMaxGrid, &grid);
+        const DcGeom g{ 0ull, block_log2, r.slots - 1 };
+        const DcPrev pv{ 0ull, 0.0f, 0.0f };
+        const unsigned long long k_end = (unsigned long long)n >> block_log2;
+        const int dst16 = ((reinterpret_cast<uintptr_t>(d_out) + (uintptr_t)sp.head * 8u) & 15u) == 0 ? 1 : 0;
+        rc = dc_clear_slots(r, 0, ((n - 1) >> block_log2) + 1, cs.s);
+        // (one warm-up launch of each in front of the events)
+        for (int i = -1; rc == 0 && i < reps; i++) {
+            if (i == 0) (void)hipEventRecord(ev[0], cs.s);
+            fmt_dispatch(format, [&](auto f) {
+                hipLaunchKernelGGL((dc_sums_kernel<decltype(f)::value>), dim3(grid), dim3(kChunkNT), 0, cs.s, d_in, sp, g, r.d_acc);
+            });
+        }
+        (void)hipEventRecord(ev[1], cs.s);
+        for (int i = -1; rc == 0 && i < reps; i++) {
+            if (i == 0) (void)hipEventRecord(ev[2], cs.s);
+            hipLaunchKernelGGL((dc_close_kernel<kDcCopies>), dim3(1), dim3(64), 0, cs.s, r.d_acc, r.d_means, r.d_rec, g, 0ull, k_end, 1,
+                               k_end < ((n - 1) >> block_log2) + 1 ? 1 : 0);
+        }
+        (void)hipEventRecord(ev[3], cs.s);
+        for (int i = -1; rc == 0 && i < reps; i++) {
+            if (i == 0) (void)hipEventRecord(ev[4], cs.s);
+            fmt_dispatch(format, [&](auto f) {
+                hipLaunchKernelGGL((dc_sub_kernel<decltype(f)::value>), dim3(grid), dim3(kChunkNT), 0, cs.s, d_out, d_in, sp, g, r.d_means, pv, dst16);
+            });
+        }
+        (void)hipEventRecord(ev[5], cs.s);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(cs.s) != hipSuccess) rc = -1;
+        for (int k = 0; rc == 0 && k < 3; k++) {
+            float ms = 0.0f;
+            if (hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess) rc = -1;
+            us[k] = ms * 1e3f / (float)reps;
+        }
+    }
+    rc = cs.finish(rc);
+    for (auto &e : ev)
+        if (e) (void)hipEventDestroy(e);
+    r.free();
+    return rc;
 }
 
 // ---- option "scrub" (scrub.hpp): the blocks of the passes, when the option is first set on a cf32 context ----

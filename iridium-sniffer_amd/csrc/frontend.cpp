@@ -37,6 +37,7 @@ void fe_free(irdm_frontend *fe)
     fe_save_off(fe);
     fe->is.free();
     fe->scrub.free();
+    dc_free(fe->dc);
     fe->iqm.free();
     if (fe->bal.d_wire) (void)hipFree(fe->bal.d_wire);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
@@ -344,6 +345,35 @@ extern "C" int irdm_frontend_iq_balance(irdm_frontend_t *fe, int wire_format, do
     return 0;
 }
 
+// irdm_frontend_dc_block is on and the caller hands over a device buffer of its own: refused, with the remedy
+static bool fe_dc_refuses(const irdm_frontend *fe)
+{
+    if (!fe->dc.on || fe->feed_inner) return false;
+    fprintf(stderr, "irdm_hip: front end: irdm_frontend_dc_block corrects the chunks of irdm_frontend_feed_host only: a device "
+                    "feed takes the caller's buffer as it is -- correct it with irdm_dc_block_device first\n");
+    return true;
+}
+
+extern "C" int irdm_frontend_dc_block(irdm_frontend_t *fe, int wire_format, int block_log2, float seed_i, float seed_q)
+{
+    // as irdm_frontend_iq_balance: a cf32 front end, and only before the capture's first chunk
+    if (!fe || fe->fmt != IRDM_FMT_CF32 || fe->st.total != 0 || fe->st.dc.pos != 0) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    if (block_log2 >= 0) IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+    return dc_configure(fe->dc, wire_format, block_log2, seed_i, seed_q, 0);
+}
+
+extern "C" int irdm_frontend_dc_stats(irdm_frontend_t *fe, irdm_dc_stats_t *out)
+{
+    if (!fe || !out || !fe->dc.on) return -1;
+    (void)hipSetDevice(fe->cfg.device);
+    IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
+    return dc_result(fe->dc, fe->st.dc, out);
+}
+
+// the format of the bytes irdm_frontend_feed_host takes
+static int fe_wire_fmt(const irdm_frontend *fe) { return fe->dc.on ? fe->dc.wire_fmt : (fe->bal.on ? fe->bal.wire_fmt : fe->fmt); }
+
 // irdm_frontend_swap_iq is on and the caller hands over a device buffer of its own: refused, with the remedy
 static bool fe_swap_refuses(const irdm_frontend *fe)
 {
@@ -394,7 +424,7 @@ extern "C" int irdm_frontend_scrub_stats(irdm_frontend_t *fe, irdm_scrub_stats_t
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
-    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe)) return -1;
+    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe) || fe_dc_refuses(fe)) return -1;
     const uint64_t m1 = fe_outputs(fe, fe->st.total + n_in, false);
     const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
@@ -491,7 +521,7 @@ static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
 
 extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream_v)
 {
-    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe)) return -1;
+    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe) || fe_dc_refuses(fe)) return -1;
     pipeline_enter(p);
     if (stream_v && static_cast<hipStream_t>(stream_v) != fe->stream) {
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
@@ -522,23 +552,32 @@ static int fe_land_host(irdm_frontend *fe, const void *h_in, size_t n_in, bool c
     }
     // (one staging buffer: the copy is ordered behind the kernels that read the previous chunk, on the same stream)
     // irdm_frontend_iq_balance: the caller's bytes are the wire format's; other than cf32 they land in the wire staging buffer
-    const bool wired = fe->bal.on && fe->bal.wire_fmt != IRDM_FMT_CF32;
-    const size_t wire_bytes = wired ? n_in * (size_t)fmt_bytes(fe->bal.wire_fmt) : bytes;
-    if (wired && wire_bytes > fe->bal.wire_bytes) {
+    // irdm_frontend_dc_block: likewise, the wire format and the buffer its own
+    const int wfmt = fe_wire_fmt(fe);
+    const bool wired = (fe->dc.on || fe->bal.on) && wfmt != IRDM_FMT_CF32;
+    const size_t wire_bytes = wired ? n_in * (size_t)fmt_bytes(wfmt) : bytes;
+    void *&d_wire = fe->dc.on ? fe->dc.d_wire : fe->bal.d_wire;
+    size_t &wire_cap = fe->dc.on ? fe->dc.wire_bytes : fe->bal.wire_bytes;
+    if (wired && wire_bytes > wire_cap) {
         IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
-        if (fe->bal.d_wire) (void)hipFree(fe->bal.d_wire);
-        fe->bal.d_wire = nullptr;
-        fe->bal.wire_bytes = 0;
-        IRDM_HIP_CHECK(hipMalloc(&fe->bal.d_wire, wire_bytes));
-        fe->bal.wire_bytes = wire_bytes;
+        if (d_wire) (void)hipFree(d_wire);
+        d_wire = nullptr;
+        wire_cap = 0;
+        IRDM_HIP_CHECK(hipMalloc(&d_wire, wire_bytes));
+        wire_cap = wire_bytes;
     }
-    void *const land = wired ? fe->bal.d_wire : fe->d_stage;
+    void *const land = wired ? d_wire : fe->d_stage;
     if (bytes) IRDM_HIP_CHECK(hipMemcpyAsync(land, h_in, wire_bytes, hipMemcpyHostToDevice, fe->stream));
     IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
     // irdm_frontend_swap_iq: the capture's components exchanged where it landed, in front of the statistics pass and K0 / K0r
-    if (fe->swap_iq && launch_iq_swap(fe->bal.on ? fe->bal.wire_fmt : fe->fmt, land, n_in, fe->stream) != 0) return -1;
+    if (fe->swap_iq && launch_iq_swap(wfmt, land, n_in, fe->stream) != 0) return -1;
+    // irdm_frontend_dc_block: then the DC offset tracked and subtracted into the cf32 staging buffer (a cf32 wire format: in
+    // place), the tone gone before the shift; irdm_frontend_iq_balance behind it on cf32, in place
+    if (fe->dc.on && dc_feed(fe->dc, fe->st.dc, fe->d_stage, land, n_in, fe->stream) != 0) return -1;
     // irdm_frontend_iq_balance: then corrected into the cf32 staging buffer (a cf32 wire format: in place)
-    if (fe->bal.on && launch_iq_balance(fe->bal.wire_fmt, fe->d_stage, land, n_in, fe->bal.alpha, fe->bal.beta, fe->stream) != 0) return -1;
+    if (fe->bal.on && launch_iq_balance(fe->dc.on ? IRDM_FMT_CF32 : fe->bal.wire_fmt, fe->d_stage, fe->dc.on ? fe->d_stage : land, n_in,
+                                        fe->bal.alpha, fe->bal.beta, fe->stream) != 0)
+        return -1;
     // irdm_frontend_scrub: then its non-finite and out-of-range samples zeroed (cf32 alone), positions counted in the capture
     if (fe->scrub.on && fe->fmt == IRDM_FMT_CF32) {
         if (count) {
@@ -616,7 +655,7 @@ extern "C" int irdm_frontend_prime_host(irdm_frontend_t *fe, irdm_pipeline_t *p,
     for (size_t off = 0; rc == 0 && off < n_in; off += piece_max) {
         const size_t piece = std::min(piece_max, n_in - off);
         const uint64_t m1 = fe_outputs(fe, fe->st.total + piece, false);
-        rc = fe_land_host(fe, static_cast<const char *>(h_in) + off * (size_t)(fe->bal.on ? fmt_bytes(fe->bal.wire_fmt) : fe->bps), piece, false);
+        rc = fe_land_host(fe, static_cast<const char *>(h_in) + off * (size_t)fmt_bytes(fe_wire_fmt(fe)), piece, false);
         if (rc == 0) rc = fe_emit(fe, fe->d_stage, piece, m1, d_band + fe->st.n_out, fe->stream);
         if (rc == 0) rc = fe_commit(fe, fe->d_stage, piece, fe->stream);
         if (rc == 0 && hipEventSynchronize(fe->ev_caller) != hipSuccess) rc = -1;

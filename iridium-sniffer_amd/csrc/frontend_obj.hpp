@@ -42,6 +42,8 @@ struct irdm_frontend {
         irdm::ScrubStream scrub;
         // irdm_frontend_iq_moments: the sums of the capture and the passes in flight (iq_moments.hpp)
         irdm::IqMomentsStream iqm;
+        // irdm_frontend_dc_block: the samples the pass has taken and the blocks it has opened (dc_block.hpp)
+        irdm::DcStream dc;
     } st;
     // Saving the band (irdm_frontend_save; off: sink == nullptr and nothing below exists).  fe_emit requantises what its
     // kernel wrote in pieces of at most slot_samples, each into one of two slots: device staging d[i] copied to the pinned
@@ -75,6 +77,9 @@ struct irdm_frontend {
     // irdm_frontend_iq_balance: irdm_frontend_feed_host takes the wire format's bytes and corrects them into the cf32
     // staging buffer (configuration; the wire staging buffer: cache, grown as d_stage is)
     irdm::IqBalance bal;
+    // irdm_frontend_dc_block: irdm_frontend_feed_host takes the wire format's bytes, tracks the DC offset block by block and
+    // subtracts it into the cf32 staging buffer (configuration; the rings and the wire staging buffer: cache)
+    irdm::DcBlock dc;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

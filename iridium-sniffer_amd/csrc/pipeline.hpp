@@ -42,6 +42,7 @@
 #include "scrub.hpp"
 #include "iq_moments.hpp"
 #include "iq_balance.hpp"
+#include "dc_block.hpp"
 #include "iq_sense.hpp"
 
 using namespace irdm;
@@ -244,6 +245,8 @@ struct StreamState {
     ScrubStream scrub;
     // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)
     IqMomentsStream iqm;
+    // irdm_dc_block: the samples the pass has taken and the blocks it has opened (dc_block.hpp)
+    DcStream dc;
     // irdm_prime_host / _device (feed.cpp): the samples of the prefix fed in front of the recording (0: not primed), the
     // whole frames of the recording's head it was tiled from, and what the prefix moved start_time_ns back by -- the side
     // passes count positions and times from the recording's first sample, that is from primed_samples and
@@ -464,6 +467,10 @@ struct irdm_pipeline {
     // irdm_iq_balance (feed.cpp, iq_balance.hpp): irdm_feed_host takes the wire format's bytes and corrects them into cf32
     // (configuration; the wire staging buffer: cache)
     IqBalance bal;
+    // irdm_dc_block (feed.cpp, dc_block.hpp): irdm_feed_host takes the wire format's bytes, tracks the DC offset block by
+    // block and subtracts it into cf32 (switch, block length, wire format, seed: configuration; the rings and the wire
+    // staging buffer: cache)
+    DcBlock dc;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through
@@ -515,6 +522,7 @@ int symbol_clock_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
 int scrub_configure(irdm_pipeline *p, int on);
 int iq_moments_configure(irdm_pipeline *p, int on);
+int dc_block_configure(irdm_pipeline *p, int wire_format, int block_log2, float seed_i, float seed_q);
 int prime_check(const irdm_pipeline *p, size_t n_samples);
 int prime_from_device(irdm_pipeline *p, const void *d_head, int F);
 

@@ -10,7 +10,7 @@
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
- *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]]
+ *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]]
  *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
@@ -139,6 +139,20 @@
  * created as cf32 and takes the file's format as its wire format.  Raw file or container; allowed with --save-only /
  * --save-band, which then write the corrected band.  -v names the option and alpha, beta once.  Every closing line then
  * describes the stream as processed, which is cf32.  Refused with --gpus N > 1.
+ * --dc-block[=LOG2] (only the = form takes the value; an integer 12 .. 24, default 20): a receiver's DC offset -- a tone at
+ * the capture's centre, which costs every frame of the channel it falls into -- is tracked over aligned blocks of 2^LOG2
+ * samples and subtracted on the GPU where the samples arrive (irdm_dc_block, irdm_frontend_dc_block,
+ * irdm_dc_block_device): a block is corrected by the mean of the block in front of it, the first block by the seed, which
+ * is the mean of the recording's first min(2^LOG2, recording) samples (irdm_dc_mean_host on the kept head, whatever --chunk
+ * is; standard input too).  Behind --swap-iq's exchange, in front of --iq-balance, --scrub and any front end (the tone is
+ * gone before the shift; --save-band / --save-only write the corrected band).  The context or the front end is created as
+ * cf32 and takes the file's format as its wire format.  Every recording of a batch gets its own seed, state and line;
+ * --join's parts are one stream.  With --prime the prefix runs through the pass like everything else, blocks counting from
+ * the start of the prefix.  -v names the option once.  One closing line per recording on stderr, behind "image:" and in
+ * front of "scrub:" and "input:", which then describes the samples as processed:
+ *     dc: 3000000 samples cf32, 2 whole blocks of 2^20; seed I +0.03000 Q +0.01800; block means I +0.02999 .. +0.03001, Q +0.01799 .. +0.01801, last I +0.03000 Q +0.01800
+ *     dc: 500000 samples cf32, 0 whole blocks of 2^20; seed I +0.03000 Q +0.01800 (the only correction)
+ * (--save-only, which keeps no record of the blocks: "...; seed I .. Q ..; last I .. Q ..").  Refused with --gpus N > 1.
  * --prime: the detector finds nothing in a stream's first 512 FFT frames (0.37 to 0.70 s), which fill its noise history; a
  * file is all there, so every recording of the run is primed from its own head first (irdm_prime_host,
  * irdm_frontend_prime_host): the first 512 frames -- of a shorter recording the frames it has, repeated -- go through the
@@ -450,6 +464,22 @@ static void iq_line(const irdm_iq_sense_t *q)
         fprintf(stderr, " -- the recording is I/Q-swapped (spectrum inverted): every payload is wrong and every frequency mirrored about -c; run with --swap-iq");
     else if (q->verdict == IRDM_IQ_MIXED) fprintf(stderr, " -- undecided");
     fprintf(stderr, "\n");
+}
+
+/* --dc-block[=LOG2] */
+static int g_dc, g_dc_log2 = IRDM_DC_DEFAULT_LOG2;
+
+/* the closing "dc:" line of a recording; range: the smallest and largest block mean are known */
+static void dc_line(const irdm_dc_stats_t *st, int fmt, int range)
+{
+    fprintf(stderr, "dc: %llu samples %s, %llu whole block%s of 2^%d; seed I %+.5f Q %+.5f", (unsigned long long)st->n_samples,
+            format_name(fmt), (unsigned long long)st->n_blocks, st->n_blocks == 1 ? "" : "s", st->block_log2, (double)st->seed_i,
+            (double)st->seed_q);
+    if (!st->n_blocks) fprintf(stderr, " (the only correction)\n");
+    else if (!range) fprintf(stderr, "; last I %+.5f Q %+.5f\n", (double)st->last_i, (double)st->last_q);
+    else
+        fprintf(stderr, "; block means I %+.5f .. %+.5f, Q %+.5f .. %+.5f, last I %+.5f Q %+.5f\n", (double)st->min_i, (double)st->max_i,
+                (double)st->min_q, (double)st->max_q, (double)st->last_i, (double)st->last_q);
 }
 
 /* the closing "scrub:" line of a recording; rate: that of the stream the pass saw */
@@ -895,13 +925,20 @@ static int band_close(irdm_frontend_t *fe, const char *file, int fmt, float gain
 
 /* --save-only: every recording through the stage-level entries -- no context, no lines.  step: capture samples per read,
  * cap: the outputs a read can complete. */
+static seg_t region_of(FILE *f, const input_t *in, size_t bps);
+static size_t read_head(const seg_t *segs, int n_seg, size_t bps, size_t want, char *head);
+
 static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char *out_dir, int fmt, float gain, int verbose,
                          double centre, size_t step, size_t bps, size_t cap, int in_fmt, double rate)
 {
     void *h_in = irdm_host_alloc(step * bps), *d_in = irdm_device_alloc(0, step * bps), *d_out = irdm_device_alloc(0, cap * 8);
     /* --iq-balance: the front end is a cf32 one; every read is corrected into d_bal (a cf32 file: in place) */
-    const int fe_fmt = g_bal ? IRDM_FMT_CF32 : in_fmt;
-    void *d_bal = g_bal && in_fmt != IRDM_FMT_CF32 ? irdm_device_alloc(0, step * 8) : d_in;
+    /* --dc-block: likewise, in front of the balance; the first block of every recording is read ahead for the seed */
+    const int fe_fmt = g_bal || g_dc ? IRDM_FMT_CF32 : in_fmt;
+    void *d_bal = (g_bal || g_dc) && in_fmt != IRDM_FMT_CF32 ? irdm_device_alloc(0, step * 8) : d_in;
+    const size_t dc_block = (size_t)1 << g_dc_log2;
+    char *dc_head = g_dc ? malloc(dc_block * bps) : NULL;
+    if (g_dc && !dc_head) { fprintf(stderr, "--dc-block: out of memory\n"); return 1; }
     float bal_a = 0.0f, bal_b = 1.0f;
     if (g_bal) irdm_iq_balance_coeffs(g_bal_gain, g_bal_phase, &bal_a, &bal_b);
     int rc_all = 0;
@@ -921,13 +958,44 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
         irdm_scrub_stats_t sb = { 0 };                       /* --scrub: the recording's figures, summed over its reads */
         sb.limit_log2 = g_scrub_log2;
         sb.active = fe_fmt == IRDM_FMT_CF32;
+        /* --dc-block: the state of the recording's stream, seeded from its head (a pipe's head is handed out again below) */
+        irdm_dc_state_t dcs = { 0, 0, 0.0f, 0.0f };
+        irdm_dc_stats_t dst;
+        memset(&dst, 0, sizeof(dst));
+        const char *pre = NULL;
+        size_t pre_n = 0;
+        if (g_dc) {
+            const seg_t seg = region_of(f, in, bps);
+            float seed[2] = { 0.0f, 0.0f };
+            const size_t got = read_head(&seg, 1, bps, dc_block, dc_head);
+            if (seg.bytes < 0) { pre = dc_head; pre_n = got; }
+            if (irdm_dc_mean_host(in_fmt, dc_head, got, seed) != 0) rc = 1;
+            dcs.mean_i = dst.seed_i = seed[g_swap ? 1 : 0];
+            dcs.mean_q = dst.seed_q = seed[g_swap ? 0 : 1];
+            dst.block_log2 = g_dc_log2;
+        }
         for (;;) {
             const size_t want = remain < step ? (size_t)remain : step;
-            const size_t r = want ? fread(h_in, bps, want, f) : 0;
+            size_t r = 0;
+            if (pre_n && want) {
+                r = pre_n < want ? pre_n : want;
+                memcpy(h_in, pre, r * bps);
+                pre += r * bps;
+                pre_n -= r;
+            }
+            if (r < want) r += fread((char *)h_in + r * bps, bps, want - r, f);
             if (r == 0) break;
             remain -= r;
             if (irdm_device_upload(d_in, h_in, r * bps) != 0 || (g_swap && irdm_swap_iq_device(d_in, r, in_fmt, 0, NULL) != 0)) { rc = 1; break; }
-            if (g_bal && irdm_iq_balance_device(d_bal, d_in, r, in_fmt, bal_a, bal_b, 0, NULL) != 0) { rc = 1; break; }
+            if (g_dc) {
+                if (irdm_dc_block_device(in_fmt, d_bal, d_in, r, g_dc_log2, dst.n_samples, &dcs, NULL) != 0) { rc = 1; break; }
+                /* (the figures of the line: the blocks this read closed end with the mean now in the state) */
+                const uint64_t nb = ((dst.n_samples + r) >> g_dc_log2) - (dst.n_samples >> g_dc_log2);
+                dst.n_samples += r;
+                dst.n_blocks += nb;
+                if (nb) { dst.last_i = dcs.mean_i; dst.last_q = dcs.mean_q; }
+            }
+            if (g_bal && irdm_iq_balance_device(d_bal, g_dc ? d_bal : d_in, r, g_dc ? IRDM_FMT_CF32 : in_fmt, bal_a, bal_b, 0, NULL) != 0) { rc = 1; break; }
             if (g_scrub) {
                 irdm_scrub_stats_t one;
                 if (irdm_scrub_device(d_bal, r, fe_fmt, g_scrub_log2, &one, 0, NULL) != 0) { rc = 1; break; }
@@ -947,6 +1015,7 @@ static int save_only_run(irdm_frontend_t *fe, const char *save_band, const char 
         if (rc) fprintf(stderr, "%s: GPU processing failed\n", file);
         if (band_close(fe, file, fmt, gain, verbose, centre) != 0) rc = 1;
         if (has_suffix_nocase(save_band, ".sigmf-data") && band_write_meta(save_band, fmt, irdm_frontend_out_rate(fe), centre, in->start_ns) != 0) rc = 1;
+        if (g_dc) dc_line(&dst, in_fmt, 0);
         if (g_scrub) scrub_line(&sb, fe_fmt, rate);
         if (g_input_stats) {
             irdm_input_stats_t is;
@@ -1132,6 +1201,19 @@ int main(int argc, char **argv)
                 g_scrub_log2 = (int)v;
             }
         }
+        else if (!strcmp(a, "--dc-block") || !strncmp(a, "--dc-block=", 11)) {
+            /* (as --scrub: only the --dc-block=LOG2 form takes a value) */
+            g_dc = 1;
+            if (a[10] == '=') {
+                char *end;
+                const long v = strtol(a + 11, &end, 10);
+                if (end == a + 11 || *end || v < 12 || v > 24) {
+                    fprintf(stderr, "--dc-block=%s: the block length's base-2 logarithm, an integer 12 .. 24\n", a + 11);
+                    return 2;
+                }
+                g_dc_log2 = (int)v;
+            }
+        }
         else if (!strcmp(a, "--image-check")) g_image = 1;
         else if (!strcmp(a, "--prime")) prime = 1;
         else if (!strcmp(a, "--join")) join = 1;
@@ -1236,7 +1318,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1361,6 +1443,13 @@ int main(int argc, char **argv)
         }
         gpus = 0;
     }
+    if (g_dc) {
+        if (gpus > 1) {
+            fprintf(stderr, "--dc-block: one GPU only (--gpus %d): a group is fed on the device\n", gpus);
+            return 2;
+        }
+        gpus = 0;
+    }
     if (save_band) {
         if (!decimate && !resample_to) {
             fprintf(stderr, "--save-band saves the band a front end selects: give --band-center / --decimate or --resample-to\n");
@@ -1396,7 +1485,8 @@ int main(int argc, char **argv)
     const size_t bps = g_in[first].bps;
     const int fmt = g_in[first].fmt;
     /* --iq-balance: the context or the front end is a cf32 one and takes the file's format as its wire format */
-    const int proc_fmt = g_bal ? IRDM_FMT_CF32 : fmt;
+    /* --dc-block: likewise */
+    const int proc_fmt = g_bal || g_dc ? IRDM_FMT_CF32 : fmt;
     freq = g_in[first].centre;
     for (int k = 0; k < g_n_in; k++) {
         if (g_n_in > 1 && !strcmp(g_in[k].path, "-")) {
@@ -1505,6 +1595,10 @@ int main(int argc, char **argv)
         fprintf(stderr, "--iq-balance: the library refused the correction\n");
         return 1;
     }
+    if (g_dc && verbose)
+        fprintf(stderr, "--dc-block: the DC offset is tracked over blocks of 2^%d samples and subtracted on the GPU, %s in, cf32 from "
+                        "there on; each recording is seeded from its own head; the closing lines describe the corrected stream\n",
+                g_dc_log2, format_name(fmt));
     if (g_image && fe && irdm_frontend_iq_moments(fe, 1) != 0) {
         fprintf(stderr, "--image-check: the library refused the measurement\n");
         return 1;
@@ -1627,14 +1721,16 @@ int main(int argc, char **argv)
     if (!d || !segs) { fprintf(stderr, "out of memory\n"); return 1; }
     /* --prime: the capture samples that complete 512 frames in front of the detector (behind a front end: at its ratio, with
      * its taps; the library takes no more of them than it needs) */
-    size_t head_cap = 0;
+    size_t head_cap = 0, prime_cap = 0;
     char *head = NULL;
     if (prime) {
         const size_t H = (size_t)512 * (size_t)irdm_fft_size(p);
-        head_cap = !fe ? H : (resample_to ? (H * (size_t)rs_m + (size_t)irdm_frontend_ntaps(fe)) / (size_t)rs_l + 2
-                                          : H * (size_t)decimate + (size_t)irdm_frontend_ntaps(fe) + 2);
-        if (!(head = malloc(head_cap * bps))) { fprintf(stderr, "--prime: out of memory\n"); return 1; }
+        prime_cap = !fe ? H : (resample_to ? (H * (size_t)rs_m + (size_t)irdm_frontend_ntaps(fe)) / (size_t)rs_l + 2
+                                           : H * (size_t)decimate + (size_t)irdm_frontend_ntaps(fe) + 2);
     }
+    /* --dc-block: the first block, which the seed is the mean of, is kept the same way */
+    head_cap = g_dc && ((size_t)1 << g_dc_log2) > prime_cap ? (size_t)1 << g_dc_log2 : prime_cap;
+    if (head_cap && !(head = malloc(head_cap * bps))) { fprintf(stderr, "%s: out of memory\n", prime ? "--prime" : "--dc-block"); return 1; }
     for (int fi = 0; fi < n_rec; fi++) {
         const char *file = g_in[fi].path;
         const double t_file = now_s();
@@ -1761,10 +1857,26 @@ int main(int argc, char **argv)
             for (int k = 1; k < n_seg; k++)
                 if (segs[k].off && fseeko(segs[k].f, segs[k].off, SEEK_SET) != 0) { perror(g_in[k].path); return 1; }
         }
+        size_t head_got = 0;
+        if (head_cap) {
+            head_got = read_head(segs, n_seg, bps, head_cap, head);
+            if (segs[0].bytes < 0) { rd.pre = head; rd.pre_n = head_got; }
+        }
+        if (g_dc) {
+            /* the seed: the mean of the recording's first block (of a shorter recording: of all of it), in the sense the pass
+             * sees the samples in; set before anything of the recording, a --prime prefix included, reaches the GPU */
+            float seed[2] = { 0.0f, 0.0f };
+            const size_t nb = head_got < ((size_t)1 << g_dc_log2) ? head_got : (size_t)1 << g_dc_log2;
+            if (irdm_dc_mean_host(fmt, head, nb, seed) != 0 ||
+                (fe ? irdm_frontend_dc_block(fe, fmt, g_dc_log2, seed[g_swap ? 1 : 0], seed[g_swap ? 0 : 1])
+                    : irdm_dc_block(p, fmt, g_dc_log2, seed[g_swap ? 1 : 0], seed[g_swap ? 0 : 1])) != 0) {
+                fprintf(stderr, "--dc-block: the library refused the pass\n");
+                return 1;
+            }
+        }
         if (prime) {
             /* the detector's history from the recording's own head, before the recording itself is fed from its sample 0 */
-            const size_t got = read_head(segs, n_seg, bps, head_cap, head);
-            if (segs[0].bytes < 0) { rd.pre = head; rd.pre_n = got; }
+            const size_t got = head_got < prime_cap ? head_got : prime_cap;
             if ((fe ? irdm_frontend_prime_host(fe, p, head, got) : irdm_prime_host(p, head, got)) != 0) {
                 if (irdm_sample_count(p) != 0 || irdm_primed_samples(p) != 0) {
                     fprintf(stderr, "burst_detect: GPU processing failed\n");
@@ -1859,6 +1971,11 @@ int main(int argc, char **argv)
             irdm_iq_moments_t im;
             if ((fe ? irdm_frontend_iq_moments_stats(fe, &im) : irdm_iq_moments(p, &im)) == 0) image_line(&im, fe ? freq : in->centre);
             else { fprintf(stderr, "--image-check: %s: no figures\n", file); rc = 1; }
+        }
+        if (g_dc) {
+            irdm_dc_stats_t ds;
+            if ((fe ? irdm_frontend_dc_stats(fe, &ds) : irdm_dc_stats(p, &ds)) == 0) dc_line(&ds, fmt, 1);
+            else { fprintf(stderr, "--dc-block: %s: no figures\n", file); rc = 1; }
         }
         if (g_scrub) {
             irdm_scrub_stats_t sb;

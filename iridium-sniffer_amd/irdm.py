@@ -236,6 +236,22 @@ class IqMoments(C.Structure):
                 ("phase_deg", C.c_double), ("image_db", C.c_double), ("valid", C.c_int), ("reserved", C.c_int)]
 
 
+DC_DEFAULT_LOG2 = 20
+
+
+class DcState(C.Structure):
+    """irdm_dc_state_t (irdm_dc_block_device): the open block's sums and the mean it is corrected by"""
+    _fields_ = [("sum_i", C.c_int64), ("sum_q", C.c_int64), ("mean_i", C.c_float), ("mean_q", C.c_float)]
+
+
+class DcStats(C.Structure):
+    """irdm_dc_stats_t (irdm_dc_block): samples, whole blocks, the seed, and the first, last, smallest and largest block mean"""
+    _fields_ = [("n_samples", C.c_uint64), ("n_blocks", C.c_uint64), ("block_log2", C.c_int), ("wire_format", C.c_int),
+                ("seed_i", C.c_float), ("seed_q", C.c_float), ("first_i", C.c_float), ("first_q", C.c_float),
+                ("last_i", C.c_float), ("last_q", C.c_float), ("min_i", C.c_float), ("max_i", C.c_float),
+                ("min_q", C.c_float), ("max_q", C.c_float)]
+
+
 class RecordingInfo(C.Structure):
     """irdm_recording_info_t (irdm_recording_probe)"""
     _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
@@ -321,6 +337,13 @@ def lib():
             L.irdm_iq_balance_coeffs.argtypes = [C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float)]
             L.irdm_iq_balance_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_float, C.c_float, C.c_int, C.c_void_p]
             L.irdm_iq_balance.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        if hasattr(L, "irdm_dc_block_device"):
+            L.irdm_dc_mean_host.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_float)]
+            L.irdm_dc_block_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_uint64, C.POINTER(DcState),
+                                               C.c_void_p]
+            L.irdm_dc_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
+            L.irdm_dc_stats.argtypes = [C.c_void_p, C.POINTER(DcStats)]
+            L.irdm_dc_block_time_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -501,6 +524,9 @@ def lib():
                 L.irdm_frontend_iq_moments.argtypes = [C.c_void_p, C.c_int]
                 L.irdm_frontend_iq_moments_stats.argtypes = [C.c_void_p, C.POINTER(IqMoments)]
                 L.irdm_frontend_iq_balance.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+            if hasattr(L, "irdm_frontend_dc_block"):
+                L.irdm_frontend_dc_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
+                L.irdm_frontend_dc_stats.argtypes = [C.c_void_p, C.POINTER(DcStats)]
             if hasattr(L, "irdm_frontend_create_rational"):    # (csrc/resample.cpp)
                 L.irdm_frontend_create_rational.restype = C.c_void_p
                 L.irdm_frontend_create_rational.argtypes = [C.POINTER(FrontendRationalConfig)]
@@ -612,6 +638,33 @@ def iq_balance_device(d_out, d_in, n, fmt, alpha, beta, device=0, stream=None):
                                             C.c_void_p(stream or 0)))
 
 
+def dc_mean_host(fmt, raw, n):
+    """irdm_dc_mean_host: (mean_i, mean_q) as np.float32 of the n leading samples of format fmt in the array `raw`, by the
+    rule of irdm_dc_block; None where the call refuses"""
+    raw = np.ascontiguousarray(raw)
+    out = (C.c_float * 2)()
+    if lib().irdm_dc_mean_host(fmt, raw.ctypes.data_as(C.c_void_p), n, out) != 0:
+        return None
+    return np.float32(out[0]), np.float32(out[1])
+
+
+def dc_block_device(fmt, d_out, d_in, n, block_log2, first_sample, state, stream=None):
+    """irdm_dc_block_device: the n samples of format fmt at d_in, which lie at stream position first_sample, become cf32 at
+    d_out less the mean of the block in front of their own; state (a DcState) carries the stream from call to call.
+    Returns the call's result (0 or -1)"""
+    return int(lib().irdm_dc_block_device(fmt, C.c_void_p(d_out), C.c_void_p(d_in), n, block_log2, first_sample, C.byref(state),
+                                          C.c_void_p(stream or 0)))
+
+
+def dc_block_time_device(fmt, d_out, d_in, n, block_log2, reps):
+    """irdm_dc_block_time_device: microseconds per launch of the sums pass, the close pass and the subtraction over the n
+    resident samples of format fmt at d_in; None where the call refuses"""
+    us = (C.c_float * 3)()
+    if lib().irdm_dc_block_time_device(fmt, C.c_void_p(d_out), C.c_void_p(d_in), n, block_log2, reps, us) != 0:
+        return None
+    return float(us[0]), float(us[1]), float(us[2])
+
+
 def host_free(ptr):
     lib().irdm_host_free(C.c_void_p(ptr))
 
@@ -693,6 +746,21 @@ class Pipeline:
         if self.L.irdm_iq_balance(self.h, wire_fmt, float(gain_db), float(phase_deg)) != 0:
             raise RuntimeError("irdm_iq_balance refused (not a cf32 context, the stream has begun, or figures outside the limits)")
         self.wire_fmt = wire_fmt
+
+    def dc_block(self, wire_fmt=FMT_CF32, block_log2=DC_DEFAULT_LOG2, seed=(0.0, 0.0)):
+        """irdm_dc_block: from now on feed_host takes wire_fmt's samples, tracks their DC offset over blocks of 2^block_log2
+        samples and subtracts it into the cf32 context; block_log2 < 0 switches it off"""
+        if self.L.irdm_dc_block(self.h, wire_fmt, block_log2, float(seed[0]), float(seed[1])) != 0:
+            raise RuntimeError("irdm_dc_block refused (not a cf32 context, the stream has begun, or values outside the limits)")
+        if block_log2 >= 0:
+            self.wire_fmt = wire_fmt
+
+    def dc_stats(self):
+        """irdm_dc_stats: the DcStats of the stream so far"""
+        st = DcStats()
+        if self.L.irdm_dc_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_dc_stats failed (irdm_dc_block off?)")
+        return st
 
     def feed_host(self, iq):
         iq = np.ascontiguousarray(iq)
@@ -1196,6 +1264,21 @@ class Frontend:
         if self.L.irdm_frontend_iq_balance(self.h, wire_fmt, float(gain_db), float(phase_deg)) != 0:
             raise RuntimeError("irdm_frontend_iq_balance refused (not a cf32 front end, the capture has begun, or figures outside the limits)")
         self.wire_fmt = wire_fmt
+
+    def dc_block(self, wire_fmt=FMT_CF32, block_log2=DC_DEFAULT_LOG2, seed=(0.0, 0.0)):
+        """irdm_frontend_dc_block: from now on feed_host takes wire_fmt's samples, tracks their DC offset over blocks of
+        2^block_log2 samples and subtracts it into the cf32 capture; block_log2 < 0 switches it off"""
+        if self.L.irdm_frontend_dc_block(self.h, wire_fmt, block_log2, float(seed[0]), float(seed[1])) != 0:
+            raise RuntimeError("irdm_frontend_dc_block refused (not a cf32 front end, the capture has begun, or values outside the limits)")
+        if block_log2 >= 0:
+            self.wire_fmt = wire_fmt
+
+    def dc_stats(self):
+        """irdm_frontend_dc_stats: the DcStats of the capture so far"""
+        st = DcStats()
+        if self.L.irdm_frontend_dc_stats(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_frontend_dc_stats failed (irdm_frontend_dc_block off?)")
+        return st
 
     def feed_host(self, pipeline, x):
         x = np.ascontiguousarray(x)
