@@ -609,6 +609,15 @@ int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, const float
  * than direction, confidence, level, the symbol counts, bits, llr and total_phase are left zero.  Returns 0 or -1. */
 int irdm_qpsk_demod_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples,
                           const int *direction, int n, irdm_demod_t *out);
+/* The same frames on the packed record path (options "packed_records" / "parsed_records"): the kernel writes the compact
+ * records straight into the context's pinned memory, and these are what the call returns in packed_out[i] -- ok, and for an
+ * accepted frame direction, confidence, level, the symbol counts and total_phase; bits[] as the kernel left it for every
+ * frame, accepted or not; the other fields zero.  keep_bits = 1 (as "parsed_records" runs it): the kernel also writes the
+ * full records' bits and LLRs, returned in full_out[i] as irdm_qpsk_demod_batch returns them.  keep_bits = 0: full_out must
+ * be NULL.  Returns 0 or -1. */
+int irdm_qpsk_demod_packed_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples,
+                                 const int *direction, int n, int keep_bits, irdm_demod_packed_t *packed_out,
+                                 irdm_demod_t *full_out);
 
 /* Post-demod bit layer alone, batched: frame_decode() (frame_decode.h:63) for n demodulated frames -- access code,
  * de-interleave, BCH(31,21)/(7,3) syndromes, Chase decoding on the LLRs (use_llr = 0: hard decisions only, as

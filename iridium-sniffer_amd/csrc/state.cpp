@@ -311,11 +311,13 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     return ret;
 }
 
-extern "C" int irdm_qpsk_demod_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples,
-                                     const int *direction, int n, irdm_demod_t *out)
+// stage C alone on n caller-supplied frames, burst_cap of them per launch.  packed_out == nullptr: the DemodOut records come
+// back by a copy (out).  packed_out != nullptr: the packed record path -- demod_par_kernel writes the DemodPacked and work
+// records into the first batch buffer's pinned memory (demod_export), out is filled from d_demod only where keep_bits is set
+static int demod_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, const int *direction, int n,
+                       int keep_bits, irdm_demod_packed_t *packed_out, irdm_demod_t *out)
 {
-    if (!p || !samples || !num_samples || !direction || !out || n < 0) return -1;
-    pipeline_enter(p);
+    BatchCtx &b = p->bc[0];
     for (int base = 0; base < n; base += p->burst_cap) {
         const int nb = std::min(p->burst_cap, n - base);
         p->h_work.assign(nb, BurstWork());
@@ -328,13 +330,37 @@ extern "C" int irdm_qpsk_demod_batch(irdm_pipeline_t *p, const float *samples, c
         IRDM_HIP_CHECK(hipMemcpyAsync(p->d_work, p->h_work.data(), sizeof(BurstWork) * nb, hipMemcpyHostToDevice, p->stream));
         IRDM_HIP_CHECK(hipMemcpyAsync(p->d_frames, samples + (size_t)base * 2 * kMaxFrameSamples,
                                       sizeof(float2) * (size_t)nb * kMaxFrameSamples, hipMemcpyHostToDevice, p->stream));
+        if (packed_out) {
+            // (no record of an earlier launch passes for this one's)
+            memset(b.hp_packed, 0xff, sizeof(DemodPacked) * (size_t)nb);
+            memset(b.hp_work, 0xff, sizeof(BurstWork) * (size_t)nb);
+        }
         if (launch_demod(p->d_work, nb, p->d_frames, p->cfg.use_gardner, p->sps, p->d_demod_ws, p->d_demod,
-                         p->stream) != 0)
+                         p->stream, packed_out ? b.hp_packed : nullptr, packed_out ? b.hp_work_dev : nullptr, keep_bits) != 0)
             return -1;
-        p->h_demod.resize(nb);
-        IRDM_HIP_CHECK(hipMemcpyAsync(p->h_demod.data(), p->d_demod, sizeof(DemodOut) * nb, hipMemcpyDeviceToHost, p->stream));
+        if (out) {
+            p->h_demod.resize(nb);
+            IRDM_HIP_CHECK(hipMemcpyAsync(p->h_demod.data(), p->d_demod, sizeof(DemodOut) * nb, hipMemcpyDeviceToHost, p->stream));
+        }
         IRDM_HIP_CHECK(hipStreamSynchronize(p->stream));
-        for (int i = 0; i < nb; i++) {
+        for (int i = 0; packed_out && i < nb; i++) {
+            // the record as the chain queues it (chain.cpp: packed_records), the bit words as the kernel left them
+            const DemodPacked &d = b.hp_packed[i];
+            irdm_demod_packed_t &o = packed_out[base + i];
+            memset(&o, 0, sizeof(o));
+            if (b.hp_work[i].num_samples != num_samples[base + i] || b.hp_work[i].direction != direction[base + i]) return -1;
+            memcpy(o.bits, d.bits, sizeof(o.bits));
+            o.ok = d.ok;
+            if (!d.ok) continue;
+            o.direction = d.direction;
+            o.confidence = d.confidence;
+            o.level = d.level;
+            o.n_symbols = d.n_symbols;
+            o.n_payload_symbols = d.n_symbols - 12;
+            o.n_bits = 2 * d.n_symbols;
+            o.total_phase = d.total_phase;
+        }
+        for (int i = 0; out && i < nb; i++) {
             const DemodOut &d = p->h_demod[i];
             irdm_demod_t &o = out[base + i];
             memset(&o, 0, sizeof(o));
@@ -347,11 +373,33 @@ extern "C" int irdm_qpsk_demod_batch(irdm_pipeline_t *p, const float *samples, c
             o.n_payload_symbols = d.n_symbols - 12;
             o.n_bits = 2 * d.n_symbols;
             o.total_phase = d.total_phase;
-            memcpy(o.bits, d.bits, sizeof(o.bits));
-            memcpy(o.llr, d.llr, sizeof(o.llr));
+            // (the frame's own bits only, as the chain queues a record: the kernel writes 2 * n_symbols of them, behind
+            // those the row of d_demod still holds an earlier frame's)
+            const size_t nbits = (size_t)std::min(std::max(2 * d.n_symbols, 0), kMaxBits);
+            memcpy(o.bits, d.bits, nbits * sizeof(o.bits[0]));
+            memcpy(o.llr, d.llr, nbits * sizeof(o.llr[0]));
         }
     }
     return 0;
+}
+
+extern "C" int irdm_qpsk_demod_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples,
+                                     const int *direction, int n, irdm_demod_t *out)
+{
+    if (!p || !samples || !num_samples || !direction || !out || n < 0) return -1;
+    pipeline_enter(p);
+    return demod_batch(p, samples, num_samples, direction, n, 0, nullptr, out);
+}
+
+extern "C" int irdm_qpsk_demod_packed_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples,
+                                            const int *direction, int n, int keep_bits, irdm_demod_packed_t *packed_out,
+                                            irdm_demod_t *full_out)
+{
+    if (!p || !samples || !num_samples || !direction || !packed_out || n < 0) return -1;
+    if (keep_bits != 0 && keep_bits != 1) return -1;
+    if (keep_bits ? !full_out : full_out != nullptr) return -1;
+    pipeline_enter(p);
+    return demod_batch(p, samples, num_samples, direction, n, keep_bits, packed_out, full_out);
 }
 
 // the symbol clock kernel alone (symbol_clock.hpp), on the buffers of irdm_qpsk_demod_batch

@@ -406,6 +406,9 @@ def lib():
                                          C.POINTER(FrameInfo), C.POINTER(C.c_float)]
         L.irdm_qpsk_demod_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int),
                                             C.POINTER(C.c_int), C.c_int, C.POINTER(Demod)]
+        L.irdm_qpsk_demod_packed_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int),
+                                                   C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(DemodPacked),
+                                                   C.POINTER(Demod)]
         L.irdm_state_bytes.argtypes = [C.c_void_p]
         L.irdm_state_bytes.restype = C.c_size_t
         L.irdm_export_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
@@ -1097,22 +1100,40 @@ class Pipeline:
             raise RuntimeError("irdm_downmix_burst failed")
         return fi, (out[:2 * fi.num_samples].view(np.complex64).copy() if rc == 1 else None)
 
-    def qpsk_demod_batch(self, frames, directions):
-        """frames: list of complex64 arrays (<= 4440 samples); returns list of Demod."""
+    @staticmethod
+    def _frame_rows(frames, directions, pad):
         n = len(frames)
-        buf = np.zeros((n, 2 * MAX_FRAME_SAMPLES), np.float32)
+        buf = np.full((n, 2 * MAX_FRAME_SAMPLES), pad, np.float32)
         ns = np.zeros(n, np.int32)
         for i, f in enumerate(frames):
             f = np.ascontiguousarray(f, np.complex64)
             ns[i] = len(f)
             buf[i, :2 * len(f)] = f.view(np.float32)
-        dirs = np.ascontiguousarray(directions, np.int32)
+        return buf, ns, np.ascontiguousarray(directions, np.int32)
+
+    def qpsk_demod_batch(self, frames, directions, pad=0.0):
+        """frames: list of complex64 arrays (<= 4440 samples), each row filled up with `pad`; returns list of Demod."""
+        n = len(frames)
+        buf, ns, dirs = self._frame_rows(frames, directions, pad)
         out = (Demod * n)()
         rc = self.L.irdm_qpsk_demod_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)),
                                           dirs.ctypes.data_as(C.POINTER(C.c_int)), n, out)
         if rc != 0:
             raise RuntimeError("irdm_qpsk_demod_batch failed")
         return [Demod.from_buffer_copy(out[i]) for i in range(n)]
+
+    def qpsk_demod_packed_batch(self, frames, directions, keep_bits):
+        """the same frames on the packed record path; returns (list of DemodPacked, list of Demod | None: keep_bits 0)."""
+        n = len(frames)
+        buf, ns, dirs = self._frame_rows(frames, directions, 0.0)
+        packed = (DemodPacked * n)()
+        full = (Demod * n)() if keep_bits else None
+        rc = self.L.irdm_qpsk_demod_packed_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 dirs.ctypes.data_as(C.POINTER(C.c_int)), n, int(keep_bits), packed, full)
+        if rc != 0:
+            raise RuntimeError("irdm_qpsk_demod_packed_batch failed")
+        return ([DemodPacked.from_buffer_copy(packed[i]) for i in range(n)],
+                [Demod.from_buffer_copy(full[i]) for i in range(n)] if keep_bits else None)
 
     def export_state(self):
         n = self.L.irdm_state_bytes(self.h)

@@ -1446,8 +1446,8 @@ static float uw_soft(const cf *pll_out, int n, int direction)
     return total;
 }
 
-/* qpsk_demod.c:393-535 */
-int orc_qpsk_demod(const orc_frame_t *in, int use_gardner, orc_demod_t *out)
+/* qpsk_demod.c:393-535; tr (may be NULL) only receives what the function decides on the way, it changes nothing */
+static int qpsk_demod_core(const orc_frame_t *in, int use_gardner, orc_demod_t *out, orc_demod_trace_t *tr)
 {
     static const int dq[4] = { 0, 2, 3, 1 };                       /* :46 */
     memset(out, 0, sizeof(*out));
@@ -1468,9 +1468,35 @@ int orc_qpsk_demod(const orc_frame_t *in, int use_gardner, orc_demod_t *out)
 
     int direction = in->direction;
     int dl = uw_hard(sym, ns, 1), ul = uw_hard(sym, ns, 2);
+    if (tr) {
+        memset(tr, 0, sizeof(*tr));
+        tr->n_decimated = nsym;
+        tr->n_sliced = ns;
+        tr->hard_dl = dl;
+        tr->hard_ul = ul;
+        tr->soft_dl = tr->soft_ul = -1.0f;
+        for (int i = 0; i < nsym; i++) {
+            /* the PLL's `continue` (:174): |conj(xh) * out[i]| = |out[i]| up to rounding; recomputed as pll() computes it */
+            float re = crealf(po[i]), im = cimagf(po[i]);
+            cf xh;
+            if (re >= 0 && im >= 0)      xh = CMPLXF(SQRT1_2F, SQRT1_2F);
+            else if (re >= 0)            xh = CMPLXF(SQRT1_2F, -SQRT1_2F);
+            else if (im < 0)             xh = CMPLXF(-SQRT1_2F, -SQRT1_2F);
+            else                         xh = CMPLXF(-SQRT1_2F, SQRT1_2F);
+            if (cabsf(cmul(conjf(xh), po[i])) < 1e-10f) tr->pll_skips++;
+        }
+        for (int i = 0; i < IR_UW_LENGTH && i < nsym; i++) {
+            tr->uw_re[i] = crealf(po[i]);
+            tr->uw_im[i] = cimagf(po[i]);
+        }
+    }
     if (!dl && !ul) {
         float de = uw_soft(po, ns, 1), ue = uw_soft(po, ns, 2);
         float mn = de < ue ? de : ue;
+        if (tr) {
+            tr->soft_dl = de;
+            tr->soft_ul = ue;
+        }
         if (mn > 3.0f) {
             free(dec); free(po); free(sym);
             out->id = in->id;
@@ -1522,6 +1548,16 @@ int orc_qpsk_demod(const orc_frame_t *in, int use_gardner, orc_demod_t *out)
     }
     free(dec); free(po); free(sym);
     return 1;
+}
+
+int orc_qpsk_demod(const orc_frame_t *in, int use_gardner, orc_demod_t *out)
+{
+    return qpsk_demod_core(in, use_gardner, out, NULL);
+}
+
+int orc_qpsk_demod_trace(const orc_frame_t *in, int use_gardner, orc_demod_t *out, orc_demod_trace_t *tr)
+{
+    return qpsk_demod_core(in, use_gardner, out, tr);
 }
 
 /* =====================================================================

@@ -163,6 +163,16 @@ const float *orc_downmix_cfo_window(const orc_downmix_t *dm, int *n);
 
 /* ---- stage C: qpsk demod ---- */
 int orc_qpsk_demod(const orc_frame_t *in, int use_gardner, orc_demod_t *out);
+/* The same call, and what it decided on the way (test corpora are designed with it: tests/stage_c_cases.py): the symbols the
+ * decimator made, the symbols the end-of-frame rule left, the two hard unique-word checks, the two soft errors (-1 where
+ * the hard check made them unnecessary, 999 below 12 symbols), the symbols at which the PLL took its `continue`, and the PLL's
+ * output for the unique word. */
+typedef struct {
+    int32_t n_decimated, n_sliced, hard_dl, hard_ul, pll_skips;
+    float soft_dl, soft_ul;
+    float uw_re[12], uw_im[12];
+} orc_demod_trace_t;
+int orc_qpsk_demod_trace(const orc_frame_t *in, int use_gardner, orc_demod_t *out, orc_demod_trace_t *tr);
 
 /* ---- RAW line (frame_output.c:160-199) ---- */
 /* t0 = 0 -> derive from this frame's timestamp as ensure_initialized does; returns

@@ -42,6 +42,13 @@ class Demod(C.Structure):
                 ("llr", C.c_float * MAX_BITS)]
 
 
+class DemodTrace(C.Structure):
+    """orc_demod_trace_t: what orc_qpsk_demod decided on the way"""
+    _fields_ = [("n_decimated", C.c_int32), ("n_sliced", C.c_int32), ("hard_dl", C.c_int32), ("hard_ul", C.c_int32),
+                ("pll_skips", C.c_int32), ("soft_dl", C.c_float), ("soft_ul", C.c_float),
+                ("uw_re", C.c_float * 12), ("uw_im", C.c_float * 12)]
+
+
 class StreamCfg(C.Structure):
     _fields_ = [("center_frequency", C.c_double), ("sample_rate", C.c_int),
                 ("threshold_db", C.c_float), ("format", C.c_int), ("block", C.c_int),
@@ -115,6 +122,7 @@ def lib():
         L.orc_downmix_cfo_window.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.orc_downmix_cfo_window.restype = C.POINTER(C.c_float)
         L.orc_qpsk_demod.argtypes = [C.POINTER(Frame), C.c_int, C.POINTER(Demod)]
+        L.orc_qpsk_demod_trace.argtypes = [C.POINTER(Frame), C.c_int, C.POINTER(Demod), C.POINTER(DemodTrace)]
         L.orc_format_raw.argtypes = [C.POINTER(Demod), C.c_char_p, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
         L.orc_run_stream.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(StreamCfg), C.POINTER(StreamOut)]
         L.orc_rotator_rotate_n.argtypes = [C.POINTER(C.c_float)] * 2 + [C.POINTER(C.c_float)] * 2 + [C.c_int]

@@ -222,6 +222,45 @@ def test_stage_c_matches_reference(oracle, refpins, gardner):
     assert n_ok >= 8
 
 
+@pytest.mark.parametrize("gardner", [1, 0])
+def test_stage_c_designed_frames_match_reference(oracle, refpins, gardner):
+    """the designed frames of tests/stage_c_cases.py (what the product's stage C is compared with the oracle on): the oracle
+    against the reference's qpsk_demod.c, the same fields as above bit for bit.  Every case goes to the reference but those
+    marked reference_safe = False: frames built to make the timing loop run early, on which the reference makes more symbols
+    than its buffers of num_samples / 10 + 1 hold (qpsk_demod.c:398) and writes behind them."""
+    import stage_c_cases as sc
+    reflib = refpins.lib
+    cs = [c for c in sc.cases() if c.reference_safe]
+    left_out = [c.name for c in sc.cases() if not c.reference_safe]
+    assert left_out and all(n.startswith("drift_early_") for n in left_out) and len(cs) >= 120, left_out
+    if reflib:
+        reflib.ref_set_use_gardner(gardner)
+    ours, theirs = [], []
+    n_ok = 0
+    for c in cs:
+        f = sc.oracle_frame(c.iq, c.direction)
+        f.center_frequency = 1622000000.0
+        d = orc.Demod()
+        r_o = oracle.orc_qpsk_demod(C.byref(f), gardner, C.byref(d))
+        n_ok += r_o
+        ours.append((r_o, d.direction, d.confidence, np.float32(d.level), d.n_symbols, d.n_payload_symbols, d.n_bits,
+                     bytes(d.bits[:d.n_bits]), np.array(d.llr[:d.n_bits], np.float32), d.center_frequency)
+                    if r_o else (r_o,))
+        if reflib:
+            r = _ref_demod(reflib, f)
+            theirs.append((r[0], r[1], r[2], np.float32(r[3])) + r[4:] if r[0] else (r[0],))
+            assert refpins_bytes(ours[-1]) == refpins_bytes(theirs[-1]), c.name
+    if reflib:
+        reflib.ref_set_use_gardner(1)
+    refpins.same("qpsk_demod/designed/gardner%d" % gardner, ours, theirs)
+    assert n_ok >= 0.7 * len(cs) and len(cs) - n_ok >= 8
+
+
+def refpins_bytes(x):
+    import refpins as rp
+    return rp.as_bytes(x)
+
+
 def test_fir_ccf_dec_avx2_order(oracle, refpins):
     """orc_fir_ccf_dec_avx2 == the reference's avx2_fir_ccf_dec (simd_avx2.c:62-108, compiled in place with the
     reference's own flags: -std=c99 -O3 -mavx2 -mfma), bit for bit: four fused accumulators, horizontal sum, scalar tail.
