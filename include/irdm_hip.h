@@ -1252,7 +1252,9 @@ int irdm_iq_sense_batch(irdm_pipeline_t *p, const irdm_demod_t *in, int n, irdm_
  *   capture chunk in its staging buffer, in front of K0 / K0r and of the front end's statistics pass, so the band that
  *   irdm_frontend_save writes is the corrected one.  With it on, irdm_frontend_feed_device and irdm_frontend_run_device
  *   return -1 with a line on stderr (they take the caller's buffer as it is).  Returns 0; -1 for a change between the
- *   stream's first chunk and irdm_frontend_reset. */
+ *   stream's first chunk and irdm_frontend_reset.  (With irdm_frontend_dc_block, _iq_balance and _scrub, below: exchange, DC,
+ *   balance, scrub, in that order, the DC tracker's wire format in effect when both it and the balance are on -- DESIGN.md
+ *   section 5, "The host feed's corrections in one place".) */
 int irdm_frontend_swap_iq(irdm_frontend_t *fe, int on);
 
 /* ---- non-finite and out-of-range samples (irdm_scrub_stats_t above) ----

@@ -43,32 +43,32 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     if (!strcmp(key, "swap_iq")) {
         // 0 / 1; not for a member of a group (it is fed on the device), and no change between a stream's first feed and
         // irdm_reset: the history ring would hold both senses
-        if (p->in_group || (p->st.begin_no != 0 && (value != 0) != (p->swap_iq != 0))) return -1;
-        p->swap_iq = value ? 1 : 0;
+        if (p->in_group || (p->st.begin_no != 0 && (value != 0) != (p->hc.swap_iq != 0))) return -1;
+        p->hc.swap_iq = value ? 1 : 0;
         return 0;
     }
     if (!strcmp(key, "scrub")) {
         // 0 / 1; not for a member of a group (it is fed on the device), and no change between a stream's first feed and
         // irdm_reset: the figures would describe half a stream
-        if (p->in_group || (p->st.begin_no != 0 && (value != 0) != (p->scrub.on != 0))) return -1;
+        if (p->in_group || (p->st.begin_no != 0 && (value != 0) != (p->hc.scrub.on != 0))) return -1;
         return scrub_configure(p, value);
     }
     if (!strcmp(key, "dc_block")) {
         // irdm_dc_block with a cf32 wire format, the block length of "dc_block_log2" and a zero seed (0: off)
-        if (!value && !p->dc.on) return 0;
-        return dc_block_configure(p, IRDM_FMT_CF32, value ? p->dc.log2 : -1, 0.0f, 0.0f);
+        if (!value && !p->hc.dc.on) return 0;
+        return dc_block_configure(p, IRDM_FMT_CF32, value ? p->hc.dc.log2 : -1, 0.0f, 0.0f);
     }
     if (!strcmp(key, "dc_block_log2")) {
         // 12 .. 24: the block length "dc_block" switches on with; as "dc_block", and not while it is on
-        if (value < kDcMinLog2 || value > kDcMaxLog2 || p->in_group || p->dc.on || p->st.begin_no != 0) return -1;
-        p->dc.DcRings::free();
-        p->dc.log2 = value;
+        if (value < kDcMinLog2 || value > kDcMaxLog2 || p->in_group || p->hc.dc.on || p->st.begin_no != 0) return -1;
+        p->hc.dc.DcRings::free();
+        p->hc.dc.log2 = value;
         return 0;
     }
     if (!strcmp(key, "scrub_limit_log2")) {
         // 0 .. 127; as "scrub"
-        if (value < 0 || value > 127 || p->in_group || (p->st.begin_no != 0 && value != p->scrub.limit_log2)) return -1;
-        p->scrub.limit_log2 = value;
+        if (value < 0 || value > 127 || p->in_group || (p->st.begin_no != 0 && value != p->hc.scrub.limit_log2)) return -1;
+        p->hc.scrub.limit_log2 = value;
         return 0;
     }
     if (!strcmp(key, "iq_moments")) {

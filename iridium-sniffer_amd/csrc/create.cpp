@@ -73,10 +73,8 @@ void pipeline_free(irdm_pipeline *p)
     for (auto &e : p->ev_spec)
         if (e) (void)hipEventDestroy(e);
     p->in_stats.free();
-    p->scrub.free();
-    dc_free(p->dc);
+    hc_free(p->hc);
     p->iqm.free();
-    if (p->bal.d_wire) (void)hipFree(p->bal.d_wire);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);
     for (float2 *q : p->rot_retired) (void)hipFree(q);
     for (float2 *q : p->scratch_retired) (void)hipFree(q);

@@ -436,14 +436,12 @@ static inline int dc_enqueue(const DcRings &r, int log2, int fmt, void *d_out, c
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
-// irdm_dc_block / irdm_frontend_dc_block: the setting (configuration: it survives a reset), the rings and the wire staging
-// buffer (cache: max_chunk samples of the wire format; none for cf32, which is corrected where it lands)
+// irdm_dc_block / irdm_frontend_dc_block: the setting (configuration: it survives a reset) and the rings (cache);
+// host_chain.hpp holds it and the staging buffer for a wire format other than cf32
 struct DcBlock : DcRings {
     int on = 0, log2 = kDcDefaultLog2, wire_fmt = 2;
     float seed_i = 0.0f, seed_q = 0.0f;
     size_t span = 0;                    // samples per round of three launches (what the rings were made for)
-    void *d_wire = nullptr;
-    size_t wire_bytes = 0;
 };
 // Stream state: the samples the pass has taken and the blocks whose slots it has opened.  The open block's sums, the means
 // and the figures lie in the rings and the record on the device, which these two numbers give their meaning: a fresh
@@ -488,8 +486,8 @@ static inline int dc_result(const DcBlock &dc, const DcStream &st, irdm_dc_stats
 }
 
 // the setting taken: 0, or -1 for a block length outside 12 .. 24, an unknown wire format, a seed that is not finite or
-// lies beyond +-64, or memory that could not be had.  max_chunk: the longest chunk a feed brings (0: any -- the caller grows
-// the wire staging buffer itself).  A negative log2 switches the pass off (the cache stays).
+// lies beyond +-64, or memory that could not be had.  max_chunk: the longest chunk a feed brings (0: any).  A negative log2
+// switches the pass off (the cache stays).
 static inline int dc_configure(DcBlock &dc, int wire_fmt, int log2, float seed_i, float seed_q, size_t max_chunk)
 {
     if (log2 < 0) {
@@ -502,28 +500,12 @@ static inline int dc_configure(DcBlock &dc, int wire_fmt, int log2, float seed_i
     if (span > dc.span) dc.DcRings::free();
     if (dc.alloc(span, log2) != 0) return -1;
     dc.span = std::max(span, dc.span);
-    const size_t need = wire_fmt == IRDM_FMT_CF32 ? 0 : max_chunk * (size_t)fmt_bytes(wire_fmt);
-    if (need > dc.wire_bytes) {
-        if (dc.d_wire) (void)hipFree(dc.d_wire);
-        dc.d_wire = nullptr;
-        dc.wire_bytes = 0;
-        if (hipMalloc(&dc.d_wire, need) != hipSuccess) return -1;
-        dc.wire_bytes = need;
-    }
     dc.on = 1;
     dc.log2 = log2;
     dc.wire_fmt = wire_fmt;
     dc.seed_i = seed_i;
     dc.seed_q = seed_q;
     return 0;
-}
-
-static inline void dc_free(DcBlock &dc)
-{
-    dc.DcRings::free();
-    if (dc.d_wire) (void)hipFree(dc.d_wire);
-    dc.d_wire = nullptr;
-    dc.wire_bytes = 0;
 }
 
 // ---- irdm_dc_mean_host: the same rule on host memory ----

@@ -370,27 +370,7 @@ extern "C" int irdm_reset(irdm_pipeline_t *p, double center_frequency, uint64_t 
 // two back to back.
 extern "C" int irdm_feed_begin(irdm_pipeline_t *p, const void *d_iq, size_t n_samples, void *stream_v)
 {
-    if (!p || (!d_iq && n_samples)) return -1;
-    if (p->swap_iq && !p->feed_inner) {
-        fprintf(stderr, "irdm_hip: option swap_iq exchanges the chunks of irdm_feed_host only: a device feed takes the caller's "
-                        "buffer as it is -- exchange it with irdm_swap_iq_device first\n");
-        return -1;
-    }
-    if (p->scrub.on && !p->feed_inner) {
-        fprintf(stderr, "irdm_hip: option scrub cleans the chunks of irdm_feed_host only: a device feed takes the caller's buffer "
-                        "as it is -- scrub it with irdm_scrub_device first\n");
-        return -1;
-    }
-    if (p->bal.on && !p->feed_inner) {
-        fprintf(stderr, "irdm_hip: irdm_iq_balance corrects the chunks of irdm_feed_host only: a device feed takes the caller's "
-                        "buffer as it is -- correct it with irdm_iq_balance_device first\n");
-        return -1;
-    }
-    if (p->dc.on && !p->feed_inner) {
-        fprintf(stderr, "irdm_hip: irdm_dc_block corrects the chunks of irdm_feed_host only: a device feed takes the caller's "
-                        "buffer as it is -- correct it with irdm_dc_block_device first\n");
-        return -1;
-    }
+    if (!p || (!d_iq && n_samples) || hc_refuses(p->hc, 0)) return -1;
     if (p->st.begin_no - p->st.end_no > (p->depth ? kLookAhead : 0u)) return -1;    // two chunks of look-ahead, pipeline_depth >= 1 only
     if (p->st.stream_closed) {
         fprintf(stderr, "irdm_hip: stream already ended by a chunk that was not a multiple of feed_block\n");
@@ -649,45 +629,27 @@ extern "C" int irdm_device_copy(void *dst, const void *src, size_t bytes)
     return 0;
 }
 
-// a chunk of irdm_feed_host where its copy lands it on fstream (the ring slot of irdm_ingest_ptr or d_stage): option
-// "swap_iq" exchanges its components there, behind the copy and in front of everything that reads the chunk; option
-// "scrub" then zeroes its non-finite and out-of-range samples (cf32 alone: the other formats hold none).  With
-// irdm_iq_balance the chunk has arrived at d_wire in the wire format (nullptr: cf32, at d_iq itself): the exchange happens
-// there, and the correction writes d_iq between the two.  With irdm_dc_block the wire format and d_wire are its own: the
-// exchange there, its three launches write d_iq, and irdm_iq_balance follows on cf32 in place.
-// The format irdm_feed_host's bytes have, and where they land when that is not the chunk's own place (nullptr: it is).
-static int feed_wire_fmt(const irdm_pipeline *p) { return p->dc.on ? p->dc.wire_fmt : (p->bal.on ? p->bal.wire_fmt : p->dev_fmt); }
-static void *feed_wire_buf(const irdm_pipeline *p)
+// The own place of the next chunk of irdm_feed_host, n_samples long.  Throughput mode: its slot of the history ring, where it
+// is fed in place (no staging buffer, no device-to-device copy behind K1); else d_stage -- irdm_feed_device returns only
+// after K1 and the history-ring copy of its chunk are done, so one staging buffer is enough.  nullptr: no memory.
+static void *feed_host_place(irdm_pipeline *p, size_t n_samples)
 {
-    if (p->dc.on) return p->dc.wire_fmt != IRDM_FMT_CF32 ? p->dc.d_wire : nullptr;
-    return p->bal.on && p->bal.wire_fmt != IRDM_FMT_CF32 ? p->bal.d_wire : nullptr;
+    if (void *slot = irdm_ingest_ptr(p, n_samples)) return slot;
+    if (!p->d_stage && hipMalloc(&p->d_stage, p->max_chunk * p->bps) != hipSuccess) return nullptr;
+    return p->d_stage;
 }
 
-static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples, void *d_wire = nullptr)
+// a chunk of irdm_feed_host whose bytes have been put at hc_landing(d_iq) on fstream: corrected into d_iq, its own place,
+// behind the copy and in front of everything that reads it (host_chain.hpp; the prefix of irdm_prime_* like any chunk, without
+// figures), and fed from there
+static int feed_host_arrived(irdm_pipeline *p, void *d_iq, size_t n_samples)
 {
-    if (p->dc.on) {
-        void *src = d_wire ? d_wire : d_iq;
-        if (p->swap_iq && launch_iq_swap(p->dc.wire_fmt, src, n_samples, p->fstream) != 0) return -1;
-        if (dc_feed(p->dc, p->st.dc, d_iq, src, n_samples, p->fstream) != 0) return -1;
-        if (p->bal.on && launch_iq_balance(IRDM_FMT_CF32, d_iq, d_iq, n_samples, p->bal.alpha, p->bal.beta, p->fstream) != 0) return -1;
-    } else if (p->bal.on) {
-        void *src = d_wire ? d_wire : d_iq;
-        if (p->swap_iq && launch_iq_swap(p->bal.wire_fmt, src, n_samples, p->fstream) != 0) return -1;
-        if (launch_iq_balance(p->bal.wire_fmt, d_iq, src, n_samples, p->bal.alpha, p->bal.beta, p->fstream) != 0) return -1;
-    } else if (p->swap_iq && launch_iq_swap(p->dev_fmt, d_iq, n_samples, p->fstream) != 0) return -1;
-    if (p->scrub.on && p->dev_fmt == IRDM_FMT_CF32) {
-        if (p->priming) {
-            // (the prefix of irdm_prime_*: cleaned like any chunk, no figures)
-            for (size_t off = 0; off < n_samples; off += kChunkMaxLaunch)
-                if (launch_scrub(static_cast<char *>(d_iq) + off * 8, std::min(kChunkMaxLaunch, n_samples - off), p->scrub.limit_log2,
-                                 nullptr, p->fstream) != 0)
-                    return -1;
-        } else if (scrub_enqueue(p->scrub, p->st.scrub, d_iq, n_samples, p->st.begun_samples - p->st.primed_samples, p->fstream) != 0)
-            return -1;
-    }
-    p->feed_inner = true;
+    if (hc_apply(p->hc, p->st.hc, p->dev_fmt, d_iq, hc_landing(p->hc, d_iq), n_samples, p->st.begun_samples - p->st.primed_samples,
+                 !p->priming, p->fstream) != 0)
+        return -1;
+    p->hc.inner = true;
     const int rc = irdm_feed_device(p, d_iq, n_samples, p->fstream);
-    p->feed_inner = false;
+    p->hc.inner = false;
     return rc;
 }
 
@@ -696,26 +658,14 @@ extern "C" int irdm_feed_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sam
     if (!p || (!h_iq && n_samples)) return -1;
     if (n_samples > p->max_chunk) return -1;
     pipeline_enter(p);
-    // throughput mode: the H2D copy lands in the chunk's slot of the history ring and the chunk is fed in place (no staging
-    // buffer, no device-to-device copy behind K1)
-    // irdm_iq_balance with a wire format other than cf32: the bytes land in the wire staging buffer (the previous chunk's
-    // correction, which read it, lies in front of the copy on the same stream)
-    // irdm_dc_block: likewise, its own wire staging buffer
-    void *wire = feed_wire_buf(p);
-    const size_t wire_bytes = n_samples * (size_t)fmt_bytes(feed_wire_fmt(p));
-    if (void *slot = irdm_ingest_ptr(p, n_samples)) {
-        IRDM_HIP_CHECK(hipMemcpyAsync(wire ? wire : slot, h_iq, wire_bytes, hipMemcpyHostToDevice, p->fstream));
-        return feed_host_arrived(p, slot, n_samples, wire);
-    }
-    if (!p->d_stage) {
-        if (hipMalloc(&p->d_stage, p->max_chunk * p->bps) != hipSuccess) return -1;
-    }
-    // Raw bytes in the configured format (the ci16 narrowing of main.c:245-246 happens in the kernels' load stage).
+    void *place = feed_host_place(p, n_samples);
+    if (!place) return -1;
+    // Raw bytes in the wire format (the ci16 narrowing of main.c:245-246 happens in the kernels' load stage).
     // The copy goes on K1's stream, never the null stream: with pipeline_depth 1 the previous chunk's detector scan is
-    // still running and must not be waited for.  irdm_feed_device returns only after K1 and the history-ring copy of
-    // its chunk are done, so one staging buffer is enough.
-    IRDM_HIP_CHECK(hipMemcpyAsync(wire ? wire : p->d_stage, h_iq, wire_bytes, hipMemcpyHostToDevice, p->fstream));
-    return feed_host_arrived(p, p->d_stage, n_samples, wire);
+    // still running and must not be waited for.
+    IRDM_HIP_CHECK(hipMemcpyAsync(hc_landing(p->hc, place), h_iq, n_samples * (size_t)fmt_bytes(hc_wire_fmt(p->hc, p->dev_fmt)),
+                                  hipMemcpyHostToDevice, p->fstream));
+    return feed_host_arrived(p, place, n_samples);
 }
 
 // ---- irdm_prime_host / irdm_prime_device: the detector's 512-frame history filled from the recording's own head ----
@@ -743,8 +693,7 @@ int prime_check(const irdm_pipeline *p, size_t n_samples)
 int prime_from_device(irdm_pipeline *p, const void *d_head, int F)
 {
     const size_t N = (size_t)p->P.n, H = (size_t)kHistory * N, period = (size_t)F * N;
-    void *wire = feed_wire_buf(p);
-    const size_t wb = (size_t)fmt_bytes(feed_wire_fmt(p));
+    const size_t wb = (size_t)fmt_bytes(hc_wire_fmt(p->hc, p->dev_fmt));
     const size_t step = p->max_chunk / (size_t)p->feed_block * (size_t)p->feed_block;
     // (the origin first: the records of bursts that end inside the prefix are built during these feeds)
     const uint64_t shift = (uint64_t)H * 1000000000ull / (uint64_t)p->cfg.sample_rate;
@@ -756,12 +705,9 @@ int prime_from_device(irdm_pipeline *p, const void *d_head, int F)
     p->priming = true;
     for (size_t s0 = 0; rc >= 0 && s0 < H; s0 += step) {
         const size_t len = std::min(step, H - s0);
-        void *slot = irdm_ingest_ptr(p, len);
-        if (!slot) {
-            if (!p->d_stage && hipMalloc(&p->d_stage, p->max_chunk * p->bps) != hipSuccess) rc = -1;
-            slot = p->d_stage;
-        }
-        char *land = static_cast<char *>(wire ? wire : slot);
+        void *place = feed_host_place(p, len);
+        if (!place) rc = -1;
+        char *land = static_cast<char *>(hc_landing(p->hc, place));
         for (size_t pos = s0; rc >= 0 && pos < s0 + len;) {
             const size_t o = pos % period, run = std::min(period - o, s0 + len - pos);
             if (hipMemcpyAsync(land + (pos - s0) * wb, static_cast<const char *>(d_head) + o * wb, run * wb, hipMemcpyDeviceToDevice,
@@ -769,7 +715,7 @@ int prime_from_device(irdm_pipeline *p, const void *d_head, int F)
                 rc = -1;
             pos += run;
         }
-        if (rc >= 0) rc = feed_host_arrived(p, slot, len, wire);
+        if (rc >= 0) rc = feed_host_arrived(p, place, len);
     }
     p->priming = false;
     if (rc < 0) return -1;
@@ -783,7 +729,7 @@ extern "C" int irdm_prime_host(irdm_pipeline_t *p, const void *h_iq, size_t n_sa
     const int F = prime_check(p, n_samples);
     if (F < 0 || !h_iq) return -1;
     pipeline_enter(p);
-    const size_t bytes = (size_t)F * (size_t)p->P.n * (size_t)fmt_bytes(feed_wire_fmt(p));
+    const size_t bytes = (size_t)F * (size_t)p->P.n * (size_t)fmt_bytes(hc_wire_fmt(p->hc, p->dev_fmt));
     void *d_head = nullptr;
     if (hipMalloc(&d_head, bytes) != hipSuccess) return -1;
     int rc = hipMemcpyAsync(d_head, h_iq, bytes, hipMemcpyHostToDevice, p->fstream) == hipSuccess ? 0 : -1;
@@ -897,20 +843,11 @@ extern "C" int irdm_iq_balance(irdm_pipeline_t *p, int wire_format, double gain_
     float alpha, beta;
     if (iq_balance_coeffs(gain_db, phase_deg, &alpha, &beta) != 0) return -1;
     pipeline_enter(p);
-    const size_t need = wire_format == IRDM_FMT_CF32 ? 0 : p->max_chunk * (size_t)fmt_bytes(wire_format);
-    if (need > p->bal.wire_bytes) {
-        IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
-        if (p->bal.d_wire) (void)hipFree(p->bal.d_wire);
-        p->bal.d_wire = nullptr;
-        p->bal.wire_bytes = 0;
-        if (hipMalloc(&p->bal.d_wire, need) != hipSuccess) return -1;
-        p->bal.wire_bytes = need;
-    }
-    p->bal.on = 1;
-    p->bal.wire_fmt = wire_format;
-    p->bal.alpha = alpha;
-    p->bal.beta = beta;
-    return 0;
+    p->hc.bal = IqBalance{ 1, wire_format, alpha, beta };
+    // (a whole chunk of the wire format now: a feed never allocates; without the memory the correction is off)
+    if (hc_reserve(p->hc, p->max_chunk, p->fstream) == 0) return 0;
+    p->hc.bal.on = 0;
+    return -1;
 }
 
 // ---- irdm_dc_block (dc_block.hpp) ----
@@ -920,7 +857,11 @@ int dc_block_configure(irdm_pipeline *p, int wire_format, int block_log2, float 
     if (!p || p->dev_fmt != IRDM_FMT_CF32 || p->in_group || p->st.begin_no != 0) return -1;
     pipeline_enter(p);
     if (block_log2 >= 0) IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
-    return dc_configure(p->dc, wire_format, block_log2, seed_i, seed_q, p->max_chunk);
+    if (dc_configure(p->hc.dc, wire_format, block_log2, seed_i, seed_q, p->max_chunk) != 0) return -1;
+    // (on or off, the wire format in effect may have changed: as irdm_iq_balance)
+    if (hc_reserve(p->hc, p->max_chunk, p->fstream) == 0) return 0;
+    p->hc.dc.on = 0;
+    return -1;
 }
 
 extern "C" int irdm_dc_block(irdm_pipeline_t *p, int wire_format, int block_log2, float seed_i, float seed_q)
@@ -930,10 +871,10 @@ extern "C" int irdm_dc_block(irdm_pipeline_t *p, int wire_format, int block_log2
 
 extern "C" int irdm_dc_stats(irdm_pipeline_t *p, irdm_dc_stats_t *out)
 {
-    if (!p || !out || !p->dc.on) return -1;
+    if (!p || !out || !p->hc.dc.on) return -1;
     pipeline_enter(p);
     IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
-    return dc_result(p->dc, p->st.dc, out);
+    return dc_result(p->hc.dc, p->st.hc.dc, out);
 }
 
 extern "C" int irdm_dc_mean_host(int format, const void *h_iq, size_t n, float out[2]) { return dc_mean_host(format, h_iq, n, out); }
@@ -1060,18 +1001,18 @@ extern "C" int irdm_dc_block_time_device(int format, void *d_out, const void *d_
 // ---- option "scrub" (scrub.hpp): the blocks of the passes, when the option is first set on a cf32 context ----
 int scrub_configure(irdm_pipeline *p, int on)
 {
-    if (on && p->dev_fmt == IRDM_FMT_CF32 && p->scrub.alloc(kSbBlockBytes, false) != 0) return -1;
-    p->scrub.on = on ? 1 : 0;
+    if (on && p->dev_fmt == IRDM_FMT_CF32 && p->hc.scrub.alloc(kSbBlockBytes, false) != 0) return -1;
+    p->hc.scrub.on = on ? 1 : 0;
     return 0;
 }
 
 extern "C" int irdm_scrub_stats(irdm_pipeline_t *p, irdm_scrub_stats_t *out)
 {
-    if (!p || !out || !p->scrub.on) return -1;
+    if (!p || !out || !p->hc.scrub.on) return -1;
     pipeline_enter(p);
     IRDM_HIP_CHECK(hipStreamSynchronize(p->fstream));
-    if (scrub_settle(p->scrub, p->st.scrub) != 0) return -1;
-    scrub_result(p->st.scrub.run, p->scrub.limit_log2, p->dev_fmt == IRDM_FMT_CF32 ? 1 : 0, out);
+    if (scrub_settle(p->hc.scrub, p->st.hc.scrub) != 0) return -1;
+    scrub_result(p->st.hc.scrub.run, p->hc.scrub.limit_log2, p->dev_fmt == IRDM_FMT_CF32 ? 1 : 0, out);
     return 0;
 }
 
@@ -1089,14 +1030,9 @@ extern "C" int irdm_scrub_device(void *d_iq, size_t n_samples, int format, int l
     }
     CallerStream cs(device, stream_v);
     if (!cs.ok()) return -1;
-    int rc = 0;
-    if (!stats) {
-        for (size_t off = 0; rc == 0 && off < n_samples; off += kChunkMaxLaunch)
-            rc = launch_scrub(static_cast<char *>(d_iq) + off * 8, std::min(kChunkMaxLaunch, n_samples - off), limit_log2, nullptr, cs.s);
-        return cs.finish(rc);
-    }
+    if (!stats) return cs.finish(scrub_plain(d_iq, n_samples, limit_log2, cs.s));
     // (with stats: one block for the call, read back after every launch of at most 2^31 samples)
-    rc = cs.finish(one_block_pass(
+    const int rc = cs.finish(one_block_pass(
         d_iq, n_samples, 8, kChunkMaxLaunch, kSbBlockBytes, cs.s,
         [&](const void *in, size_t piece, void *d_block) {
             if (hipMemsetAsync(d_block, 0, kSbBlockBytes, cs.s) != hipSuccess) return -1ll;

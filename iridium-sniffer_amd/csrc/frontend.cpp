@@ -36,10 +36,8 @@ void fe_free(irdm_frontend *fe)
     if (fe->stream) (void)hipStreamSynchronize(fe->stream);
     fe_save_off(fe);
     fe->is.free();
-    fe->scrub.free();
-    dc_free(fe->dc);
+    hc_free(fe->hc);
     fe->iqm.free();
-    if (fe->bal.d_wire) (void)hipFree(fe->bal.d_wire);
     void *ptrs[] = { fe->d_hr, fe->d_G, fe->d_T, fe->d_tail[0], fe->d_tail[1], fe->d_kclk, fe->d_scratch, fe->d_stage, fe->d_desc };
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
@@ -323,108 +321,66 @@ extern "C" int irdm_frontend_iq_moments_stats(irdm_frontend_t *fe, irdm_iq_momen
     return 0;
 }
 
-// irdm_frontend_iq_balance is on and the caller hands over a device buffer of its own: refused, with the remedy
-static bool fe_balance_refuses(const irdm_frontend *fe)
-{
-    if (!fe->bal.on || fe->feed_inner) return false;
-    fprintf(stderr, "irdm_hip: front end: irdm_frontend_iq_balance corrects the chunks of irdm_frontend_feed_host only: a device "
-                    "feed takes the caller's buffer as it is -- correct it with irdm_iq_balance_device first\n");
-    return true;
-}
-
 extern "C" int irdm_frontend_iq_balance(irdm_frontend_t *fe, int wire_format, double gain_db, double phase_deg)
 {
     // a cf32 front end, and only before the capture's first chunk: the carried tail would hold uncorrected samples
     if (!fe || fe->fmt != IRDM_FMT_CF32 || fe->st.total != 0 || !fmt_valid(wire_format)) return -1;
     float alpha, beta;
     if (iq_balance_coeffs(gain_db, phase_deg, &alpha, &beta) != 0) return -1;
-    fe->bal.on = 1;
-    fe->bal.wire_fmt = wire_format;
-    fe->bal.alpha = alpha;
-    fe->bal.beta = beta;
+    fe->hc.bal = IqBalance{ 1, wire_format, alpha, beta };
     return 0;
-}
-
-// irdm_frontend_dc_block is on and the caller hands over a device buffer of its own: refused, with the remedy
-static bool fe_dc_refuses(const irdm_frontend *fe)
-{
-    if (!fe->dc.on || fe->feed_inner) return false;
-    fprintf(stderr, "irdm_hip: front end: irdm_frontend_dc_block corrects the chunks of irdm_frontend_feed_host only: a device "
-                    "feed takes the caller's buffer as it is -- correct it with irdm_dc_block_device first\n");
-    return true;
 }
 
 extern "C" int irdm_frontend_dc_block(irdm_frontend_t *fe, int wire_format, int block_log2, float seed_i, float seed_q)
 {
     // as irdm_frontend_iq_balance: a cf32 front end, and only before the capture's first chunk
-    if (!fe || fe->fmt != IRDM_FMT_CF32 || fe->st.total != 0 || fe->st.dc.pos != 0) return -1;
+    if (!fe || fe->fmt != IRDM_FMT_CF32 || fe->st.total != 0 || fe->st.hc.dc.pos != 0) return -1;
     (void)hipSetDevice(fe->cfg.device);
     if (block_log2 >= 0) IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
-    return dc_configure(fe->dc, wire_format, block_log2, seed_i, seed_q, 0);
+    return dc_configure(fe->hc.dc, wire_format, block_log2, seed_i, seed_q, 0);
 }
 
 extern "C" int irdm_frontend_dc_stats(irdm_frontend_t *fe, irdm_dc_stats_t *out)
 {
-    if (!fe || !out || !fe->dc.on) return -1;
+    if (!fe || !out || !fe->hc.dc.on) return -1;
     (void)hipSetDevice(fe->cfg.device);
     IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
-    return dc_result(fe->dc, fe->st.dc, out);
-}
-
-// the format of the bytes irdm_frontend_feed_host takes
-static int fe_wire_fmt(const irdm_frontend *fe) { return fe->dc.on ? fe->dc.wire_fmt : (fe->bal.on ? fe->bal.wire_fmt : fe->fmt); }
-
-// irdm_frontend_swap_iq is on and the caller hands over a device buffer of its own: refused, with the remedy
-static bool fe_swap_refuses(const irdm_frontend *fe)
-{
-    if (!fe->swap_iq || fe->feed_inner) return false;
-    fprintf(stderr, "irdm_hip: front end: irdm_frontend_swap_iq exchanges the chunks of irdm_frontend_feed_host only: a device "
-                    "feed takes the caller's buffer as it is -- exchange it with irdm_swap_iq_device first\n");
-    return true;
+    return dc_result(fe->hc.dc, fe->st.hc.dc, out);
 }
 
 extern "C" int irdm_frontend_swap_iq(irdm_frontend_t *fe, int on)
 {
     // no change between a stream's first chunk and irdm_frontend_reset: the carried tail would hold the other sense
-    if (!fe || (fe->st.total != 0 && (on != 0) != (fe->swap_iq != 0))) return -1;
-    fe->swap_iq = on ? 1 : 0;
+    if (!fe || (fe->st.total != 0 && (on != 0) != (fe->hc.swap_iq != 0))) return -1;
+    fe->hc.swap_iq = on ? 1 : 0;
     return 0;
-}
-
-// irdm_frontend_scrub is on and the caller hands over a device buffer of its own: refused, with the remedy
-static bool fe_scrub_refuses(const irdm_frontend *fe)
-{
-    if (!fe->scrub.on || fe->feed_inner) return false;
-    fprintf(stderr, "irdm_hip: front end: irdm_frontend_scrub cleans the chunks of irdm_frontend_feed_host only: a device feed "
-                    "takes the caller's buffer as it is -- scrub it with irdm_scrub_device first\n");
-    return true;
 }
 
 extern "C" int irdm_frontend_scrub(irdm_frontend_t *fe, int on, int limit_log2)
 {
     // no change between a stream's first chunk and irdm_frontend_reset: the figures would describe half a capture
     if (!fe || limit_log2 < 0 || limit_log2 > 127) return -1;
-    if (fe->st.total != 0 && ((on != 0) != (fe->scrub.on != 0) || limit_log2 != fe->scrub.limit_log2)) return -1;
+    if (fe->st.total != 0 && ((on != 0) != (fe->hc.scrub.on != 0) || limit_log2 != fe->hc.scrub.limit_log2)) return -1;
     (void)hipSetDevice(fe->cfg.device);
-    if (on && fe->fmt == IRDM_FMT_CF32 && fe->scrub.alloc(kSbBlockBytes, false) != 0) return -1;
-    fe->scrub.on = on ? 1 : 0;
-    fe->scrub.limit_log2 = limit_log2;
+    if (on && fe->fmt == IRDM_FMT_CF32 && fe->hc.scrub.alloc(kSbBlockBytes, false) != 0) return -1;
+    fe->hc.scrub.on = on ? 1 : 0;
+    fe->hc.scrub.limit_log2 = limit_log2;
     return 0;
 }
 
 extern "C" int irdm_frontend_scrub_stats(irdm_frontend_t *fe, irdm_scrub_stats_t *out)
 {
-    if (!fe || !out || !fe->scrub.on) return -1;
+    if (!fe || !out || !fe->hc.scrub.on) return -1;
     (void)hipSetDevice(fe->cfg.device);
-    if (scrub_settle(fe->scrub, fe->st.scrub) != 0) return -1;
-    scrub_result(fe->st.scrub.run, fe->scrub.limit_log2, fe->fmt == IRDM_FMT_CF32 ? 1 : 0, out);
+    if (scrub_settle(fe->hc.scrub, fe->st.hc.scrub) != 0) return -1;
+    scrub_result(fe->st.hc.scrub.run, fe->hc.scrub.limit_log2, fe->fmt == IRDM_FMT_CF32 ? 1 : 0, out);
     return 0;
 }
 
 extern "C" long long irdm_frontend_run_device(irdm_frontend_t *fe, const void *d_in, size_t n_in, void *d_out, size_t out_cap,
                                               void *stream_v)
 {
-    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe) || fe_dc_refuses(fe)) return -1;
+    if (!fe || fe->st.finished || (!d_in && n_in) || !d_out || hc_refuses(fe->hc, 1)) return -1;
     const uint64_t m1 = fe_outputs(fe, fe->st.total + n_in, false);
     const uint64_t n = m1 - fe->st.n_out;
     if (n > out_cap) return -1;
@@ -521,7 +477,7 @@ static int fe_check(const irdm_frontend *fe, const irdm_pipeline *p)
 
 extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *d_in, size_t n_in, void *stream_v)
 {
-    if (fe_check(fe, p) != 0 || (!d_in && n_in) || fe_swap_refuses(fe) || fe_scrub_refuses(fe) || fe_balance_refuses(fe) || fe_dc_refuses(fe)) return -1;
+    if (fe_check(fe, p) != 0 || (!d_in && n_in) || hc_refuses(fe->hc, 1)) return -1;
     pipeline_enter(p);
     if (stream_v && static_cast<hipStream_t>(stream_v) != fe->stream) {
         IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, static_cast<hipStream_t>(stream_v)));
@@ -537,59 +493,19 @@ extern "C" int irdm_frontend_feed_device(irdm_frontend_t *fe, irdm_pipeline_t *p
 }
 
 // n_in capture samples at h_in into the staging buffer on the front end's stream, the way irdm_frontend_feed_host takes a
-// chunk: irdm_frontend_swap_iq, irdm_frontend_iq_balance and irdm_frontend_scrub applied (count: with the scrub's figures,
-// positions from fe->st.total).  ev_caller is recorded behind the copy from h_in.
+// chunk: the corrections of host_chain.hpp applied in front of the statistics pass and K0 / K0r, the DC tone gone before the
+// shift (count: with the scrub's figures, positions in the capture).  ev_caller is recorded behind the copy from h_in.
 static int fe_land_host(irdm_frontend *fe, const void *h_in, size_t n_in, bool count)
 {
-    const size_t bytes = n_in * (size_t)fe->bps;
-    if (bytes > fe->stage_bytes) {
-        IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
-        if (fe->d_stage) (void)hipFree(fe->d_stage);
-        fe->d_stage = nullptr;
-        fe->stage_bytes = 0;
-        IRDM_HIP_CHECK(hipMalloc(&fe->d_stage, bytes));
-        fe->stage_bytes = bytes;
-    }
-    // (one staging buffer: the copy is ordered behind the kernels that read the previous chunk, on the same stream)
-    // irdm_frontend_iq_balance: the caller's bytes are the wire format's; other than cf32 they land in the wire staging buffer
-    // irdm_frontend_dc_block: likewise, the wire format and the buffer its own
-    const int wfmt = fe_wire_fmt(fe);
-    const bool wired = (fe->dc.on || fe->bal.on) && wfmt != IRDM_FMT_CF32;
-    const size_t wire_bytes = wired ? n_in * (size_t)fmt_bytes(wfmt) : bytes;
-    void *&d_wire = fe->dc.on ? fe->dc.d_wire : fe->bal.d_wire;
-    size_t &wire_cap = fe->dc.on ? fe->dc.wire_bytes : fe->bal.wire_bytes;
-    if (wired && wire_bytes > wire_cap) {
-        IRDM_HIP_CHECK(hipStreamSynchronize(fe->stream));
-        if (d_wire) (void)hipFree(d_wire);
-        d_wire = nullptr;
-        wire_cap = 0;
-        IRDM_HIP_CHECK(hipMalloc(&d_wire, wire_bytes));
-        wire_cap = wire_bytes;
-    }
-    void *const land = wired ? d_wire : fe->d_stage;
-    if (bytes) IRDM_HIP_CHECK(hipMemcpyAsync(land, h_in, wire_bytes, hipMemcpyHostToDevice, fe->stream));
-    IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
-    // irdm_frontend_swap_iq: the capture's components exchanged where it landed, in front of the statistics pass and K0 / K0r
-    if (fe->swap_iq && launch_iq_swap(wfmt, land, n_in, fe->stream) != 0) return -1;
-    // irdm_frontend_dc_block: then the DC offset tracked and subtracted into the cf32 staging buffer (a cf32 wire format: in
-    // place), the tone gone before the shift; irdm_frontend_iq_balance behind it on cf32, in place
-    if (fe->dc.on && dc_feed(fe->dc, fe->st.dc, fe->d_stage, land, n_in, fe->stream) != 0) return -1;
-    // irdm_frontend_iq_balance: then corrected into the cf32 staging buffer (a cf32 wire format: in place)
-    if (fe->bal.on && launch_iq_balance(fe->dc.on ? IRDM_FMT_CF32 : fe->bal.wire_fmt, fe->d_stage, fe->dc.on ? fe->d_stage : land, n_in,
-                                        fe->bal.alpha, fe->bal.beta, fe->stream) != 0)
+    // (one staging buffer, and one for a wire format other than cf32, both grown on demand: the copy is ordered behind the
+    // kernels that read the previous chunk, on the same stream)
+    if (hc_grow(&fe->d_stage, &fe->stage_bytes, n_in * (size_t)fe->bps, fe->stream) != 0 || hc_reserve(fe->hc, n_in, fe->stream) != 0)
         return -1;
-    // irdm_frontend_scrub: then its non-finite and out-of-range samples zeroed (cf32 alone), positions counted in the capture
-    if (fe->scrub.on && fe->fmt == IRDM_FMT_CF32) {
-        if (count) {
-            if (scrub_enqueue(fe->scrub, fe->st.scrub, fe->d_stage, n_in, fe->st.total, fe->stream) != 0) return -1;
-        } else {
-            for (size_t off = 0; off < n_in; off += kChunkMaxLaunch)
-                if (launch_scrub(static_cast<char *>(fe->d_stage) + off * 8, std::min(kChunkMaxLaunch, n_in - off), fe->scrub.limit_log2,
-                                 nullptr, fe->stream) != 0)
-                    return -1;
-        }
-    }
-    return 0;
+    void *const land = hc_landing(fe->hc, fe->d_stage);
+    if (n_in)
+        IRDM_HIP_CHECK(hipMemcpyAsync(land, h_in, n_in * (size_t)fmt_bytes(hc_wire_fmt(fe->hc, fe->fmt)), hipMemcpyHostToDevice, fe->stream));
+    IRDM_HIP_CHECK(hipEventRecord(fe->ev_caller, fe->stream));
+    return hc_apply(fe->hc, fe->st.hc, fe->fmt, fe->d_stage, land, n_in, fe->st.total, count, fe->stream);
 }
 
 extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, const void *h_in, size_t n_in)
@@ -597,9 +513,9 @@ extern "C" int irdm_frontend_feed_host(irdm_frontend_t *fe, irdm_pipeline_t *p, 
     if (fe_check(fe, p) != 0 || (!h_in && n_in)) return -1;
     pipeline_enter(p);
     if (fe_land_host(fe, h_in, n_in, true) != 0) return -1;
-    fe->feed_inner = true;
+    fe->hc.inner = true;
     const int bursts = irdm_frontend_feed_device(fe, p, fe->d_stage, n_in, nullptr);
-    fe->feed_inner = false;
+    fe->hc.inner = false;
     IRDM_HIP_CHECK(hipEventSynchronize(fe->ev_caller));          // the host buffer has been read
     return bursts;
 }
@@ -655,7 +571,7 @@ extern "C" int irdm_frontend_prime_host(irdm_frontend_t *fe, irdm_pipeline_t *p,
     for (size_t off = 0; rc == 0 && off < n_in; off += piece_max) {
         const size_t piece = std::min(piece_max, n_in - off);
         const uint64_t m1 = fe_outputs(fe, fe->st.total + piece, false);
-        rc = fe_land_host(fe, static_cast<const char *>(h_in) + off * (size_t)fmt_bytes(fe_wire_fmt(fe)), piece, false);
+        rc = fe_land_host(fe, static_cast<const char *>(h_in) + off * (size_t)fmt_bytes(hc_wire_fmt(fe->hc, fe->fmt)), piece, false);
         if (rc == 0) rc = fe_emit(fe, fe->d_stage, piece, m1, d_band + fe->st.n_out, fe->stream);
         if (rc == 0) rc = fe_commit(fe, fe->d_stage, piece, fe->stream);
         if (rc == 0 && hipEventSynchronize(fe->ev_caller) != hipSuccess) rc = -1;

@@ -38,12 +38,11 @@ struct irdm_frontend {
         uint64_t sv_samples = 0;
         // input statistics: the totals of the capture and the passes in flight (input_stats.hpp)
         irdm::InputStatsStream is;
-        // irdm_frontend_scrub: the totals of the pass and the launches whose figures are on their way (scrub.hpp)
-        irdm::ScrubStream scrub;
         // irdm_frontend_iq_moments: the sums of the capture and the passes in flight (iq_moments.hpp)
         irdm::IqMomentsStream iqm;
-        // irdm_frontend_dc_block: the samples the pass has taken and the blocks it has opened (dc_block.hpp)
-        irdm::DcStream dc;
+        // the corrections of irdm_frontend_feed_host: the scrub's totals and launches in flight (positions in the capture), the
+        // DC tracker's position (host_chain.hpp)
+        irdm::HostChainStream hc;
     } st;
     // Saving the band (irdm_frontend_save; off: sink == nullptr and nothing below exists).  fe_emit requantises what its
     // kernel wrote in pieces of at most slot_samples, each into one of two slots: device staging d[i] copied to the pinned
@@ -63,23 +62,15 @@ struct irdm_frontend {
     } sv;
     // irdm_frontend_input_stats_enable: the pass over the capture's samples in front of the kernel (cache; is.on the switch)
     irdm::InputStatsPass is;
-    // irdm_frontend_swap_iq: irdm_frontend_feed_host exchanges I and Q of every capture chunk in its staging buffer
-    // (configuration); feed_inner marks that call's own device feed, the only one the switch allows
-    int swap_iq = 0;
-    bool feed_inner = false;
+    // irdm_frontend_swap_iq, _scrub, _iq_balance and _dc_block (host_chain.hpp): what irdm_frontend_feed_host does to every
+    // capture chunk on its way into the cf32 staging buffer (the switches and their settings: configuration; the scrub's
+    // blocks, the DC tracker's rings and the wire staging buffer, grown as d_stage is: cache), and the mark of that call's own
+    // device feed
+    irdm::HostChain hc;
     // irdm_frontend_prime_host is running the capture's head through the kernel: fe_emit saves nothing of it
     bool priming = false;
-    // irdm_frontend_scrub: irdm_frontend_feed_host zeroes the non-finite and out-of-range samples of every cf32 capture
-    // chunk in its staging buffer (scrub.on, scrub.limit_log2: configuration; the blocks: cache)
-    irdm::ScrubPass scrub;
     // irdm_frontend_iq_moments: the pass over the capture's samples in front of the kernel (cache; iqm.on the switch)
     irdm::IqMomentsPass iqm;
-    // irdm_frontend_iq_balance: irdm_frontend_feed_host takes the wire format's bytes and corrects them into the cf32
-    // staging buffer (configuration; the wire staging buffer: cache, grown as d_stage is)
-    irdm::IqBalance bal;
-    // irdm_frontend_dc_block: irdm_frontend_feed_host takes the wire format's bytes, tracks the DC offset block by block and
-    // subtracts it into the cf32 staging buffer (configuration; the rings and the wire staging buffer: cache)
-    irdm::DcBlock dc;
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_caller = nullptr;
     unsigned long long *d_kclk = nullptr;

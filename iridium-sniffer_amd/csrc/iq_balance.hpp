@@ -154,13 +154,10 @@ static inline int launch_iq_balance(int fmt, void *d_out, const void *d_in, size
     return 0;
 }
 
-// irdm_iq_balance / irdm_frontend_iq_balance: the setting (configuration: it survives a reset) and the wire staging buffer
-// (cache: max_chunk samples of the wire format; none for cf32, which is corrected where it lands)
+// irdm_iq_balance / irdm_frontend_iq_balance: the setting (configuration: it survives a reset; host_chain.hpp)
 struct IqBalance {
     int on = 0, wire_fmt = 2;
     float alpha = 0.0f, beta = 1.0f;
-    void *d_wire = nullptr;
-    size_t wire_bytes = 0;
 };
 
 }  // namespace irdm

@@ -10,8 +10,7 @@
 //   * the buffer need only be aligned to a sample: the span geometry of chunk_span.hpp.
 // Bounds: it reads and writes the span's samples (chunk_span.hpp) and nothing else.
 //
-// Included by the translation units that launch it (feed.cpp: irdm_feed_host of a context and irdm_swap_iq_device;
-// frontend.cpp: the capture in front of K0 / K0r).
+// Launched by host_chain.hpp (the host feeds of a context and a front end) and by irdm_swap_iq_device (feed.cpp).
 #pragma once
 #include "common.hpp"
 #include "chunk_span.hpp"

@@ -38,11 +38,8 @@
 #include "record_queues.hpp"
 #include "input_stats.hpp"
 #include "symbol_clock.hpp"
-#include "iq_swap.hpp"
-#include "scrub.hpp"
 #include "iq_moments.hpp"
-#include "iq_balance.hpp"
-#include "dc_block.hpp"
+#include "host_chain.hpp"
 #include "iq_sense.hpp"
 
 using namespace irdm;
@@ -241,12 +238,10 @@ struct StreamState {
     SymbolClockStream clock;
     // option "iq_sense": the per-frame votes until they are polled and the counts of the summary (iq_sense.hpp)
     IqSenseStream iq;
-    // option "scrub": the totals of the pass and the launches whose figures are still on their way (scrub.hpp)
-    ScrubStream scrub;
     // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)
     IqMomentsStream iqm;
-    // irdm_dc_block: the samples the pass has taken and the blocks it has opened (dc_block.hpp)
-    DcStream dc;
+    // the corrections of irdm_feed_host: the scrub's totals and launches in flight, the DC tracker's position (host_chain.hpp)
+    HostChainStream hc;
     // irdm_prime_host / _device (feed.cpp): the samples of the prefix fed in front of the recording (0: not primed), the
     // whole frames of the recording's head it was tiled from, and what the prefix moved start_time_ns back by -- the side
     // passes count positions and times from the recording's first sample, that is from primed_samples and
@@ -451,26 +446,16 @@ struct irdm_pipeline {
     // option "iq_sense" (chain.cpp, iq_sense.hpp): the switch (configuration); the batch contexts' hp_sense are the cache,
     // allocated when the option is first set
     int iq_sense = 0;
-    // option "swap_iq" (feed.cpp, iq_swap.hpp): irdm_feed_host exchanges I and Q of every chunk on the device (configuration);
-    // feed_inner marks irdm_feed_host's own call of irdm_feed_device, the only device feed the option allows
-    int swap_iq = 0;
-    bool feed_inner = false;
+    // options "swap_iq", "scrub" / "scrub_limit_log2", irdm_iq_balance and irdm_dc_block (feed.cpp, host_chain.hpp): what
+    // irdm_feed_host does to every chunk on the device before anything reads it -- the switches and their settings
+    // (configuration), the scrub's blocks, the DC tracker's rings and the wire staging buffer (cache: allocated when a
+    // setting first needs them), and the mark of irdm_feed_host's own call of irdm_feed_device
+    HostChain hc;
     // irdm_prime_*'s own feeds of the prefix are under way: every side pass is off for them (feed.cpp)
     bool priming = false;
-    // options "scrub" / "scrub_limit_log2" (feed.cpp, scrub.hpp): irdm_feed_host zeroes the non-finite and out-of-range
-    // samples of every cf32 chunk on the device; scrub.on and scrub.limit_log2 are configuration, the blocks cache
-    // (allocated when the option is first set on a cf32 context)
-    ScrubPass scrub;
     // option "iq_moments" (feed.cpp, iq_moments.hpp): the pass over every chunk on its side stream (iqm.on: configuration;
     // the stream and the blocks: cache, allocated when the option is first set)
     IqMomentsPass iqm;
-    // irdm_iq_balance (feed.cpp, iq_balance.hpp): irdm_feed_host takes the wire format's bytes and corrects them into cf32
-    // (configuration; the wire staging buffer: cache)
-    IqBalance bal;
-    // irdm_dc_block (feed.cpp, dc_block.hpp): irdm_feed_host takes the wire format's bytes, tracks the DC offset block by
-    // block and subtracts it into cf32 (switch, block length, wire format, seed: configuration; the rings and the wire
-    // staging buffer: cache)
-    DcBlock dc;
     // irdm_reset (feed.cpp)
     bool in_group = false;      // option group_member: a member of an irdm_group (group.cpp), irdm_reset is refused
     uint64_t stat_resets = 0;   // irdm_reset calls that went through

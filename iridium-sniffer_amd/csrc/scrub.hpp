@@ -22,8 +22,7 @@
 // Every thread reaches every shuffle.
 // Bounds: it reads and writes the span's samples (chunk_span.hpp) and, counting, its block of kSbRows figures.
 //
-// Included by the translation units that launch it (feed.cpp: irdm_feed_host of a context and irdm_scrub_device;
-// frontend.cpp: the capture in front of K0 / K0r).
+// Launched by host_chain.hpp (the host feeds of a context and a front end) and by irdm_scrub_device (feed.cpp).
 #pragma once
 #include <string.h>
 #include <algorithm>
@@ -128,6 +127,14 @@ static inline int launch_scrub(void *d_buf, size_t n, int limit_log2, ScrubAcc *
     else
         hipLaunchKernelGGL((scrub_kernel<false>), dim3(grid), dim3(kChunkNT), 0, stream, d_buf, sp, scrub_limit_bits(limit_log2), d_acc);
     return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// n cf32 samples at d_buf scrubbed on `stream` without figures, in launches of at most kChunkMaxLaunch
+static inline int scrub_plain(void *d_buf, size_t n, int limit_log2, hipStream_t stream)
+{
+    for (size_t off = 0; off < n; off += kChunkMaxLaunch)
+        if (launch_scrub(static_cast<char *>(d_buf) + off * 8, std::min(kChunkMaxLaunch, n - off), limit_log2, nullptr, stream) != 0) return -1;
+    return 0;
 }
 
 // the running totals of a stream; first / last are stream positions, valid when zeroed > 0
