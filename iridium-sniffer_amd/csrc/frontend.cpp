@@ -75,26 +75,27 @@ static int fe_launch_k0(irdm_frontend *fe, const FrontendArgs &a, hipStream_t s)
     return launch_frontend(fe->D, a, fe->d_hr, fe->d_G, fe->d_T, s, fe->d_kclk);
 }
 
-extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *cfg)
+// the prototype P of the ratio L / M = out_rate / in_rate (resample.cpp's header comment); L = 1: K0's taps at D = M
+std::vector<float> fe_resample_taps(int in_rate, int out_rate, long long L)
 {
-    if (!cfg) return nullptr;
-    if (cfg->decim < 2 || cfg->decim > 16) {
-        fprintf(stderr, "irdm_hip: front end: decimation %d outside 2 .. 16\n", cfg->decim);
-        return nullptr;
-    }
-    if (cfg->in_rate <= 0 || cfg->in_rate % cfg->decim != 0) {
-        fprintf(stderr, "irdm_hip: front end: sample rate %d is not a multiple of the decimation %d\n", cfg->in_rate, cfg->decim);
-        return nullptr;
-    }
+    const float f_min = (float)std::min(in_rate, out_rate);
+    return design_lpf((float)L, (float)(L * (long long)in_rate), 0.5f * f_min, 0.09f * f_min);
+}
+
+irdm_frontend *fe_new(const irdm_frontend_rational_config_t *cfg, int decim, long long L, long long M)
+{
     if (!fmt_valid(cfg->in_format)) {
         fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
         return nullptr;
     }
-    const int out_rate = cfg->in_rate / cfg->decim;
     int fft = 0;
-    if (!rate_supported(out_rate, &fft)) {
-        fprintf(stderr, "irdm_hip: front end: output rate %d (%d / %d) is not one the pipeline takes (fft_size %d)\n", out_rate,
-                cfg->in_rate, cfg->decim, fft);
+    if (!rate_supported(cfg->out_rate, &fft)) {
+        if (decim)
+            fprintf(stderr, "irdm_hip: front end: output rate %d (%d / %d) is not one the pipeline takes (fft_size %d)\n",
+                    cfg->out_rate, cfg->in_rate, decim, fft);
+        else
+            fprintf(stderr, "irdm_hip: front end: output rate %d (%d * %lld / %lld) is not one the pipeline takes (fft_size %d)\n",
+                    cfg->out_rate, cfg->in_rate, L, M, fft);
         return nullptr;
     }
     const long long q = llround(cfg->shift_hz * 65536.0 / (double)cfg->in_rate);
@@ -110,18 +111,40 @@ extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *c
     if (hipSetDevice(cfg->device) != hipSuccess) return nullptr;
     irdm_frontend *fe = new (std::nothrow) irdm_frontend();
     if (!fe) return nullptr;
-    fe->cfg = *cfg;
-    fe->D = cfg->decim;
-    fe->L = 1;
-    fe->M = cfg->decim;
-    fe->launch = fe_launch_k0;
+    memset(&fe->cfg, 0, sizeof(fe->cfg));
+    fe->cfg.device = cfg->device;
+    fe->cfg.in_rate = cfg->in_rate;
+    fe->cfg.in_format = cfg->in_format;
+    fe->cfg.decim = decim;
+    fe->cfg.shift_hz = cfg->shift_hz;
+    fe->D = decim;
+    fe->L = (int)L;
+    fe->M = (int)M;
     fe->fmt = cfg->in_format;
     fe->bps = fmt_bytes(fe->fmt);
-    fe->out_rate = out_rate;
+    fe->out_rate = cfg->out_rate;
     fe->q = q;
-    fe->taps = design_lpf(1.0f, (float)cfg->in_rate, 0.5f * (float)out_rate, 0.09f * (float)out_rate);
+    fe->taps = fe_resample_taps(cfg->in_rate, cfg->out_rate, L);
     fe->ntaps = (int)fe->taps.size();
     fe->c = (fe->ntaps - 1) / 2;
+    return fe;
+}
+
+extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *cfg)
+{
+    if (!cfg) return nullptr;
+    if (cfg->decim < 2 || cfg->decim > 16) {
+        fprintf(stderr, "irdm_hip: front end: decimation %d outside 2 .. 16\n", cfg->decim);
+        return nullptr;
+    }
+    if (cfg->in_rate <= 0 || cfg->in_rate % cfg->decim != 0) {
+        fprintf(stderr, "irdm_hip: front end: sample rate %d is not a multiple of the decimation %d\n", cfg->in_rate, cfg->decim);
+        return nullptr;
+    }
+    const irdm_frontend_rational_config_t rc = { cfg->device, cfg->in_rate, cfg->in_format, cfg->in_rate / cfg->decim, cfg->shift_hz };
+    irdm_frontend *fe = fe_new(&rc, cfg->decim, 1, cfg->decim);
+    if (!fe) return nullptr;
+    fe->launch = fe_launch_k0;
     const int R = 8, D = fe->D, nt = fe->ntaps;
     if (nt < (R - 1) * D + 1 || frontend_lds_bytes(D, nt) > 160 * 1024) {
         fprintf(stderr, "irdm_hip: front end: %d taps at decimation %d do not fit the kernel\n", nt, D);
@@ -133,15 +156,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create(const irdm_frontend_config_t *c
     for (int j = 0; j < nt; j++) hr[j] = fe->taps[nt - 1 - j];
     for (int i = (R - 1) * D; i < nt; i++)
         for (int r = 0; r < R; r++) G[(size_t)(i - (R - 1) * D) * R + r] = hr[i - r * D];
-    bool ok = (fe->d_hr = dev_upload(hr.data(), hr.size())) != nullptr;
-    ok = ok && (fe->d_G = dev_upload(G.data(), G.size())) != nullptr;
-    ok = ok && fe_alloc_common(fe, (size_t)(nt + D + 16));
-    if (!ok) {
-        fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
-        fe_free(fe);
-        return nullptr;
-    }
-    return fe;
+    return fe_finish(fe, &fe->d_hr, hr, G);
 }
 
 extern "C" void irdm_frontend_destroy(irdm_frontend_t *fe) { fe_free(fe); }

@@ -21,24 +21,17 @@
 // end, where only some of the 8 outputs take part, are unrolled with their taps from the plain reversed array.
 // Finished outputs go through LDS once more so that the global stores are consecutive 8-byte stores per lane.
 //
-// Bounds: every global read goes through fe_load, which returns zero for a position outside [tail | chunk]; every global
-// write is guarded by m < m1.  LDS: (cnt + cnt / (8 D) + 1) samples, the host computes the same expression.
+// Bounds: every global read of the capture is the load stage's (fe_stage.hpp: zero for a position outside
+// [tail | chunk]); every global write is guarded by m < m1.  LDS: (cnt + cnt / (8 D) + 1) samples, the host computes the
+// same expression.
 #include "common.hpp"
 #include "types.hpp"
 #include "kernels.hpp"
+#include "fe_stage.hpp"
 
 namespace irdm {
 
 constexpr int kFeR = 8;               // outputs per lane
-
-// a pair of fused multiply-adds with a common factor (v_pk_fma_f32)
-#if defined(IRDM_HIP_EMULATED)
-struct fe_v2 { float x, y; };
-static inline fe_v2 fe_fma(float t, fe_v2 s, fe_v2 a) { return fe_v2{ fmaf(t, s.x, a.x), fmaf(t, s.y, a.y) }; }
-#else
-typedef float fe_v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ fe_v2 fe_fma(float t, fe_v2 s, fe_v2 a) { return __builtin_elementwise_fma(fe_v2{ t, t }, s, a); }
-#endif
 
 int frontend_threads(int D)
 {
@@ -54,47 +47,11 @@ size_t frontend_lds_bytes(int D, int ntaps)
     return (size_t)(cnt + cnt / (kFeR * D) + 1) * sizeof(float2);
 }
 
-// stream position n -> the rotated sample r[n]
-__device__ __forceinline__ float2 fe_load(const FrontendArgs &a, long long n, const float2 *__restrict__ T)
-{
-    const long long v = n - a.pos0;
-    if (n < 0 || v < 0 || v >= a.n_tail + a.n_in) return make_float2(0.0f, 0.0f);
-    const float2 x = v < a.n_tail ? load_iq(a.fmt, a.tail, (size_t)v) : load_iq(a.fmt, a.in, (size_t)(v - a.n_tail));
-    const unsigned i = (a.q16 * (unsigned)((unsigned long long)n & 0xffffull)) & 0xffffu;
-    return cmul(x, T[i]);
-}
-
-// The load stage of a tile that lies wholly inside the chunk (all but the first and last tiles of a launch): no bounds, one
-// format, eight samples and their table entries requested before the first is used -- a lane's loads are otherwise
-// issued and waited for one at a time, and with one or two wavefronts per SIMD nothing hides them (measured at D = 5:
-// the kernel's span 4.0 ms per 64 Mi outputs with the general loop alone).  The same operations on the same operands.
-template <int FMT, int NT, int RD>
-__device__ __forceinline__ void fe_stage_inside(const FrontendArgs &a, long long v0, long long n_start, int cnt,
-                                                const float2 *__restrict__ T, fe_v2 *s, int tid)
-{
-    constexpr int U = 8;
-    int g = tid;
-    for (; g + (U - 1) * NT < cnt; g += U * NT) {
-        float2 x[U], t[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int gu = g + u * NT;
-            x[u] = load_iq<FMT>(a.in, (size_t)(v0 + gu));
-            t[u] = T[(a.q16 * (unsigned)((unsigned long long)(n_start + gu) & 0xffffull)) & 0xffffu];
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int gu = g + u * NT;
-            const float2 r = cmul(x[u], t[u]);
-            s[gu + gu / RD] = fe_v2{ r.x, r.y };
-        }
-    }
-    for (; g < cnt; g += NT) {
-        const float2 x = load_iq<FMT>(a.in, (size_t)(v0 + g));
-        const float2 r = cmul(x, T[(a.q16 * (unsigned)((unsigned long long)(n_start + g) & 0xffffull)) & 0xffffu]);
-        s[g + g / RD] = fe_v2{ r.x, r.y };
-    }
-}
+// the pad samples in front of staged sample g: one behind every row of RD staged samples
+template <int RD>
+struct fe_pad {
+    __device__ __forceinline__ int operator()(int g) const { return g / RD; }
+};
 
 template <int D, int NT>
 __global__ __launch_bounds__(NT) void frontend_kernel(FrontendArgs a, const float *__restrict__ hr, const float *__restrict__ G,
@@ -111,24 +68,7 @@ __global__ __launch_bounds__(NT) void frontend_kernel(FrontendArgs a, const floa
     const int cnt = (TO - 1) * D + ntaps;
 
     // ---- load stage: convert, rotate, into LDS ----
-    const long long v0 = n_start - a.pos0 - a.n_tail;                   // the tile's first sample as an index into the chunk
-    if (n_start >= 0 && v0 >= 0 && v0 + cnt <= a.n_in) {
-        switch (a.fmt) {
-        case 2: fe_stage_inside<2, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        case 1: fe_stage_inside<1, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        case 3: fe_stage_inside<3, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        case 4: fe_stage_inside<4, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        case 6: fe_stage_inside<6, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        case 8: fe_stage_inside<8, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        case 9: fe_stage_inside<9, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        default: fe_stage_inside<0, NT, RD>(a, v0, n_start, cnt, T, s, tid); break;
-        }
-    } else {
-        for (int g = tid; g < cnt; g += NT) {
-            const float2 r = fe_load(a, n_start + g, T);
-            s[g + g / RD] = fe_v2{ r.x, r.y };
-        }
-    }
+    fe_stage<NT>(a, n_start, cnt, T, s, tid, fe_pad<RD>{});
     __syncthreads();
 
     // ---- the taps: lane `tid` owns outputs mt + R tid + r; in step i it reads its sample i (input (mt + R tid) D - c + i) ----

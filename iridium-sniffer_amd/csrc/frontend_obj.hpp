@@ -2,7 +2,8 @@
 // decimation), irdm_frontend_create_rational (resample.cpp: K0r, L / M) and irdm_frontend_create_wide (resample_wide.cpp:
 // K0w, L / M at large L or M).  Everything behind creation -- the stream bookkeeping, the feeder, reset -- is frontend.cpp's
 // and works on the ratio L / M (1 / D for K0); the object carries its kernel's launch function, so frontend.cpp refers to
-// no kernel file by name beyond K0's.
+// no kernel file by name beyond K0's.  The three makers share one path (fe_new, fe_finish below); each keeps its domain
+// check, its plan, its tables and its launch function.
 #pragma once
 #include "pipeline.hpp"
 
@@ -81,14 +82,31 @@ struct irdm_frontend {
 
 namespace irdmh {
 void fe_free(irdm_frontend *fe);
-// what both modes allocate: the rotation table, the kernel clock record, the two tail buffers (tail_samples each, 8 bytes
-// per sample), the stream in K1's priority class and the events.  fe->cfg.device is current.  false: allocation failed.
+// The maker path (frontend.cpp).  A maker checks its own domain, then:
+//   fe_new     what the three kernels share of creation, for the ratio L / M in lowest terms (decim: K0's D, 1 / D; 0
+//              otherwise): the checks of format, output rate, shift and device, the object and its prototype
+//              (fe_resample_taps: the design of out_rate / in_rate = L / M).  nullptr with a message on stderr.
+//   ...        the maker's launch function, its plan and its two tables
+//   fe_finish  the two tables to the device (d_hr or d_desc, and d_G) and what every kernel needs beside them
+//              (fe_alloc_common: the rotation table, the kernel clock record, the two tail buffers of tail_samples each,
+//              8 bytes per sample, the stream in K1's priority class and the events; fe->cfg.device is current).  The
+//              object, or nullptr with the message on stderr and the object freed.
+std::vector<float> fe_resample_taps(int in_rate, int out_rate, long long L);
+irdm_frontend *fe_new(const irdm_frontend_rational_config_t *cfg, int decim, long long L, long long M);
 bool fe_alloc_common(irdm_frontend *fe, size_t tail_samples);
-// resample.cpp.  out_rate / in_rate in lowest terms, L / M (false, with a message: a rate that is not positive).  K0r's limits: 0 inside them, 1 L or M too large, 2 M / L outside its
-// range.  The prototype of out_rate / in_rate = L / M.  What K0r and K0w share of creation: the checks behind the ratio, the object and its prototype -- launch function,
-// kernel tables and device memory are the caller's; nullptr with a message on stderr.
+template <typename T>
+irdm_frontend *fe_finish(irdm_frontend *fe, T **d_first, const std::vector<T> &first, const std::vector<float> &G)
+{
+    bool ok = (*d_first = dev_upload(first.data(), first.size())) != nullptr;
+    ok = ok && (fe->d_G = dev_upload(G.data(), G.size())) != nullptr;
+    ok = ok && fe_alloc_common(fe, (size_t)(fe->ntaps / fe->L + fe->M + 16));
+    if (ok) return fe;
+    fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
+    fe_free(fe);
+    return nullptr;
+}
+// resample.cpp.  out_rate / in_rate in lowest terms, L / M (false, with a message: a rate that is not positive).  K0r's
+// limits: 0 inside them, 1 L or M too large, 2 M / L outside its range.
 bool fe_ratio(int in_rate, int out_rate, long long *L, long long *M);
 int fe_rational_domain(long long L, long long M);
-std::vector<float> fe_resample_taps(int in_rate, int out_rate, long long L);
-irdm_frontend *fe_new_resampled(const irdm_frontend_rational_config_t *cfg, long long L, long long M);
 }  // namespace irdmh

@@ -1,6 +1,6 @@
 // resample.cpp -- irdm_frontend_create_rational: the front end's rational mode (K0r, resample.hip), output rate = input rate
-// * L / M.  It makes the same object irdm_frontend_create makes (frontend_obj.hpp); everything behind creation is
-// frontend.cpp's.  An integer ratio 2 .. 16 is handed to irdm_frontend_create: K0, bit for bit.
+// * L / M.  It makes the same object irdm_frontend_create makes, on the same maker path (frontend_obj.hpp: fe_new, fe_finish);
+// everything behind creation is frontend.cpp's.  An integer ratio 2 .. 16 is handed to irdm_frontend_create: K0, bit for bit.
 //
 // The prototype P is the pipeline's own low-pass design at the rate L * in_rate with gain L, cut-off 0.5 f_min and
 // transition parameter 0.09 f_min, f_min = min(in_rate, out_rate).  design_lpf takes the rate as a float: L * in_rate is
@@ -63,59 +63,6 @@ extern "C" int irdm_frontend_rational_ratio(int in_rate, int out_rate, int *L_ou
     return 0;
 }
 
-// the prototype P of the ratio L / M = out_rate / in_rate (the header comment)
-std::vector<float> fe_resample_taps(int in_rate, int out_rate, long long L)
-{
-    const float f_min = (float)std::min(in_rate, out_rate);
-    return design_lpf((float)L, (float)(L * (long long)in_rate), 0.5f * f_min, 0.09f * f_min);
-}
-
-// What K0r and K0w (resample_wide.cpp) share of creation, for the ratio L / M in lowest terms: the checks of format, output
-// rate, shift and device, the object and its prototype.  The kernel's tables, the launch function and the device memory
-// are the caller's.  nullptr with a message on stderr.
-irdm_frontend *fe_new_resampled(const irdm_frontend_rational_config_t *cfg, long long L, long long M)
-{
-    if (!fmt_valid(cfg->in_format)) {
-        fprintf(stderr, "irdm_hip: front end: unknown sample format %d\n", cfg->in_format);
-        return nullptr;
-    }
-    int fft = 0;
-    if (!rate_supported(cfg->out_rate, &fft)) {
-        fprintf(stderr, "irdm_hip: front end: output rate %d (%d * %lld / %lld) is not one the pipeline takes (fft_size %d)\n",
-                cfg->out_rate, cfg->in_rate, L, M, fft);
-        return nullptr;
-    }
-    const long long q = llround(cfg->shift_hz * 65536.0 / (double)cfg->in_rate);
-    if (q < -32768 || q > 32768) {
-        fprintf(stderr, "irdm_hip: front end: shift %.1f Hz is beyond half the capture rate %d\n", cfg->shift_hz, cfg->in_rate);
-        return nullptr;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        fprintf(stderr, "irdm_hip: no HIP device -- there is no CPU fallback in this library\n");
-        return nullptr;
-    }
-    if (hipSetDevice(cfg->device) != hipSuccess) return nullptr;
-    irdm_frontend *fe = new (std::nothrow) irdm_frontend();
-    if (!fe) return nullptr;
-    memset(&fe->cfg, 0, sizeof(fe->cfg));
-    fe->cfg.device = cfg->device;
-    fe->cfg.in_rate = cfg->in_rate;
-    fe->cfg.in_format = cfg->in_format;
-    fe->cfg.shift_hz = cfg->shift_hz;
-    fe->D = 0;
-    fe->L = (int)L;
-    fe->M = (int)M;
-    fe->fmt = cfg->in_format;
-    fe->bps = fmt_bytes(fe->fmt);
-    fe->out_rate = cfg->out_rate;
-    fe->q = q;
-    fe->taps = fe_resample_taps(cfg->in_rate, cfg->out_rate, L);
-    fe->ntaps = (int)fe->taps.size();
-    fe->c = (fe->ntaps - 1) / 2;
-    return fe;
-}
-
 extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_rational_config_t *cfg)
 {
     if (!cfg) return nullptr;
@@ -132,7 +79,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_ra
         ic.shift_hz = cfg->shift_hz;
         return irdm_frontend_create(&ic);
     }
-    irdm_frontend *fe = fe_new_resampled(cfg, L, M);
+    irdm_frontend *fe = fe_new(cfg, 0, L, M);
     if (!fe) return nullptr;
     fe->launch = fe_launch_k0r;
     std::vector<int> desc;
@@ -142,15 +89,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create_rational(const irdm_frontend_ra
         delete fe;
         return nullptr;
     }
-    bool ok = (fe->d_desc = dev_upload(desc.data(), desc.size())) != nullptr;
-    ok = ok && (fe->d_G = dev_upload(G.data(), G.size())) != nullptr;
-    ok = ok && fe_alloc_common(fe, (size_t)(fe->ntaps / fe->L + fe->M + 16));
-    if (!ok) {
-        fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
-        fe_free(fe);
-        return nullptr;
-    }
-    return fe;
+    return fe_finish(fe, &fe->d_desc, desc, G);
 }
 
 }  // namespace irdmh

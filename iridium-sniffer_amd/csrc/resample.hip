@@ -11,7 +11,7 @@
 // Shape.  Output m = L p + r (period p, phase r) reads the inputs p M + nlo(r) .. p M + a(r), a(r) = floor((r M + C) / L),
 // nlo(r) = floor((r M + C - Np) / L) + 1, with the taps P[r M + C - (n - p M) L]: they depend on the phase alone.  A tile is
 // `nper` whole periods, so it starts at a multiple of L.  Its (nper - 1) M + a(L - 1) - nlo(0) + 1 input samples are
-// converted and rotated ONCE into LDS, as K0's load stage does.  A lane owns R consecutive outputs of ONE period -- a phase
+// converted and rotated ONCE into LDS, by K0's load stage (fe_stage.hpp).  A lane owns R consecutive outputs of ONE period -- a phase
 // block -- and the 64 lanes of a wavefront own the same phase block of 64 consecutive periods: in step i every lane
 // multiplies by the SAME taps, read as one aligned 8-dword scalar load per step from the block's table (host-laid,
 // resample_plan), and lane l's window starts l M samples further on.  A sample read from LDS goes into up to R accumulator
@@ -26,13 +26,14 @@
 // multiply-adds per step (L = 25 with one group: R = 7 makes 4 units, one round; R = 5 made 5 units, two rounds with
 // three wavefronts idle in the second).
 //
-// Bounds: every global read goes through rs_load (zero outside [tail | chunk]) or, for a tile wholly inside the chunk, is
-// covered by the test in front of rs_stage_inside; every global write is guarded by m0 <= m < m1.  LDS: the host computes
+// Bounds: every global read of the capture is the load stage's (fe_stage.hpp: zero outside [tail | chunk], or a tile that
+// its test finds wholly inside the chunk); every global write is guarded by m0 <= m < m1.  LDS: the host computes
 // the same expressions (resample_plan, resample_lds_bytes); a lane beyond the tile's periods works on period 0's samples
 // and stores nothing.
 #include "common.hpp"
 #include "types.hpp"
 #include "kernels.hpp"
+#include "fe_stage.hpp"
 
 namespace irdm {
 
@@ -40,16 +41,10 @@ constexpr int kRsNT = 256;            // threads per workgroup (4 wavefronts)
 constexpr int kRsU = 4;               // steps per block of the tap loop, at most
 
 #if defined(IRDM_HIP_EMULATED)
-struct rs_v2 { float x, y; };
-static inline rs_v2 rs_fma(float t, rs_v2 s, rs_v2 a) { return rs_v2{ fmaf(t, s.x, a.x), fmaf(t, s.y, a.y) }; }
 static inline int rs_uniform(int v) { return v; }
 #else
-typedef float rs_v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ rs_v2 rs_fma(float t, rs_v2 s, rs_v2 a) { return __builtin_elementwise_fma(rs_v2{ t, t }, s, a); }
 __device__ __forceinline__ int rs_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 #endif
-
-static inline long long rs_fdiv(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // descriptor of a phase block (kRsDesc ints): 0 S steps, 1 / 2 the steps [f0, f1) in which every phase of the block takes
 // part, 3 r0, 4 rb phases, 5 / 6 / 7 offsets (dwords) into G of the block's tap rows (kRsRow floats per step), its LDS
@@ -60,8 +55,8 @@ bool resample_plan(int L, int M, const float *taps, int ntaps, ResampleGeom *g, 
 {
     if (L < 2 || M < 2 || ntaps < 1 || !(ntaps & 1)) return false;
     const long long Np = ntaps, C = (Np - 1) / 2;
-    auto a_of = [&](int r) { return (int)rs_fdiv((long long)r * M + C, L); };
-    auto nlo_of = [&](int r) { return (int)rs_fdiv((long long)r * M + C - Np, L) + 1; };
+    auto a_of = [&](int r) { return (int)fe_fdiv((long long)r * M + C, L); };
+    auto nlo_of = [&](int r) { return (int)fe_fdiv((long long)r * M + C - Np, L) + 1; };
     g->L = L;
     g->M = M;
     g->lo_min = nlo_of(0);
@@ -137,51 +132,11 @@ bool resample_plan(int L, int M, const float *taps, int ntaps, ResampleGeom *g, 
 
 size_t resample_lds_bytes(const ResampleGeom &g) { return (size_t)(g.out_off + g.nper * g.L) * sizeof(float2); }
 
-// staged index -> LDS index
-__device__ __forceinline__ int rs_slot(const ResampleGeom &g, int gi)
-{
-    return gi + (int)(((unsigned long long)(unsigned)gi * g.magic) >> 32);
-}
-
-// stream position n -> the rotated sample r[n] (K0's fe_load)
-__device__ __forceinline__ float2 rs_load(const FrontendArgs &a, long long n, const float2 *__restrict__ T)
-{
-    const long long v = n - a.pos0;
-    if (n < 0 || v < 0 || v >= a.n_tail + a.n_in) return make_float2(0.0f, 0.0f);
-    const float2 x = v < a.n_tail ? load_iq(a.fmt, a.tail, (size_t)v) : load_iq(a.fmt, a.in, (size_t)(v - a.n_tail));
-    const unsigned i = (a.q16 * (unsigned)((unsigned long long)n & 0xffffull)) & 0xffffu;
-    return cmul(x, T[i]);
-}
-
-// the load stage of a tile that lies wholly inside the chunk: no bounds, one format, eight samples and their table entries
-// requested before the first is used (K0's fe_stage_inside)
-template <int FMT>
-__device__ __forceinline__ void rs_stage_inside(const FrontendArgs &a, const ResampleGeom &g, long long v0, long long n_start,
-                                                const float2 *__restrict__ T, rs_v2 *s, int tid)
-{
-    constexpr int U = 8, NT = kRsNT;
-    const int cnt = g.cnt;
-    int gi = tid;
-    for (; gi + (U - 1) * NT < cnt; gi += U * NT) {
-        float2 x[U], t[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int gu = gi + u * NT;
-            x[u] = load_iq<FMT>(a.in, (size_t)(v0 + gu));
-            t[u] = T[(a.q16 * (unsigned)((unsigned long long)(n_start + gu) & 0xffffull)) & 0xffffu];
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const float2 r = cmul(x[u], t[u]);
-            s[rs_slot(g, gi + u * NT)] = rs_v2{ r.x, r.y };
-        }
-    }
-    for (; gi < cnt; gi += NT) {
-        const float2 x = load_iq<FMT>(a.in, (size_t)(v0 + gi));
-        const float2 r = cmul(x, T[(a.q16 * (unsigned)((unsigned long long)(n_start + gi) & 0xffffull)) & 0xffffu]);
-        s[rs_slot(g, gi)] = rs_v2{ r.x, r.y };
-    }
-}
+// the pad samples in front of staged sample gi: gi / M (magic 0: none)
+struct rs_pad {
+    unsigned magic;
+    __device__ __forceinline__ int operator()(int gi) const { return (int)(((unsigned long long)(unsigned)gi * magic) >> 32); }
+};
 
 template <int R>
 __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, ResampleGeom g, const int *__restrict__ desc,
@@ -190,8 +145,8 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rs_lds[];
     static_assert(R <= kRsRow, "a row of the tap table holds the block's phases");
-    rs_v2 *s = reinterpret_cast<rs_v2 *>(rs_lds);
-    rs_v2 *so = s + g.out_off;
+    fe_v2 *s = reinterpret_cast<fe_v2 *>(rs_lds);
+    fe_v2 *so = s + g.out_off;
     const int tid = threadIdx.x;
     const int L = g.L, M = g.M, pad = g.pad;
     kclk_enter(kclk);
@@ -199,24 +154,7 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
     const long long n_start = pt * M + g.lo_min;                        // ... and its first input sample
 
     // ---- load stage: convert, rotate, into LDS ----
-    const long long v0 = n_start - a.pos0 - a.n_tail;                   // the tile's first sample as an index into the chunk
-    if (n_start >= 0 && v0 >= 0 && v0 + g.cnt <= a.n_in) {
-        switch (a.fmt) {
-        case 2: rs_stage_inside<2>(a, g, v0, n_start, T, s, tid); break;
-        case 1: rs_stage_inside<1>(a, g, v0, n_start, T, s, tid); break;
-        case 3: rs_stage_inside<3>(a, g, v0, n_start, T, s, tid); break;
-        case 4: rs_stage_inside<4>(a, g, v0, n_start, T, s, tid); break;
-        case 6: rs_stage_inside<6>(a, g, v0, n_start, T, s, tid); break;
-        case 8: rs_stage_inside<8>(a, g, v0, n_start, T, s, tid); break;
-        case 9: rs_stage_inside<9>(a, g, v0, n_start, T, s, tid); break;
-        default: rs_stage_inside<0>(a, g, v0, n_start, T, s, tid); break;
-        }
-    } else {
-        for (int gi = tid; gi < g.cnt; gi += kRsNT) {
-            const float2 r = rs_load(a, n_start + gi, T);
-            s[rs_slot(g, gi)] = rs_v2{ r.x, r.y };
-        }
-    }
+    fe_stage<kRsNT>(a, n_start, g.cnt, T, s, tid, rs_pad{ g.magic });
     __syncthreads();
 
     // ---- the taps: a wavefront takes the units (64 periods x one phase block) wave, wave + 4, ... ----
@@ -232,20 +170,20 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
         const int *__restrict__ mask = reinterpret_cast<const int *>(G + d[7]);
         const int pl = grp * 64 + lane;
         const bool live = pl < g.nper;
-        const rs_v2 *w = s + (live ? pl : 0) * (M + pad);
-        rs_v2 acc[R];
+        const fe_v2 *w = s + (live ? pl : 0) * (M + pad);
+        fe_v2 acc[R];
 #pragma unroll
-        for (int r = 0; r < R; r++) acc[r] = rs_v2{ 0.0f, 0.0f };
+        for (int r = 0; r < R; r++) acc[r] = fe_v2{ 0.0f, 0.0f };
         // the steps at either end, where only some of the block's phases take part: [0, f0) and [f1, S)
         auto edge = [&](int i0, int i1) {
 #pragma unroll 1
             for (int i = i0; i < i1; i++) {
-                const rs_v2 x = w[offs[i]];
+                const fe_v2 x = w[offs[i]];
                 const float *t = gt + i * kRsRow;
                 const int mk = mask[i];
 #pragma unroll
                 for (int r = 0; r < R; r++)
-                    if (mk & (1 << r)) acc[r] = rs_fma(t[r], x, acc[r]);
+                    if (mk & (1 << r)) acc[r] = fe_fma(t[r], x, acc[r]);
             }
         };
         edge(0, f0);
@@ -256,9 +194,9 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
         {
             constexpr int U = R > 5 ? kRsU / 2 : kRsU;      // (a scalar tap takes an aligned register pair: 2 U R of them)
             float tc[U * R];
-            rs_v2 xc[U];
+            fe_v2 xc[U];
             int oc[U];
-            auto fetch = [&](float (&t)[U * R], rs_v2 (&x)[U], const int (&o)[U], int at) {
+            auto fetch = [&](float (&t)[U * R], fe_v2 (&x)[U], const int (&o)[U], int at) {
                 const float *gp = gt + at * kRsRow;
 #pragma unroll
                 for (int k = 0; k < U; k++)
@@ -275,7 +213,7 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
 #pragma unroll 1
             for (; i + U <= f1; i += U) {
                 float tn[U * R];
-                rs_v2 xn[U];
+                fe_v2 xn[U];
                 int on[U];
                 fetch(tn, xn, oc, i + U);
 #pragma unroll
@@ -284,7 +222,7 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
 #pragma unroll
                 for (int k = 0; k < U; k++)
 #pragma unroll
-                    for (int r = 0; r < R; r++) acc[r] = rs_fma(tc[k * R + r], xc[k], acc[r]);
+                    for (int r = 0; r < R; r++) acc[r] = fe_fma(tc[k * R + r], xc[k], acc[r]);
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int k = 0; k < U * R; k++) tc[k] = tn[k];
@@ -299,7 +237,7 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
             for (int k = 0; k < U - 1; k++)
                 if (i + k < f1) {
 #pragma unroll
-                    for (int r = 0; r < R; r++) acc[r] = rs_fma(tc[k * R + r], xc[k], acc[r]);
+                    for (int r = 0; r < R; r++) acc[r] = fe_fma(tc[k * R + r], xc[k], acc[r]);
                 }
             i = f1;
         }
@@ -318,7 +256,7 @@ __global__ __launch_bounds__(kRsNT) void resample_kernel(FrontendArgs a, Resampl
     for (int o = tid; o < n_tile; o += kRsNT) {
         const long long m = mt + o;
         if (m >= a.m0 && m < a.m1) {
-            const rs_v2 y = so[o];
+            const fe_v2 y = so[o];
             a.out[m - a.m0] = make_float2(y.x, y.y);
         }
     }
@@ -330,16 +268,7 @@ static int launch_resample_r(const ResampleGeom &g, const FrontendArgs &a, const
                              hipStream_t stream, unsigned long long *kclk, long long tiles)
 {
     const size_t lds = resample_lds_bytes(g);
-    // (once per instantiation and device: the most the kernel is ever given)
-    static bool raised[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    if (!raised[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&resample_kernel<R>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess)
-            return -1;
-        raised[dev] = true;
-    }
+    if (!fe_raise_lds<&resample_kernel<R>>()) return -1;
     hipLaunchKernelGGL((resample_kernel<R>), dim3((unsigned)tiles), dim3(kRsNT), lds, stream, a, g, desc, G, T, kclk);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

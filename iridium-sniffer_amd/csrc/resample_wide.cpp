@@ -1,6 +1,6 @@
 // resample_wide.cpp -- irdm_frontend_create_wide and irdm_frontend_create_resampler: the front end's rational mode on K0w
 // (resample_wide.hip), for the ratios beyond K0r's L <= 125 and M <= 768 -- 2 <= L <= 4096, M <= 65536, 24/25 <= M / L <= 16,
-// a prototype of at most 2^20 taps.  The object is irdm_frontend_create_rational's (frontend_obj.hpp, fe_new_resampled): the
+// a prototype of at most 2^20 taps.  The object is irdm_frontend_create_rational's (frontend_obj.hpp, fe_new): the
 // same checks, the same prototype from the same design_lpf call, so a ratio both kernels take has one set of taps and one
 // output; everything behind creation is frontend.cpp's.  irdm_frontend_create_resampler picks the kernel: wherever
 // irdm_frontend_create or irdm_frontend_create_rational make the object it hands over to them.
@@ -69,7 +69,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create_wide(const irdm_frontend_ration
     if (!cfg) return nullptr;
     long long L = 0, M = 0;
     if (!fe_ratio(cfg->in_rate, cfg->out_rate, &L, &M) || wide_domain(cfg->in_rate, cfg->out_rate, L, M) != 0) return nullptr;
-    irdm_frontend *fe = fe_new_resampled(cfg, L, M);
+    irdm_frontend *fe = fe_new(cfg, 0, L, M);
     if (!fe) return nullptr;
     fe->launch = fe_launch_k0w;
     std::vector<int> nlo;
@@ -78,15 +78,7 @@ extern "C" irdm_frontend_t *irdm_frontend_create_wide(const irdm_frontend_ration
         delete fe;
         return nullptr;
     }
-    bool ok = (fe->d_desc = dev_upload(nlo.data(), nlo.size())) != nullptr;
-    ok = ok && (fe->d_G = dev_upload(W.data(), W.size())) != nullptr;
-    ok = ok && fe_alloc_common(fe, (size_t)(fe->ntaps / fe->L + fe->M + 16));
-    if (!ok) {
-        fprintf(stderr, "irdm_hip: front end: device allocation failed\n");
-        fe_free(fe);
-        return nullptr;
-    }
-    return fe;
+    return fe_finish(fe, &fe->d_desc, nlo, W);
 }
 
 extern "C" irdm_frontend_t *irdm_frontend_create_resampler(const irdm_frontend_rational_config_t *cfg)

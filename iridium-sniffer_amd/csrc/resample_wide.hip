@@ -15,7 +15,7 @@
 // inputs p M + nlo(r) + i, i = 0 .. S(r) - 1, nlo(r) = floor((r M + C - Np) / L) + 1, with the taps
 // P[r M + C - (nlo(r) + i) L]: window start and taps depend on the phase alone, and every index that depends on p is
 // formed once per tile in 64 bits.  The tile's inputs -- from the first input of its first output to the last of its last,
-// at most floor(((B - 1) M + Np) / L) + 1 samples -- are converted and rotated ONCE into LDS, as K0's load stage does.
+// at most floor(((B - 1) M + Np) / L) + 1 samples -- are converted and rotated ONCE into LDS, by K0's load stage (fe_stage.hpp).
 // The prototype lies in memory as W[step i][phase r] (host-laid, resample_wide_plan): since gcd(L, M) = 1 consecutive
 // outputs have consecutive phases, so in step i the lanes of a wavefront load consecutive floats (up to the wrap of
 // m mod L, where the row starts again), and their LDS reads lie about M / L samples apart.  Where that stride, rounded, is
@@ -27,27 +27,18 @@
 // blocks of kRwU steps; the next block's taps (vector loads) and samples (LDS reads) are requested before the current
 // block's multiply-adds, as K0r's loop does.
 //
-// Bounds: every global read of the capture goes through rw_load (zero outside [tail | chunk]) or, for a tile wholly inside
-// the chunk, is covered by the test in front of rw_stage_inside; every global write is guarded by o < nout, that is
-// m < m1.  The requests that run ahead of the last step stay inside the slack of 2 kRwU rows behind W and of 2 kRwU + 2
-// samples behind the staged window (resample_wide_plan, resample_wide_lds_bytes) and are not used.
+// Bounds: every global read of the capture is the load stage's (fe_stage.hpp: zero outside [tail | chunk], or a tile that
+// its test finds wholly inside the chunk); every global write is guarded by o < nout, that is m < m1.  The requests that run
+// ahead of the last step stay inside the slack of 2 kRwU rows behind W and of 2 kRwU + 2 samples behind the staged window
+// (resample_wide_plan, resample_wide_lds_bytes) and are not used.
 #include "common.hpp"
 #include "types.hpp"
 #include "kernels.hpp"
+#include "fe_stage.hpp"
 
 namespace irdm {
 
 constexpr int kRwNT = 256;            // threads per workgroup (4 wavefronts)
-
-#if defined(IRDM_HIP_EMULATED)
-struct rw_v2 { float x, y; };
-static inline rw_v2 rw_fma(float t, rw_v2 s, rw_v2 a) { return rw_v2{ fmaf(t, s.x, a.x), fmaf(t, s.y, a.y) }; }
-#else
-typedef float rw_v2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ rw_v2 rw_fma(float t, rw_v2 s, rw_v2 a) { return __builtin_elementwise_fma(rw_v2{ t, t }, s, a); }
-#endif
-
-static inline long long rw_fdiv(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
 // staged samples -> LDS samples, pad samples counted
 static inline long long rw_slots(int pad_s, long long n) { return n + (pad_s ? n / pad_s : 0); }
@@ -87,7 +78,7 @@ bool resample_wide_plan(int L, int M, const float *taps, int ntaps, WideGeom *g,
     nlo->resize(L);
     W->assign((size_t)(g->S + 2 * kRwU) * L, 0.0f);
     for (int r = 0; r < L; r++) {
-        const long long lo = rw_fdiv((long long)r * M + C - Np, L) + 1;
+        const long long lo = fe_fdiv((long long)r * M + C - Np, L) + 1;
         (*nlo)[r] = (int)lo;
         for (int i = 0; i < g->S; i++) {
             const long long k = (long long)r * M + C - (lo + i) * L;
@@ -98,50 +89,16 @@ bool resample_wide_plan(int L, int M, const float *taps, int ntaps, WideGeom *g,
     return true;
 }
 
-// staged index -> LDS index
+// the pad samples in front of staged sample gi; staged index -> LDS index
+template <bool PAD>
+__device__ __forceinline__ int rw_pad(const WideGeom &g, int gi)
+{
+    return PAD ? (int)(((unsigned long long)(unsigned)gi * g.magic) >> 32) : 0;
+}
 template <bool PAD>
 __device__ __forceinline__ int rw_slot(const WideGeom &g, int gi)
 {
-    return PAD ? gi + (int)(((unsigned long long)(unsigned)gi * g.magic) >> 32) : gi;
-}
-
-// stream position n -> the rotated sample r[n] (K0's fe_load)
-__device__ __forceinline__ float2 rw_load(const FrontendArgs &a, long long n, const float2 *__restrict__ T)
-{
-    const long long v = n - a.pos0;
-    if (n < 0 || v < 0 || v >= a.n_tail + a.n_in) return make_float2(0.0f, 0.0f);
-    const float2 x = v < a.n_tail ? load_iq(a.fmt, a.tail, (size_t)v) : load_iq(a.fmt, a.in, (size_t)(v - a.n_tail));
-    const unsigned i = (a.q16 * (unsigned)((unsigned long long)n & 0xffffull)) & 0xffffu;
-    return cmul(x, T[i]);
-}
-
-// the load stage of a tile that lies wholly inside the chunk: no bounds, one format, eight samples and their table entries
-// requested before the first is used (K0's fe_stage_inside)
-template <int FMT, bool PAD>
-__device__ __forceinline__ void rw_stage_inside(const FrontendArgs &a, const WideGeom &g, int cnt, long long v0, long long n_start,
-                                                const float2 *__restrict__ T, rw_v2 *s, int tid)
-{
-    constexpr int U = 8, NT = kRwNT;
-    int gi = tid;
-    for (; gi + (U - 1) * NT < cnt; gi += U * NT) {
-        float2 x[U], t[U];
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const int gu = gi + u * NT;
-            x[u] = load_iq<FMT>(a.in, (size_t)(v0 + gu));
-            t[u] = T[(a.q16 * (unsigned)((unsigned long long)(n_start + gu) & 0xffffull)) & 0xffffu];
-        }
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const float2 r = cmul(x[u], t[u]);
-            s[rw_slot<PAD>(g, gi + u * NT)] = rw_v2{ r.x, r.y };
-        }
-    }
-    for (; gi < cnt; gi += NT) {
-        const float2 x = load_iq<FMT>(a.in, (size_t)(v0 + gi));
-        const float2 r = cmul(x, T[(a.q16 * (unsigned)((unsigned long long)(n_start + gi) & 0xffffull)) & 0xffffu]);
-        s[rw_slot<PAD>(g, gi)] = rw_v2{ r.x, r.y };
-    }
+    return gi + rw_pad<PAD>(g, gi);
 }
 
 template <bool PAD>
@@ -150,7 +107,7 @@ __global__ __launch_bounds__(kRwNT) void resample_wide_kernel(FrontendArgs a, Wi
                                                               unsigned long long *__restrict__ kclk)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char rw_lds[];
-    rw_v2 *s = reinterpret_cast<rw_v2 *>(rw_lds);
+    fe_v2 *s = reinterpret_cast<fe_v2 *>(rw_lds);
     const int tid = threadIdx.x;
     const int L = g.L, M = g.M, S = g.S;
     kclk_enter(kclk);
@@ -166,24 +123,7 @@ __global__ __launch_bounds__(kRwNT) void resample_wide_kernel(FrontendArgs a, Wi
     const int cnt = span < g.cnt_max ? span : g.cnt_max;                // (span <= cnt_max: see the header comment)
 
     // ---- load stage: convert, rotate, into LDS ----
-    const long long v0 = n_start - a.pos0 - a.n_tail;                   // the tile's first sample as an index into the chunk
-    if (n_start >= 0 && v0 >= 0 && v0 + cnt <= a.n_in) {
-        switch (a.fmt) {
-        case 2: rw_stage_inside<2, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        case 1: rw_stage_inside<1, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        case 3: rw_stage_inside<3, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        case 4: rw_stage_inside<4, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        case 6: rw_stage_inside<6, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        case 8: rw_stage_inside<8, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        case 9: rw_stage_inside<9, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        default: rw_stage_inside<0, PAD>(a, g, cnt, v0, n_start, T, s, tid); break;
-        }
-    } else {
-        for (int gi = tid; gi < cnt; gi += kRwNT) {
-            const float2 r = rw_load(a, n_start + gi, T);
-            s[rw_slot<PAD>(g, gi)] = rw_v2{ r.x, r.y };
-        }
-    }
+    fe_stage<kRwNT>(a, n_start, cnt, T, s, tid, [&](int gi) { return rw_pad<PAD>(g, gi); });
     __syncthreads();
 
     // ---- the taps: thread tid takes the outputs tid, tid + 256, ... of the tile ----
@@ -196,10 +136,10 @@ __global__ __launch_bounds__(kRwNT) void resample_wide_kernel(FrontendArgs a, Wi
         const int w0 = dp * M + lo - lo_t;                              // the output's first input, as a staged index
         const bool last = r * M + g.C - (lo + F) * L >= 0;              // step F is a term: its tap index is inside the prototype
         const float *__restrict__ wp = W + r;
-        rw_v2 acc = rw_v2{ 0.0f, 0.0f };
+        fe_v2 acc = fe_v2{ 0.0f, 0.0f };
         float tc[U];
-        rw_v2 xc[U];
-        auto fetch = [&](float (&t)[U], rw_v2 (&x)[U], int at) {
+        fe_v2 xc[U];
+        auto fetch = [&](float (&t)[U], fe_v2 (&x)[U], int at) {
 #pragma unroll
             for (int k = 0; k < U; k++) t[k] = wp[(size_t)(at + k) * L];
 #pragma unroll
@@ -210,11 +150,11 @@ __global__ __launch_bounds__(kRwNT) void resample_wide_kernel(FrontendArgs a, Wi
 #pragma unroll 1
         for (; i + U <= F; i += U) {
             float tn[U];
-            rw_v2 xn[U];
+            fe_v2 xn[U];
             fetch(tn, xn, i + U);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int k = 0; k < U; k++) acc = rw_fma(tc[k], xc[k], acc);
+            for (int k = 0; k < U; k++) acc = fe_fma(tc[k], xc[k], acc);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int k = 0; k < U; k++) {
@@ -225,7 +165,7 @@ __global__ __launch_bounds__(kRwNT) void resample_wide_kernel(FrontendArgs a, Wi
         // the rest of [0, F) and step F are in tc / xc already
 #pragma unroll
         for (int k = 0; k < U; k++)
-            if (i + k < F || (i + k == F && last)) acc = rw_fma(tc[k], xc[k], acc);
+            if (i + k < F || (i + k == F && last)) acc = fe_fma(tc[k], xc[k], acc);
         a.out[mt - a.m0 + o] = make_float2(acc.x, acc.y);
     }
     kclk_leave(kclk);
@@ -236,16 +176,7 @@ static int launch_resample_wide_p(const WideGeom &g, const FrontendArgs &a, cons
                                   hipStream_t stream, unsigned long long *kclk, long long tiles)
 {
     const size_t lds = resample_wide_lds_bytes(g);
-    // (once per instantiation and device: the most the kernel is ever given)
-    static bool raised[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-    if (!raised[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(&resample_wide_kernel<PAD>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-            return -1;
-        raised[dev] = true;
-    }
+    if (!fe_raise_lds<&resample_wide_kernel<PAD>>()) return -1;
     hipLaunchKernelGGL((resample_wide_kernel<PAD>), dim3((unsigned)tiles), dim3(kRwNT), lds, stream, a, g, nlo, W, T, kclk);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
