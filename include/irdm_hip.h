@@ -743,7 +743,7 @@ int irdm_poll_chunk_marks(irdm_pipeline_t *p, irdm_chunk_mark_t *out, int max);
 uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
 
 /* Options (irdm_set_option; every one a field of THIS context -- two contexts of a process may differ in all of them; set them
- * before the first feed unless noted; irdm_reset keeps them all).  Twenty-two keys:
+ * before the first feed unless noted; irdm_reset keeps them all).  Twenty-four keys:
  *
  *   what a caller chooses
  *   "keep_frame_samples"  0/1, default 0: irdm_poll_frames returns metadata only
@@ -786,6 +786,17 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         for parsed_records).  One pinned buffer of 8 bytes per burst and batch context is allocated
  *                         when the option is first set to 1, never before; with 0 nothing is launched.  -1 for a member
  *                         of a group and while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
+ *   "burst_resample"      0/1, default 0: 1 = at a sample rate that is no multiple of 250 kHz, one more stage in the per-burst
+ *                         chain of every chunk fed from then on, between the decimator and the 25-tap low-pass: every
+ *                         burst's decimated row (at sample_rate / decim, decim = round(sample_rate / 250000)) is resampled to
+ *                         exactly 250 000 samples/s by a rational polyphase filter at L / M = decim 250000 / sample_rate
+ *                         in lowest terms, see irdm_burst_resample_ratio.  The default, 0, is the reference's arithmetic:
+ *                         the row is taken for 250 kHz whatever its rate, and frames at a rate off the grid lose their tail.
+ *                         The table (L x 20 floats) and one more row scratch per batch context are allocated when the option
+ *                         is first set to 1 at such a rate, never before; at a rate on the grid, and with 0, nothing is
+ *                         allocated and nothing launched, and every record is the one of the option off.  -1 where L
+ *                         exceeds 4096 (a line on stderr names it), while a chunk handed over with irdm_feed_begin waits
+ *                         for its irdm_feed_end, and while a batch of bursts is in flight (irdm_flush first).  A member of a group takes it (irdm_group_set_option sets every member's)
  *   "swap_iq"             0/1, default 0: 1 = irdm_feed_host exchanges the two components of every sample of every chunk
  *                         on the device (irdm_swap_iq_device's kernel on the feed's stream, between the host-to-device
  *                         copy and the feed; the ring slot of irdm_ingest_ptr and the staging buffer alike), so the
@@ -864,7 +875,7 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  * "rot_rows_cap", "rot_blocks", "rot_blocks_cap", "rot_builds", "rot_runs", "rot_ckpts", "rot_grows" (rotator checkpoints:
  * centre bins with a row / runs per bin prebuilt / the arena in whole rows / blocks of 2048 checkpoints in use / allocated /
  * build launches on chains / runs built / checkpoints built / times the arena doubled), "band_steps" (update steps the scans'
- * last rounds walked), "scratch_outputs", "scratch_grows", "scratch_peak" (decimated samples a batch context holds / times it
+ * last rounds walked), "burst_resample_launches" (launches of burst_resample_kernel by the chains), "scratch_outputs", "scratch_grows", "scratch_peak" (decimated samples a batch context holds / times it
  * doubled / most a batch needed). */
 int irdm_set_option(irdm_pipeline_t *p, const char *key, int value);
 int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key);
@@ -1227,6 +1238,29 @@ int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_s
 int irdm_poll_symbol_clock(irdm_pipeline_t *p, irdm_clock_est_t *out, int max);
 int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out);
 int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out);
+
+/* ---- per-burst resampling (option "burst_resample") ----
+ * Output m of a decimated row x[0 .. n) is the band-limited interpolation of x at input time m M / L: q = floor(m M / L),
+ * ph = (m M) mod L, y[m] = sum_k taps[ph][k] x[q - T/2 + 1 + k] over T = taps_per_phase taps, x zero outside the row,
+ * res_len = floor(n L / M) outputs.  The filter adds no delay (an impulse at input i is centred at output i L / M).  The
+ * prototype is a windowed sinc designed in binary64 at rate L f_in: flat within 0.01 dB to 50 kHz, 80 dB down from
+ * 165 kHz.  Per component the sum is ONE chain of float32 fused multiply-adds in ascending k from 0: a row's result depends
+ * on the row and the ratio alone.  Behind the stage frequencies and times are in units of a true 250 kHz; the frame record's
+ * dec_len is res_len.
+ * irdm_burst_resample_ratio: the ratio in force and the taps per phase; 1 / 1 with 0 taps at a rate on the grid.  0, or -1
+ *   with the option off.
+ * irdm_burst_resample_taps: the phase-major table, L x taps_per_phase floats, as irdm_frontend_taps: the floats copied,
+ *   0 at a rate on the grid, -1 with the option off or cap too small.
+ * irdm_burst_resample_batch: the kernel alone, without a context: n rows of interleaved float pairs, row i at
+ *   rows + 2 * stride * i with lens[i] <= stride samples, resampled at L / M (7/8 <= L / M <= 8/7, L <= 4096, the table
+ *   designed by the same function) into out + 2 * out_stride * i, res_lens[i] <= out_stride samples each.  0 or -1.
+ * irdm_burst_resample_design: that table, L x 20 floats phase-major, for a ratio given directly (4096/4097 is no sample
+ *   rate's): the floats copied, -1 for a ratio the stage refuses or cap too small.  Host only. */
+int irdm_burst_resample_ratio(irdm_pipeline_t *p, int *L, int *M, int *taps_per_phase);
+int irdm_burst_resample_taps(irdm_pipeline_t *p, float *out, int cap);
+int irdm_burst_resample_design(int L, int M, float *out, int cap);
+int irdm_burst_resample_batch(int device, const float *rows, const int *lens, int n, int stride, int L, int M, float *out,
+                              int out_stride, int *res_lens);
 
 /* ---- exchanged I and Q (irdm_iq_vote_t / irdm_iq_sense_t above) ----
  * irdm_swap_iq_device: the two components of each of n_samples samples of `format` (IRDM_FMT_*) at d_iq exchanged in

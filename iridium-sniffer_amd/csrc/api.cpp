@@ -40,6 +40,12 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
         return iq_sense_configure(p, value);
     }
+    if (!strcmp(key, "burst_resample")) {
+        // 0 / 1; members of a group take it (no summary, no stream state); not while a chunk handed over with irdm_feed_begin
+        // waits for its irdm_feed_end
+        if (p->st.begin_no != p->st.end_no) return -1;
+        return burst_resample_configure(p, value);
+    }
     if (!strcmp(key, "swap_iq")) {
         // 0 / 1; not for a member of a group (it is fed on the device), and no change between a stream's first feed and
         // irdm_reset: the history ring would hold both senses
@@ -119,6 +125,10 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
             (void)hipFree(b.d_lpf);
             b.d_dec = d2;
             b.d_lpf = l2;
+            if (b.d_res) {
+                (void)hipFree(b.d_res);
+                if (!(b.d_res = dev_alloc<float2>((size_t)value))) return -1;
+            }
             b.dec_cap = (size_t)value;
             if (!b.owns_buffers) { p->d_dec = d2; p->d_lpf = l2; }
         }
@@ -151,6 +161,75 @@ extern "C" int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out)
     if (!p || !out || !p->bc[0].hp_clock) return -1;
     symbol_clock_result(p->st.clock, p->decim, out);
     return 0;
+}
+
+// ---- option "burst_resample" (burst_resample.hpp) ----
+// L / M = decim 250000 / sample_rate in lowest terms
+bool burst_resample_ratio(int sample_rate, int decim, long long *L, long long *M)
+{
+    if (sample_rate <= 0 || decim < 1) return false;
+    long long a = (long long)decim * 250000, b = sample_rate;
+    long long x = a, y = b;
+    while (y) { const long long t = x % y; x = y; y = t; }
+    *L = a / x;
+    *M = b / x;
+    return true;
+}
+
+// the ratio, its table on the device and the second scratch of every batch context, when the option is first set at a rate
+// off the 250 kHz grid; at a rate on it, and with 0, nothing is allocated
+int burst_resample_configure(irdm_pipeline *p, int on)
+{
+    if (!on) {
+        p->burst_resample = 0;
+        return 0;
+    }
+    long long L = 1, M = 1;
+    if (!burst_resample_ratio(p->cfg.sample_rate, p->decim, &L, &M)) return -1;
+    if (L > kBrMaxL) {
+        fprintf(stderr, "irdm_hip: burst_resample: %d samples/s needs the ratio %lld/%lld, L = %lld is beyond %d\n",
+                p->cfg.sample_rate, L, M, L, kBrMaxL);
+        return -1;
+    }
+    if (L != M) {
+        if (!burst_resample_ratio_ok(L, M)) return -1;
+        for (int i = 0; i < p->n_bc; i++)
+            if (p->bc[i].st.n != 0) return -1;
+        if (!p->d_br_taps) {
+            p->br_taps = design_resample_taps((int)L, (int)M, kBrTaps);
+            if (!(p->d_br_taps = dev_upload(p->br_taps.data(), p->br_taps.size()))) return -1;
+        }
+        for (int i = 0; i < p->n_bc; i++) {
+            BatchCtx &b = p->bc[i];
+            if (!b.d_res && !(b.d_res = dev_alloc<float2>(b.dec_cap))) return -1;
+        }
+    }
+    p->br_L = (int)L;
+    p->br_M = (int)M;
+    p->burst_resample = 1;
+    return 0;
+}
+
+extern "C" int irdm_burst_resample_ratio(irdm_pipeline_t *p, int *L, int *M, int *taps_per_phase)
+{
+    if (!p || !p->burst_resample) return -1;
+    const bool on_grid = p->br_L == p->br_M;
+    if (L) *L = on_grid ? 1 : p->br_L;
+    if (M) *M = on_grid ? 1 : p->br_M;
+    if (taps_per_phase) *taps_per_phase = on_grid ? 0 : kBrTaps;
+    return 0;
+}
+
+// the phase-major table [L][taps_per_phase] (irdm_burst_resample_ratio says how large): the floats copied, 0 at a rate on the
+// grid, -1 where `cap` is too small -- as irdm_frontend_taps
+extern "C" int irdm_burst_resample_taps(irdm_pipeline_t *p, float *out, int cap)
+{
+    if (!p || !p->burst_resample) return -1;
+    if (p->br_L == p->br_M) return 0;
+    const int n = (int)p->br_taps.size();
+    if (!out || cap < n) return -1;
+    memcpy(out, p->br_taps.data(), sizeof(float) * (size_t)n);
+    return n;
 }
 
 // ---- option "iq_sense" (iq_sense.hpp): the pinned records of every batch context, when the option is first set ----
@@ -221,6 +300,7 @@ extern "C" int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key)
     if (!strcmp(key, "scratch_peak")) return (int64_t)p->stat_scratch_peak;
     if (!strcmp(key, "band_last_flags")) return (int64_t)p->last_band_flags;
     if (!strcmp(key, "scan_dense_frames")) return (int64_t)p->stat_dense_frames;
+    if (!strcmp(key, "burst_resample_launches")) return (int64_t)p->stat_br_launches;
     return -1;
 }
 

@@ -414,6 +414,10 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
     b.st.recs.assign(nb, irdm_burst_t());
     size_t n_tiles = 0, dec_need = 0;
     int max_dec_len = 0;         // the longest decimated burst of the batch: the tile grid of post_tiles_kernel
+    // option "burst_resample" at a rate off the 250 kHz grid: the decimated rows go through burst_resample_kernel into
+    // b.d_res, and post1 and everything behind it see rows of res_len = floor(dec_len L / M) samples at 250 kHz
+    const bool resample = p->br_active() && b.d_res;
+    int max_res_len = 0;
     // (the register-resident decimator also needs the chunk to start at a multiple of 8 samples: a caller's burst window
     // presented as a chunk -- irdm_downmix_burst -- may not; such sources take the LDS kernel)
     const int fir_aligned = p->ring_len % 8 == 0 && p->ref_ring % 8 == 0 && (src.chunk_start == ~0ull || src.chunk_start % 8 == 0);
@@ -457,13 +461,18 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
             if (n_out < 0) n_out = 0;
             w.dec_len = n_out;
             if (n_out < 100) w.drop_reason = 2;                          // burst_downmix.c:677
+            // (the rule on the row the later stages get: a row resampled to fewer than 100 samples is dropped as well)
+            if (resample && burst_resample_len(n_out, p->br_L, p->br_M) < 100) w.drop_reason = 2;
         }
         w.tile_base = (int32_t)n_tiles;
         w.dec_off = (int32_t)dec_need;
         if (!w.drop_reason) {
             max_dec_len = std::max(max_dec_len, w.dec_len);
             n_tiles += (size_t)(w.dec_len + tile_out - 1) / tile_out;
-            dec_need += ((size_t)w.dec_len + 15) & ~(size_t)15;           // rows start on 128-byte lines
+            // (resampled: a row has its offset in both scratches, spaced for the longer of its two lengths -- up to 8/7)
+            const int res_len = resample ? burst_resample_len(w.dec_len, p->br_L, p->br_M) : w.dec_len;
+            max_res_len = std::max(max_res_len, res_len);
+            dec_need += ((size_t)std::max(w.dec_len, res_len) + 15) & ~(size_t)15;   // rows start on 128-byte lines
         }
     }
     b.st.ring_lo = b.st.ring_hi = 0;
@@ -491,14 +500,20 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
             return -1;
         }
         float2 *d2 = dev_alloc<float2>(cap2), *l2 = dev_alloc<float2>(lpf_alloc(cap2));
-        if (!d2 || !l2) {
+        float2 *r2 = b.d_res ? dev_alloc<float2>(cap2) : nullptr;
+        if (!d2 || !l2 || (b.d_res && !r2)) {
             if (d2) (void)hipFree(d2);
             if (l2) (void)hipFree(l2);
+            if (r2) (void)hipFree(r2);
             fprintf(stderr, "irdm_hip: no memory for %zu decimated samples per batch\n", cap2);
             return -1;
         }
         p->scratch_retired.push_back(b.d_dec);
         p->scratch_retired.push_back(b.d_lpf);
+        if (b.d_res) {
+            p->scratch_retired.push_back(b.d_res);
+            b.d_res = r2;
+        }
         b.d_dec = d2;
         b.d_lpf = l2;
         b.dec_cap = cap2;
@@ -542,7 +557,11 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
                             p->kclk_fir((int)(&b - p->bc)), p->d_rot_slot, p->fir_order, p->fir_generic) != 0)
         return -1;
     IRDM_HIP_CHECK(hipEventRecord(b.ev[1], st));
-    if (launch_downmix_post1(b.d_work, nb, max_dec_len, b.d_dec, b.d_lpf, box_of(b.d_lpf, b.dec_cap), p->d_noise_taps,
+    if (resample && max_dec_len > 0) {
+        if (launch_burst_resample(b.d_work, nb, max_dec_len, b.d_dec, b.d_res, p->d_br_taps, p->br_L, p->br_M, st) != 0) return -1;
+        p->stat_br_launches++;
+    }
+    if (launch_downmix_post1(b.d_work, nb, resample ? max_res_len : max_dec_len, resample ? b.d_res : b.d_dec, b.d_lpf, box_of(b.d_lpf, b.dec_cap), p->d_noise_taps,
                              p->noise_ntaps, p->d_start_taps, p->start_ntaps, p->search_depth,
                              p->pre_start, p->d_cfo_window, p->d_tw4096, p->dev_cfo ? nullptr : b.hp_work_dev, st,
                              p->kclk_fir((int)(&b - p->bc)), p->fir_order, p->post_generic) != 0)

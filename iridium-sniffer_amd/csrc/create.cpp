@@ -51,6 +51,7 @@ void pipeline_free(irdm_pipeline *p)
         if (b.hp_frame) (void)hipHostFree(b.hp_frame);
         if (b.hp_clock) (void)hipHostFree(b.hp_clock);
         if (b.hp_sense) (void)hipHostFree(b.hp_sense);
+        if (b.d_res) (void)hipFree(b.d_res);
         if (b.owns_buffers) {
             void *own[] = { b.d_work, b.d_tiles, b.d_dec, b.d_lpf, b.d_rrc_ws, b.d_frames, b.d_demod_ws, b.d_demod,
                             b.d_decoded, b.d_ida };
@@ -75,6 +76,7 @@ void pipeline_free(irdm_pipeline *p)
     p->in_stats.free();
     hc_free(p->hc);
     p->iqm.free();
+    if (p->d_br_taps) (void)hipFree(p->d_br_taps);
     if (p->d_rot_table) (void)hipFree(p->d_rot_table);
     for (float2 *q : p->rot_retired) (void)hipFree(q);
     for (float2 *q : p->scratch_retired) (void)hipFree(q);

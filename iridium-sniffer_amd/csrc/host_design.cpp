@@ -45,6 +45,33 @@ std::vector<float> design_lpf(float gain, float sample_rate, float cutoff, float
     return taps;
 }
 
+std::vector<float> design_resample_taps(int L, int M, int taps_per_phase)
+{
+    // (binary64 throughout, every operation in the order tests/burst_resample_model.py states it)
+    const int n = L * taps_per_phase, half = n / 2;
+    const double omega = 2.0 * M_PI * 107500.0 / (250000.0 * (double)M);
+    std::vector<double> p((size_t)n);
+    double total = 0.0;
+    for (int i = 0; i < n; i++) {
+        const int j = i - half + 1;                                  // P[j], j = -n / 2 + 1 .. n / 2
+        double h;
+        if (j == 0) h = omega / M_PI;
+        else        h = sin(omega * (double)j) / (M_PI * (double)j);
+        const double x = (double)(i + 1) / (double)n;
+        const double w = 0.35875 - 0.48829 * cos(2.0 * M_PI * x) + 0.14128 * cos(4.0 * M_PI * x) - 0.01168 * cos(6.0 * M_PI * x);
+        p[(size_t)i] = h * w;
+        total += p[(size_t)i];
+    }
+    const double scale = (double)L / total;
+    std::vector<float> table((size_t)n);
+    for (int ph = 0; ph < L; ph++)
+        for (int k = 0; k < taps_per_phase; k++) {
+            const int j = (k - taps_per_phase / 2 + 1) * L - ph;
+            table[(size_t)ph * taps_per_phase + k] = (float)(p[(size_t)(j + half - 1)] * scale);
+        }
+    return table;
+}
+
 std::vector<float> design_rrc(float gain, float sample_rate, float symbol_rate, float alpha, int ntaps)
 {
     ntaps |= 1;

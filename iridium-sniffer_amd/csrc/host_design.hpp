@@ -18,6 +18,11 @@ std::vector<float> design_rrc(float gain, float sample_rate, float symbol_rate, 
 std::vector<float> design_rc(float sample_rate, float symbol_rate, float alpha, int ntaps);
 std::vector<float> design_box(int length);
 
+// option "burst_resample" (burst_resample.hpp): the prototype of the ratio L / M -- design_lpf's windowed sinc (fir_filter.c's
+// Blackman-Harris window) in binary64 at rate L f_in, f_in = 250000 M / L, cutoff 107.5 kHz, taps_per_phase L taps centred on
+// 0, gain L -- rounded to float, phase-major: table[ph * taps_per_phase + k] = P[(k - taps_per_phase / 2 + 1) L - ph]
+std::vector<float> design_resample_taps(int L, int M, int taps_per_phase);
+
 // pinned FFT twiddles tw[k], k < n/2 (DESIGN.md "Pinned FFT")
 std::vector<cfloat> design_twiddles(int n);
 // pinned radix-2 DIT FFT on the host (used only for the create-time sync templates)

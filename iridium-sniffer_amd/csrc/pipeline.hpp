@@ -41,6 +41,7 @@
 #include "iq_moments.hpp"
 #include "host_chain.hpp"
 #include "iq_sense.hpp"
+#include "burst_resample.hpp"
 
 using namespace irdm;
 
@@ -127,6 +128,8 @@ struct BatchCtx {
     size_t tiles_cap;
     float2 *d_dec, *d_lpf, *d_rrc_ws, *d_frames, *d_demod_ws;
     size_t dec_cap;              // outputs (float2) d_dec and d_lpf hold each: a batch's rows lie end to end by actual length
+    float2 *d_res = nullptr;     // burst_resample: the rows at 250 kHz, dec_cap outputs at the offsets of d_dec (this context's own,
+                                 // allocated when the option is first set at a rate off the grid)
     DemodOut *d_demod;
     DecodedOut *d_decoded;
     IdaOut *d_ida;
@@ -446,6 +449,15 @@ struct irdm_pipeline {
     // option "iq_sense" (chain.cpp, iq_sense.hpp): the switch (configuration); the batch contexts' hp_sense are the cache,
     // allocated when the option is first set
     int iq_sense = 0;
+    // option "burst_resample" (chain.cpp, burst_resample.hpp): the switch, the ratio decim 250000 / sample_rate in lowest
+    // terms and its phase-major table (configuration: kept across irdm_reset; br_L == br_M == 1 at a rate on the grid, where
+    // there is no table and nothing is launched); the batch contexts' d_res are the cache
+    int burst_resample = 0;
+    int br_L = 1, br_M = 1;
+    std::vector<float> br_taps;
+    float *d_br_taps = nullptr;
+    uint64_t stat_br_launches = 0;
+    bool br_active() const { return burst_resample && br_L != br_M && d_br_taps; }
     // options "swap_iq", "scrub" / "scrub_limit_log2", irdm_iq_balance and irdm_dc_block (feed.cpp, host_chain.hpp): what
     // irdm_feed_host does to every chunk on the device before anything reads it -- the switches and their settings
     // (configuration), the scrub's blocks, the DC tracker's rings and the wire staging buffer (cache: allocated when a
@@ -505,6 +517,8 @@ int spectrum_configure(irdm_pipeline *p, int R);
 int input_stats_configure(irdm_pipeline *p, int on);
 int symbol_clock_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
+int burst_resample_configure(irdm_pipeline *p, int on);      // api.cpp
+bool burst_resample_ratio(int sample_rate, int decim, long long *L, long long *M);
 int scrub_configure(irdm_pipeline *p, int on);
 int iq_moments_configure(irdm_pipeline *p, int on);
 int dc_block_configure(irdm_pipeline *p, int wire_format, int block_log2, float seed_i, float seed_q);

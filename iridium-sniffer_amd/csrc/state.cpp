@@ -601,4 +601,59 @@ extern "C" int irdm_iq_sense_batch(irdm_pipeline_t *p, const irdm_demod_t *in, i
     return rc;
 }
 
+// the table irdm_burst_resample_batch resamples at L / M with: what a context at that ratio holds
+extern "C" int irdm_burst_resample_design(int L, int M, float *out, int cap)
+{
+    if (!burst_resample_ratio_ok(L, M) || !out || cap < L * kBrTaps) return -1;
+    const std::vector<float> taps = design_resample_taps(L, M, kBrTaps);
+    memcpy(out, taps.data(), sizeof(float) * taps.size());
+    return (int)taps.size();
+}
+
+// burst_resample_kernel alone (burst_resample.hpp) on n caller-supplied rows: no context, its own table by the same design
+extern "C" int irdm_burst_resample_batch(int device, const float *rows, const int *lens, int n, int stride, int L, int M,
+                                         float *out, int out_stride, int *res_lens)
+{
+    if (!rows || !lens || !out || !res_lens || n < 0 || stride < 0 || out_stride < 0) return -1;
+    if (!burst_resample_ratio_ok(L, M)) {
+        fprintf(stderr, "irdm_hip: burst_resample: the ratio %d/%d is outside 7/8 .. 8/7 or L = %d is beyond %d\n", L, M, L, kBrMaxL);
+        return -1;
+    }
+    if (n == 0) return 0;
+    std::vector<BurstWork> work((size_t)n);
+    size_t need = 0;
+    int max_len = 0;
+    for (int i = 0; i < n; i++) {
+        const int len = lens[i], rl = len >= 0 ? burst_resample_len(len, L, M) : 0;
+        if (len < 0 || len > stride || rl > out_stride) return -1;
+        BurstWork &w = work[(size_t)i];
+        memset(&w, 0, sizeof(w));
+        w.dec_len = len;
+        w.dec_off = (int32_t)need;
+        need += ((size_t)std::max(len, rl) + 15) & ~(size_t)15;
+        if (need > (size_t)0x7fffffff) return -1;
+        max_len = std::max(max_len, len);
+        res_lens[i] = rl;
+    }
+    IRDM_HIP_CHECK(hipSetDevice(device));
+    const std::vector<float> taps = design_resample_taps(L, M, kBrTaps);
+    float *d_taps = dev_upload(taps.data(), taps.size());
+    BurstWork *d_work = dev_upload(work.data(), work.size());
+    float2 *d_in = dev_alloc<float2>(std::max<size_t>(need, 16)), *d_out = dev_alloc<float2>(std::max<size_t>(need, 16));
+    int rc = d_taps && d_work && d_in && d_out ? 0 : -1;
+    for (int i = 0; rc == 0 && i < n; i++)
+        if (lens[i] > 0 && hipMemcpy(d_in + work[(size_t)i].dec_off, rows + (size_t)i * 2 * stride, sizeof(float2) * (size_t)lens[i],
+                                     hipMemcpyHostToDevice) != hipSuccess)
+            rc = -1;
+    if (rc == 0) rc = launch_burst_resample(d_work, n, max_len, d_in, d_out, d_taps, L, M, nullptr);
+    if (rc == 0 && hipDeviceSynchronize() != hipSuccess) rc = -1;
+    for (int i = 0; rc == 0 && i < n; i++)
+        if (res_lens[i] > 0 && hipMemcpy(out + (size_t)i * 2 * out_stride, d_out + work[(size_t)i].dec_off,
+                                         sizeof(float2) * (size_t)res_lens[i], hipMemcpyDeviceToHost) != hipSuccess)
+            rc = -1;
+    for (void *q : { (void *)d_taps, (void *)d_work, (void *)d_in, (void *)d_out })
+        if (q) (void)hipFree(q);
+    return rc;
+}
+
 }  // namespace irdmh

@@ -11,7 +11,7 @@
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
  *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]]
- *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]
+ *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
  * (burst_detect.c:350-351, the line test-configurations.sh:140 greps); with --position, the Doppler position estimate's
@@ -92,6 +92,15 @@
  * R0 the grid rate the pipeline assumed, R rounded to 0.05 % of it (the estimator's resolution).  Behind a front end the
  * line describes the stream the detector sees; R and R0 are scaled back to the capture's -r.  stdout and the rest of
  * stderr are those of the run without the flag.  Refused with --gpus N > 1 and with --save-only (no context, no frames).
+ * --burst-resample: at a rate that is no multiple of 250 kHz every burst's decimated row is resampled on the GPU to exactly
+ * 250 000 samples/s before it is demodulated (option "burst_resample", on every member with --gpus N): frames come out whole,
+ * their frequencies and times right, without resampling the whole stream.  With every input kind, behind --band-center /
+ * --decimate / --resample-to (the front end's output rate is the rate it applies to), with --prime, --join, batches and
+ * --gpus N.  -v says once "burst resample: F_IN -> 250000 samples/s per burst (L/M), 20 taps per phase", or "burst resample:
+ * RATE is on the 250 kHz grid; nothing to do"; without -v a run at a rate on the grid prints what the run without the flag
+ * prints.  The warning about a container rate off the grid is not printed.  A rate whose L exceeds 4096 exits 2 before
+ * anything runs.  --clock-check behind it describes the resampled frames: its clause names RATE (1 + median) against the
+ * declared RATE and says "check -r" only.  --save-bursts .meta files then state a true 250 000.
  * --swap-iq: the two components of every sample of every recording of the run are exchanged on the GPU where they arrive
  * (option "swap_iq", irdm_frontend_swap_iq, irdm_swap_iq_device), raw file or container, in front of --band-center /
  * --decimate / --resample-to: for a Q/I WAV, a SigMF file of the other convention, an inverting mixer.  Allowed with
@@ -382,6 +391,8 @@ static int g_input_stats, g_diag;
 static int g_clock;
 /* --iq-check, --swap-iq */
 static int g_iq, g_swap;
+/* --burst-resample */
+static int g_burst_resample;
 /* --scrub[=LOG2] */
 static int g_scrub, g_scrub_log2 = IRDM_SCRUB_DEFAULT_LOG2;
 /* --image-check, --iq-balance=G,P */
@@ -426,7 +437,7 @@ static void input_line(const irdm_input_stats_t *st, int fmt)
 
 /* the closing "clock:" line of a recording.  nominal: the rate the detector's stream was taken for (its context's rate);
  * capture: the -r of the file in front of it (the same without a front end) */
-static void clock_line(const irdm_symbol_clock_t *sc, double nominal, double capture, int front_end)
+static void clock_line(const irdm_symbol_clock_t *sc, double nominal, double capture, int front_end, int per_burst)
 {
     if (sc->frames_used < 5) {
         fprintf(stderr, "clock: %llu frames; too few to judge\n", (unsigned long long)sc->frames_used);
@@ -435,7 +446,13 @@ static void clock_line(const irdm_symbol_clock_t *sc, double nominal, double cap
     fprintf(stderr, "clock: %llu frames; symbol clock %+.2f %% (quartiles %+.2f %% .. %+.2f %%); %llu not ok, %llu out of range",
             (unsigned long long)sc->frames_used, 100.0 * sc->median, 100.0 * sc->q25, 100.0 * sc->q75,
             (unsigned long long)sc->frames_not_ok, (unsigned long long)sc->frames_out_of_range);
-    if (fabs(sc->median) >= 0.0015 - 1e-12) {
+    if (per_burst && fabs(sc->median) >= 0.0015 - 1e-12) {
+        /* --burst-resample at a rate off the grid: the frames were resampled from the declared rate to 250 kHz, so what is
+         * left is the error of the declared rate itself, in steps of 0.05 % of it */
+        const double step = capture / 2000.0;
+        fprintf(stderr, " -- the samples look like %.0f S/s, not %.0f: check -r", floor(capture * (1.0 + sc->median) / step + 0.5) * step,
+                capture);
+    } else if (fabs(sc->median) >= 0.0015 - 1e-12) {
         /* the grid rate the pipeline assumed and the rate the samples look like, both as rates of the capture; the latter in
          * steps of 0.05 % of the former */
         const double grid = sc->implied_rate_hz / (1.0 + sc->median), scale = capture / nominal;
@@ -1187,6 +1204,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--diagnostic")) g_input_stats = g_diag = 1;     /* options.c:376 */
         else if (!strcmp(a, "--clock-check")) g_clock = 1;
         else if (!strcmp(a, "--iq-check")) g_iq = 1;
+        else if (!strcmp(a, "--burst-resample")) g_burst_resample = 1;
         else if (!strcmp(a, "--swap-iq")) g_swap = 1;
         else if (!strcmp(a, "--scrub") || !strncmp(a, "--scrub=", 8)) {
             /* (as --position: only the --scrub=LOG2 form takes a value) */
@@ -1318,7 +1336,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--prime] [--join]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1509,7 +1527,7 @@ int main(int argc, char **argv)
                 return 2;
             }
     }
-    if (n_cont && !resample_to && (long long)rate % 250000 != 0)
+    if (n_cont && !resample_to && !g_burst_resample && (long long)rate % 250000 != 0)
         fprintf(stderr, "warning: %.0f samples/s is no multiple of 250 kHz: frames may decode only in part; resample with --resample-to HZ\n", rate);
     if (verbose)
         for (int k = 0; k < g_n_in; k++) {
@@ -1556,6 +1574,27 @@ int main(int argc, char **argv)
     c.feed_block = 32768;
     c.use_gardner = gardner;
     c.start_time_ns = g_in[first].start_ns;
+    /* --burst-resample: the ratio decim 250000 / rate of the context's rate in lowest terms (the library's arithmetic); one
+     * whose L the kernel does not take ends the run here, before a context exists */
+    long long br_l = 1, br_m = 1;
+    if (g_burst_resample) {
+        long long decim = (long long)roundf((float)c.sample_rate / 250000.0f);
+        if (decim < 1) decim = 1;
+        long long x = decim * 250000, y = c.sample_rate;
+        while (y) { const long long t = x % y; x = y; y = t; }
+        br_l = decim * 250000 / x;
+        br_m = c.sample_rate / x;
+        if (br_l > 4096) {
+            fprintf(stderr, "--burst-resample: %d samples/s needs the ratio %lld/%lld, L = %lld is beyond 4096; resample the stream with --resample-to HZ\n",
+                    c.sample_rate, br_l, br_m, br_l);
+            return 2;
+        }
+        if (verbose && br_l != br_m)
+            fprintf(stderr, "burst resample: %.10g -> 250000 samples/s per burst (%lld/%lld), 20 taps per phase\n",
+                    (double)c.sample_rate / (double)decim, br_l, br_m);
+        else if (verbose)
+            fprintf(stderr, "burst resample: %d is on the 250 kHz grid; nothing to do\n", c.sample_rate);
+    }
     /* (several GPUs: a chunk must hold the samples a member is given from in front of its chunk -- 2 s of signal, the
      * reference's ring -- so the default grows with the rate) */
     if (gpus > 1 && !chunk_given) chunk = (size_t)(2.75 * rate);
@@ -1671,6 +1710,10 @@ int main(int argc, char **argv)
     }
     if (g_input_stats && !fe && irdm_set_option(p, "input_stats", 1) != 0) {
         fprintf(stderr, "--input-stats: the library refused the statistics\n");
+        return 1;
+    }
+    if (g_burst_resample && SET_OPTION("burst_resample", 1) != 0) {
+        fprintf(stderr, "--burst-resample: the library refused the option\n");
         return 1;
     }
     if (g_clock && irdm_set_option(p, "symbol_clock", 1) != 0) {
@@ -1959,7 +2002,7 @@ int main(int argc, char **argv)
                 (unsigned long)(g_group ? (uint64_t)irdm_group_get_stat(g_group, "tagged") : irdm_tagged_bursts(p)));
         if (g_clock) {
             irdm_symbol_clock_t sc;
-            if (irdm_symbol_clock(p, &sc) == 0) clock_line(&sc, (double)c.sample_rate, rate, fe != NULL);
+            if (irdm_symbol_clock(p, &sc) == 0) clock_line(&sc, (double)c.sample_rate, rate, fe != NULL, br_l != br_m);
             else { fprintf(stderr, "--clock-check: %s: no estimate\n", file); rc = 1; }
         }
         if (g_iq) {

@@ -323,6 +323,12 @@ def lib():
             L.irdm_poll_symbol_clock.argtypes = [C.c_void_p, C.POINTER(ClockEst), C.c_int]
             L.irdm_symbol_clock.argtypes = [C.c_void_p, C.POINTER(SymbolClock)]
             L.irdm_symbol_clock_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(ClockEst)]
+        if hasattr(L, "irdm_burst_resample_batch"):
+            L.irdm_burst_resample_ratio.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+            L.irdm_burst_resample_taps.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+            L.irdm_burst_resample_design.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]
+            L.irdm_burst_resample_batch.argtypes = [C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
+                                                    C.c_int, C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int)]
         if hasattr(L, "irdm_iq_sense"):
             L.irdm_swap_iq_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p]
             L.irdm_poll_iq_votes.argtypes = [C.c_void_p, C.POINTER(IqVote), C.c_int]
@@ -707,6 +713,35 @@ class GpuBurstFFT:
         self.close()
 
 
+def burst_resample_design(L, M, taps_per_phase=20):
+    """irdm_burst_resample_design: the phase-major table of the ratio L / M as a float32 array [L, taps_per_phase]"""
+    out = np.empty(L * taps_per_phase, np.float32)
+    if lib().irdm_burst_resample_design(L, M, _fp(out), len(out)) != len(out):
+        raise RuntimeError("irdm_burst_resample_design failed")
+    return out.reshape(L, taps_per_phase)
+
+
+def burst_resample_batch(rows, L, M, device=0):
+    """irdm_burst_resample_batch: rows = list of complex64 arrays, resampled at L / M by burst_resample_kernel alone (no
+    context); returns the list of resampled rows (floor(len L / M) samples each)"""
+    n = len(rows)
+    stride = max([len(r) for r in rows] + [1])
+    out_stride = stride * L // M + 1
+    buf = np.zeros((max(n, 1), 2 * stride), np.float32)
+    lens = np.zeros(max(n, 1), np.int32)
+    for i, r in enumerate(rows):
+        r = np.ascontiguousarray(r, np.complex64)
+        lens[i] = len(r)
+        buf[i, :2 * len(r)] = r.view(np.float32)
+    out = np.zeros((max(n, 1), 2 * out_stride), np.float32)
+    res = np.zeros(max(n, 1), np.int32)
+    ip = C.POINTER(C.c_int)
+    if lib().irdm_burst_resample_batch(device, _fp(buf), lens.ctypes.data_as(ip), n, stride, L, M, _fp(out), out_stride,
+                                       res.ctypes.data_as(ip)) != 0:
+        raise RuntimeError("irdm_burst_resample_batch failed")
+    return [out[i, :2 * res[i]].copy().view(np.complex64) for i in range(n)]
+
+
 class Pipeline:
     """irdm_* batched detect -> downmix -> demod context."""
 
@@ -1007,6 +1042,23 @@ class Pipeline:
         if self.L.irdm_symbol_clock_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
             raise RuntimeError("irdm_symbol_clock_batch failed")
         return [ClockEst.from_buffer_copy(out[i]) for i in range(n)]
+
+    def burst_resample_ratio(self):
+        """irdm_burst_resample_ratio (option burst_resample): (L, M, taps_per_phase); (1, 1, 0) at a rate on the 250 kHz grid"""
+        l, m, t = C.c_int(0), C.c_int(0), C.c_int(0)
+        if self.L.irdm_burst_resample_ratio(self.h, C.byref(l), C.byref(m), C.byref(t)) != 0:
+            raise RuntimeError("irdm_burst_resample_ratio failed (option burst_resample off?)")
+        return l.value, m.value, t.value
+
+    def burst_resample_taps(self):
+        """irdm_burst_resample_taps: the phase-major table as a float32 array [L, taps_per_phase] ([0, 0] on the grid)"""
+        l, _, t = self.burst_resample_ratio()
+        if t == 0:
+            return np.zeros((0, 0), np.float32)
+        out = np.empty(l * t, np.float32)
+        if self.L.irdm_burst_resample_taps(self.h, _fp(out), l * t) != l * t:
+            raise RuntimeError("irdm_burst_resample_taps failed")
+        return out.reshape(l, t)
 
     def poll_iq_votes(self):
         """option iq_sense 1: one IqVote per demodulator record, in their order"""
