@@ -338,6 +338,38 @@ typedef struct {
     uint64_t frames_invalid;         /* unique word passed, record invalid */
 } irdm_symbol_clock_t;
 
+/* option "fine_freq": the carrier frequency of one downmixed frame, estimated on the device from the samples the
+ * demodulator is handed (irdm_poll_fine_freq, irdm_fine_freq_batch).  The fourth power of a QPSK frame carries a spectral
+ * line at four times its residual carrier offset: the line is looked for on the grid -1000 + 20 k Hz, k = 0 .. 100, then on
+ * 11 points 4 Hz apart around the maximum, and refined by a three-point parabola; df is a quarter of its place.  The result
+ * is the frequency at the middle of the frame, to about 1 Hz at the signal levels the detector decodes at all (README:
+ * "Carrier frequency to 1 Hz").  Beyond +-300 Hz of the downmixer's value the estimator is blind: the line is then past the
+ * guard points and the grid shows the frame's modulation. */
+#define IRDM_FINE_FREQ_INVALID       1u   /* no estimate (df = quality = 0): the frame was dropped in front of the demodulator,
+                                           * is shorter than 64 samples, all zero, or holds a sample that is not finite */
+#define IRDM_FINE_FREQ_OUT_OF_RANGE  2u   /* the coarse maximum is at an edge of the grid, or one of 10 guard points of the same
+                                           * step beyond an edge (to +-1200 Hz) exceeds it: df is that edge, +-250 Hz */
+#define IRDM_FINE_FREQ_NOT_OK        4u   /* (set by the context, never by the stage call) the demodulator rejected the frame's
+                                           * unique word: no demodulator record goes with this one */
+typedef struct {
+    uint64_t id;               /* the burst's id; irdm_fine_freq_batch: the frame's index */
+    double   freq_hz;          /* the downmixer's centre frequency of the frame + df_hz; irdm_fine_freq_batch: df_hz */
+    float    df_hz;            /* what the frame's samples add to the downmixer's value */
+    float    quality;          /* the coarse maximum over the mean of the coarse grid: 9 .. 14 on a clean frame, 3 .. 4 on noise */
+    uint32_t flags;            /* IRDM_FINE_FREQ_* */
+    uint32_t n;                /* samples of the frame */
+} irdm_fine_freq_t;
+
+/* irdm_fine_freq: the stream so far.  A frame counts as applied when its unique word passed and its record is neither invalid
+ * nor out of range: its demodulator record then carries freq_hz as center_frequency.  median and quartiles are those of
+ * (refined - PLL), the PLL's being the value the record carries with the option off; they are centres of the 1 Hz bins of a
+ * histogram over +-500 Hz, so they do not depend on how the stream was cut into chunks or feeds (0 while frames_applied is 0). */
+typedef struct {
+    uint64_t frames_seen;                 /* frames that reached the demodulator: the sum of the four below */
+    uint64_t frames_applied, frames_not_ok, frames_out_of_range, frames_invalid;
+    double   median, q25, q75;            /* Hz */
+} irdm_fine_freq_summary_t;
+
 /* option "iq_sense": which way round I and Q of one demodulated frame were (irdm_poll_iq_votes, irdm_iq_sense_batch).
  * A recording with its two components exchanged (a Q/I WAV, the other SigMF convention, an inverting mixer) demodulates
  * with ok = 1 and full confidence -- preamble and unique words use the DQPSK states 0 and 2 alone, which conjugation maps
@@ -779,6 +811,16 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         set to 1, never before; with 0 nothing is launched.  -1 for a member of a group (and so through
  *                         irdm_group_set_option) and while a chunk handed over with irdm_feed_begin waits for its
  *                         irdm_feed_end
+ *   "fine_freq"           0/1, default 0: 1 = one more kernel in the per-burst chain of every chunk fed from then on, behind
+ *                         the downmixer and beside the demodulator: the carrier frequency of every frame from its own
+ *                         samples, see irdm_poll_fine_freq / irdm_fine_freq.  center_frequency of every demodulator record
+ *                         (irdm_demod_t, irdm_demod_packed_t, and the irdm_decoded_t / irdm_ida_t derived from them) whose
+ *                         estimate is neither invalid nor out of range is then the refined frequency; a flagged frame keeps
+ *                         the PLL's value bit for bit, and no other field of any record changes (irdm_frame_info_t keeps the
+ *                         downmixer's frequency).  One pinned buffer of 16 bytes per burst and batch context is allocated
+ *                         when the option is first set to 1, never before; with 0 nothing is launched (stat
+ *                         "fine_freq_launches").  -1 for a member of a group (and so through irdm_group_set_option) and
+ *                         while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
  *   "iq_sense"            0/1, default 0: 1 = one more kernel in the per-burst chain of every chunk fed from then on, behind
  *                         the demodulator: whether each frame's bits make sense as they are or with I and Q exchanged, see
  *                         irdm_poll_iq_votes / irdm_iq_sense.  It reads the demodulator's bits and LLRs only: no other
@@ -875,7 +917,7 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  * "rot_rows_cap", "rot_blocks", "rot_blocks_cap", "rot_builds", "rot_runs", "rot_ckpts", "rot_grows" (rotator checkpoints:
  * centre bins with a row / runs per bin prebuilt / the arena in whole rows / blocks of 2048 checkpoints in use / allocated /
  * build launches on chains / runs built / checkpoints built / times the arena doubled), "band_steps" (update steps the scans'
- * last rounds walked), "burst_resample_launches" (launches of burst_resample_kernel by the chains), "scratch_outputs", "scratch_grows", "scratch_peak" (decimated samples a batch context holds / times it
+ * last rounds walked), "burst_resample_launches" (launches of burst_resample_kernel by the chains), "fine_freq_launches" (of fine_freq_kernel), "scratch_outputs", "scratch_grows", "scratch_peak" (decimated samples a batch context holds / times it
  * doubled / most a batch needed). */
 int irdm_set_option(irdm_pipeline_t *p, const char *key, int value);
 int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key);
@@ -1238,6 +1280,22 @@ int irdm_input_stats_device(const void *d_in, size_t n, int format, irdm_input_s
 int irdm_poll_symbol_clock(irdm_pipeline_t *p, irdm_clock_est_t *out, int max);
 int irdm_symbol_clock(irdm_pipeline_t *p, irdm_symbol_clock_t *out);
 int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out);
+
+/* ---- carrier frequency from the frame's samples (irdm_fine_freq_t / irdm_fine_freq_summary_t above) ----
+ * irdm_set_option(p, "fine_freq", 1): every frame that reaches the demodulator from then on gets an estimate of its
+ * carrier frequency, by one kernel on the chain's stream that only reads the frames; the demodulator records carry it.
+ * irdm_poll_fine_freq: up to `max` per-frame records, one for every frame that reached the demodulator, in the order
+ *   of the demodulator's records: those without IRDM_FINE_FREQ_NOT_OK pair one to one with the records of
+ *   irdm_poll_demods / irdm_poll_demods_packed.  A frame's record depends on its samples and the downmixer's frequency
+ *   alone, not on pipeline_depth or how the stream was fed.  Returns the number written (0 with the option off), -1 on error.
+ * irdm_fine_freq: the summary of the stream so far (of the records queued so far: irdm_flush first for the whole
+ *   stream).  irdm_reset starts it over.  Returns 0, or -1 (the option never set included).
+ * irdm_fine_freq_batch: the kernel alone on n frames, with the calling convention of irdm_symbol_clock_batch: samples =
+ *   n rows of IRDM_MAX_FRAME_SAMPLES interleaved float pairs, num_samples[i] <= IRDM_MAX_FRAME_SAMPLES.  freq_hz of a
+ *   record is df_hz (there is no downmixer's value).  Works with the option off.  Returns 0 or -1. */
+int irdm_poll_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_t *out, int max);
+int irdm_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_summary_t *out);
+int irdm_fine_freq_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_fine_freq_t *out);
 
 /* ---- per-burst resampling (option "burst_resample") ----
  * Output m of a decimated row x[0 .. n) is the band-limited interpolation of x at input time m M / L: q = floor(m M / L),

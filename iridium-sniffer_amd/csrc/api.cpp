@@ -34,6 +34,12 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
         return symbol_clock_configure(p, value);
     }
+    if (!strcmp(key, "fine_freq")) {
+        // 0 / 1; not for a member of a group (the summary is a context's, and a group merges no such records), and not while
+        // a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
+        if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
+        return fine_freq_configure(p, value);
+    }
     if (!strcmp(key, "iq_sense")) {
         // 0 / 1; not for a member of a group (the summary is a context's, and a group merges no votes), and not while a chunk
         // handed over with irdm_feed_begin waits for its irdm_feed_end
@@ -232,6 +238,32 @@ extern "C" int irdm_burst_resample_taps(irdm_pipeline_t *p, float *out, int cap)
     return n;
 }
 
+// ---- option "fine_freq" (fine_freq.hpp): the pinned records of every batch context, when the option is first set ----
+int fine_freq_configure(irdm_pipeline *p, int on)
+{
+    for (int i = 0; on && i < p->n_bc; i++) {
+        BatchCtx &b = p->bc[i];
+        if (!b.hp_fine &&
+            hipHostMalloc(reinterpret_cast<void **>(&b.hp_fine), sizeof(FineRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
+            return -1;
+    }
+    p->fine_freq = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_poll_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_t *out, int max)
+{
+    if (!p || !out || max < 0) return -1;
+    return drain(p->st.fine.q, out, max);
+}
+
+extern "C" int irdm_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_summary_t *out)
+{
+    if (!p || !out || !p->bc[0].hp_fine) return -1;
+    fine_freq_result(p->st.fine, out);
+    return 0;
+}
+
 // ---- option "iq_sense" (iq_sense.hpp): the pinned records of every batch context, when the option is first set ----
 int iq_sense_configure(irdm_pipeline *p, int on)
 {
@@ -301,6 +333,7 @@ extern "C" int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key)
     if (!strcmp(key, "band_last_flags")) return (int64_t)p->last_band_flags;
     if (!strcmp(key, "scan_dense_frames")) return (int64_t)p->stat_dense_frames;
     if (!strcmp(key, "burst_resample_launches")) return (int64_t)p->stat_br_launches;
+    if (!strcmp(key, "fine_freq_launches")) return (int64_t)p->stat_ff_launches;
     return -1;
 }
 

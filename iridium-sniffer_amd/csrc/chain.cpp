@@ -612,6 +612,12 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
     // option "symbol_clock": the clock error of every frame, from the frames post2 left (read only), into pinned memory
     b.clocked = p->symbol_clock && b.hp_clock;
     if (b.clocked && launch_symbol_clock(b.d_work, nb, b.d_frames, p->sps, b.hp_clock, st) != 0) return -1;
+    // option "fine_freq": the carrier frequency of every frame, likewise
+    b.fined = p->fine_freq && b.hp_fine;
+    if (b.fined) {
+        if (launch_fine_freq(b.d_work, nb, b.d_frames, (double)p->out_rate, b.hp_fine, st) != 0) return -1;
+        p->stat_ff_launches++;
+    }
     // option "iq_sense": each frame's bits judged as they are and with I and Q exchanged, from the DemodOut the demodulator
     // left on the device (read only), into pinned memory
     if (b.sensed && launch_iq_sense(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_sense, st) != 0)
@@ -704,6 +710,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             p->st.last_bursts.push_back(r);
             const DemodPacked &d = b.hp_packed[i];
             if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], d.ok != 0);
+            if (b.fined && w.drop_reason == 0 && !d.ok) fine_freq_fold(p->st.fine, r.id, b.hp_fine[i], b.h_cfreq[i], false, 0.0);
             if (w.drop_reason != 0 || !d.ok) continue;
             if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
             uint64_t timestamp = p->st.start_time_ns + (uint64_t)((double)r.start / fs * 1e9);
@@ -739,6 +746,8 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             } else {
                 o.center_frequency = b.h_cfreq[i];
             }
+            // option "fine_freq": the frame's own estimate in place of the PLL's, unless its record is flagged
+            if (b.fined) o.center_frequency = fine_freq_fold(p->st.fine, r.id, b.hp_fine[i], b.h_cfreq[i], true, o.center_frequency);
         }
         clock_gettime(CLOCK_MONOTONIC, &ts_);
         p->host_us[9] += ts_.tv_sec * 1e6 + ts_.tv_nsec * 1e-3 - t_rec0;
@@ -789,6 +798,7 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             p->st.q.frame_samples.push_back(std::move(sv));
         }
         if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], b.hp_demod[i].ok != 0);
+        if (b.fined && w.drop_reason == 0 && !b.hp_demod[i].ok) fine_freq_fold(p->st.fine, r.id, b.hp_fine[i], f.center_frequency, false, 0.0);
         if (w.drop_reason == 0 && b.hp_demod[i].ok) {
             const DemodOut &d = b.hp_demod[i];
             if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
@@ -820,6 +830,8 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             } else {
                 o.center_frequency = f.center_frequency;
             }
+            // option "fine_freq": the frame's own estimate in place of the PLL's, unless its record is flagged
+            if (b.fined) o.center_frequency = fine_freq_fold(p->st.fine, r.id, b.hp_fine[i], f.center_frequency, true, o.center_frequency);
             if (p->decode_frames) p->st.q.decoded.push_back(finish_decoded(p->h_decoded[i], o.id, o.timestamp, o.center_frequency));
             if (p->decode_ida) p->st.q.ida.push_back(finish_ida(p->h_ida[i], o));
         }

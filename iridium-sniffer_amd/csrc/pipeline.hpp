@@ -38,6 +38,7 @@
 #include "record_queues.hpp"
 #include "input_stats.hpp"
 #include "symbol_clock.hpp"
+#include "fine_freq.hpp"
 #include "iq_moments.hpp"
 #include "host_chain.hpp"
 #include "iq_sense.hpp"
@@ -139,6 +140,7 @@ struct BatchCtx {
     DemodPacked *hp_packed;                 // packed_records: the demodulator's result without LLRs, bits 8 per byte (pinned; written by demod_par_kernel)
     IdaPacked *hp_ida;                      // parsed_records: ida_decode() of each of them (pinned; written by ida_packed_kernel)
     FramePacked *hp_frame;                  // frame_records: frame_decode() of each of them (pinned; written by frame_packed_kernel)
+    FineRec *hp_fine;                       // fine_freq: one record per burst (pinned; written by fine_freq_kernel; allocated with the option)
     ClockRec *hp_clock;                     // symbol_clock: one record per burst (pinned; written by symbol_clock_kernel; allocated with the option)
     SenseRec *hp_sense;                     // iq_sense: one record per burst (pinned; written by iq_sense_kernel; allocated with the option)
     uint32_t *hp_flag, *hp_flag_dev;    // [0] sequence number the helper publishes, [1] time-out flag of the waiting kernel
@@ -147,6 +149,7 @@ struct BatchCtx {
     bool packed;                 // this batch came back as DemodPacked records
     bool parsed;                 // ... and IdaPacked records
     bool framed;                 // ... and FramePacked records
+    bool fined;                  // this batch ran the carrier frequency kernel: hp_fine holds its records
     bool clocked;                // this batch ran the symbol clock kernel: hp_clock holds its records
     bool sensed;                 // this batch ran the I/Q sense kernel: hp_sense holds its records
     bool cfo_on_device;          // this batch's libm step ran on the device: h_cfreq is filled from the returned records
@@ -239,6 +242,8 @@ struct StreamState {
     InputStatsStream in_stats;
     // option "symbol_clock": the per-frame records until they are polled and the summary's histogram (symbol_clock.hpp)
     SymbolClockStream clock;
+    // option "fine_freq": the per-frame records until they are polled and the summary's histogram (fine_freq.hpp)
+    FineFreqStream fine;
     // option "iq_sense": the per-frame votes until they are polled and the counts of the summary (iq_sense.hpp)
     IqSenseStream iq;
     // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)
@@ -446,6 +451,8 @@ struct irdm_pipeline {
     // option "symbol_clock" (chain.cpp, symbol_clock.hpp): the switch (configuration); the batch contexts' hp_clock are the
     // cache, allocated when the option is first set
     int symbol_clock = 0;
+    // option "fine_freq" (chain.cpp, fine_freq.hpp): likewise, with the batch contexts' hp_fine
+    int fine_freq = 0;
     // option "iq_sense" (chain.cpp, iq_sense.hpp): the switch (configuration); the batch contexts' hp_sense are the cache,
     // allocated when the option is first set
     int iq_sense = 0;
@@ -457,6 +464,7 @@ struct irdm_pipeline {
     std::vector<float> br_taps;
     float *d_br_taps = nullptr;
     uint64_t stat_br_launches = 0;
+    uint64_t stat_ff_launches = 0;      // fine_freq_kernel launches by the chains
     bool br_active() const { return burst_resample && br_L != br_M && d_br_taps; }
     // options "swap_iq", "scrub" / "scrub_limit_log2", irdm_iq_balance and irdm_dc_block (feed.cpp, host_chain.hpp): what
     // irdm_feed_host does to every chunk on the device before anything reads it -- the switches and their settings
@@ -516,6 +524,7 @@ int process_bursts(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
 int spectrum_configure(irdm_pipeline *p, int R);
 int input_stats_configure(irdm_pipeline *p, int on);
 int symbol_clock_configure(irdm_pipeline *p, int on);
+int fine_freq_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
 int burst_resample_configure(irdm_pipeline *p, int on);      // api.cpp
 bool burst_resample_ratio(int sample_rate, int decim, long long *L, long long *M);

@@ -279,10 +279,11 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     p->decode_frames = 0;
     p->decode_ida = 0;
     p->detect_only = 0;          // a stage-B call on a detect-only context still runs stage B
-    const int marks = p->chunk_marks, clock = p->symbol_clock, sense = p->iq_sense;
+    const int marks = p->chunk_marks, clock = p->symbol_clock, sense = p->iq_sense, fine = p->fine_freq;
     p->chunk_marks = 0;          // (the records go to private queues: no chunk mark for them)
     p->symbol_clock = 0;         // (and the probe's frame is none of the stream's)
     p->iq_sense = 0;
+    p->fine_freq = 0;
     const uint64_t tagged = p->st.tagged;
     std::vector<irdm_burst_t> last; last.swap(p->st.last_bursts);
     p->keep_frame_samples = 1;
@@ -303,6 +304,7 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     p->chunk_marks = marks;
     p->symbol_clock = clock;
     p->iq_sense = sense;
+    p->fine_freq = fine;
     p->detect_only = det;
     p->decode_frames = dec;
     p->decode_ida = dec_ida;
@@ -427,6 +429,41 @@ extern "C" int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples,
             irdm_clock_est_t &o = out[base + i];
             o.id = (uint64_t)(base + i);
             o.eps = hp[i].eps;
+            o.quality = hp[i].quality;
+            o.flags = hp[i].flags;
+            o.n = hp[i].n;
+        }
+    }
+    (void)hipHostFree(hp);
+    return rc;
+}
+
+// the carrier frequency kernel alone (fine_freq.hpp), on the buffers of irdm_qpsk_demod_batch
+extern "C" int irdm_fine_freq_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_fine_freq_t *out)
+{
+    if (!p || !samples || !num_samples || !out || n < 0) return -1;
+    for (int i = 0; i < n; i++)
+        if (num_samples[i] < 0 || num_samples[i] > kMaxFrameSamples) return -1;
+    pipeline_enter(p);
+    FineRec *hp = nullptr;
+    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(FineRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
+                                 hipHostMallocDefault));
+    int rc = 0;
+    for (int base = 0; base < n && rc == 0; base += p->burst_cap) {
+        const int nb = std::min(p->burst_cap, n - base);
+        p->h_work.assign(nb, BurstWork());
+        for (int i = 0; i < nb; i++) p->h_work[i].num_samples = num_samples[base + i];
+        rc = hipMemcpyAsync(p->d_work, p->h_work.data(), sizeof(BurstWork) * nb, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
+                     hipMemcpyAsync(p->d_frames, samples + (size_t)base * 2 * kMaxFrameSamples,
+                                    sizeof(float2) * (size_t)nb * kMaxFrameSamples, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
+                     launch_fine_freq(p->d_work, nb, p->d_frames, (double)p->out_rate, hp, p->stream) == 0 &&
+                     hipStreamSynchronize(p->stream) == hipSuccess
+                 ? 0 : -1;
+        for (int i = 0; rc == 0 && i < nb; i++) {
+            irdm_fine_freq_t &o = out[base + i];
+            o.id = (uint64_t)(base + i);
+            o.freq_hz = (double)hp[i].df;
+            o.df_hz = hp[i].df;
             o.quality = hp[i].quality;
             o.flags = hp[i].flags;
             o.n = hp[i].n;

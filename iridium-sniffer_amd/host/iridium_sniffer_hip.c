@@ -10,7 +10,7 @@
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
- *                         [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]]
+ *                         [--input-stats] [--diagnostic] [--clock-check] [--fine-freq] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]]
  *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
@@ -92,6 +92,14 @@
  * R0 the grid rate the pipeline assumed, R rounded to 0.05 % of it (the estimator's resolution).  Behind a front end the
  * line describes the stream the detector sees; R and R0 are scaled back to the capture's -r.  stdout and the rest of
  * stderr are those of the run without the flag.  Refused with --gpus N > 1 and with --save-only (no context, no frames).
+ * --fine-freq: every frame's carrier frequency estimated on the GPU from the frame's own samples (option "fine_freq": the line
+ * of the fourth power, to about 1 Hz where the PLL's arithmetic is 10 to 30 Hz off), at the middle of the frame.  The
+ * frequency field of every RAW: / IDA: line, and what --position, --acars and --parsed make of it, is then the refined one;
+ * a frame whose estimate is out of range (beyond +-250 Hz of the downmixer's value; beyond +-300 Hz the estimator is blind) or
+ * invalid keeps the PLL's value.  One closing line per recording on stderr, directly behind "clock:" and in front of "iq:":
+ *     freq: N frames refined (K kept the PLL's value: A out of range, B invalid); refined - PLL median %+.0f Hz (quartiles %+.0f .. %+.0f)
+ * or "freq: 0 frames".  -v says once "fine freq: carrier frequency from each frame's samples (+-250 Hz of the downmixer's)".
+ * --save-bursts .meta files state the downmixer's frequency as before.  Refused with --gpus N > 1 and with --save-only.
  * --burst-resample: at a rate that is no multiple of 250 kHz every burst's decimated row is resampled on the GPU to exactly
  * 250 000 samples/s before it is demodulated (option "burst_resample", on every member with --gpus N): frames come out whole,
  * their frequencies and times right, without resampling the whole stream.  With every input kind, behind --band-center /
@@ -389,6 +397,8 @@ static irdm_group_t *g_group;
 static int g_input_stats, g_diag;
 /* --clock-check */
 static int g_clock;
+/* --fine-freq */
+static int g_fine;
 /* --iq-check, --swap-iq */
 static int g_iq, g_swap;
 /* --burst-resample */
@@ -578,6 +588,19 @@ static void image_line(const irdm_iq_moments_t *m, double centre)
     fprintf(stderr, "\n");
 }
 
+/* the closing "freq:" line of a recording (--fine-freq) */
+static void freq_line(const irdm_fine_freq_summary_t *ff)
+{
+    if (ff->frames_seen - ff->frames_not_ok == 0) {
+        fprintf(stderr, "freq: 0 frames\n");
+        return;
+    }
+    fprintf(stderr, "freq: %llu frames refined (%llu kept the PLL's value: %llu out of range, %llu invalid); "
+            "refined - PLL median %+.0f Hz (quartiles %+.0f .. %+.0f)\n",
+            (unsigned long long)ff->frames_applied, (unsigned long long)(ff->frames_out_of_range + ff->frames_invalid),
+            (unsigned long long)ff->frames_out_of_range, (unsigned long long)ff->frames_invalid, ff->median, ff->q25, ff->q75);
+}
+
 /* --diagnostic: the reference's closing status line (main.c:444-480) over the recording's stream time */
 static void diagnostic_line(double elapsed, unsigned long det, unsigned long sub, float noise_floor, float peak_signal)
 {
@@ -649,6 +672,11 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         /* (the summary is the library's; the per-frame records are not printed) */
         static irdm_clock_est_t ce[256];
         while (irdm_poll_symbol_clock(p, ce, 256) > 0) {}
+    }
+    if (g_fine) {
+        /* (likewise; the demodulator records carry the refined frequency) */
+        static irdm_fine_freq_t ff[256];
+        while (irdm_poll_fine_freq(p, ff, 256) > 0) {}
     }
     if (g_iq) {
         /* (likewise: the summary is the library's) */
@@ -1203,6 +1231,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--input-stats")) g_input_stats = 1;
         else if (!strcmp(a, "--diagnostic")) g_input_stats = g_diag = 1;     /* options.c:376 */
         else if (!strcmp(a, "--clock-check")) g_clock = 1;
+        else if (!strcmp(a, "--fine-freq")) g_fine = 1;
         else if (!strcmp(a, "--iq-check")) g_iq = 1;
         else if (!strcmp(a, "--burst-resample")) g_burst_resample = 1;
         else if (!strcmp(a, "--swap-iq")) g_swap = 1;
@@ -1336,7 +1365,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--fine-freq] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1414,6 +1443,17 @@ int main(int argc, char **argv)
         }
         if (save_only) {
             fprintf(stderr, "--clock-check with --save-only: no context runs, so there are no frames to judge\n");
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_fine) {
+        if (gpus > 1) {
+            fprintf(stderr, "--fine-freq: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if (save_only) {
+            fprintf(stderr, "--fine-freq with --save-only: no context runs, so there are no frames to refine\n");
             return 2;
         }
         gpus = 0;
@@ -1720,6 +1760,11 @@ int main(int argc, char **argv)
         fprintf(stderr, "--clock-check: the library refused the estimator\n");
         return 1;
     }
+    if (g_fine && irdm_set_option(p, "fine_freq", 1) != 0) {
+        fprintf(stderr, "--fine-freq: the library refused the estimator\n");
+        return 1;
+    }
+    if (g_fine && verbose) fprintf(stderr, "fine freq: carrier frequency from each frame's samples (+-250 Hz of the downmixer's)\n");
     if (g_iq && irdm_set_option(p, "iq_sense", 1) != 0) {
         fprintf(stderr, "--iq-check: the library refused the check\n");
         return 1;
@@ -2004,6 +2049,11 @@ int main(int argc, char **argv)
             irdm_symbol_clock_t sc;
             if (irdm_symbol_clock(p, &sc) == 0) clock_line(&sc, (double)c.sample_rate, rate, fe != NULL, br_l != br_m);
             else { fprintf(stderr, "--clock-check: %s: no estimate\n", file); rc = 1; }
+        }
+        if (g_fine) {
+            irdm_fine_freq_summary_t ff;
+            if (irdm_fine_freq(p, &ff) == 0) freq_line(&ff);
+            else { fprintf(stderr, "--fine-freq: %s: no estimate\n", file); rc = 1; }
         }
         if (g_iq) {
             irdm_iq_sense_t iq;

@@ -252,6 +252,22 @@ class DcStats(C.Structure):
                 ("min_q", C.c_float), ("max_q", C.c_float)]
 
 
+FINE_FREQ_INVALID, FINE_FREQ_OUT_OF_RANGE, FINE_FREQ_NOT_OK = 1, 2, 4
+
+
+class FineFreq(C.Structure):
+    """irdm_fine_freq_t (option fine_freq): the carrier frequency of one frame from its own samples, flags FINE_FREQ_*"""
+    _fields_ = [("id", C.c_uint64), ("freq_hz", C.c_double), ("df_hz", C.c_float), ("quality", C.c_float),
+                ("flags", C.c_uint32), ("n", C.c_uint32)]
+
+
+class FineFreqSummary(C.Structure):
+    """irdm_fine_freq_summary_t (irdm_fine_freq): the summary of the stream so far; median and quartiles of refined - PLL in Hz"""
+    _fields_ = [("frames_seen", C.c_uint64), ("frames_applied", C.c_uint64), ("frames_not_ok", C.c_uint64),
+                ("frames_out_of_range", C.c_uint64), ("frames_invalid", C.c_uint64),
+                ("median", C.c_double), ("q25", C.c_double), ("q75", C.c_double)]
+
+
 class RecordingInfo(C.Structure):
     """irdm_recording_info_t (irdm_recording_probe)"""
     _fields_ = [("kind", C.c_int), ("format", C.c_int), ("sample_rate", C.c_int), ("has_center", C.c_int),
@@ -350,6 +366,10 @@ def lib():
             L.irdm_dc_block.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float]
             L.irdm_dc_stats.argtypes = [C.c_void_p, C.POINTER(DcStats)]
             L.irdm_dc_block_time_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_float)]
+        if hasattr(L, "irdm_fine_freq"):
+            L.irdm_poll_fine_freq.argtypes = [C.c_void_p, C.POINTER(FineFreq), C.c_int]
+            L.irdm_fine_freq.argtypes = [C.c_void_p, C.POINTER(FineFreqSummary)]
+            L.irdm_fine_freq_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(FineFreq)]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -1090,6 +1110,35 @@ class Pipeline:
         if self.L.irdm_iq_sense_batch(self.h, arr, n, out) != 0:
             raise RuntimeError("irdm_iq_sense_batch failed")
         return [IqVote.from_buffer_copy(out[i]) for i in range(n)]
+
+    def poll_fine_freq(self):
+        """option fine_freq 1: one FineFreq per frame that reached the demodulator, in the order of the demod records"""
+        return self._poll(self.L.irdm_poll_fine_freq, FineFreq)
+
+    def poll_fine_freq_raw(self, chunk=4096):
+        """the same as one numpy byte matrix [n, 32]"""
+        return self._poll_raw(self.L.irdm_poll_fine_freq, FineFreq, chunk)
+
+    def fine_freq(self):
+        """irdm_fine_freq (option fine_freq): the FineFreqSummary of the stream so far"""
+        st = FineFreqSummary()
+        if self.L.irdm_fine_freq(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_fine_freq failed (option fine_freq never set?)")
+        return st
+
+    def fine_freq_batch(self, frames):
+        """irdm_fine_freq_batch: frames = list of complex64 arrays (<= 4440 samples); returns a list of FineFreq"""
+        n = len(frames)
+        buf = np.zeros((max(n, 1), 2 * MAX_FRAME_SAMPLES), np.float32)
+        ns = np.zeros(max(n, 1), np.int32)
+        for i, f in enumerate(frames):
+            f = np.ascontiguousarray(f, np.complex64)
+            ns[i] = len(f)
+            buf[i, :2 * len(f)] = f.view(np.float32)
+        out = (FineFreq * max(n, 1))()
+        if self.L.irdm_fine_freq_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
+            raise RuntimeError("irdm_fine_freq_batch failed")
+        return [FineFreq.from_buffer_copy(out[i]) for i in range(n)]
 
     def poll_spectrum(self, chunk=64):
         """option spectrum_frames: (headers, mean, peak) of the rows finished so far -- a list of SpectrumRow and two float32
