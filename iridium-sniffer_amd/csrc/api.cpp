@@ -143,15 +143,22 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
     return -1;
 }
 
-// ---- option "symbol_clock" (symbol_clock.hpp): the pinned records of every batch context, when the option is first set ----
-int symbol_clock_configure(irdm_pipeline *p, int on)
+// ---- the frame line estimators (frame_line.hpp): the pinned records `hp` of every batch context, when an option is first set ----
+static int line_records_alloc(irdm_pipeline *p, LineRec *BatchCtx::*hp)
 {
-    for (int i = 0; on && i < p->n_bc; i++) {
+    for (int i = 0; i < p->n_bc; i++) {
         BatchCtx &b = p->bc[i];
-        if (!b.hp_clock &&
-            hipHostMalloc(reinterpret_cast<void **>(&b.hp_clock), sizeof(ClockRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
+        if (!(b.*hp) &&
+            hipHostMalloc(reinterpret_cast<void **>(&(b.*hp)), sizeof(LineRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
             return -1;
     }
+    return 0;
+}
+
+// ---- option "symbol_clock" (symbol_clock.hpp) ----
+int symbol_clock_configure(irdm_pipeline *p, int on)
+{
+    if (on && line_records_alloc(p, &BatchCtx::hp_clock) != 0) return -1;
     p->symbol_clock = on ? 1 : 0;
     return 0;
 }
@@ -238,15 +245,10 @@ extern "C" int irdm_burst_resample_taps(irdm_pipeline_t *p, float *out, int cap)
     return n;
 }
 
-// ---- option "fine_freq" (fine_freq.hpp): the pinned records of every batch context, when the option is first set ----
+// ---- option "fine_freq" (fine_freq.hpp) ----
 int fine_freq_configure(irdm_pipeline *p, int on)
 {
-    for (int i = 0; on && i < p->n_bc; i++) {
-        BatchCtx &b = p->bc[i];
-        if (!b.hp_fine &&
-            hipHostMalloc(reinterpret_cast<void **>(&b.hp_fine), sizeof(FineRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
-            return -1;
-    }
+    if (on && line_records_alloc(p, &BatchCtx::hp_fine) != 0) return -1;
     p->fine_freq = on ? 1 : 0;
     return 0;
 }

@@ -9,6 +9,8 @@
 //   feed.cpp        irdm_feed_* / irdm_flush / irdm_advance / irdm_reset, the polls, buffers for hosts without HIP headers
 //   state.cpp       detector-state export / import (time-chunk sharding), the stage-level batch calls
 //   api.cpp         options, statistics, kernel clock, RAW line formatting, --save-bursts
+//   frame_line.hpp  the per-frame line estimators' core and stream summary; symbol_clock.hpp and fine_freq.hpp are the two
+//                   kernels on it (launched by chain.cpp and state.cpp)
 //
 // Every field of a context is configuration, cache or stream state.  The third kind lives in types of
 // its own -- StreamState (irdm_pipeline::st), BatchCtx::State, FeedSlot::State, with the record queues of record_queues.hpp
@@ -140,8 +142,8 @@ struct BatchCtx {
     DemodPacked *hp_packed;                 // packed_records: the demodulator's result without LLRs, bits 8 per byte (pinned; written by demod_par_kernel)
     IdaPacked *hp_ida;                      // parsed_records: ida_decode() of each of them (pinned; written by ida_packed_kernel)
     FramePacked *hp_frame;                  // frame_records: frame_decode() of each of them (pinned; written by frame_packed_kernel)
-    FineRec *hp_fine;                       // fine_freq: one record per burst (pinned; written by fine_freq_kernel; allocated with the option)
-    ClockRec *hp_clock;                     // symbol_clock: one record per burst (pinned; written by symbol_clock_kernel; allocated with the option)
+    LineRec *hp_fine;                       // fine_freq: one record per burst (pinned; written by fine_freq_kernel; allocated with the option)
+    LineRec *hp_clock;                      // symbol_clock: one record per burst (pinned; written by symbol_clock_kernel; allocated with the option)
     SenseRec *hp_sense;                     // iq_sense: one record per burst (pinned; written by iq_sense_kernel; allocated with the option)
     uint32_t *hp_flag, *hp_flag_dev;    // [0] sequence number the helper publishes, [1] time-out flag of the waiting kernel
     int4 *hp_rot_new, *hp_rot_new_dev, *d_rot_new;   // (bin, row, from, to) of the checkpoint runs this batch has to build: mapped pinned / device
@@ -241,9 +243,9 @@ struct StreamState {
     // option "input_stats": the totals of the stream's raw samples and the passes in flight (input_stats.hpp)
     InputStatsStream in_stats;
     // option "symbol_clock": the per-frame records until they are polled and the summary's histogram (symbol_clock.hpp)
-    SymbolClockStream clock;
+    SymbolClockStream clock{ kScHist };
     // option "fine_freq": the per-frame records until they are polled and the summary's histogram (fine_freq.hpp)
-    FineFreqStream fine;
+    FineFreqStream fine{ kFfHist };
     // option "iq_sense": the per-frame votes until they are polled and the counts of the summary (iq_sense.hpp)
     IqSenseStream iq;
     // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)

@@ -404,15 +404,18 @@ extern "C" int irdm_qpsk_demod_packed_batch(irdm_pipeline_t *p, const float *sam
     return demod_batch(p, samples, num_samples, direction, n, keep_bits, packed_out, full_out);
 }
 
-// the symbol clock kernel alone (symbol_clock.hpp), on the buffers of irdm_qpsk_demod_batch
-extern "C" int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out)
+// A frame line estimator's kernel alone (frame_line.hpp), on the buffers of irdm_qpsk_demod_batch: frames in, one record per
+// frame out, in launches of burst_cap.  launch(nb, hp) starts the kernel on the first nb rows of d_work / d_frames;
+// fill(o, r) copies its record into the public one.
+template <typename PublicRec, typename Launch, typename Fill>
+static int line_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, PublicRec *out, Launch launch, Fill fill)
 {
     if (!p || !samples || !num_samples || !out || n < 0) return -1;
     for (int i = 0; i < n; i++)
         if (num_samples[i] < 0 || num_samples[i] > kMaxFrameSamples) return -1;
     pipeline_enter(p);
-    ClockRec *hp = nullptr;
-    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(ClockRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
+    LineRec *hp = nullptr;
+    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(LineRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
                                  hipHostMallocDefault));
     int rc = 0;
     for (int base = 0; base < n && rc == 0; base += p->burst_cap) {
@@ -422,55 +425,33 @@ extern "C" int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples,
         rc = hipMemcpyAsync(p->d_work, p->h_work.data(), sizeof(BurstWork) * nb, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
                      hipMemcpyAsync(p->d_frames, samples + (size_t)base * 2 * kMaxFrameSamples,
                                     sizeof(float2) * (size_t)nb * kMaxFrameSamples, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
-                     launch_symbol_clock(p->d_work, nb, p->d_frames, p->sps, hp, p->stream) == 0 &&
-                     hipStreamSynchronize(p->stream) == hipSuccess
+                     launch(nb, hp) == 0 && hipStreamSynchronize(p->stream) == hipSuccess
                  ? 0 : -1;
         for (int i = 0; rc == 0 && i < nb; i++) {
-            irdm_clock_est_t &o = out[base + i];
+            PublicRec &o = out[base + i];
             o.id = (uint64_t)(base + i);
-            o.eps = hp[i].eps;
             o.quality = hp[i].quality;
             o.flags = hp[i].flags;
             o.n = hp[i].n;
+            fill(o, hp[i]);
         }
     }
     (void)hipHostFree(hp);
     return rc;
 }
 
-// the carrier frequency kernel alone (fine_freq.hpp), on the buffers of irdm_qpsk_demod_batch
+extern "C" int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out)
+{
+    return line_batch(p, samples, num_samples, n, out,
+                      [p](int nb, LineRec *hp) { return launch_symbol_clock(p->d_work, nb, p->d_frames, p->sps, hp, p->stream); },
+                      [](irdm_clock_est_t &o, const LineRec &r) { o.eps = r.value; });
+}
+
 extern "C" int irdm_fine_freq_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_fine_freq_t *out)
 {
-    if (!p || !samples || !num_samples || !out || n < 0) return -1;
-    for (int i = 0; i < n; i++)
-        if (num_samples[i] < 0 || num_samples[i] > kMaxFrameSamples) return -1;
-    pipeline_enter(p);
-    FineRec *hp = nullptr;
-    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(FineRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
-                                 hipHostMallocDefault));
-    int rc = 0;
-    for (int base = 0; base < n && rc == 0; base += p->burst_cap) {
-        const int nb = std::min(p->burst_cap, n - base);
-        p->h_work.assign(nb, BurstWork());
-        for (int i = 0; i < nb; i++) p->h_work[i].num_samples = num_samples[base + i];
-        rc = hipMemcpyAsync(p->d_work, p->h_work.data(), sizeof(BurstWork) * nb, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
-                     hipMemcpyAsync(p->d_frames, samples + (size_t)base * 2 * kMaxFrameSamples,
-                                    sizeof(float2) * (size_t)nb * kMaxFrameSamples, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
-                     launch_fine_freq(p->d_work, nb, p->d_frames, (double)p->out_rate, hp, p->stream) == 0 &&
-                     hipStreamSynchronize(p->stream) == hipSuccess
-                 ? 0 : -1;
-        for (int i = 0; rc == 0 && i < nb; i++) {
-            irdm_fine_freq_t &o = out[base + i];
-            o.id = (uint64_t)(base + i);
-            o.freq_hz = (double)hp[i].df;
-            o.df_hz = hp[i].df;
-            o.quality = hp[i].quality;
-            o.flags = hp[i].flags;
-            o.n = hp[i].n;
-        }
-    }
-    (void)hipHostFree(hp);
-    return rc;
+    return line_batch(p, samples, num_samples, n, out,
+                      [p](int nb, LineRec *hp) { return launch_fine_freq(p->d_work, nb, p->d_frames, (double)p->out_rate, hp, p->stream); },
+                      [](irdm_fine_freq_t &o, const LineRec &r) { o.df_hz = r.value; o.freq_hz = (double)r.value; });
 }
 
 extern "C" int irdm_poll_decoded(irdm_pipeline_t *p, irdm_decoded_t *out, int max)

@@ -1049,8 +1049,8 @@ class Pipeline:
             raise RuntimeError("irdm_symbol_clock failed (option symbol_clock never set?)")
         return st
 
-    def symbol_clock_batch(self, frames):
-        """irdm_symbol_clock_batch: frames = list of complex64 arrays (<= 4440 samples); returns a list of ClockEst"""
+    def _frames_batch(self, fn, Rec, frames, what):
+        """a stage call that takes frames (list of complex64 arrays, <= 4440 samples) and gives one Rec per frame"""
         n = len(frames)
         buf = np.zeros((max(n, 1), 2 * MAX_FRAME_SAMPLES), np.float32)
         ns = np.zeros(max(n, 1), np.int32)
@@ -1058,10 +1058,14 @@ class Pipeline:
             f = np.ascontiguousarray(f, np.complex64)
             ns[i] = len(f)
             buf[i, :2 * len(f)] = f.view(np.float32)
-        out = (ClockEst * max(n, 1))()
-        if self.L.irdm_symbol_clock_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
-            raise RuntimeError("irdm_symbol_clock_batch failed")
-        return [ClockEst.from_buffer_copy(out[i]) for i in range(n)]
+        out = (Rec * max(n, 1))()
+        if fn(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
+            raise RuntimeError(what + " failed")
+        return [Rec.from_buffer_copy(out[i]) for i in range(n)]
+
+    def symbol_clock_batch(self, frames):
+        """irdm_symbol_clock_batch: frames = list of complex64 arrays (<= 4440 samples); returns a list of ClockEst"""
+        return self._frames_batch(self.L.irdm_symbol_clock_batch, ClockEst, frames, "irdm_symbol_clock_batch")
 
     def burst_resample_ratio(self):
         """irdm_burst_resample_ratio (option burst_resample): (L, M, taps_per_phase); (1, 1, 0) at a rate on the 250 kHz grid"""
@@ -1128,17 +1132,7 @@ class Pipeline:
 
     def fine_freq_batch(self, frames):
         """irdm_fine_freq_batch: frames = list of complex64 arrays (<= 4440 samples); returns a list of FineFreq"""
-        n = len(frames)
-        buf = np.zeros((max(n, 1), 2 * MAX_FRAME_SAMPLES), np.float32)
-        ns = np.zeros(max(n, 1), np.int32)
-        for i, f in enumerate(frames):
-            f = np.ascontiguousarray(f, np.complex64)
-            ns[i] = len(f)
-            buf[i, :2 * len(f)] = f.view(np.float32)
-        out = (FineFreq * max(n, 1))()
-        if self.L.irdm_fine_freq_batch(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
-            raise RuntimeError("irdm_fine_freq_batch failed")
-        return [FineFreq.from_buffer_copy(out[i]) for i in range(n)]
+        return self._frames_batch(self.L.irdm_fine_freq_batch, FineFreq, frames, "irdm_fine_freq_batch")
 
     def poll_spectrum(self, chunk=64):
         """option spectrum_frames: (headers, mean, peak) of the rows finished so far -- a list of SpectrumRow and two float32

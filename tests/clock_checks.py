@@ -7,6 +7,8 @@ import numpy as np
 
 import clock_model as cm
 import irdm
+import line_checks
+from line_checks import ragged3      # noqa: F401 (the tests call it through this module too)
 import orc
 import resample_model as rm
 import siggen
@@ -69,14 +71,7 @@ def kernel_frames():
 def batch_frames(n):
     """n frames for a batch: the kernel frames in turn, then cuts of the oracle's frames at lengths and offsets of their own"""
     fr = oracle_frames(10_025_000)
-    out = list(kernel_frames().values())[:n]
-    k = 0
-    while len(out) < n:
-        x = fr[k % len(fr)]
-        off = 7 * k % 400
-        out.append(x[off:off + 64 + (131 * k) % (len(x) - off - 64)])
-        k += 1
-    return out
+    return line_checks.fill_with_cuts(list(kernel_frames().values())[:n], fr, n)
 
 
 def compare(got, frames, what):
@@ -124,13 +119,6 @@ def stage_cases(p):
                 far_edge_quality=float(by["resampled_0.9"].quality))
 
 
-def ragged3(n, block=32768):
-    """n samples in three feeds of whole blocks, the remainder on the last"""
-    b = n // block
-    a, c = max(1, b // 5), max(1, b // 2)
-    return [a * block, c * block, n - (a + c) * block]
-
-
 def context_run(iq, fs, sizes, depth, options=(("symbol_clock", 1),), packed=False, after=None):
     """iq through a context; returns (SymbolClock or None, ClockEst byte matrix, demod byte matrix, stats)"""
     p = irdm.Pipeline(fs, max_chunk_samples=max(sizes), max_bursts_per_chunk=1024, pipeline_depth=depth)
@@ -162,15 +150,7 @@ def context_run(iq, fs, sizes, depth, options=(("symbol_clock", 1),), packed=Fal
         p.close()
 
 
-def group_refuses():
-    """a member of a group refuses the option, directly and through irdm_group_set_option"""
-    g = irdm.Group(2_000_000, 1, max_chunk_samples=32768 * 8)
-    try:
-        L = irdm.lib()
-        assert L.irdm_set_option(g.member(0), b"symbol_clock", 1) == -1
-        assert L.irdm_group_set_option(g.g, b"symbol_clock", 1) == -1
-    finally:
-        g.close()
+group_refuses = functools.partial(line_checks.group_refuses, b"symbol_clock")
 
 
 def check_summary(st, clock):

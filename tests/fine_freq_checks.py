@@ -9,6 +9,8 @@ import numpy as np
 import fine_freq_model as fm
 import fine_freq_scenes as sc
 import irdm
+import line_checks
+from line_checks import ragged3
 
 # |df_device - df_model| [Hz].  A wrong grid point is off by 1 Hz and more (a fine step of 4 Hz is 1 Hz of df), so this bound
 # cannot hide one.  The largest difference seen is in the docstring of tests/test_fine_freq_emul.py.
@@ -64,14 +66,7 @@ def batch_frames(n):
     """n frames for a batch: the kernel frames in turn, then cuts of the oracle's frames at lengths and offsets of their own"""
     kf = kernel_frames()
     fr = [kf[k] for k in kf if k.startswith("oracle")]
-    out = list(kf.values())[:n]
-    k = 0
-    while len(out) < n:
-        x = fr[k % len(fr)]
-        off = 7 * k % 400
-        out.append(x[off:off + 64 + (131 * k) % (len(x) - off - 64)])
-        k += 1
-    return out
+    return line_checks.fill_with_cuts(list(kf.values())[:n], fr, n)
 
 
 def compare(got, frames, what):
@@ -122,13 +117,6 @@ def stage_cases(p):
     assert p.fine_freq_batch([]) == []
     assert p.stat("fine_freq_launches") == 0          # (the stage call is none of the chain's)
     return dict(frames=len(names), worst=worst, worst_quality=worst_q)
-
-
-def ragged3(n, block=32768):
-    """n samples in three feeds of whole blocks, the remainder on the last"""
-    b = n // block
-    a, c = max(1, b // 5), max(1, b // 2)
-    return [a * block, c * block, n - (a + c) * block]
 
 
 def context_run(iq, fs, sizes, depth, options=(("fine_freq", 1),), packed=False, after=None):
@@ -269,12 +257,4 @@ def context_checks(kind, key, min_frames, lengths=(), thorough=True):
     return seen
 
 
-def group_refuses():
-    """a member of a group refuses the option, directly and through irdm_group_set_option"""
-    g = irdm.Group(2_000_000, 1, max_chunk_samples=32768 * 8)
-    try:
-        L = irdm.lib()
-        assert L.irdm_set_option(g.member(0), b"fine_freq", 1) == -1
-        assert L.irdm_group_set_option(g.g, b"fine_freq", 1) == -1
-    finally:
-        g.close()
+group_refuses = functools.partial(line_checks.group_refuses, b"fine_freq")
