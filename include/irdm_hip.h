@@ -370,6 +370,50 @@ typedef struct {
     double   median, q25, q75;            /* Hz */
 } irdm_fine_freq_summary_t;
 
+/* option "fine_time": the arrival time of one downmixed frame's first symbol, refined on the device from the samples the
+ * demodulator is handed (irdm_poll_fine_time, irdm_fine_time_batch).  |x|^2 of a frame carries a spectral line at the symbol
+ * rate, and the phase of that line is the symbol timing.  Over the window W = min(n, 131 sps) samples (simplex: 80 sps) at the
+ * context's nominal sps = 10, with p' = |x|^2 less its mean over the window and S(f) = sum p'[k] exp(-2 pi i f k):
+ *   tau = -arg S(1 / sps) / 2 pi * sps, in [-sps / 2, sps / 2): the distance in samples from the frame's sample 0 to the
+ *   nearest symbol centre.
+ * The device leaves S(1 / sps) and the floor in doubles, bit for bit the same on every build; arg is taken on the host.
+ * Without the option a demodulator record's timestamp is the reference's: the burst's time plus the first sample at which the
+ * smoothed magnitude crosses 0.28 of its maximum, about 0.73 ms in front of the frame and wandering by 6 to 60 us with the
+ * noise.  With it the timestamp is the time of the frame's sample 0 -- the centre of the unique word's first symbol on a
+ * downlink frame, 32 symbols behind the start of the correlator's match on an uplink one, as the reference cuts it --
+ * to about 0.3 us at the levels the detector decodes at all (README: "Arrival time to 0.1 us"):
+ *   timestamp + llrint((uw_start_idx + delta) 1e9 / 250000), delta = tau, or corr where the record carries a flag. */
+#define IRDM_FINE_TIME_INVALID    1u   /* no estimate (tau = quality = s_re = s_im = floor = 0): the frame was dropped in front of
+                                        * the demodulator, is shorter than 64 samples, all zero, or holds a sample that is not
+                                        * finite */
+#define IRDM_FINE_TIME_AMBIGUOUS  2u   /* (set by the context, never by the stage call) |tau - corr| is above sps / 4: the line
+                                        * and the correlator name different places; the time is the correlator's */
+#define IRDM_FINE_TIME_NOT_OK     4u   /* (set by the context, never by the stage call) the demodulator rejected the frame's
+                                        * unique word: no demodulator record goes with this one */
+typedef struct {
+    uint64_t id;               /* the burst's id; irdm_fine_time_batch: the frame's index */
+    uint64_t time_ns;          /* the time of the frame's sample 0 as its demodulator record carries it; irdm_fine_time_batch: 0 */
+    double   tau;              /* samples; the double the time was computed from */
+    double   s_re, s_im;       /* S(1 / sps): the kernel's sums */
+    double   floor;            /* the mean of |S|^2 at 1 / sps (1 + 0.02 j), j = +-2 .. +-9 */
+    float    corr;             /* the correlator's parabola correction (irdm_frame_info_t.uw_start), samples; irdm_fine_time_batch: 0 */
+    float    quality;          /* |S(1 / sps)|^2 / floor.  Reported, and flags nothing: 3 .. 30 on frames whose unique word
+                                * passed, up to 7 on pure noise */
+    uint32_t flags;            /* IRDM_FINE_TIME_* */
+    uint32_t n;                /* samples of the frame */
+} irdm_fine_time_t;
+
+/* irdm_fine_time: the stream so far.  A frame counts as applied when its unique word passed and its record is neither invalid
+ * nor ambiguous: its demodulator record then carries the line's time; an ambiguous or invalid one carries the correlator's.
+ * median and quartiles are those of tau - corr over the applied frames, in samples; they are centres of the 0.01-sample bins of
+ * a histogram over +-2.5 samples, so they do not depend on how the stream was cut into chunks or feeds (0 while
+ * frames_applied is 0). */
+typedef struct {
+    uint64_t frames_seen;                 /* frames that reached the demodulator: the sum of the four below */
+    uint64_t frames_applied, frames_not_ok, frames_ambiguous, frames_invalid;
+    double   median, q25, q75;            /* samples */
+} irdm_fine_time_summary_t;
+
 /* option "iq_sense": which way round I and Q of one demodulated frame were (irdm_poll_iq_votes, irdm_iq_sense_batch).
  * A recording with its two components exchanged (a Q/I WAV, the other SigMF convention, an inverting mixer) demodulates
  * with ok = 1 and full confidence -- preamble and unique words use the DQPSK states 0 and 2 alone, which conjugation maps
@@ -821,6 +865,16 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  *                         when the option is first set to 1, never before; with 0 nothing is launched (stat
  *                         "fine_freq_launches").  -1 for a member of a group (and so through irdm_group_set_option) and
  *                         while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
+ *   "fine_time"           0/1, default 0: 1 = one more kernel in the per-burst chain of every chunk fed from then on, behind
+ *                         the downmixer and beside the demodulator: the symbol timing of every frame from its own samples,
+ *                         see irdm_poll_fine_time / irdm_fine_time.  timestamp of every demodulator record (irdm_demod_t,
+ *                         irdm_demod_packed_t, and the irdm_decoded_t / irdm_ida_t derived from them) is then the time of
+ *                         the frame's sample 0, from the line where the estimate is neither invalid nor ambiguous and from
+ *                         the correlator otherwise; no other field of any record changes (irdm_frame_info_t keeps the
+ *                         downmixer's timestamp).  One pinned buffer of 32 bytes per burst and batch context is allocated
+ *                         when the option is first set to 1, never before; with 0 nothing is launched (stat
+ *                         "fine_time_launches").  -1 for a member of a group (and so through irdm_group_set_option) and
+ *                         while a chunk handed over with irdm_feed_begin waits for its irdm_feed_end
  *   "iq_sense"            0/1, default 0: 1 = one more kernel in the per-burst chain of every chunk fed from then on, behind
  *                         the demodulator: whether each frame's bits make sense as they are or with I and Q exchanged, see
  *                         irdm_poll_iq_votes / irdm_iq_sense.  It reads the demodulator's bits and LLRs only: no other
@@ -917,7 +971,7 @@ uint64_t irdm_chunks_complete(const irdm_pipeline_t *p);
  * "rot_rows_cap", "rot_blocks", "rot_blocks_cap", "rot_builds", "rot_runs", "rot_ckpts", "rot_grows" (rotator checkpoints:
  * centre bins with a row / runs per bin prebuilt / the arena in whole rows / blocks of 2048 checkpoints in use / allocated /
  * build launches on chains / runs built / checkpoints built / times the arena doubled), "band_steps" (update steps the scans'
- * last rounds walked), "burst_resample_launches" (launches of burst_resample_kernel by the chains), "fine_freq_launches" (of fine_freq_kernel), "scratch_outputs", "scratch_grows", "scratch_peak" (decimated samples a batch context holds / times it
+ * last rounds walked), "burst_resample_launches" (launches of burst_resample_kernel by the chains), "fine_freq_launches" (of fine_freq_kernel), "fine_time_launches" (of fine_time_kernel),"scratch_outputs", "scratch_grows", "scratch_peak" (decimated samples a batch context holds / times it
  * doubled / most a batch needed). */
 int irdm_set_option(irdm_pipeline_t *p, const char *key, int value);
 int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key);
@@ -1296,6 +1350,26 @@ int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int 
 int irdm_poll_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_t *out, int max);
 int irdm_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_summary_t *out);
 int irdm_fine_freq_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_fine_freq_t *out);
+
+/* ---- arrival time from the frame's samples (irdm_fine_time_t / irdm_fine_time_summary_t above) ----
+ * irdm_set_option(p, "fine_time", 1): every frame that reaches the demodulator from then on gets an estimate of its
+ * symbol timing, by one kernel on the chain's stream that only reads the frames; the demodulator records carry the time.
+ * irdm_poll_fine_time: up to `max` per-frame records, one for every frame that reached the demodulator, in the order
+ *   of the demodulator's records: those without IRDM_FINE_TIME_NOT_OK pair one to one with the records of
+ *   irdm_poll_demods / irdm_poll_demods_packed, and time_ns is that record's timestamp.  A frame's record depends on its
+ *   samples, its class (simplex or not), the downmixer's timestamp and the correlator's place alone, not on pipeline_depth or
+ *   how the stream was fed.  Returns the number written (0 with the option off), -1 on error.
+ * irdm_fine_time: the summary of the stream so far (of the records queued so far: irdm_flush first for the whole
+ *   stream).  irdm_reset starts it over.  Returns 0, or -1 (the option never set included).
+ * irdm_fine_time_batch: the kernel alone on n frames, with the calling convention of irdm_fine_freq_batch: samples =
+ *   n rows of IRDM_MAX_FRAME_SAMPLES interleaved float pairs, num_samples[i] <= IRDM_MAX_FRAME_SAMPLES; simplex[i] != 0:
+ *   frame i takes the simplex window (NULL: none does).  tau, s_re, s_im, floor, quality, flags and n of a record are
+ *   filled, corr and time_ns are 0 and the ambiguity rule is not applied (there is no correlator).  Works with the option
+ *   off.  Returns 0 or -1. */
+int irdm_poll_fine_time(irdm_pipeline_t *p, irdm_fine_time_t *out, int max);
+int irdm_fine_time(irdm_pipeline_t *p, irdm_fine_time_summary_t *out);
+int irdm_fine_time_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, const int *simplex, int n,
+                         irdm_fine_time_t *out);
 
 /* ---- per-burst resampling (option "burst_resample") ----
  * Output m of a decimated row x[0 .. n) is the band-limited interpolation of x at input time m M / L: q = floor(m M / L),

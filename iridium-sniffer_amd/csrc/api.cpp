@@ -40,6 +40,11 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
         if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
         return fine_freq_configure(p, value);
     }
+    if (!strcmp(key, "fine_time")) {
+        // 0 / 1; as "fine_freq"
+        if (p->in_group || p->st.begin_no != p->st.end_no) return -1;
+        return fine_time_configure(p, value);
+    }
     if (!strcmp(key, "iq_sense")) {
         // 0 / 1; not for a member of a group (the summary is a context's, and a group merges no votes), and not while a chunk
         // handed over with irdm_feed_begin waits for its irdm_feed_end
@@ -144,12 +149,13 @@ extern "C" int irdm_set_option(irdm_pipeline_t *p, const char *key, int value)
 }
 
 // ---- the frame line estimators (frame_line.hpp): the pinned records `hp` of every batch context, when an option is first set ----
-static int line_records_alloc(irdm_pipeline *p, LineRec *BatchCtx::*hp)
+template <typename Rec>
+static int line_records_alloc(irdm_pipeline *p, Rec *BatchCtx::*hp)
 {
     for (int i = 0; i < p->n_bc; i++) {
         BatchCtx &b = p->bc[i];
         if (!(b.*hp) &&
-            hipHostMalloc(reinterpret_cast<void **>(&(b.*hp)), sizeof(LineRec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
+            hipHostMalloc(reinterpret_cast<void **>(&(b.*hp)), sizeof(Rec) * (size_t)p->burst_cap, hipHostMallocDefault) != hipSuccess)
             return -1;
     }
     return 0;
@@ -266,6 +272,27 @@ extern "C" int irdm_fine_freq(irdm_pipeline_t *p, irdm_fine_freq_summary_t *out)
     return 0;
 }
 
+// ---- option "fine_time" (fine_time.hpp) ----
+int fine_time_configure(irdm_pipeline *p, int on)
+{
+    if (on && line_records_alloc(p, &BatchCtx::hp_ftime) != 0) return -1;
+    p->fine_time = on ? 1 : 0;
+    return 0;
+}
+
+extern "C" int irdm_poll_fine_time(irdm_pipeline_t *p, irdm_fine_time_t *out, int max)
+{
+    if (!p || !out || max < 0) return -1;
+    return drain(p->st.ftime.q, out, max);
+}
+
+extern "C" int irdm_fine_time(irdm_pipeline_t *p, irdm_fine_time_summary_t *out)
+{
+    if (!p || !out || !p->bc[0].hp_ftime) return -1;
+    fine_time_result(p->st.ftime, out);
+    return 0;
+}
+
 // ---- option "iq_sense" (iq_sense.hpp): the pinned records of every batch context, when the option is first set ----
 int iq_sense_configure(irdm_pipeline *p, int on)
 {
@@ -336,6 +363,7 @@ extern "C" int64_t irdm_get_stat(const irdm_pipeline_t *p, const char *key)
     if (!strcmp(key, "scan_dense_frames")) return (int64_t)p->stat_dense_frames;
     if (!strcmp(key, "burst_resample_launches")) return (int64_t)p->stat_br_launches;
     if (!strcmp(key, "fine_freq_launches")) return (int64_t)p->stat_ff_launches;
+    if (!strcmp(key, "fine_time_launches")) return (int64_t)p->stat_ft_launches;
     return -1;
 }
 

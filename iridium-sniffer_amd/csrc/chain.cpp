@@ -618,6 +618,12 @@ int bursts_enqueue(irdm_pipeline *p, BatchCtx &b, const SampleSource &src, const
         if (launch_fine_freq(b.d_work, nb, b.d_frames, (double)p->out_rate, b.hp_fine, st) != 0) return -1;
         p->stat_ff_launches++;
     }
+    // option "fine_time": the symbol timing of every frame, likewise
+    b.timed = p->fine_time && b.hp_ftime;
+    if (b.timed) {
+        if (launch_fine_time(b.d_work, nb, b.d_frames, p->sps, b.hp_ftime, st) != 0) return -1;
+        p->stat_ft_launches++;
+    }
     // option "iq_sense": each frame's bits judged as they are and with I and Q exchanged, from the DemodOut the demodulator
     // left on the device (read only), into pinned memory
     if (b.sensed && launch_iq_sense(b.d_demod, nb, p->d_syn_da, p->d_syn_l1, p->d_syn_l2, p->d_syn_l3, b.hp_sense, st) != 0)
@@ -711,14 +717,19 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             const DemodPacked &d = b.hp_packed[i];
             if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], d.ok != 0);
             if (b.fined && w.drop_reason == 0 && !d.ok) fine_freq_fold(p->st.fine, r.id, b.hp_fine[i], b.h_cfreq[i], false, 0.0);
-            if (w.drop_reason != 0 || !d.ok) continue;
-            if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
             uint64_t timestamp = p->st.start_time_ns + (uint64_t)((double)r.start / fs * 1e9);
             if (w.dec_len > 0) timestamp += (uint64_t)((p->in_ntaps / 2) * 1000000000ULL / fs);
+            if (b.timed && w.drop_reason == 0 && !d.ok)
+                fine_time_fold(p->st.ftime, r.id, b.hp_ftime[i], p->sps, timestamp + (uint64_t)((double)w.start_idx / p->out_rate * 1e9), w.uw_start,
+                               w.uw_corr, (double)p->out_rate, false);
+            if (w.drop_reason != 0 || !d.ok) continue;
+            if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
             p->st.q.packed.emplace_back();
             irdm_demod_packed_t &o = p->st.q.packed.back();
             o.id = r.id;
             o.timestamp = timestamp + (uint64_t)((double)w.start_idx / p->out_rate * 1e9);
+            // option "fine_time": the time of the frame's sample 0 in place of the downmixer's, from the line or the correlator
+            if (b.timed) o.timestamp = fine_time_fold(p->st.ftime, r.id, b.hp_ftime[i], p->sps, o.timestamp, w.uw_start, w.uw_corr, (double)p->out_rate, true);
             o.direction = d.direction;
             o.magnitude = r.magnitude;
             o.noise = r.noise;
@@ -799,6 +810,8 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
         }
         if (b.clocked && w.drop_reason == 0) symbol_clock_fold(p->st.clock, r.id, b.hp_clock[i], b.hp_demod[i].ok != 0);
         if (b.fined && w.drop_reason == 0 && !b.hp_demod[i].ok) fine_freq_fold(p->st.fine, r.id, b.hp_fine[i], f.center_frequency, false, 0.0);
+        if (b.timed && w.drop_reason == 0 && !b.hp_demod[i].ok)
+            fine_time_fold(p->st.ftime, r.id, b.hp_ftime[i], p->sps, f.timestamp, w.uw_start, w.uw_corr, (double)p->out_rate, false);
         if (w.drop_reason == 0 && b.hp_demod[i].ok) {
             const DemodOut &d = b.hp_demod[i];
             if (b.sensed) iq_sense_fold(p->st.iq, r.id, b.hp_sense[i]);
@@ -810,6 +823,8 @@ int bursts_finish_records(irdm_pipeline *p, BatchCtx &b)
             memset(&o, 0, offsetof(irdm_demod_t, bits));
             o.id = r.id;
             o.timestamp = f.timestamp;
+            // option "fine_time": the time of the frame's sample 0 in place of the downmixer's, from the line or the correlator
+            if (b.timed) o.timestamp = fine_time_fold(p->st.ftime, r.id, b.hp_ftime[i], p->sps, f.timestamp, w.uw_start, w.uw_corr, (double)p->out_rate, true);
             o.direction = d.direction;
             o.magnitude = r.magnitude;
             o.noise = r.noise;

@@ -51,6 +51,7 @@ void pipeline_free(irdm_pipeline *p)
         if (b.hp_frame) (void)hipHostFree(b.hp_frame);
         if (b.hp_clock) (void)hipHostFree(b.hp_clock);
         if (b.hp_fine) (void)hipHostFree(b.hp_fine);
+        if (b.hp_ftime) (void)hipHostFree(b.hp_ftime);
         if (b.hp_sense) (void)hipHostFree(b.hp_sense);
         if (b.d_res) (void)hipFree(b.d_res);
         if (b.owns_buffers) {

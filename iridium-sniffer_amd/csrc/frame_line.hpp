@@ -1,6 +1,7 @@
-// frame_line.hpp -- the core of the per-frame line estimators: symbol_clock_kernel (symbol_clock.hpp: the symbol rate's
-// line in |x|^2) and fine_freq_kernel (fine_freq.hpp: the carrier's line in x^4).  Each is a __global__ function of its own
-// that stages its signal in LDS as doubles and composes the pieces below; every piece is resolved at compile time.
+// frame_line.hpp -- the core of the per-frame line estimators: symbol_clock_kernel (symbol_clock.hpp: the place of the symbol
+// rate's line in |x|^2), fine_freq_kernel (fine_freq.hpp: the carrier's line in x^4) and fine_time_kernel (fine_time.hpp: the
+// phase of the symbol rate's line).  Each is a __global__ function of its own that stages its signal in LDS as doubles and
+// composes the pieces below; every piece is resolved at compile time.
 //
 //   line_open / line_vote   a row that holds no usable frame, or a sample that is not finite: the INVALID record
 //   line_segment_sum        sum_n y[n] exp(-2 pi i f n) over a segment by Goertzel's second-order recurrence
@@ -31,16 +32,22 @@ namespace irdm {
 
 constexpr int kLineMinSamples = 64;                     // a shorter frame has no estimate
 
-// the flags of a record: both public sets, value for value
+// the flags of a record: the three public sets, value for value (fine_time's "ambiguous" is its "out of range": the line's
+// place is further from the correlator's than a quarter of a symbol)
 enum : uint32_t { kLineInvalid = 1u, kLineOutOfRange = 2u, kLineNotOk = 4u };
-static_assert(IRDM_CLOCK_INVALID == kLineInvalid && IRDM_FINE_FREQ_INVALID == kLineInvalid, "one flag set for both estimators");
-static_assert(IRDM_CLOCK_OUT_OF_RANGE == kLineOutOfRange && IRDM_FINE_FREQ_OUT_OF_RANGE == kLineOutOfRange, "one flag set for both estimators");
-static_assert(IRDM_CLOCK_NOT_OK == kLineNotOk && IRDM_FINE_FREQ_NOT_OK == kLineNotOk, "one flag set for both estimators");
+static_assert(IRDM_CLOCK_INVALID == kLineInvalid && IRDM_FINE_FREQ_INVALID == kLineInvalid && IRDM_FINE_TIME_INVALID == kLineInvalid,
+              "one flag set for the three estimators");
+static_assert(IRDM_CLOCK_OUT_OF_RANGE == kLineOutOfRange && IRDM_FINE_FREQ_OUT_OF_RANGE == kLineOutOfRange &&
+              IRDM_FINE_TIME_AMBIGUOUS == kLineOutOfRange, "one flag set for the three estimators");
+static_assert(IRDM_CLOCK_NOT_OK == kLineNotOk && IRDM_FINE_FREQ_NOT_OK == kLineNotOk && IRDM_FINE_TIME_NOT_OK == kLineNotOk,
+              "one flag set for the three estimators");
 
-// a kernel's record: the public one without the burst id (and what the context adds to it)
+// a kernel's record: the public one without the burst id (and what the context adds to it).  Every record type has
+// invalid(n): the record of a row without an estimate
 struct LineRec {
     float value, quality;               // eps (symbol_clock), df in Hz (fine_freq)
     uint32_t flags, n;
+    __host__ __device__ static LineRec invalid(uint32_t n) { return LineRec{ 0.0f, 0.0f, kLineInvalid, n }; }
 };
 
 // (sin, cos) of 2 pi t for |t| <= 1/2: t = q / 4 + r with |r| <= 1/8 exactly, the polynomials on 2 pi r, the quadrant by
@@ -57,13 +64,44 @@ __host__ __device__ __forceinline__ void sc_sincos_turns(double t, double *s_out
     *c_out = (qi & 2) ? -c1 : c1;
 }
 
+// The same to binary64's precision, for an estimator that reads the line's PHASE (fine_time.hpp): the polynomials above are
+// sinf's and cosf's, good to 1e-9, which a power does not see and a phase does -- 1e-8 rad of the phase a segment's sum is
+// turned by.  Taylor's polynomials to x^15 and x^16 in Horner's scheme on x^2, |x| <= pi / 4: the next terms are 5e-17 and
+// 2e-18.  Products and sums are rounded separately, so the device and the CPU emulation give the same bits.
+__host__ __device__ __forceinline__ void sc_sincos_turns_exact(double t, double *s_out, double *c_out)
+{
+    const double q = rint(t * 4.0);
+    const double x = (t - q * 0.25) * 6.283185307179586476925;
+    const double z = x * x;
+    double ps = -1.0 / 1307674368000.0, pc = 1.0 / 20922789888000.0;             // -1 / 15!, 1 / 16!
+    ps = ps * z + 1.0 / 6227020800.0;                                            // 1 / 13!
+    pc = pc * z - 1.0 / 87178291200.0;                                           // -1 / 14!
+    ps = ps * z - 1.0 / 39916800.0;
+    pc = pc * z + 1.0 / 479001600.0;
+    ps = ps * z + 1.0 / 362880.0;
+    pc = pc * z - 1.0 / 3628800.0;
+    ps = ps * z - 1.0 / 5040.0;
+    pc = pc * z + 1.0 / 40320.0;
+    ps = ps * z + 1.0 / 120.0;
+    pc = pc * z - 1.0 / 720.0;
+    ps = ps * z - 1.0 / 6.0;
+    pc = pc * z + 1.0 / 24.0;
+    pc = pc * z - 0.5;
+    const double s = x + x * (z * ps), c = 1.0 + z * pc;
+    const int qi = (int)q & 3;
+    const double s1 = (qi & 1) ? c : s, c1 = (qi & 1) ? -s : c;
+    *s_out = (qi & 2) ? -s1 : s1;
+    *c_out = (qi & 2) ? -c1 : c1;
+}
+
 // The whole workgroup: true, with the INVALID record written, where row w holds no frame of a usable length; else the vote
 // "a sample is not finite" is opened
-__device__ __forceinline__ bool line_open(const BurstWork &w, int *sh_bad, LineRec *out)
+template <typename Rec>
+__device__ __forceinline__ bool line_open(const BurstWork &w, int *sh_bad, Rec *out)
 {
     const int N = w.num_samples;
     if (w.drop_reason != 0 || N < kLineMinSamples || N > kMaxFrameSamples) {
-        if (threadIdx.x == 0) *out = LineRec{ 0.0f, 0.0f, kLineInvalid, w.drop_reason != 0 || N < 0 ? 0u : (uint32_t)N };
+        if (threadIdx.x == 0) *out = Rec::invalid(w.drop_reason != 0 || N < 0 ? 0u : (uint32_t)N);
         return true;
     }
     if (threadIdx.x == 0) *sh_bad = 0;
@@ -73,25 +111,28 @@ __device__ __forceinline__ bool line_open(const BurstWork &w, int *sh_bad, LineR
 
 // The whole workgroup, behind the staging loop: true, with the INVALID record written, where a thread saw `bad`.  (Its barrier
 // also stands behind whatever the threads wrote to LDS before it.)
-__device__ __forceinline__ bool line_vote(bool bad, int *sh_bad, int N, LineRec *out)
+template <typename Rec>
+__device__ __forceinline__ bool line_vote(bool bad, int *sh_bad, int N, Rec *out)
 {
     if (bad) *sh_bad = 1;
     __syncthreads();
     if (!*sh_bad) return false;
-    if (threadIdx.x == 0) *out = LineRec{ 0.0f, 0.0f, kLineInvalid, (uint32_t)N };
+    if (threadIdx.x == 0) *out = Rec::invalid((uint32_t)N);
     return true;
 }
 
 // sum_{n in [n0, n1)} y[n] exp(-2 pi i f n), f in cycles per sample, |f| <= 1/2 (both grids lie far inside: 0.09 .. 0.12
 // of the clock's at ten samples per symbol, 0.005 of the frequency's): y is CH interleaved real sequences of doubles, one
 // (a real signal) or two (re, im).  AHEAD samples are read ahead of the dependent steps that use them: a step is two
-// instructions per sequence, an LDS read waited for in every step is sixty cycles and more.
-template <int CH, int AHEAD>
+// instructions per sequence, an LDS read waited for in every step is sixty cycles and more.  EXACT: the two phases by
+// sc_sincos_turns_exact.
+template <int CH, int AHEAD, bool EXACT = false>
 __device__ __forceinline__ void line_segment_sum(const double *y, int n0, int n1, double f, double *re_out, double *im_out)
 {
     static_assert(CH == 1 || CH == 2, "a real or a complex signal");
     double es, ec;
-    sc_sincos_turns(f, &es, &ec);                                                // exp(i w), w = 2 pi f
+    if constexpr (EXACT) sc_sincos_turns_exact(f, &es, &ec);
+    else sc_sincos_turns(f, &es, &ec);                                           // exp(i w), w = 2 pi f
     const double c2 = 2.0 * ec;
     double s1[CH] = {}, s2[CH] = {};
     int n = n0;
@@ -122,15 +163,19 @@ __device__ __forceinline__ void line_segment_sum(const double *y, int n0, int n1
     }
     const double t = f * (double)(n1 - 1);
     double zs, zc;
-    sc_sincos_turns(t - rint(t), &zs, &zc);                                      // exp(i w m), the phase from the fraction of f m
+    if constexpr (EXACT) sc_sincos_turns_exact(t - rint(t), &zs, &zc);
+    else sc_sincos_turns(t - rint(t), &zs, &zc);                                 // exp(i w m), the phase from the fraction of f m
     *re_out = yr * zc + yi * zs;
     *im_out = yi * zc - yr * zs;
 }
 
 // The whole workgroup of SEG * LANES threads: |sum_n y[n] exp(-2 pi i freq(j) n)|^2 of the N samples at y into sh_P[j],
 // j < POINTS <= LANES.  Thread (seg, j) sums point j over samples [seg L, (seg + 1) L); the first POINTS threads add the
-// segments in their order.  sh_part: 2 * SEG * LANES doubles.  Every lane of a wavefront reads the same y[n] (a broadcast).
-template <int POINTS, int LANES, int SEG, int CH, int AHEAD, typename Freq>
+// segments in their order.  sh_part: 2 * SEG * LANES doubles; behind the call it still holds the segments' sums, real parts
+// at [seg LANES + j], imaginary parts SEG LANES further on (fine_time_kernel reads its line's from there).  The LANES threads
+// of a segment read the same y[n]: from 32 LANES on a broadcast within each 32-lane half of a wavefront, which is what an
+// 8-byte LDS read is served by (fine_freq's fine stage, 16 lanes, reads two addresses per half).
+template <int POINTS, int LANES, int SEG, int CH, int AHEAD, bool EXACT = false, typename Freq>
 __device__ __forceinline__ void line_grid_power(const double *y, int N, double *sh_part, double *sh_P, Freq freq)
 {
     static_assert(POINTS <= LANES && SEG * LANES <= 1024, "a workgroup is SEG segments of LANES threads");
@@ -140,7 +185,7 @@ __device__ __forceinline__ void line_grid_power(const double *y, int N, double *
     const int L = (N + SEG - 1) / SEG;
     const int n0 = seg * L, n1 = (seg + 1) * L < N ? (seg + 1) * L : N;
     double ar = 0.0, ai = 0.0;
-    if (j < POINTS && n0 < n1) line_segment_sum<CH, AHEAD>(y, n0, n1, freq(j), &ar, &ai);
+    if (j < POINTS && n0 < n1) line_segment_sum<CH, AHEAD, EXACT>(y, n0, n1, freq(j), &ar, &ai);
     sh_part[tid] = ar;
     sh_part[NT + tid] = ai;
     __syncthreads();

@@ -9,7 +9,7 @@
 //   feed.cpp        irdm_feed_* / irdm_flush / irdm_advance / irdm_reset, the polls, buffers for hosts without HIP headers
 //   state.cpp       detector-state export / import (time-chunk sharding), the stage-level batch calls
 //   api.cpp         options, statistics, kernel clock, RAW line formatting, --save-bursts
-//   frame_line.hpp  the per-frame line estimators' core and stream summary; symbol_clock.hpp and fine_freq.hpp are the two
+//   frame_line.hpp  the per-frame line estimators' core and stream summary; symbol_clock.hpp, fine_freq.hpp and fine_time.hpp are the three
 //                   kernels on it (launched by chain.cpp and state.cpp)
 //
 // Every field of a context is configuration, cache or stream state.  The third kind lives in types of
@@ -41,6 +41,7 @@
 #include "input_stats.hpp"
 #include "symbol_clock.hpp"
 #include "fine_freq.hpp"
+#include "fine_time.hpp"
 #include "iq_moments.hpp"
 #include "host_chain.hpp"
 #include "iq_sense.hpp"
@@ -143,6 +144,7 @@ struct BatchCtx {
     IdaPacked *hp_ida;                      // parsed_records: ida_decode() of each of them (pinned; written by ida_packed_kernel)
     FramePacked *hp_frame;                  // frame_records: frame_decode() of each of them (pinned; written by frame_packed_kernel)
     LineRec *hp_fine;                       // fine_freq: one record per burst (pinned; written by fine_freq_kernel; allocated with the option)
+    TimeRec *hp_ftime;                      // fine_time: one record per burst (pinned; written by fine_time_kernel; allocated with the option)
     LineRec *hp_clock;                      // symbol_clock: one record per burst (pinned; written by symbol_clock_kernel; allocated with the option)
     SenseRec *hp_sense;                     // iq_sense: one record per burst (pinned; written by iq_sense_kernel; allocated with the option)
     uint32_t *hp_flag, *hp_flag_dev;    // [0] sequence number the helper publishes, [1] time-out flag of the waiting kernel
@@ -152,6 +154,7 @@ struct BatchCtx {
     bool parsed;                 // ... and IdaPacked records
     bool framed;                 // ... and FramePacked records
     bool fined;                  // this batch ran the carrier frequency kernel: hp_fine holds its records
+    bool timed;                  // this batch ran the symbol timing kernel: hp_ftime holds its records
     bool clocked;                // this batch ran the symbol clock kernel: hp_clock holds its records
     bool sensed;                 // this batch ran the I/Q sense kernel: hp_sense holds its records
     bool cfo_on_device;          // this batch's libm step ran on the device: h_cfreq is filled from the returned records
@@ -246,6 +249,8 @@ struct StreamState {
     SymbolClockStream clock{ kScHist };
     // option "fine_freq": the per-frame records until they are polled and the summary's histogram (fine_freq.hpp)
     FineFreqStream fine{ kFfHist };
+    // option "fine_time": likewise (fine_time.hpp)
+    FineTimeStream ftime{ kFtHist };
     // option "iq_sense": the per-frame votes until they are polled and the counts of the summary (iq_sense.hpp)
     IqSenseStream iq;
     // option "iq_moments": the sums of the stream and the passes whose rows are still on their way (iq_moments.hpp)
@@ -455,6 +460,8 @@ struct irdm_pipeline {
     int symbol_clock = 0;
     // option "fine_freq" (chain.cpp, fine_freq.hpp): likewise, with the batch contexts' hp_fine
     int fine_freq = 0;
+    // option "fine_time" (chain.cpp, fine_time.hpp): likewise, with the batch contexts' hp_ftime
+    int fine_time = 0;
     // option "iq_sense" (chain.cpp, iq_sense.hpp): the switch (configuration); the batch contexts' hp_sense are the cache,
     // allocated when the option is first set
     int iq_sense = 0;
@@ -467,6 +474,7 @@ struct irdm_pipeline {
     float *d_br_taps = nullptr;
     uint64_t stat_br_launches = 0;
     uint64_t stat_ff_launches = 0;      // fine_freq_kernel launches by the chains
+    uint64_t stat_ft_launches = 0;      // fine_time_kernel launches by the chains
     bool br_active() const { return burst_resample && br_L != br_M && d_br_taps; }
     // options "swap_iq", "scrub" / "scrub_limit_log2", irdm_iq_balance and irdm_dc_block (feed.cpp, host_chain.hpp): what
     // irdm_feed_host does to every chunk on the device before anything reads it -- the switches and their settings
@@ -527,6 +535,7 @@ int spectrum_configure(irdm_pipeline *p, int R);
 int input_stats_configure(irdm_pipeline *p, int on);
 int symbol_clock_configure(irdm_pipeline *p, int on);
 int fine_freq_configure(irdm_pipeline *p, int on);
+int fine_time_configure(irdm_pipeline *p, int on);
 int iq_sense_configure(irdm_pipeline *p, int on);
 int burst_resample_configure(irdm_pipeline *p, int on);      // api.cpp
 bool burst_resample_ratio(int sample_rate, int decim, long long *L, long long *M);

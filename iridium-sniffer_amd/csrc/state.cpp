@@ -279,11 +279,12 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     p->decode_frames = 0;
     p->decode_ida = 0;
     p->detect_only = 0;          // a stage-B call on a detect-only context still runs stage B
-    const int marks = p->chunk_marks, clock = p->symbol_clock, sense = p->iq_sense, fine = p->fine_freq;
+    const int marks = p->chunk_marks, clock = p->symbol_clock, sense = p->iq_sense, fine = p->fine_freq, ftime = p->fine_time;
     p->chunk_marks = 0;          // (the records go to private queues: no chunk mark for them)
     p->symbol_clock = 0;         // (and the probe's frame is none of the stream's)
     p->iq_sense = 0;
     p->fine_freq = 0;
+    p->fine_time = 0;
     const uint64_t tagged = p->st.tagged;
     std::vector<irdm_burst_t> last; last.swap(p->st.last_bursts);
     p->keep_frame_samples = 1;
@@ -305,6 +306,7 @@ extern "C" int irdm_downmix_burst(irdm_pipeline_t *p, const irdm_burst_t *info, 
     p->symbol_clock = clock;
     p->iq_sense = sense;
     p->fine_freq = fine;
+    p->fine_time = ftime;
     p->detect_only = det;
     p->decode_frames = dec;
     p->decode_ida = dec_ida;
@@ -404,24 +406,38 @@ extern "C" int irdm_qpsk_demod_packed_batch(irdm_pipeline_t *p, const float *sam
     return demod_batch(p, samples, num_samples, direction, n, keep_bits, packed_out, full_out);
 }
 
+// what the public records of symbol_clock and fine_freq share with the kernel's
+template <typename PublicRec>
+static inline void line_public(PublicRec &o, const LineRec &r)
+{
+    o.quality = r.quality;
+    o.flags = r.flags;
+    o.n = r.n;
+}
+
 // A frame line estimator's kernel alone (frame_line.hpp), on the buffers of irdm_qpsk_demod_batch: frames in, one record per
-// frame out, in launches of burst_cap.  launch(nb, hp) starts the kernel on the first nb rows of d_work / d_frames;
-// fill(o, r) copies its record into the public one.
-template <typename PublicRec, typename Launch, typename Fill>
-static int line_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, PublicRec *out, Launch launch, Fill fill)
+// frame out, in launches of burst_cap.  launch(nb, hp) starts the kernel on the first nb rows of d_work / d_frames, whose
+// records are KernelRec; fill(o, r) makes the public record of one (its id is set here).  simplex: BurstWork::simplex of
+// every frame, or nullptr for 0.
+template <typename KernelRec, typename PublicRec, typename Launch, typename Fill>
+static int line_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, const int *simplex, int n, PublicRec *out,
+                      Launch launch, Fill fill)
 {
     if (!p || !samples || !num_samples || !out || n < 0) return -1;
     for (int i = 0; i < n; i++)
         if (num_samples[i] < 0 || num_samples[i] > kMaxFrameSamples) return -1;
     pipeline_enter(p);
-    LineRec *hp = nullptr;
-    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(LineRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
+    KernelRec *hp = nullptr;
+    IRDM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&hp), sizeof(KernelRec) * (size_t)std::max(1, std::min(n, p->burst_cap)),
                                  hipHostMallocDefault));
     int rc = 0;
     for (int base = 0; base < n && rc == 0; base += p->burst_cap) {
         const int nb = std::min(p->burst_cap, n - base);
         p->h_work.assign(nb, BurstWork());
-        for (int i = 0; i < nb; i++) p->h_work[i].num_samples = num_samples[base + i];
+        for (int i = 0; i < nb; i++) {
+            p->h_work[i].num_samples = num_samples[base + i];
+            p->h_work[i].simplex = simplex && simplex[base + i] ? 1 : 0;
+        }
         rc = hipMemcpyAsync(p->d_work, p->h_work.data(), sizeof(BurstWork) * nb, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
                      hipMemcpyAsync(p->d_frames, samples + (size_t)base * 2 * kMaxFrameSamples,
                                     sizeof(float2) * (size_t)nb * kMaxFrameSamples, hipMemcpyHostToDevice, p->stream) == hipSuccess &&
@@ -429,11 +445,8 @@ static int line_batch(irdm_pipeline_t *p, const float *samples, const int *num_s
                  ? 0 : -1;
         for (int i = 0; rc == 0 && i < nb; i++) {
             PublicRec &o = out[base + i];
-            o.id = (uint64_t)(base + i);
-            o.quality = hp[i].quality;
-            o.flags = hp[i].flags;
-            o.n = hp[i].n;
             fill(o, hp[i]);
+            o.id = (uint64_t)(base + i);
         }
     }
     (void)hipHostFree(hp);
@@ -442,16 +455,24 @@ static int line_batch(irdm_pipeline_t *p, const float *samples, const int *num_s
 
 extern "C" int irdm_symbol_clock_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_clock_est_t *out)
 {
-    return line_batch(p, samples, num_samples, n, out,
-                      [p](int nb, LineRec *hp) { return launch_symbol_clock(p->d_work, nb, p->d_frames, p->sps, hp, p->stream); },
-                      [](irdm_clock_est_t &o, const LineRec &r) { o.eps = r.value; });
+    return line_batch<LineRec>(p, samples, num_samples, nullptr, n, out,
+                               [p](int nb, LineRec *hp) { return launch_symbol_clock(p->d_work, nb, p->d_frames, p->sps, hp, p->stream); },
+                               [](irdm_clock_est_t &o, const LineRec &r) { line_public(o, r); o.eps = r.value; });
 }
 
 extern "C" int irdm_fine_freq_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, int n, irdm_fine_freq_t *out)
 {
-    return line_batch(p, samples, num_samples, n, out,
-                      [p](int nb, LineRec *hp) { return launch_fine_freq(p->d_work, nb, p->d_frames, (double)p->out_rate, hp, p->stream); },
-                      [](irdm_fine_freq_t &o, const LineRec &r) { o.df_hz = r.value; o.freq_hz = (double)r.value; });
+    return line_batch<LineRec>(p, samples, num_samples, nullptr, n, out,
+                               [p](int nb, LineRec *hp) { return launch_fine_freq(p->d_work, nb, p->d_frames, (double)p->out_rate, hp, p->stream); },
+                               [](irdm_fine_freq_t &o, const LineRec &r) { line_public(o, r); o.df_hz = r.value; o.freq_hz = (double)r.value; });
+}
+
+extern "C" int irdm_fine_time_batch(irdm_pipeline_t *p, const float *samples, const int *num_samples, const int *simplex, int n,
+                                    irdm_fine_time_t *out)
+{
+    return line_batch<TimeRec>(p, samples, num_samples, simplex, n, out,
+                               [p](int nb, TimeRec *hp) { return launch_fine_time(p->d_work, nb, p->d_frames, p->sps, hp, p->stream); },
+                               [p](irdm_fine_time_t &o, const TimeRec &r) { fine_time_public(r, p->sps, &o); });
 }
 
 extern "C" int irdm_poll_decoded(irdm_pipeline_t *p, irdm_decoded_t *out, int max)

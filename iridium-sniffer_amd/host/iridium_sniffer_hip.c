@@ -10,7 +10,7 @@
  *                         [-f FILE2 ...] [--files-from LIST] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR]
  *                         [--spectrum FILE [--spectrum-frames R]]
  *                         [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]]
- *                         [--input-stats] [--diagnostic] [--clock-check] [--fine-freq] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]]
+ *                         [--input-stats] [--diagnostic] [--clock-check] [--fine-freq] [--fine-time] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]]
  *                         [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]
  * IQ file in, iridium-toolkit "RAW:" lines on stdout (IDA: lines with --parsed; ACARS lines instead of RAW ones with
  * --acars / --acars-json, main.c:357-361), "burst_detect: tagged N bursts total" on stderr
@@ -100,6 +100,18 @@
  *     freq: N frames refined (K kept the PLL's value: A out of range, B invalid); refined - PLL median %+.0f Hz (quartiles %+.0f .. %+.0f)
  * or "freq: 0 frames".  -v says once "fine freq: carrier frequency from each frame's samples (+-250 Hz of the downmixer's)".
  * --save-bursts .meta files state the downmixer's frequency as before.  Refused with --gpus N > 1 and with --save-only.
+ * --fine-time: every frame's arrival time refined on the GPU from the frame's own samples (option "fine_time": the phase of the
+ * symbol rate's line in |x|^2, to about 0.3 us).  The time field of every RAW: / IDA: line, and what --position, --acars and
+ * --parsed make of it, is then the time of the frame's first symbol -- the unique word's first on a downlink frame -- about
+ * 0.73 ms later than without the flag, where it is the time the burst's magnitude crosses a threshold, which wanders by 6 to
+ * 60 us with the noise.  A frame whose estimate is ambiguous (further than a quarter of a symbol from the correlator's) or
+ * invalid takes the correlator's place instead, so every time of a run means the same.  One closing line per recording on
+ * stderr, directly behind "freq:" and in front of "iq:":
+ *     time: N frames refined (K kept the correlator's place: A ambiguous, B invalid); line - correlator median %+.2f samples (quartiles %+.2f .. %+.2f)
+ * or "time: 0 frames".  At a rate that is no multiple of 250 kHz the frames' samples are not 4 us apart and the estimate
+ * inherits the clock error: one warning names --burst-resample, with which nothing more is needed.  -v says once "fine time:
+ * arrival time of each frame's first symbol from its samples".  --save-bursts .meta files state the downmixer's timestamp as
+ * before.  Refused with --gpus N > 1 and with --save-only.
  * --burst-resample: at a rate that is no multiple of 250 kHz every burst's decimated row is resampled on the GPU to exactly
  * 250 000 samples/s before it is demodulated (option "burst_resample", on every member with --gpus N): frames come out whole,
  * their frequencies and times right, without resampling the whole stream.  With every input kind, behind --band-center /
@@ -399,6 +411,8 @@ static int g_input_stats, g_diag;
 static int g_clock;
 /* --fine-freq */
 static int g_fine;
+/* --fine-time */
+static int g_ftime;
 /* --iq-check, --swap-iq */
 static int g_iq, g_swap;
 /* --burst-resample */
@@ -601,6 +615,19 @@ static void freq_line(const irdm_fine_freq_summary_t *ff)
             (unsigned long long)ff->frames_out_of_range, (unsigned long long)ff->frames_invalid, ff->median, ff->q25, ff->q75);
 }
 
+/* the closing "time:" line of a recording (--fine-time) */
+static void time_line(const irdm_fine_time_summary_t *ft)
+{
+    if (ft->frames_seen - ft->frames_not_ok == 0) {
+        fprintf(stderr, "time: 0 frames\n");
+        return;
+    }
+    fprintf(stderr, "time: %llu frames refined (%llu kept the correlator's place: %llu ambiguous, %llu invalid); "
+            "line - correlator median %+.2f samples (quartiles %+.2f .. %+.2f)\n",
+            (unsigned long long)ft->frames_applied, (unsigned long long)(ft->frames_ambiguous + ft->frames_invalid),
+            (unsigned long long)ft->frames_ambiguous, (unsigned long long)ft->frames_invalid, ft->median, ft->q25, ft->q75);
+}
+
 /* --diagnostic: the reference's closing status line (main.c:444-480) over the recording's stream time */
 static void diagnostic_line(double elapsed, unsigned long det, unsigned long sub, float noise_floor, float peak_signal)
 {
@@ -677,6 +704,11 @@ static void drain(irdm_pipeline_t *p, irdm_demod_t *d, const char *file_info, ui
         /* (likewise; the demodulator records carry the refined frequency) */
         static irdm_fine_freq_t ff[256];
         while (irdm_poll_fine_freq(p, ff, 256) > 0) {}
+    }
+    if (g_ftime) {
+        /* (likewise; the demodulator records carry the refined time) */
+        static irdm_fine_time_t ft[256];
+        while (irdm_poll_fine_time(p, ft, 256) > 0) {}
     }
     if (g_iq) {
         /* (likewise: the summary is the library's) */
@@ -1232,6 +1264,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--diagnostic")) g_input_stats = g_diag = 1;     /* options.c:376 */
         else if (!strcmp(a, "--clock-check")) g_clock = 1;
         else if (!strcmp(a, "--fine-freq")) g_fine = 1;
+        else if (!strcmp(a, "--fine-time")) g_ftime = 1;
         else if (!strcmp(a, "--iq-check")) g_iq = 1;
         else if (!strcmp(a, "--burst-resample")) g_burst_resample = 1;
         else if (!strcmp(a, "--swap-iq")) g_swap = 1;
@@ -1365,7 +1398,7 @@ int main(int argc, char **argv)
                 fprintf(stderr, "warning: %s: -r %.0f overrides the header's %d samples/s\n", g_in[k].path, rate, g_in[k].hdr_rate);
     }
     if (!g_n_in || rate <= 0) {
-        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--fine-freq] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]\n", argv[0]);
+        fprintf(stderr, "usage: %s -f FILE [-f FILE2 ...] [--files-from LIST] [-r RATE] [-c FREQ] [--format ci8|cu8|ci16|cf32|ci16-full|sc16q11|ci32|ci32-24] [--container wav|sigmf|sdriq|raw] [--probe] [-d DB] [--file-info STR] [--no-simd] [--save-bursts DIR] [--parsed] [--acars] [--acars-json] [--station ID] [--position[=HEIGHT_M]] [--gpus N] [--band-center HZ --decimate D] [--resample-to HZ [--band-center HZ]] [--start-time SEC[.NNNNNNNNN]] [--out-dir DIR] [--spectrum FILE [--spectrum-frames R]] [--save-band FILE [--save-format ci8|ci16|cf32] [--save-gain G] [--save-only]] [--input-stats] [--diagnostic] [--clock-check] [--fine-freq] [--fine-time] [--iq-check] [--swap-iq] [--scrub[=LOG2]] [--dc-block[=LOG2]] [--image-check] [--iq-balance=GAIN_DB,PHASE_DEG] [--burst-resample] [--prime] [--join]\n", argv[0]);
         return 2;
     }
     if (resample_to && decimate) {
@@ -1454,6 +1487,17 @@ int main(int argc, char **argv)
         }
         if (save_only) {
             fprintf(stderr, "--fine-freq with --save-only: no context runs, so there are no frames to refine\n");
+            return 2;
+        }
+        gpus = 0;
+    }
+    if (g_ftime) {
+        if (gpus > 1) {
+            fprintf(stderr, "--fine-time: one GPU only (--gpus %d)\n", gpus);
+            return 2;
+        }
+        if (save_only) {
+            fprintf(stderr, "--fine-time with --save-only: no context runs, so there are no frames to refine\n");
             return 2;
         }
         gpus = 0;
@@ -1765,6 +1809,14 @@ int main(int argc, char **argv)
         return 1;
     }
     if (g_fine && verbose) fprintf(stderr, "fine freq: carrier frequency from each frame's samples (+-250 Hz of the downmixer's)\n");
+    if (g_ftime && irdm_set_option(p, "fine_time", 1) != 0) {
+        fprintf(stderr, "--fine-time: the library refused the estimator\n");
+        return 1;
+    }
+    if (g_ftime && !g_burst_resample && c.sample_rate % 250000 != 0)
+        fprintf(stderr, "warning: --fine-time at %d samples/s, no multiple of 250 kHz: the frames' samples are not 4 us apart and the "
+                        "refined times inherit the clock error; add --burst-resample\n", c.sample_rate);
+    if (g_ftime && verbose) fprintf(stderr, "fine time: arrival time of each frame's first symbol from its samples\n");
     if (g_iq && irdm_set_option(p, "iq_sense", 1) != 0) {
         fprintf(stderr, "--iq-check: the library refused the check\n");
         return 1;
@@ -2054,6 +2106,11 @@ int main(int argc, char **argv)
             irdm_fine_freq_summary_t ff;
             if (irdm_fine_freq(p, &ff) == 0) freq_line(&ff);
             else { fprintf(stderr, "--fine-freq: %s: no estimate\n", file); rc = 1; }
+        }
+        if (g_ftime) {
+            irdm_fine_time_summary_t ft;
+            if (irdm_fine_time(p, &ft) == 0) time_line(&ft);
+            else { fprintf(stderr, "--fine-time: %s: no estimate\n", file); rc = 1; }
         }
         if (g_iq) {
             irdm_iq_sense_t iq;

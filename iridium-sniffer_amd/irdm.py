@@ -261,6 +261,22 @@ class FineFreq(C.Structure):
                 ("flags", C.c_uint32), ("n", C.c_uint32)]
 
 
+FINE_TIME_INVALID, FINE_TIME_AMBIGUOUS, FINE_TIME_NOT_OK = 1, 2, 4
+
+
+class FineTime(C.Structure):
+    """irdm_fine_time_t (option fine_time): the time of one frame's sample 0 from its own samples, flags FINE_TIME_*"""
+    _fields_ = [("id", C.c_uint64), ("time_ns", C.c_uint64), ("tau", C.c_double), ("s_re", C.c_double), ("s_im", C.c_double),
+                ("floor", C.c_double), ("corr", C.c_float), ("quality", C.c_float), ("flags", C.c_uint32), ("n", C.c_uint32)]
+
+
+class FineTimeSummary(C.Structure):
+    """irdm_fine_time_summary_t (irdm_fine_time): the summary of the stream so far; median and quartiles of tau - corr in samples"""
+    _fields_ = [("frames_seen", C.c_uint64), ("frames_applied", C.c_uint64), ("frames_not_ok", C.c_uint64),
+                ("frames_ambiguous", C.c_uint64), ("frames_invalid", C.c_uint64),
+                ("median", C.c_double), ("q25", C.c_double), ("q75", C.c_double)]
+
+
 class FineFreqSummary(C.Structure):
     """irdm_fine_freq_summary_t (irdm_fine_freq): the summary of the stream so far; median and quartiles of refined - PLL in Hz"""
     _fields_ = [("frames_seen", C.c_uint64), ("frames_applied", C.c_uint64), ("frames_not_ok", C.c_uint64),
@@ -370,6 +386,11 @@ def lib():
             L.irdm_poll_fine_freq.argtypes = [C.c_void_p, C.POINTER(FineFreq), C.c_int]
             L.irdm_fine_freq.argtypes = [C.c_void_p, C.POINTER(FineFreqSummary)]
             L.irdm_fine_freq_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.c_int, C.POINTER(FineFreq)]
+        if hasattr(L, "irdm_fine_time"):
+            L.irdm_poll_fine_time.argtypes = [C.c_void_p, C.POINTER(FineTime), C.c_int]
+            L.irdm_fine_time.argtypes = [C.c_void_p, C.POINTER(FineTimeSummary)]
+            L.irdm_fine_time_batch.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                               C.POINTER(FineTime)]
         if hasattr(L, "irdm_recording_probe"):
             L.irdm_recording_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(RecordingInfo), C.c_char_p, C.c_size_t]
         if hasattr(L, "irdm_format_bytes"):
@@ -1049,8 +1070,9 @@ class Pipeline:
             raise RuntimeError("irdm_symbol_clock failed (option symbol_clock never set?)")
         return st
 
-    def _frames_batch(self, fn, Rec, frames, what):
-        """a stage call that takes frames (list of complex64 arrays, <= 4440 samples) and gives one Rec per frame"""
+    def _frames_batch(self, fn, Rec, frames, what, extra=False):
+        """a stage call that takes frames (list of complex64 arrays, <= 4440 samples) and gives one Rec per frame; extra: one
+        int per frame, handed over behind the lengths (None: a null pointer; False: the call has no such argument)"""
         n = len(frames)
         buf = np.zeros((max(n, 1), 2 * MAX_FRAME_SAMPLES), np.float32)
         ns = np.zeros(max(n, 1), np.int32)
@@ -1059,7 +1081,14 @@ class Pipeline:
             ns[i] = len(f)
             buf[i, :2 * len(f)] = f.view(np.float32)
         out = (Rec * max(n, 1))()
-        if fn(self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int)), n, out) != 0:
+        args = [self.h, _fp(buf), ns.ctypes.data_as(C.POINTER(C.c_int))]
+        if extra is None:
+            args.append(None)
+        elif extra is not False:
+            ex = np.zeros(max(n, 1), np.int32)
+            ex[:n] = extra
+            args.append(ex.ctypes.data_as(C.POINTER(C.c_int)))
+        if fn(*args, n, out) != 0:
             raise RuntimeError(what + " failed")
         return [Rec.from_buffer_copy(out[i]) for i in range(n)]
 
@@ -1133,6 +1162,27 @@ class Pipeline:
     def fine_freq_batch(self, frames):
         """irdm_fine_freq_batch: frames = list of complex64 arrays (<= 4440 samples); returns a list of FineFreq"""
         return self._frames_batch(self.L.irdm_fine_freq_batch, FineFreq, frames, "irdm_fine_freq_batch")
+
+    def poll_fine_time(self):
+        """option fine_time 1: one FineTime per frame that reached the demodulator, in the order of the demod records"""
+        return self._poll(self.L.irdm_poll_fine_time, FineTime)
+
+    def poll_fine_time_raw(self, chunk=4096):
+        """the same as one numpy byte matrix [n, 64]"""
+        return self._poll_raw(self.L.irdm_poll_fine_time, FineTime, chunk)
+
+    def fine_time(self):
+        """irdm_fine_time (option fine_time): the FineTimeSummary of the stream so far"""
+        st = FineTimeSummary()
+        if self.L.irdm_fine_time(self.h, C.byref(st)) != 0:
+            raise RuntimeError("irdm_fine_time failed (option fine_time never set?)")
+        return st
+
+    def fine_time_batch(self, frames, simplex=None):
+        """irdm_fine_time_batch: frames = list of complex64 arrays (<= 4440 samples), simplex = one flag per frame (None: all 0);
+        returns a list of FineTime"""
+        return self._frames_batch(self.L.irdm_fine_time_batch, FineTime, frames, "irdm_fine_time_batch",
+                                  extra=None if simplex is None else [int(bool(v)) for v in simplex])
 
     def poll_spectrum(self, chunk=64):
         """option spectrum_frames: (headers, mean, peak) of the rows finished so far -- a list of SpectrumRow and two float32
